@@ -12,7 +12,21 @@ upload is inside it.
 N > 1 (torchrun, one process per GPU): frame-parallel -- every rank renders its own frame of the
 same workload (camera yaw offset per rank), no data-path collective; "scaling": "weak".
 
-Also reported (rank 0, N = 1):
+A plain run does only what the headline needs: set-up, clock ramp, warm-up, the --steps timed steps
+(ms_per_step = their wall time / --steps), the optional --dump-outputs, the result line.  For the
+legacy configs the line still carries kernels_ms and the roofline's event-time figures: their HIP
+events are recorded inside the timed steps themselves.
+
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32 / float64, under
+64 MB in all; dump_legacy / dump_lib say which arrays).  The inputs are the same for the same
+arguments, so the files of two builds compare array for array.
+
+--full adds every other leg (rank 0, N = 1 unless noted), each switched off by its --no-* option:
+  single_frame  the single-frame latency figure (one shs_render_legacy per step), before the headline loop.
+  strong_c4/c5  the tile-sharded 4K legs after the headline C2 loop (every N).
+  seam1_pcie    render + D2H of every frame's present staging, last in the process.
+  kernels_ms    c4 / c5: kernel event times of 20 frames on one context alone after the timed loop
+                (and the roofline computed from them).
   roofline      dominant kernel (k_raster, which writes every output byte of the frame): SURVEY.md
                 8(d) algorithmic bytes per frame (N_tri*72 + W*H*8) / its mean HIP-event duration
                 over the timed region, against 8 TB/s (frame_frac: the same bytes over k_setup +
@@ -92,6 +106,66 @@ def batch_poses(name, n_frames, rank=0):
     return frame, sets
 
 
+DUMP_BUDGET = 60_000_000   # bytes of .npy per --dump-outputs (the limit is 64 MB in all)
+DUMP_SEED = 0x5EED
+
+
+def sample_pixels(n_px, k):
+    """k of a frame's n_px flat pixel indices (y * W + x), ascending: the same for every run."""
+    k = int(max(1, min(n_px, k)))
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n_px, size=k, replace=False))
+
+
+def save_arrays(out_dir, arrays):
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.int64 else np.float32)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        total += a.nbytes
+    assert total <= DUMP_BUDGET, total
+
+
+def dump_legacy(ctx, frame, n_frames, out_dir):
+    """The colour (RGBA8 canvas) and depth (f32) framebuffers of the last batch, as shs_resolve_frame
+    hands them to a caller: frame 0 whole (color_frame0 [H, W, 4], depth_frame0 [H, W]) and a fixed
+    seeded sample of K pixels of every frame (color [F, K, 4], depth [F, K]; sample_pixels [K] are
+    their flat indices y * W + x)."""
+    n_px = frame.width * frame.height
+    whole = n_px * 20 <= DUMP_BUDGET * 3 // 4     # 20 B per pixel as float32: colour 16 + depth 4
+    budget = DUMP_BUDGET - (n_px * 20 if whole else 0)
+    idx = sample_pixels(n_px, min(8192, budget // (n_frames * 20 + 8)))
+    color = np.empty((n_frames, idx.size, 4), np.float32)
+    depth = np.empty((n_frames, idx.size), np.float32)
+    arrays = {"sample_pixels": idx.astype(np.int64)}
+    for i in range(n_frames):
+        c, d = ctx.resolve_frame(i)
+        color[i] = c.reshape(n_px, 4)[idx]
+        depth[i] = d.reshape(n_px)[idx]
+        if i == 0 and whole:
+            arrays["color_frame0"], arrays["depth_frame0"] = c, d
+    arrays["color"], arrays["depth"] = color, depth
+    save_arrays(out_dir, arrays)
+
+
+def dump_lib(ctx, out_dir):
+    """A fixed seeded sample of K pixels of the frame's targets, as shs_resolve_lib / shs_resolve_ldr
+    hand them to a caller: hdr [K, 4], depth [K], motion [K, 2] (rows y-up), present [K, 4] (the RGBA8
+    staging, rows top-down); sample_pixels [K] are the flat indices row * W + x into each."""
+    hdr, depth, motion = ctx.resolve_lib()
+    _, present = ctx.resolve_ldr()
+    n_px = hdr.shape[0] * hdr.shape[1]
+    idx = sample_pixels(n_px, 1_000_000)
+    arrays = {"sample_pixels": idx.astype(np.int64), "hdr": hdr.reshape(n_px, 4)[idx]}
+    if depth is not None:
+        arrays["depth"] = depth.reshape(n_px)[idx]
+    if motion is not None:
+        arrays["motion"] = motion.reshape(n_px, 2)[idx]
+    if present is not None:
+        arrays["present"] = present.reshape(n_px, 4)[idx]
+    save_arrays(out_dir, arrays)
+
+
 def run_gpu(args, rank, local_rank, world, dist):
     """One step = one shs_render_legacy_batch of F frames (F = --frames-per-step): one k_setup + one
     k_raster launch render F independent frames, each into its own colour + depth framebuffers.
@@ -107,11 +181,11 @@ def run_gpu(args, rank, local_rank, world, dist):
         ctx.set_raster_loop(args.raster_loop)
     prepared = [ctx.prepare_batch(frame, fds) for fds in sets]
     render = ctx.render_batch_prepared
-    # The auxiliary legs run BEFORE the headline loop: every frame they render is measured for its own
-    # figure, and the loop that follows starts on a GPU that has been rendering (clocks up), as a render
+    # The auxiliary legs (--full) run BEFORE the headline loop: every frame they render is measured for its
+    # own figure, and the loop that follows starts on a GPU that has been rendering (clocks up), as a render
     # loop's frames do -- not right after process start-up (tools/diag_short_window.py).
     single = None
-    if F > 1 and not args.child and not args.no_single:
+    if args.full and F > 1 and not args.child and not args.no_single:
         # the single-frame latency figure: one shs_render_legacy per step
         one = ctx.prepare(frame, sets[0][0])
         for _ in range(10):
@@ -168,6 +242,8 @@ def run_gpu(args, rank, local_rank, world, dist):
     elapsed = time.perf_counter() - t0
     n_launches, kms = ctx.timing_read()
     ctx.enable_timing(False)
+    if args.dump_outputs and rank == 0:
+        dump_legacy(ctx, frame, F, args.dump_outputs)
     ctx.close()
     return frame, sets, stats, elapsed, n_launches, kms, single, ramp
 
@@ -348,16 +424,20 @@ def lib_timed_loop(args, slots, frame_fn, dist, frame=None, rank=0, world=1, on_
         frame_fn(slots[i % D])
     barrier_sync()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:   # the last timed frame's targets
+        dump_lib(slots[(args.steps - 1) % D].ctx, args.dump_outputs)
     ctx = slots[0].ctx
-    ctx.enable_timing(True)
-    ctx.lib_timing_reset()
-    if dist is not None:
-        slots[0].gather_events = []
-    for _ in range(20):
-        frame_fn(slots[0])
-    barrier_sync()
-    n_passes, kms = ctx.lib_timing_read()
-    ctx.enable_timing(False)
+    n_passes, kms = {"camera": 0}, {}
+    if args.full:   # the isolated kernel-timing leg
+        ctx.enable_timing(True)
+        ctx.lib_timing_reset()
+        if dist is not None:
+            slots[0].gather_events = []
+        for _ in range(20):
+            frame_fn(slots[0])
+        barrier_sync()
+        n_passes, kms = ctx.lib_timing_read()
+        ctx.enable_timing(False)
     if slots[0].gather_events:   # the gather's own time on the slot stream (rank 0: receives + unpack)
         kms = dict(kms, gather=float(np.mean([a.elapsed_time(b) for a, b in slots[0].gather_events])))
         slots[0].gather_events = None
@@ -531,6 +611,7 @@ def strong_legs(args, rank, local_rank, world, dist):
         a = copy.copy(args)
         a.config, a.steps, a.warmup = cfg, args.strong_frames, 20
         a.shard_layout, a.inflight = "regions", 3
+        a.full, a.dump_outputs = True, None   # the legs' kernel timing; --dump-outputs is the headline's
         runner = run_gpu_c4 if cfg == "c4" else run_gpu_lib
         ok, err = 1.0, None
         try:
@@ -586,7 +667,7 @@ def collect_pmc(args):
         for counter in ("FETCH_SIZE", "WRITE_SIZE"):
             d = os.path.join(tmp, counter)
             cmd = [exe, "--pmc", counter, "--output-format", "csv", "-d", d, "-o", "pmc", "--",
-                   sys.executable, os.path.abspath(__file__), "--child", "--config", args.config,
+                   sys.executable, os.path.abspath(__file__), "--child", "--full", "--config", args.config,
                    "--steps", "20", "--warmup", "3", "--frames-per-step", str(args.frames_per_step)]
             r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300, text=True)
             if r.returncode != 0:
@@ -813,9 +894,14 @@ def main():
     ap.add_argument("--shadow-full", action="store_true",
                     help="c5: render the whole shadow map every frame (default: the camera pass's footprint, "
                          "SHS_OPT_SHADOW_FOOTPRINT)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every auxiliary leg (single-frame latency, strong-scaling legs, PCIe leg, c4/c5 "
+                         "isolated kernel timing, PMC traffic passes, CPU baseline); each has its own --no-* switch")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (rank 0)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--strong", default="c4,c5", type=lambda x: [c for c in x.split(",") if c],
-                    help="legacy configs: the tile-sharded 4K legs run after the headline loop at every N "
+                    help="--full, legacy configs: the tile-sharded 4K legs run after the headline loop at every N "
                          "(strong_c4 / strong_c5 keys; '' to skip)")
     ap.add_argument("--strong-frames", type=int, default=200, help="timed frames of each strong leg")
     ap.add_argument("--no-pmc", action="store_true")
@@ -856,7 +942,7 @@ def main():
         return
 
     pmc, pmc_err = (None, "skipped")
-    if world == 1 and not args.no_pmc:
+    if args.full and world == 1 and not args.no_pmc:
         pmc, pmc_err = collect_pmc(args)   # before this process initialises the GPU
 
     dist = None
@@ -872,9 +958,11 @@ def main():
     frame, sets, stats, elapsed, n_launches, kms, single, ramp = run_gpu(args, rank, local_rank, world, dist)
     draws = sets[0][0]
     # the strong-scaling legs ride on the headline configuration's line (the driver's `--gpus N` run)
-    strong = strong_legs_guarded(args, rank, local_rank, world, dist) if args.strong and not args.child and args.config == "c2" else {}
+    strong = {}
+    if args.full and args.strong and not args.child and args.config == "c2":
+        strong = strong_legs_guarded(args, rank, local_rank, world, dist)
     pcie = None   # (last: seam1_pcie)
-    if args.frames_per_step > 1 and world == 1 and not args.child and not args.no_pcie:
+    if args.full and args.frames_per_step > 1 and world == 1 and not args.child and not args.no_pcie:
         pcie = seam1_pcie(args, frame, sets)
     B1, n_tri1 = algorithmic_bytes(frame, draws)
     F = args.frames_per_step
@@ -956,7 +1044,7 @@ def main():
     if pcie is not None:
         line["seam1_pcie"] = pcie
     line.update(strong)
-    if world == 1 and not args.no_cpu:
+    if args.full and world == 1 and not args.no_cpu:
         line["cpu_baseline"] = cpu_baseline(args)
     print(json.dumps(line), flush=True)
     if dist is not None:
@@ -985,7 +1073,7 @@ def main_lib(args, world, rank, local_rank, dist, pmc, pmc_err):
             dist.destroy_process_group()
         return
     steps = args.steps
-    t_k = kms["raster"]
+    t_k = kms.get("raster", 0.0)   # (no kernel times without --full: the keys built from them are dropped below)
     achieved = B_k / (t_k * 1e-3) / 1e9 if t_k > 0 else None
     t_frame = sum(v for k, v in kms.items() if k != "gather")
     # at N > 1 the timed kernels are rank 0's: its frame bytes are the whole frame's minus the 32 B of
@@ -1034,7 +1122,10 @@ def main_lib(args, world, rank, local_rank, dist, pmc, pmc_err):
         "roofline": roofline,
         "clock_ramp": dict(getattr(args, "lib_ramp", {}), what="untimed frames before the warm-up: steady-state GPU clocks"),
     }
-    if world == 1 and not args.no_cpu:
+    if not args.full:   # the isolated kernel-timing leg did not run
+        for k in ("kernels_ms", "kernel_timing", "roofline"):
+            del line[k]
+    if args.full and world == 1 and not args.no_cpu:
         line["cpu_baseline"] = cpu_baseline(args)
     print(json.dumps(line), flush=True)
     if dist is not None:

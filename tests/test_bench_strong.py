@@ -30,7 +30,8 @@ def test_strong_summary_single_gpu_is_whole_frame():
 
 
 def test_strong_legs_default_on():
-    """The driver's plain `bench.py --gpus N` runs both legs (argparse default)."""
+    """`bench.py --full --gpus N` runs both legs unless --strong says otherwise (argparse default); --full
+    itself is off by default (tests/test_bench_plain.py: a plain run calls no auxiliary leg)."""
     import argparse
     old = sys.argv
     try:
@@ -52,6 +53,7 @@ def test_strong_legs_default_on():
     finally:
         sys.argv = old
     assert ap_args.strong == ["c4", "c5"] and ap_args.strong_frames > 0
+    assert ap_args.full is False
 
 
 def test_strong_legs_failure_keeps_the_headline(monkeypatch):

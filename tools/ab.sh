@@ -3,7 +3,7 @@
 # up to commit 1dc90d1; DESIGN.md cites them by name).  Runs on the GPU box from the repository root:
 #
 #   TAG=r6a TESTS="tests/test_regions.py tests/test_fullsize.py" LIBS="base gpu" REPS=2 \
-#     bash tools/ab.sh "python tools/exp_pipeline.py c4 60 1,8 3" "python bench.py --config c5 --no-pmc --no-cpu"
+#     bash tools/ab.sh "python tools/exp_pipeline.py c4 60 1,8 3" "python bench.py --full --config c5 --no-pmc --no-cpu"
 #
 #   TESTS   -m gpu test files run first with the default library (empty: none); a failure ends the run
 #   LIBS    libraries to compare: "gpu" = the default shs_gpu/libshs_gpu.so, NAME = shs_gpu/libshs_NAME.so

@@ -5,7 +5,7 @@ export SHS_GPU_LIB=${SHS_GPU_LIB:-$PWD/leisure-software-renderer_amd/shs_gpu/lib
 set -o pipefail
 mkdir -p gpurun_out
 for e in ${ENVS:-X=0}; do
-  env $e timeout -k 10 200 python bench.py --config ${CONFIG:-c5} --no-pmc --no-cpu --no-single --no-pcie --steps 100 --warmup 10 \
+  env $e timeout -k 10 200 python bench.py --full --config ${CONFIG:-c5} --no-pmc --no-cpu --no-single --no-pcie --steps 100 --warmup 10 \
     > gpurun_out/env_$e.log 2>&1 || { tail -20 gpurun_out/env_$e.log; exit 1; }
   python - gpurun_out/env_$e.log "$e" <<'PY'
 import json,sys

@@ -6,7 +6,7 @@ export SHS_GPU_LIB=${SHS_GPU_LIB:-$PWD/leisure-software-renderer_amd/shs_gpu/lib
 set -o pipefail
 mkdir -p gpurun_out
 for f in 0 1 4 5 2; do
-  SHS_LIB_EXP=$f timeout -k 10 200 python bench.py --config c4 --no-pmc --no-cpu --no-single --no-pcie --steps 50 --warmup 5 \
+  SHS_LIB_EXP=$f timeout -k 10 200 python bench.py --full --config c4 --no-pmc --no-cpu --no-single --no-pcie --steps 50 --warmup 5 \
     > gpurun_out/expf_$f.log 2>&1 || { tail -5 gpurun_out/expf_$f.log; exit 1; }
   python - gpurun_out/expf_$f.log $f <<'PY'
 import json,sys

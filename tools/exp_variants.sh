@@ -6,7 +6,7 @@ mkdir -p gpurun_out
 for v in ${VARIANTS:-default}; do
   for c in ${CONFIGS:-c4}; do
     if [ $v = default ]; then L=; else L=$(pwd)/leisure-software-renderer_amd/shs_gpu/libshs_$v.so; fi
-    SHS_GPU_LIB=$L timeout -k 10 200 python bench.py --config $c --no-pmc --no-cpu --no-single --no-pcie --steps 100 --warmup 10 \
+    SHS_GPU_LIB=$L timeout -k 10 200 python bench.py --full --config $c --no-pmc --no-cpu --no-single --no-pcie --steps 100 --warmup 10 \
       > gpurun_out/var_${v}_$c.log 2>&1 || { tail -20 gpurun_out/var_${v}_$c.log; exit 1; }
     python - gpurun_out/var_${v}_$c.log $v $c <<'PY'
 import json,sys

@@ -6,7 +6,7 @@ set -o pipefail
 mkdir -p gpurun_out
 for c in ${CONFIGS:-c4 c5}; do
   for st in ${STS:-0 1 2 4}; do
-    SHS_LIB_XCD_ST=$st timeout -k 10 200 python bench.py --config $c --no-pmc --no-cpu --steps 100 --warmup 10 \
+    SHS_LIB_XCD_ST=$st timeout -k 10 200 python bench.py --full --config $c --no-pmc --no-cpu --steps 100 --warmup 10 \
       > gpurun_out/xcd_${c}_$st.log 2>&1 || { tail -20 gpurun_out/xcd_${c}_$st.log; exit 1; }
     python - gpurun_out/xcd_${c}_$st.log $c $st <<'PY'
 import json,sys
