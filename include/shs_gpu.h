@@ -148,9 +148,19 @@ int shs_present_device(shs_ctx *ctx, int32_t frame_index, void **present_dev);
 int shs_resolve_prequant(shs_ctx *ctx, float *prequant);
 int shs_resolve_prequant_frame(shs_ctx *ctx, int32_t frame_index, float *prequant);
 /* Device pointers of the current batch's colour / depth planes (zero-copy hand-off to torch / RCCL);
- * finished and valid as for shs_present_device. */
+ * finished and valid as for shs_present_device.
+ * The pointers are writable and the library cannot see what is done through them, so the next legacy
+ * batch after shs_device_framebuffers or shs_present_device clears every idle tile again
+ * (SHS_OPT_LEGACY_STALE_CLEAR below): a render loop that takes the pointers every batch gets full
+ * clears every batch. */
 int shs_device_framebuffers(shs_ctx *ctx, void **color_dev, void **depth_dev);
 int shs_get_stats(shs_ctx *ctx, shs_raster_stats *stats);
+/* The 32x8 raster tiles the last legacy batch's clear strips wrote the clear values into (a batch
+ * total; finishes the batch first, as shs_get_stats).  Busy tiles, which the raster writes whole, are
+ * not counted.  Under SHS_OPT_LEGACY_STALE_CLEAR it is every idle owned tile of every frame for a batch
+ * that clears fully, and only the tiles an earlier batch left non-clear otherwise (0 for a batch that
+ * repeats the previous one). */
+int shs_legacy_cleared_tiles(shs_ctx *ctx, uint64_t *tiles);
 
 /* Per-kernel device timing of the last frame, recorded with HIP events on the context stream
  * (k_setup, k_ghost, unused, k_raster) in milliseconds.  Enabled by shs_enable_timing(ctx, 1). */
@@ -242,6 +252,17 @@ int shs_debug_records(shs_ctx *ctx, void *out, int64_t capacity, int64_t *n_out)
  * what changes is that a batch's frames are final only after such a call -- work the caller queues on
  * the context stream right after shs_render_legacy_batch does not see them.  0 (default): off. */
 #define SHS_OPT_LEGACY_PIPELINE 12
+/* SHS_OPT_LEGACY_STALE_CLEAR: 1 (default) = a legacy batch clears only the raster tiles that an earlier
+ * batch of this context left non-clear and that it does not itself draw into.  The context keeps one
+ * flag per (frame of the batch, 32x8 raster tile); frame f of every batch lands at the same addresses,
+ * so outside the busy tiles the planes already hold the clear values of the previous batch.  A batch
+ * clears every idle tile as before whenever the library cannot vouch for the planes: the first batch,
+ * another width / height / frame count / clear colour / PRESENT or PREQUANT flag / shard than the
+ * previous batch, reallocated planes, after shs_device_framebuffers, shs_present_device or a
+ * shs_tiles_unpack* into SHS_TARGET_LEGACY / SHS_TARGET_PRESENT, after a failed render call, and always
+ * under SHS_OPT_LEGACY_PIPELINE.  0 = every batch clears every idle tile.  Images are identical either
+ * way. */
+#define SHS_OPT_LEGACY_STALE_CLEAR 13
 int shs_set_option(shs_ctx *ctx, int option, int64_t value);
 /* The regions of the last region-sharded camera pass: rects[4 r .. 4 r + 3] = (bx0, by0, bx1, by1) of
  * rank r, bin tiles, inclusive (bx1 < bx0: rank r owns nothing). */

@@ -97,7 +97,7 @@ int shs_destroy(shs_ctx *ctx) {
         if (w.h_ov) (void)hipHostFree(const_cast<uint32_t *>(w.h_ov));
     }
     release(ctx->counters); release(ctx->timeline);
-    release(ctx->color); release(ctx->depth); release(ctx->prequant); release(ctx->present);
+    release(ctx->color); release(ctx->depth); release(ctx->prequant); release(ctx->present); release(ctx->stale);
     for (int i = 0; i < 5; ++i)
         if (ctx->tev[i]) (void)hipEventDestroy(ctx->tev[i]);
     for (int k = 0; k < shs_ctx::RING; ++k)
@@ -277,6 +277,9 @@ static int enqueue_frame(shs_ctx *ctx) {
     const int rtiles_y = (f.height + shs_dev::RTH - 1) / shs_dev::RTH;
     const int n_rt = tiles_x * rtiles_y;
     const size_t npx = (size_t)f.width * f.height;
+    // whatever this enqueue leaves behind if it fails, the planes are vouched for again only at its end
+    const bool planes_were_known = ctx->planes_known;
+    ctx->planes_known = false;
 
     int64_t total = 0;
     for (int i = 0; i < n_draws; ++i) total += ctx->meshes[ctx->last_draws[i].mesh_id].n_tris;
@@ -330,6 +333,27 @@ static int enqueue_frame(shs_ctx *ctx) {
     if (want_pq && ensure(ctx, ctx->prequant, npx * n_frames)) return SHS_ERR_HIP;
     const bool want_present = (f.flags & SHS_FRAME_PRESENT) != 0;
     if (want_present && ensure(ctx, ctx->present, npx * n_frames)) return SHS_ERR_HIP;
+    if (ensure(ctx, ctx->stale, (size_t)n_rt * n_frames)) return SHS_ERR_HIP;
+    // Stale-tile clears: the strips clear every idle tile (RF_FULL_CLEAR) unless the planes are known to
+    // hold what this context's last batch left under the same description -- size, frames, clear colour,
+    // plane set, shard and the very same allocations (a reallocation changes pointer or capacity).
+    // Pipelined batches and the experiments build's debug bits always clear fully, and so does the
+    // batch after them.
+    shs_ctx::PlanesKey pkey;
+    std::memset(&pkey, 0, sizeof pkey);
+    pkey.w = f.width; pkey.h = f.height; pkey.n_frames = n_frames;
+    pkey.shard_rank = f.shard_rank; pkey.shard_count = f.shard_count;
+    pkey.clear_rgba = (uint32_t)f.clear_color[0] | ((uint32_t)f.clear_color[1] << 8) | ((uint32_t)f.clear_color[2] << 16) |
+                      ((uint32_t)f.clear_color[3] << 24);
+    pkey.plane_flags = f.flags & (SHS_FRAME_PREQUANT | SHS_FRAME_PRESENT);
+    pkey.buf[0] = ctx->color.p; pkey.cap[0] = ctx->color.cap;
+    pkey.buf[1] = ctx->depth.p; pkey.cap[1] = ctx->depth.cap;
+    pkey.buf[2] = ctx->prequant.p; pkey.cap[2] = ctx->prequant.cap;
+    pkey.buf[3] = ctx->present.p; pkey.cap[3] = ctx->present.cap;
+    pkey.buf[4] = ctx->stale.p; pkey.cap[4] = ctx->stale.cap;
+    const bool dbg_bits = SHS_EXPERIMENTS && (f.flags & shs_dev::DBG_MASK) != 0u;
+    const bool full_clear = !ctx->stale_clear || !planes_were_known || pipe || dbg_bits ||
+                            std::memcmp(&pkey, &ctx->planes_key, sizeof pkey) != 0;
 
     // ---- setup_stream: wait for the slot's last k_raster, reset, upload, set up ----
     if (ws.used) HIP_TRY(ctx, hipStreamWaitEvent(sst, ws.raster_done, 0));
@@ -398,7 +422,8 @@ static int enqueue_frame(shs_ctx *ctx) {
     fp.n_tris = n_tris; fp.n_draws = n_draws;
     fp.clear_rgba = (uint32_t)f.clear_color[0] | ((uint32_t)f.clear_color[1] << 8) | ((uint32_t)f.clear_color[2] << 16) |
                     ((uint32_t)f.clear_color[3] << 24);
-    fp.flags = (f.flags & (SHS_EXPERIMENTS ? ~0u : ~shs_dev::DBG_MASK) & ~(shs_dev::RF_PER_PIXEL | shs_dev::RF_NO_RECS | shs_dev::RF_SHARED_VARY | shs_dev::RF_GHOST_INLINE | shs_dev::RF_XCD_ROWS)) | (ctx->pair_loop ? 0u : shs_dev::RF_PER_PIXEL);
+    fp.flags = (f.flags & (SHS_EXPERIMENTS ? ~0u : ~shs_dev::DBG_MASK) & ~(shs_dev::RF_PER_PIXEL | shs_dev::RF_NO_RECS | shs_dev::RF_SHARED_VARY | shs_dev::RF_GHOST_INLINE | shs_dev::RF_XCD_ROWS | shs_dev::RF_FULL_CLEAR)) | (ctx->pair_loop ? 0u : shs_dev::RF_PER_PIXEL) |
+               (full_clear ? shs_dev::RF_FULL_CLEAR : 0u);
     fp.bin_cap = ctx->bin_cap;
     fp.spill_cap = (uint32_t)std::min<size_t>(ws.spill.cap, 0xffffffffu);
     fp.frag_cap = (uint32_t)std::min<size_t>(ws.frags.cap, 0xffffffffu);
@@ -495,6 +520,7 @@ static int enqueue_frame(shs_ctx *ctx) {
     fb.busy_list = ws.busy_list.p;
     fb.blk_stat = ws.blk_stat.p;
     fb.rstat = ws.rstat.p;
+    fb.stale = ctx->stale.p;
     fb.timeline = ctx->want_timeline ? ctx->timeline.p : nullptr;
     fb.boxes = ws.boxes.p;
     fb.tdraw = no_recs ? ws.tdraw.p : nullptr;
@@ -555,6 +581,8 @@ static int enqueue_frame(shs_ctx *ctx) {
     ctx->last_setup_grid = fp.setup_grid;
     ctx->last_ghost_blocks = fp.ghost_blocks;
     ctx->last_clear_blocks = fp.clear_blocks;
+    ctx->planes_key = pkey;
+    ctx->planes_known = !(pipe || dbg_bits);
     return SHS_OK;
 }
 
@@ -580,14 +608,16 @@ static int finish_frame(shs_ctx *ctx) {
         if (ctx->last_setup_blocks)
             HIP_TRY(ctx, hipMemcpy(ctx->h_blk_stat.data(), ctx->lslot[ctx->last_slot].blk_stat.p, ctx->last_setup_blocks * sizeof(uint4),
                                    hipMemcpyDeviceToHost));
-        HIP_TRY(ctx, hipMemcpy(ctx->h_rstat.data(), ctx->lslot[ctx->last_slot].rstat.p, ctx->last_raster_grid * sizeof(uint2),
+        HIP_TRY(ctx, hipMemcpy(ctx->h_rstat.data(), ctx->lslot[ctx->last_slot].rstat.p, ctx->last_raster_grid * sizeof(uint4),
                                hipMemcpyDeviceToHost));
         ctx->last_covered = ctx->last_bins = ctx->last_maxbin = ctx->last_setup = ctx->last_ghost = ctx->last_unb = 0;
+        ctx->last_cleared = 0;
         for (const uint4 &b : ctx->h_blk_stat) {
             ctx->last_setup += b.x; ctx->last_ghost += b.y; ctx->last_unb += b.z; ctx->last_bins += b.w;
         }
-        for (const uint2 &r : ctx->h_rstat) {
+        for (const uint4 &r : ctx->h_rstat) {
             ctx->last_covered += r.x;
+            ctx->last_cleared += r.z;
             ctx->last_maxbin = std::max<uint64_t>(ctx->last_maxbin, r.y);
         }
         // adapt the per-tile bin capacity to the fullest tile (spilled entries stay exact)
@@ -726,6 +756,7 @@ int shs_present_device(shs_ctx *ctx, int32_t frame_index, void **present_dev) {
     int rc = finish_frame(ctx);
     if (rc) return rc;
     *present_dev = ctx->present.p + (size_t)ctx->frame.width * ctx->frame.height * frame_index;
+    ctx->planes_known = false;   // a writable pointer leaves the library: the next batch clears fully
     return SHS_OK;
 }
 
@@ -750,6 +781,16 @@ int shs_device_framebuffers(shs_ctx *ctx, void **color_dev, void **depth_dev) {
     if (rc) return rc;
     if (color_dev) *color_dev = ctx->color.p;
     if (depth_dev) *depth_dev = ctx->depth.p;
+    ctx->planes_known = false;   // writable pointers leave the library: the next batch clears fully
+    return SHS_OK;
+}
+
+int shs_legacy_cleared_tiles(shs_ctx *ctx, uint64_t *tiles) {
+    if (!ctx || !tiles || !ctx->have_frame) return SHS_ERR_INVALID;
+    if (set_dev(ctx)) return SHS_ERR_HIP;
+    int rc = finish_frame(ctx);
+    if (rc) return rc;
+    *tiles = ctx->last_cleared;
     return SHS_OK;
 }
 
@@ -881,6 +922,11 @@ int shs_set_option(shs_ctx *ctx, int option, int64_t value) {
             if (flush_pending(ctx)) return SHS_ERR_HIP;
         }
         ctx->legacy_pipeline = value != 0;
+        return SHS_OK;
+    }
+    if (option == SHS_OPT_LEGACY_STALE_CLEAR) {
+        if (value < 0 || value > 1) return SHS_ERR_INVALID;
+        ctx->stale_clear = value != 0;
         return SHS_OK;
     }
     if (option == SHS_OPT_SHADOW_FOOTPRINT) {

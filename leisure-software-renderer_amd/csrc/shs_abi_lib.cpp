@@ -1561,6 +1561,8 @@ int shs_tiles_unpack(shs_ctx *ctx, int target, int32_t rank, int32_t count, cons
     if (set_dev(ctx)) return SHS_ERR_HIP;
     const int rc = final_before_copy(ctx, target);
     if (rc) return rc;
+    // tiles land in the legacy planes from outside the rasters: the next legacy batch clears fully
+    if (target == SHS_TARGET_LEGACY || target == SHS_TARGET_PRESENT) ctx->planes_known = false;
     HIP_TRY(ctx, shs_internal::launch_tiles_copy(p, false, const_cast<void *>(src_dev), ctx->stream));
     return SHS_OK;
 }
@@ -1572,6 +1574,7 @@ int shs_tiles_unpack_ranks(shs_ctx *ctx, int target, int32_t count, const void *
         const int rc = final_before_copy(ctx, target);
         if (rc) return rc;
     }
+    if (target == SHS_TARGET_LEGACY || target == SHS_TARGET_PRESENT) ctx->planes_known = false;   // as shs_tiles_unpack
     shs_dev::TileUnpackMulti m;
     std::memset(&m, 0, sizeof m);
     for (int32_t r = 0; r < count; ++r) {

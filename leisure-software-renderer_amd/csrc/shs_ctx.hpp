@@ -89,7 +89,7 @@ struct shs_ctx {
         DevBuf<uint32_t> busy;               // per raster tile: the epoch of the last batch that marked it
         DevBuf<uint32_t> busy_list;          // busy tiles of the batch (k_raster's work items)
         DevBuf<uint4> blk_stat;              // per setup block
-        DevBuf<uint2> rstat;                 // per raster block
+        DevBuf<uint4> rstat;                 // per raster block
         hipEvent_t setup_done = nullptr, raster_done = nullptr;
         // the batch's overflow word in mapped, coherent host memory: the setup kernels store 1 into it
         // with every overflow bit, so once setup_done has fired the host reads it without a copy and
@@ -108,7 +108,7 @@ struct shs_ctx {
     bool timeline_shadow = false;    // SHS_OPT_TIMELINE 2: the library's shadow raster records it instead
     int last_setup_grid = 0, last_ghost_blocks = 0, last_clear_blocks = 0;
     std::vector<uint4> h_blk_stat;
-    std::vector<uint2> h_rstat;
+    std::vector<uint4> h_rstat;
     uint64_t geom_key[2] = {~0ull, ~0ull};   // (tiles, shard, frames) per slot: a change resets its busy flags
     int last_setup_blocks = 0, last_raster_grid = 0;
     uint64_t last_covered = 0, last_bins = 0, last_maxbin = 0, last_setup = 0, last_ghost = 0, last_unb = 0;
@@ -121,6 +121,22 @@ struct shs_ctx {
     DevBuf<float> depth;
     DevBuf<float4> prequant;
     DevBuf<uint32_t> present;        // SHS_FRAME_PRESENT staging (per frame of the batch)
+    // Stale-tile clears (SHS_OPT_LEGACY_STALE_CLEAR).  stale: per frame of the batch
+    // and raster tile, 0 = the tile's owned pixels hold the clear values in every enabled plane; written
+    // by the rasters alone, which the context stream orders.  planes_key describes what the last
+    // completed enqueue left in the planes; a batch whose key differs, or that follows anything that
+    // may have written the planes (planes_known false), clears fully (RF_FULL_CLEAR).
+    struct PlanesKey {
+        int32_t w, h, n_frames, shard_rank, shard_count;
+        uint32_t clear_rgba, plane_flags, pad;   // (no padding bytes: compared with memcmp)
+        const void *buf[5];
+        size_t cap[5];
+    };
+    DevBuf<uint32_t> stale;
+    PlanesKey planes_key{};
+    bool planes_known = false;
+    bool stale_clear = true;         // SHS_OPT_LEGACY_STALE_CLEAR
+    uint64_t last_cleared = 0;       // tiles the last batch's clear strips cleared
 
     uint32_t *h_counters = nullptr;  // pinned, C_NCOUNTERS
 

@@ -152,6 +152,11 @@ constexpr uint32_t RF_GHOST_INLINE = 1u << 19;
 // and records to the three rows after the first.
 constexpr uint32_t RF_XCD_ROWS = 1u << 20;
 constexpr uint32_t BUSY_SKIP = 0xffffffffu;   // a padding entry of the busy list: no tile
+// Clear strips clear every owned tile that is not busy (frame flags bit 21, set by the host whenever
+// it cannot vouch for what the planes hold: first batch, another size / clear colour / plane set /
+// shard, reallocated planes, pointers handed out, SHS_OPT_LEGACY_STALE_CLEAR 0).  Without it a strip
+// clears only the tiles FrameBuffers::stale marks as left non-clear by an earlier batch.
+constexpr uint32_t RF_FULL_CLEAR = 1u << 21;
 
 // Uniforms of up to KARG_DRAWS draws travel in the kernel arguments (no per-frame copy);
 // larger scenes read the device draw table.
@@ -221,8 +226,11 @@ struct FrameBuffers {
                                      // candidates / fragments in this launch (no reset needed)
     uint32_t *busy_list;             // C_BUSY entries f * n_raster_tiles + raster tile, each busy tile of
                                      // the batch once (capacity n_frames * n_raster_tiles)
+    uint32_t *stale;                 // per frame, per raster tile, owned by the context (not the slot):
+                                     // 0 = every owned pixel of the tile holds the clear value in every
+                                     // enabled plane (k_raster / k_pipe alone read and write it)
     uint4 *blk_stat;                 // per setup block: (set up, ghost, unbounded, bin entries)
-    uint2 *rstat;                    // per raster block: (covered pixels, fullest bin seen)
+    uint4 *rstat;                    // per raster block: (covered pixels, fullest bin seen, tiles cleared, 0)
     uint64_t *timeline;              // optional: TL_STRIDE slots per workgroup, k_setup then k_raster:
                                      // start, end, then phase marks of thread 0 (first busy tile)
     uint8_t *color;                  // per frame: W*H*4, canvas rows
@@ -254,6 +262,7 @@ __device__ __forceinline__ FrameBuffers frame_view(const FrameParams &fp, const 
     v.tile_count += f * n_bt;
     v.bins += f * n_bt * fp.bin_cap;
     v.busy += f * n_rt;
+    v.stale += f * n_rt;
     v.color += f * npx * 4;
     v.depth += f * npx;
     if (v.prequant) v.prequant += f * npx;

@@ -1182,8 +1182,9 @@ struct RasterShared {
     uint32_t id[RCHUNK];
     uint32_t cand[CAND];
     float4 du[LDS_DRAWS * 4];         // per-draw {light, cam, ocol, colf} (4 KB)
-    uint8_t skip[512];                // clear strip: per raster tile across, 1 = not cleared (busy / not owned)
+    unsigned long long smask[4];      // stale clear: per wave, the tiles of a 256-tile chunk that need the clear
     uint32_t nc, item, cov, maxbin, npairs;
+    uint32_t nclr;                    // tiles this workgroup's strips cleared (rstat)
     uint16_t wown[PAIR_WORDS];        // segment (boxes: staged candidate) owning each bitmap word's first pair
 };
 
@@ -1701,6 +1702,8 @@ __device__ __forceinline__ void raster_tile(const FrameParams &fp, const FrameBu
         // copy_to_SDLSurface: surface row h-1-y takes canvas row y, i.e. the screen row
         if (fb.present) LEGACY_STORE(rgba, &fb.present[(size_t)py * fp.W + px]);
     }
+    // the tile no longer holds the clear values: a later batch that leaves it idle clears it
+    if (tid == 0) fb.stale[rt] = 1u;
     tl_mark(tl, tls, 5);
 }
 
@@ -1718,9 +1721,10 @@ __device__ __forceinline__ void clear_tile(const FrameParams &fp, const FrameBuf
     }
 }
 
-// One clear strip: raster-tile row ry of frame f, full width -- every pixel of the row's tiles that
-// are owned and not busy gets the clear colour (canvas rows) and FLT_MAX (screen rows), as 16-B
-// stores (4 pixels per lane) along whole rows when W % 4 == 0.
+// One clear strip under RF_FULL_CLEAR: raster-tile row ry of frame f, full width -- every pixel of the
+// row's tiles that are owned and not busy gets the clear colour (canvas rows) and FLT_MAX (screen rows),
+// as 16-B stores (4 pixels per lane) along whole rows when W % 4 == 0.  (The tiles' stale entries:
+// clear_item.)
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -1764,6 +1768,67 @@ __device__ __forceinline__ void clear_strip(const FrameParams &fp, const FrameBu
     }
 }
 
+// Raster-tile rows [ry0, ry1) of frame f without RF_FULL_CLEAR: the planes hold what the context's
+// earlier batches left (the host vouches for it), so only the owned tiles that are marked stale and are
+// not busy in this batch are cleared, and marked clean.  A read phase, then a store phase: every
+// thread reads the flags of one tile of a 256-tile chunk, the waves' ballots go through LDS, and the
+// whole workgroup clears each tile found (clear_tile: any width) before thread 0 rewrites its entry --
+// no entry is written while another lane may still read it.  A chunk with nothing stale costs two
+// loads and two barriers.  (A busy tile's entry may be rewritten by its own workgroup meanwhile; the
+// busy flag already excludes it here.)  Returns the tiles cleared (thread 0's count).
+__device__ __forceinline__ uint32_t clear_stale_rows(const FrameParams &fp, const FrameBuffers &fb, int f, int ry0, int ry1,
+                                                     RasterShared &sh) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const FrameBuffers fv = frame_view(fp, fb, f);
+    const int rt1 = ry1 * fp.tiles_x;
+    uint32_t n = 0;
+    for (int base = ry0 * fp.tiles_x; base < rt1; base += 256) {
+        const int rt = base + tid;
+        bool need = false;
+        if (rt < rt1) {
+            need = fv.stale[rt] != 0u && fv.busy[rt] != fp.epoch;
+            if (need && fp.count > 1) {
+                const int ry = rt / fp.tiles_x;
+                need = owned_bin_tile(fp, rt - ry * fp.tiles_x, ry / (TILE / RTH));
+            }
+        }
+        const unsigned long long m = __ballot(need);
+        __syncthreads();   // the previous chunk's masks are read
+        if (lane == 0) sh.smask[wave] = m;
+        __syncthreads();
+        for (int w = 0; w < 4; ++w) {
+            unsigned long long mm = sh.smask[w];
+            while (mm) {
+                const int t = base + 64 * w + __ffsll((long long)mm) - 1;
+                mm &= mm - 1;
+                clear_tile(fp, fv, t);
+                if (tid == 0) { fv.stale[t] = 0u; ++n; }
+            }
+        }
+    }
+    return n;
+}
+
+// One clear item: raster-tile rows [sy * STRIP_RT, (sy + 1) * STRIP_RT) of frame f, in either mode.
+__device__ __forceinline__ uint32_t clear_item(const FrameParams &fp, const FrameBuffers &fb, int f, int sy, int strip_rt,
+                                               RasterShared &sh) {
+    const int ry0 = sy * strip_rt, ry1 = min((sy + 1) * strip_rt, fp.rtiles_y);
+    if (!(fp.flags & RF_FULL_CLEAR)) return clear_stale_rows(fp, fb, f, ry0, ry1, sh);
+    // RF_FULL_CLEAR: the strips clear every owned idle tile; their stale entries are set to 0 here, a
+    // tile per thread (whole lines per wave; nobody reads an entry in this mode), which also initialises
+    // the map.  The strip code itself is as it was before the map existed.
+    const FrameBuffers fv = frame_view(fp, fb, f);
+    uint32_t n = 0;
+    for (int rt = ry0 * fp.tiles_x + (int)threadIdx.x; rt < ry1 * fp.tiles_x; rt += 256) {
+        const int ry = rt / fp.tiles_x;
+        if (fv.busy[rt] == fp.epoch || (fp.count > 1 && !owned_bin_tile(fp, rt - ry * fp.tiles_x, ry / (TILE / RTH)))) continue;
+        fv.stale[rt] = 0u;
+        ++n;
+    }
+    for (int ry = ry0; ry < ry1; ++ry) clear_strip(fp, fb, f, ry);
+    return n;
+}
+
 // Raster-tile rows per clear item.  Eight (a 64-row strip of one frame) against two: C2 0.275 ->
 // 0.272 ms per step in five A/B pairs, C3 unchanged.  The k_raster event grows (C2 0.242 -> 0.248 ms),
 // but fewer, longer strip items let the next batch's setup take CUs sooner; 16 rows was slower
@@ -1778,8 +1843,9 @@ constexpr int STRIP_RT = SHS_STRIP_RT;
 // streaming stores), interleaved in proportion so that every CU mixes both kinds at all times.
 // Workgroup b's first item is b (no atomic: a single frame needs none); the rest come from N_WORKQ
 // ticket queues -- queue q deals items G + q + N_WORKQ * j to the workgroups b = q (mod N_WORKQ) --
-// fetched one item ahead.  Every owned pixel of every frame is written exactly once: by its busy
-// tile or by its strip.
+// fetched one item ahead.  A busy tile is written whole and marked stale; a clear item clears every
+// owned idle tile (RF_FULL_CLEAR) or only those an earlier batch left stale, and marks them clean: after
+// the batch stale[f][rt] == 0 means the tile's owned pixels hold the clear values in every enabled plane.
 #ifndef SHS_LEGACY_RASTER_WAVES
 #define SHS_LEGACY_RASTER_WAVES 4   // minimum waves per SIMD (-D...: timing experiments)
 #endif
@@ -1792,7 +1858,7 @@ __global__ __launch_bounds__(256, SHS_LEGACY_RASTER_WAVES) void k_raster(FramePa
     const int n_rt = fp.tiles_x * fp.rtiles_y;            // raster tiles per frame
     const uint64_t t_start = fb.timeline ? __builtin_amdgcn_s_memrealtime() : 0ull;
     const uint64_t c_start = fb.timeline ? __builtin_amdgcn_s_memtime() : 0ull;
-    if (tid == 0) { sh.cov = 0; sh.maxbin = 0; }
+    if (tid == 0) { sh.cov = 0; sh.maxbin = 0; sh.nclr = 0; }
     sh.key[tid] = KEY_EMPTY;
     // Every independent first-touch load is issued up front so their round trips overlap: the
     // busy-list length, the ghost-fragment count and the draws' shading uniforms.  (A single-frame
@@ -1815,6 +1881,7 @@ __global__ __launch_bounds__(256, SHS_LEGACY_RASTER_WAVES) void k_raster(FramePa
     uint32_t *queue = &cnt[C_WORK + WORKQ_STRIDE * q];
     const bool queued = (uint64_t)G + q < n_items;        // this queue deals any item at all
     uint32_t item = blockIdx.x, ticket = 0u;
+    uint32_t nclr = 0;   // tiles this thread's clear items marked clean
     bool first = true;
     while ((uint64_t)item < n_items) {
         if (tid == 0 && queued) ticket = atomicAdd(queue, 1u);   // the next item, in flight meanwhile
@@ -1825,7 +1892,7 @@ __global__ __launch_bounds__(256, SHS_LEGACY_RASTER_WAVES) void k_raster(FramePa
             const int f = (int)(s_lo / (uint32_t)strips_y);
             const int sy = (int)s_lo - f * strips_y;
             if (!SHS_DBG(fp, DBG_SKIP_CLEAR))   // (timing experiments: the busy tiles alone)
-                for (int ry = sy * STRIP_RT; ry < min((sy + 1) * STRIP_RT, fp.rtiles_y); ++ry) clear_strip(fp, fb, f, ry);
+                nclr += clear_item(fp, fb, f, sy, STRIP_RT, sh);
         } else {
             uint32_t k = item - s_lo;
             if ((fp.flags & RF_XCD_ROWS) && k < (n_busy & ~31u))   // busy item 32B + 8r + x <- entry 32B + 4x + r:
@@ -1852,8 +1919,10 @@ __global__ __launch_bounds__(256, SHS_LEGACY_RASTER_WAVES) void k_raster(FramePa
         item = sh.item;
     }
     __syncthreads();
+    if (nclr) atomicAdd(&sh.nclr, nclr);
+    __syncthreads();
     if (tid == 0) {
-        fb.rstat[blockIdx.x] = make_uint2(sh.cov, sh.maxbin);
+        fb.rstat[blockIdx.x] = make_uint4(sh.cov, sh.maxbin, sh.nclr, 0u);
         if (fb.timeline) {
             fb.timeline[TL_STRIDE * (fp.setup_grid + blockIdx.x)] = t_start;
             fb.timeline[TL_STRIDE * (fp.setup_grid + blockIdx.x) + 1] = __builtin_amdgcn_s_memrealtime();
@@ -1883,7 +1952,7 @@ __global__ __launch_bounds__(256, SHS_LEGACY_RASTER_WAVES) void k_pipe(FramePara
     uint32_t *cnt = fb.counters + fp.parity * CSET;
     const DrawGPU *draws = fb.draws;
     const int n_rt = fp.tiles_x * fp.rtiles_y;            // raster tiles per frame
-    if (tid == 0) { sh.cov = 0; sh.maxbin = 0; }
+    if (tid == 0) { sh.cov = 0; sh.maxbin = 0; sh.nclr = 0; }
     sh.key[tid] = KEY_EMPTY;
     const uint32_t n_busy = min(cnt[C_BUSY], (uint32_t)(n_rt * fp.n_frames));
     const uint32_t n_frag = min(cnt[C_FRAG], fp.frag_cap);
@@ -1900,6 +1969,7 @@ __global__ __launch_bounds__(256, SHS_LEGACY_RASTER_WAVES) void k_pipe(FramePara
     uint32_t *queue = &cnt[C_WORK + WORKQ_STRIDE * q];
     const bool queued = (uint64_t)G + q < n_items;
     uint32_t item = blockIdx.x, ticket = 0u;
+    uint32_t nclr = 0;   // tiles this thread's clear items marked clean
     while ((uint64_t)item < n_items) {
         if (tid == 0 && queued) ticket = atomicAdd(queue, 1u);   // the next item, in flight meanwhile
         const uint32_t k_lo = (uint32_t)(((uint64_t)item * n_setup) / n_items);
@@ -1913,7 +1983,7 @@ __global__ __launch_bounds__(256, SHS_LEGACY_RASTER_WAVES) void k_pipe(FramePara
             if (s_hi > s_lo) {
                 const int f = (int)(s_lo / (uint32_t)strips_y);
                 const int sy = (int)s_lo - f * strips_y;
-                for (int ry = sy * STRIP_RT; ry < min((sy + 1) * STRIP_RT, fp.rtiles_y); ++ry) clear_strip(fp, fb, f, ry);
+                nclr += clear_item(fp, fb, f, sy, STRIP_RT, sh);
             } else {
                 const uint32_t g = fb.busy_list[j - s_lo];
                 const int f = (int)(g / (uint32_t)n_rt), rt = (int)g - f * n_rt;
@@ -1928,7 +1998,9 @@ __global__ __launch_bounds__(256, SHS_LEGACY_RASTER_WAVES) void k_pipe(FramePara
         item = sh.item;
     }
     __syncthreads();
-    if (tid == 0) fb.rstat[blockIdx.x] = make_uint2(sh.cov, sh.maxbin);
+    if (nclr) atomicAdd(&sh.nclr, nclr);
+    __syncthreads();
+    if (tid == 0) fb.rstat[blockIdx.x] = make_uint4(sh.cov, sh.maxbin, sh.nclr, 0u);
 }
 
 }  // namespace shs_dev

@@ -597,6 +597,17 @@ class Context:
         (or at the next call that reads frames); results identical, frames final only after such a call."""
         self._check(self._lib.shs_set_option(self._h, _abi.OPT_LEGACY_PIPELINE, 1 if on else 0))
 
+    def set_stale_clear(self, on: bool):
+        """SHS_OPT_LEGACY_STALE_CLEAR: legacy batches clear only the tiles an earlier batch left non-clear
+        (default on); off: every batch clears every idle tile.  Images identical either way."""
+        self._check(self._lib.shs_set_option(self._h, _abi.OPT_LEGACY_STALE_CLEAR, 1 if on else 0))
+
+    def cleared_tiles(self) -> int:
+        """shs_legacy_cleared_tiles: the 32x8 raster tiles the last legacy batch's clear strips cleared."""
+        n = ctypes.c_uint64(0)
+        self._check(self._lib.shs_legacy_cleared_tiles(self._h, ctypes.byref(n)))
+        return int(n.value)
+
     def set_shadow_footprint(self, on: bool):
         """SHS_OPT_SHADOW_FOOTPRINT: shadow passes are recorded and rendered by the next camera pass over
         only the shadow-map tiles its pixels' PCF can read (default off: the whole map when called)."""

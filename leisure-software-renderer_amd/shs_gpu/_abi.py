@@ -38,6 +38,7 @@ SHARD_REGIONS = 1
 OPT_SHARD_ROOT_SHARE = 10
 OPT_SHADOW_FOOTPRINT = 11
 OPT_LEGACY_PIPELINE = 12
+OPT_LEGACY_STALE_CLEAR = 13
 
 
 class LegacyDraw(ctypes.Structure):
@@ -239,6 +240,7 @@ SIGNATURES = [
     ("shs_texture_release", ctypes.c_int, [_P, ctypes.c_int32]),
     ("shs_device_framebuffers", ctypes.c_int, [_P, ctypes.POINTER(_P), ctypes.POINTER(_P)]),
     ("shs_get_stats", ctypes.c_int, [_P, ctypes.POINTER(RasterStats)]),
+    ("shs_legacy_cleared_tiles", ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint64)]),
     ("shs_enable_timing", ctypes.c_int, [_P, ctypes.c_int]),
     ("shs_last_kernel_ms", ctypes.c_int, [_P, _F]),
     ("shs_timing_reset", ctypes.c_int, [_P]),
