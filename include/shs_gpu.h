@@ -263,6 +263,13 @@ int shs_debug_records(shs_ctx *ctx, void *out, int64_t capacity, int64_t *n_out)
  * under SHS_OPT_LEGACY_PIPELINE.  0 = every batch clears every idle tile.  Images are identical either
  * way. */
 #define SHS_OPT_LEGACY_STALE_CLEAR 13
+/* SHS_OPT_LEGACY_TILE_GROUPS: 1 (default) = a scan-mode legacy batch (scenes up to 4096 triangles) on
+ * the pair-task raster deals its busy raster tiles to the persistent raster as 2x2 groups (64x16 px)
+ * instead of one by one: the group's workgroup scans the frame's bin boxes and stages the candidates'
+ * records once, then rasters each busy tile of the group.  Ignored (tile lists as before) for single
+ * frames (fewer busy tiles than raster workgroups: latency, not throughput), for bin-mode batches, under SHS_OPT_LEGACY_PIPELINE for the batches it pipelines, and with SHS_OPT_RASTER_LOOP 0.
+ * 0 = every busy tile is its own work item.  Images and statistics are identical either way. */
+#define SHS_OPT_LEGACY_TILE_GROUPS 14
 int shs_set_option(shs_ctx *ctx, int option, int64_t value);
 /* The regions of the last region-sharded camera pass: rects[4 r .. 4 r + 3] = (bx0, by0, bx1, by1) of
  * rank r, bin tiles, inclusive (bx1 < bx0: rank r owns nothing). */
@@ -278,7 +285,7 @@ int shs_shard_balance_rects(const uint32_t *blocks, int32_t n_blocks, int32_t wi
  * phase marks of the workgroup's thread 0 (0 where a phase did not run). */
 int shs_debug_timeline(shs_ctx *ctx, uint64_t *out, int64_t capacity, int64_t *n_out);
 /* Debug / profiling hook: the last camera pass's (SHS_OPT_TIMELINE 2: shadow pass's) k_lib_raster workgroup timeline,
- * 16 uint64 per workgroup: start, end, summed ticks of gather / stage + pairs / resolve + shade over
+ * 24 uint64 per workgroup: start, end, summed ticks of gather / stage + pairs / resolve + shade over
  * its busy tiles, clear ticks, busy tiles, cleared tiles, staging passes, pairs, candidates, longest
  * busy tile, and (deep camera raster) the staging passes' selection + record + span ticks and segment
  * ticks, all busy tiles' ticks, the last busy tile's end (s_memrealtime, 100 MHz).  out = NULL: *n_out = the count only. */

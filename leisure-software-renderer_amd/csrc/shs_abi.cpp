@@ -89,7 +89,7 @@ int shs_destroy(shs_ctx *ctx) {
     shs_lib_release(ctx);
     for (auto &w : ctx->lslot) {
         release(w.draws); release(w.recs); release(w.rext); release(w.shade); release(w.tile_count); release(w.bins);
-        release(w.spill); release(w.frags); release(w.busy); release(w.boxes); release(w.slivers); release(w.busy_list);
+        release(w.spill); release(w.frags); release(w.busy); release(w.gbusy); release(w.boxes); release(w.slivers); release(w.busy_list);
         release(w.blk_stat); release(w.rstat);
         if (w.h_draws) (void)hipHostFree(w.h_draws);
         if (w.setup_done) (void)hipEventDestroy(w.setup_done);
@@ -323,6 +323,12 @@ static int enqueue_frame(shs_ctx *ctx) {
         if (ensure(ctx, ws.busy, (size_t)n_rt * n_frames)) return SHS_ERR_HIP;
         reset = true;
     }
+    // (the tile groups' flags: reset with the tiles')
+    const size_t n_gr = (size_t)((tiles_x + shs_dev::GX - 1) / shs_dev::GX) * ((rtiles_y + shs_dev::GY - 1) / shs_dev::GY);
+    if (ws.gbusy.cap < n_gr * n_frames || !ws.gbusy.p) {
+        if (ensure(ctx, ws.gbusy, n_gr * n_frames)) return SHS_ERR_HIP;
+        reset = true;
+    }
     if (ensure(ctx, ws.bins, (size_t)n_tiles * ctx->bin_cap * n_frames)) return SHS_ERR_HIP;
     const int setup_blocks = (n_tris + 63) / 64;   // a quad of lanes per triangle, per frame
     if (ensure(ctx, ws.blk_stat, (size_t)std::max(setup_blocks, 1) * n_frames)) return SHS_ERR_HIP;
@@ -360,6 +366,7 @@ static int enqueue_frame(shs_ctx *ctx) {
     if (pipe && ws.used) HIP_TRY(ctx, hipStreamWaitEvent(sst, ws.setup_done, 0));   // (a non-pipelined setup)
     if (reset) {
         HIP_TRY(ctx, hipMemsetAsync(ws.busy.p, 0, ws.busy.cap * sizeof(uint32_t), sst));
+        HIP_TRY(ctx, hipMemsetAsync(ws.gbusy.p, 0, ws.gbusy.cap * sizeof(uint32_t), sst));
         ctx->geom_key[slot] = gkey;
     }
 
@@ -422,7 +429,7 @@ static int enqueue_frame(shs_ctx *ctx) {
     fp.n_tris = n_tris; fp.n_draws = n_draws;
     fp.clear_rgba = (uint32_t)f.clear_color[0] | ((uint32_t)f.clear_color[1] << 8) | ((uint32_t)f.clear_color[2] << 16) |
                     ((uint32_t)f.clear_color[3] << 24);
-    fp.flags = (f.flags & (SHS_EXPERIMENTS ? ~0u : ~shs_dev::DBG_MASK) & ~(shs_dev::RF_PER_PIXEL | shs_dev::RF_NO_RECS | shs_dev::RF_SHARED_VARY | shs_dev::RF_GHOST_INLINE | shs_dev::RF_XCD_ROWS | shs_dev::RF_FULL_CLEAR)) | (ctx->pair_loop ? 0u : shs_dev::RF_PER_PIXEL) |
+    fp.flags = (f.flags & (SHS_EXPERIMENTS ? ~0u : ~shs_dev::DBG_MASK) & ~(shs_dev::RF_PER_PIXEL | shs_dev::RF_NO_RECS | shs_dev::RF_SHARED_VARY | shs_dev::RF_GHOST_INLINE | shs_dev::RF_XCD_ROWS | shs_dev::RF_FULL_CLEAR | shs_dev::RF_TILE_GROUPS)) | (ctx->pair_loop ? 0u : shs_dev::RF_PER_PIXEL) |
                (full_clear ? shs_dev::RF_FULL_CLEAR : 0u);
     fp.bin_cap = ctx->bin_cap;
     fp.spill_cap = (uint32_t)std::min<size_t>(ws.spill.cap, 0xffffffffu);
@@ -471,6 +478,15 @@ static int enqueue_frame(shs_ctx *ctx) {
     // experiments).
     static const bool xcd_rows_env = [] { const char *e = shs_exp_env("SHS_LEGACY_XCD_ROWS"); return !e || std::atoi(e) != 0; }();
     if (!fp.scan_mode && xcd_rows_env) fp.flags |= shs_dev::RF_XCD_ROWS;
+    // Tile groups (RF_TILE_GROUPS, SHS_OPT_LEGACY_TILE_GROUPS): only where the launch is the scan-mode pair
+    // kernel -- not k_pipe (tile lists), not the per-pixel loop, not the experiments build's clear-only tiles.
+    // A single frame keeps a work item per tile: it has fewer busy tiles than the raster has workgroups, so
+    // a group would only run its tiles one after the other (C2 single frame: raster span 13 -> 31 us).
+#ifndef SHS_SCAN_SPANS   // (timing experiments: scan-mode frames on row spans keep tile lists)
+    if (ctx->tile_groups && fp.scan_mode && n_frames > 1 && !pipe && ctx->pair_loop &&
+        !(SHS_EXPERIMENTS && (f.flags & shs_dev::DBG_CLEAR_ONLY)))
+        fp.flags |= shs_dev::RF_TILE_GROUPS;
+#endif
     const int owned_bt = (n_tiles - f.shard_rank + f.shard_count - 1) / f.shard_count;
     const int n_groups = (n_tris + 15) / 16;
     fp.setup_blocks = setup_blocks;
@@ -517,6 +533,7 @@ static int enqueue_frame(shs_ctx *ctx) {
     fb.spill = ws.spill.p; fb.frags = ws.frags.p; fb.counters = ctx->counters.p;
     fb.slivers = ws.slivers.p;
     fb.busy = ws.busy.p;
+    fb.gbusy = ws.gbusy.p;
     fb.busy_list = ws.busy_list.p;
     fb.blk_stat = ws.blk_stat.p;
     fb.rstat = ws.rstat.p;
@@ -927,6 +944,11 @@ int shs_set_option(shs_ctx *ctx, int option, int64_t value) {
     if (option == SHS_OPT_LEGACY_STALE_CLEAR) {
         if (value < 0 || value > 1) return SHS_ERR_INVALID;
         ctx->stale_clear = value != 0;
+        return SHS_OK;
+    }
+    if (option == SHS_OPT_LEGACY_TILE_GROUPS) {
+        if (value < 0 || value > 1) return SHS_ERR_INVALID;
+        ctx->tile_groups = value != 0;
         return SHS_OK;
     }
     if (option == SHS_OPT_SHADOW_FOOTPRINT) {

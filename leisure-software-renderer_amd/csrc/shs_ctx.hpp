@@ -87,7 +87,8 @@ struct shs_ctx {
         DevBuf<uint2> boxes;                 // per-triangle bin boxes
         DevBuf<int32_t> tdraw;               // per-triangle draw (binned frames: no records kept)
         DevBuf<uint32_t> busy;               // per raster tile: the epoch of the last batch that marked it
-        DevBuf<uint32_t> busy_list;          // busy tiles of the batch (k_raster's work items)
+        DevBuf<uint32_t> gbusy;              // per tile group: the epoch of the last batch that marked a tile of it
+        DevBuf<uint32_t> busy_list;          // busy tiles (tile groups: busy groups) of the batch (k_raster's work items)
         DevBuf<uint4> blk_stat;              // per setup block
         DevBuf<uint4> rstat;                 // per raster block
         hipEvent_t setup_done = nullptr, raster_done = nullptr;
@@ -137,6 +138,7 @@ struct shs_ctx {
     bool planes_known = false;
     bool stale_clear = true;         // SHS_OPT_LEGACY_STALE_CLEAR
     uint64_t last_cleared = 0;       // tiles the last batch's clear strips cleared
+    bool tile_groups = true;         // SHS_OPT_LEGACY_TILE_GROUPS
 
     uint32_t *h_counters = nullptr;  // pinned, C_NCOUNTERS
 

@@ -157,6 +157,20 @@ constexpr uint32_t BUSY_SKIP = 0xffffffffu;   // a padding entry of the busy lis
 // shard, reallocated planes, pointers handed out, SHS_OPT_LEGACY_STALE_CLEAR 0).  Without it a strip
 // clears only the tiles FrameBuffers::stale marks as left non-clear by an earlier batch.
 constexpr uint32_t RF_FULL_CLEAR = 1u << 21;
+// Scan-mode batches on the pair kernel whose raster work item is a tile group (frame flags bit 22, set
+// by the host: SHS_OPT_LEGACY_TILE_GROUPS, never for k_pipe or the per-pixel kernels): a GX x GY block of
+// raster tiles of one frame.  A tile's first marker also exchanges the epoch into gbusy[group], and the
+// group's first marker lists the group (its top-left tile) in the busy list -- each busy group once.
+// k_raster scans the bin boxes and stages the records once per group, then runs the pairs, resolve and
+// stores of each busy tile of the group.  Idle tiles of a busy group are left to the clear items.
+constexpr uint32_t RF_TILE_GROUPS = 1u << 22;
+#ifndef SHS_GROUP_X
+#define SHS_GROUP_X 2                // (-DSHS_GROUP_X=.. -DSHS_GROUP_Y=..: timing experiments)
+#endif
+#ifndef SHS_GROUP_Y
+#define SHS_GROUP_Y 2
+#endif
+constexpr int GX = SHS_GROUP_X, GY = SHS_GROUP_Y;   // raster tiles per group across / down (64x16 px)
 
 // Uniforms of up to KARG_DRAWS draws travel in the kernel arguments (no per-frame copy);
 // larger scenes read the device draw table.
@@ -224,8 +238,11 @@ struct FrameBuffers {
     uint32_t *counters;              // 2 * CSET
     uint32_t *busy;                  // per frame, per raster tile: == fp.epoch when the tile has
                                      // candidates / fragments in this launch (no reset needed)
+    uint32_t *gbusy;                 // per frame, per tile group (RF_TILE_GROUPS): == fp.epoch once a tile of
+                                     // the group has been marked busy in this launch (no reset needed)
     uint32_t *busy_list;             // C_BUSY entries f * n_raster_tiles + raster tile, each busy tile of
-                                     // the batch once (capacity n_frames * n_raster_tiles)
+                                     // the batch once (capacity n_frames * n_raster_tiles); RF_TILE_GROUPS:
+                                     // each busy group once, as its top-left tile
     uint32_t *stale;                 // per frame, per raster tile, owned by the context (not the slot):
                                      // 0 = every owned pixel of the tile holds the clear value in every
                                      // enabled plane (k_raster / k_pipe alone read and write it)
@@ -249,6 +266,14 @@ __device__ __forceinline__ void raise_overflow(uint32_t *word, uint32_t bit, uin
     if (ov_host) __hip_atomic_store(ov_host, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// Tile groups of a frame, and the group of raster tile (rx, ry).
+__device__ __host__ inline int n_groups(const FrameParams &fp) {
+    return ((fp.tiles_x + GX - 1) / GX) * ((fp.rtiles_y + GY - 1) / GY);
+}
+__device__ __forceinline__ int group_of(const FrameParams &fp, int rx, int ry) {
+    return (ry / GY) * ((fp.tiles_x + GX - 1) / GX) + rx / GX;
+}
+
 // The buffers of frame f of the batch (shared buffers unchanged).
 __device__ __forceinline__ FrameBuffers frame_view(const FrameParams &fp, const FrameBuffers &fb, int f) {
     FrameBuffers v = fb;
@@ -262,6 +287,7 @@ __device__ __forceinline__ FrameBuffers frame_view(const FrameParams &fp, const 
     v.tile_count += f * n_bt;
     v.bins += f * n_bt * fp.bin_cap;
     v.busy += f * n_rt;
+    v.gbusy += f * (size_t)n_groups(fp);
     v.stale += f * n_rt;
     v.color += f * npx * 4;
     v.depth += f * npx;
@@ -270,7 +296,7 @@ __device__ __forceinline__ FrameBuffers frame_view(const FrameParams &fp, const 
     return v;
 }
 
-constexpr int TL_STRIDE = 12;
+constexpr int TL_STRIDE = 13;   // (slot 12: busy tiles of the first tile group, RF_TILE_GROUPS)
 
 struct KArgDraws {
     DrawGPU d[KARG_DRAWS];

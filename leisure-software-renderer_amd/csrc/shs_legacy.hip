@@ -33,6 +33,8 @@
 #include <float.h>
 #include <limits.h>
 
+#include <type_traits>
+
 #include "shs_device.hpp"
 #include "shs_internal.hpp"
 #include "shs_wave.hpp"
@@ -321,10 +323,24 @@ __device__ __forceinline__ uint32_t busy_entry(const FrameParams &fp, int frame,
     return (uint32_t)(frame * fp.tiles_x * fp.rtiles_y + rt);
 }
 
+// RF_TILE_GROUPS: a newly busy tile's listing is its group's -- the group's first marker (the exchange
+// on gbusy returns another value) lists the group once, as its top-left tile.  Returns the tile to list,
+// or -1 when the group is listed already.
+__device__ __forceinline__ int group_entry_tile(const FrameParams &fp, const FrameBuffers &fb, int rx, int ry) {
+    if (atomicExch(&fb.gbusy[group_of(fp, rx, ry)], fp.epoch) == fp.epoch) return -1;
+    return (ry / GY) * GY * fp.tiles_x + (rx / GX) * GX;
+}
+
 // Mark and append directly (rare callers: ghost fragments).
 __device__ __forceinline__ void mark_busy_direct(const FrameParams &fp, const FrameBuffers &fb, uint32_t *cnt, int frame,
-                                                 int rt) {
-    if (atomicExch(&fb.busy[rt], fp.epoch) != fp.epoch) fb.busy_list[atomicAdd(&cnt[C_BUSY], 1u)] = busy_entry(fp, frame, rt);
+                                                 int rx, int ry) {
+    int rt = ry * fp.tiles_x + rx;
+    if (atomicExch(&fb.busy[rt], fp.epoch) == fp.epoch) return;
+    if (fp.flags & RF_TILE_GROUPS) {
+        rt = group_entry_tile(fp, fb, rx, ry);
+        if (rt < 0) return;
+    }
+    fb.busy_list[atomicAdd(&cnt[C_BUSY], 1u)] = busy_entry(fp, frame, rt);
 }
 
 // Setup blocks collect their newly busy tiles in LDS and append them with one atomic per block.
@@ -335,16 +351,21 @@ struct NewBusy {
 };
 
 // The tile's listing once its mark found it not yet busy (old != epoch).
-__device__ __forceinline__ void list_busy(const FrameParams &fp, const FrameBuffers &fb, uint32_t *cnt, int frame, int rt,
-                                          NewBusy &nb) {
+__device__ __forceinline__ void list_busy(const FrameParams &fp, const FrameBuffers &fb, uint32_t *cnt, int frame, int rx,
+                                          int ry, NewBusy &nb) {
+    int rt = ry * fp.tiles_x + rx;
+    if (fp.flags & RF_TILE_GROUPS) {
+        rt = group_entry_tile(fp, fb, rx, ry);
+        if (rt < 0) return;
+    }
     const uint32_t k = atomicAdd(&nb.n, 1u);
     if (k < (uint32_t)NEW_BUSY_CAP) nb.e[k] = busy_entry(fp, frame, rt);
     else fb.busy_list[atomicAdd(&cnt[C_BUSY], 1u)] = busy_entry(fp, frame, rt);
 }
 
-__device__ __forceinline__ void mark_busy(const FrameParams &fp, const FrameBuffers &fb, uint32_t *cnt, int frame, int rt,
-                                          NewBusy &nb) {
-    if (atomicExch(&fb.busy[rt], fp.epoch) != fp.epoch) list_busy(fp, fb, cnt, frame, rt, nb);
+__device__ __forceinline__ void mark_busy(const FrameParams &fp, const FrameBuffers &fb, uint32_t *cnt, int frame, int rx,
+                                          int ry, NewBusy &nb) {
+    if (atomicExch(&fb.busy[ry * fp.tiles_x + rx], fp.epoch) != fp.epoch) list_busy(fp, fb, cnt, frame, rx, ry, nb);
 }
 
 // Bin mode: the first append to bin tile t (its counter returned 0) makes the tile's raster rows busy.
@@ -607,7 +628,7 @@ __device__ __forceinline__ void sliver_pixels(const FrameParams &fp, const Frame
                     g.frame = frame;
                     g.pad[0] = g.pad[1] = 0u;
                     fb.frags[slot] = g;
-                    mark_busy_direct(fp, fb, cnt, (int)frame, (py / RTH) * fp.tiles_x + px / RTW);
+                    mark_busy_direct(fp, fb, cnt, (int)frame, px / RTW, py / RTH);
                 } else {
                     raise_overflow(&cnt[C_OVERFLOW], OV_FRAG, fb.ov_host);
                 }
@@ -827,14 +848,14 @@ __device__ __forceinline__ void setup_block(const FrameParams &fp, const FrameBu
             if (k < n_rt) {
                 const int rx = rx0 + k % nrx, ry = ry0 + k / nrx;
                 if (!sharded || owned_bin_tile(fp, rx, ry / (TILE / RTH))) {
-                    rts[i] = ry * fp.tiles_x + rx;
-                    old[i] = atomicExch(&fb.busy[rts[i]], fp.epoch);
+                    rts[i] = rx | (ry << 16);   // (tile column | row << 16)
+                    old[i] = atomicExch(&fb.busy[ry * fp.tiles_x + rx], fp.epoch);
                 }
             }
         }
 #pragma unroll
         for (int i = 0; i < SMALL_RT / 4; ++i)
-            if (rts[i] >= 0 && old[i] != fp.epoch) list_busy(fp, fb, cnt, frame, rts[i], nb);
+            if (rts[i] >= 0 && old[i] != fp.epoch) list_busy(fp, fb, cnt, frame, rts[i] & 0xffff, rts[i] >> 16, nb);
     }
     {
         uint64_t big = __ballot(n_rt > SMALL_RT && q == 0);
@@ -845,7 +866,7 @@ __device__ __forceinline__ void setup_block(const FrameParams &fp, const FrameBu
             const int nx = bx1 - bx0 + 1, n = nx * (by1 - by0 + 1);
             for (int k = lane; k < n; k += 64) {
                 const int rx = bx0 + k % nx, ry = by0 + k / nx;
-                if (!sharded || owned_bin_tile(fp, rx, ry / (TILE / RTH))) mark_busy(fp, fb, cnt, frame, ry * fp.tiles_x + rx, nb);
+                if (!sharded || owned_bin_tile(fp, rx, ry / (TILE / RTH))) mark_busy(fp, fb, cnt, frame, rx, ry, nb);
             }
         }
     }
@@ -1178,6 +1199,7 @@ struct RasterShared {
     unsigned long long bits[PAIR_WORDS]; // bit k: a staged candidate's pairs start at pair k (2 KB)
     uint32_t seg[RCHUNK * RTH];       // spans: per nonempty row span, first pair | x0 << 14 | row << 19 | candidate << 22
     uint4 pinfo[RCHUNK];              // boxes: per staged candidate first pair, x0 | y0 << 16, box width, 2^16/width
+                                      // (groups: per candidate with pairs in the tile; width | candidate << 8)
     uint32_t wtot[4];                 // per wave: pairs << 11 | segments (the staging pass's block prefix)
     uint32_t id[RCHUNK];
     uint32_t cand[CAND];
@@ -1187,6 +1209,19 @@ struct RasterShared {
     uint32_t nclr;                    // tiles this workgroup's strips cleared (rstat)
     uint16_t wown[PAIR_WORDS];        // segment (boxes: staged candidate) owning each bitmap word's first pair
 };
+
+// Tile groups (raster_group), on top of RasterShared (+9.5 KB: 35.3 KB, four workgroups per CU): the keys
+// of the group's tiles after the first, and a second copy of the pair prefix's outputs -- wave 0 lays
+// out the next tile's pairs while the other waves may still walk this one's.  Only the group kernel
+// declares it (k_pipe's and the other rasters' LDS stays what it was).
+struct GroupShared {
+    unsigned long long key[(GX * GY - 1) * RTH * RTW];
+    unsigned long long bits[PAIR_WORDS];
+    uint4 pinfo[RCHUNK];
+    uint16_t wown[PAIR_WORDS];
+    uint32_t npairs[2];               // the tile's pairs, per prefix copy
+};
+struct NoGroupShared {};
 
 // The record rebuilt from the screen corners with the stored flags and bin box: rec_from_screen's
 // float arithmetic (the Gram terms, z, float bbox, integer bbox) without danger_margin -- its only
@@ -1707,6 +1742,264 @@ __device__ __forceinline__ void raster_tile(const FrameParams &fp, const FrameBu
     tl_mark(tl, tls, 5);
 }
 
+// One busy tile group (RF_TILE_GROUPS: scan-mode frames on the pair kernel): the GX x GY raster tiles
+// from tile rt0 that exist on the grid.  What a tile's own item repeats for each of them is done once:
+// the group's busy flags travel with the box scan, the boxes are tested against the group rectangle (one
+// compaction atomic per wave), and the candidates' records, float bboxes and shade records are staged
+// once.  Each busy tile of the group then runs raster_tile's pair tasks over the staged candidates
+// clipped to it -- a candidate that misses the tile has no pairs there, so the prefix ranks only the
+// ones that hit and keeps their staging slot beside the box width -- into its own key array, and after
+// the ghost fragments its resolve, shading and stores.  Wave 0 lays out a tile's pairs into one of two
+// copies of the prefix outputs while the other waves may still walk the previous tile's: one barrier
+// per tile and staging pass.  The keys and values are raster_tile's, so the images are the same bits.
+// Idle tiles of the group (not marked, or another shard's) are not touched: the clear items own them.
+__device__ __forceinline__ void raster_group(const FrameParams &fp, const FrameBuffers &fb, const DrawGPU *draws,
+                                             uint32_t n_frag, int frame, int rt0, RasterShared &sh, GroupShared &gs, uint64_t *tl) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tls = fp.setup_grid + (int)blockIdx.x;
+    const int col0 = rt0 % fp.tiles_x, row0 = rt0 / fp.tiles_x;
+    const int ncol = min(GX, fp.tiles_x - col0), nrow = min(GY, fp.rtiles_y - row0);
+    const int GX0 = col0 * RTW, GY0 = row0 * RTH;
+    const int GX1 = GX0 + ncol * RTW - 1, GY1 = GY0 + nrow * RTH - 1;
+    const int dbase = frame * fp.n_draws;                       // the frame's slice of the draw table
+    const uint32_t n_items = (uint32_t)fp.n_tris;
+    // The group's busy flags (lane t of every wave loads tile t's: bit ty * GX + tx of the wave-uniform
+    // mask below) and the first round's boxes are vector loads issued before the round's barriers, which
+    // they stay in flight across: one round trip for both.  (As scalar loads the flags were waited for at
+    // the first barrier, before the boxes were even requested: +1.1 us per group.)
+    static_assert(GX * GY <= 32, "the group's busy mask");
+    uint32_t flag = 0u;
+    {
+        const int tx = lane % GX, ty = lane / GX;
+        if (tx < ncol && ty < nrow) flag = fb.busy[rt0 + ty * fp.tiles_x + tx];   // (ty < nrow <= GY: lanes < GX * GY)
+    }
+    uint2 bx[CAND / 256];
+#pragma unroll
+    for (int k = 0; k < CAND / 256; ++k) {
+        const uint32_t item = tid + 256u * k;
+        bx[k] = item < n_items ? fb.boxes[item] : make_uint2(1u, 1u);   // ([1, 0]: empty)
+    }
+    // the previous item's key resets precede every shared write of this one (raster_tile)
+    if (n_items == 0u) __syncthreads();
+    uint32_t seq = 0;   // candidates processed (profiling)
+    int pairs = 0;      // (candidate, pixel) tasks of the group's first busy tile (profiling)
+    const bool slot_keys = fp.n_tris < (1 << 25);
+    bool single = n_items <= (uint32_t)CAND;   // one gather round and one staging pass: winners in LDS
+    int pb = 0;         // the prefix copy the next tile's pairs are laid out in
+    const uint32_t bmask = (uint32_t)__ballot(flag == fp.epoch) & ((1u << (GX * GY)) - 1u);   // (epoch != 0)
+    const int t_first = __ffs((int)bmask) - 1;
+
+    for (uint32_t base = 0; base < n_items; base += CAND) {
+        // every bin box of the round against the group rectangle (4 independent loads per thread)
+        if (base > 0u) {
+#pragma unroll
+            for (int k = 0; k < CAND / 256; ++k) {
+                const uint32_t item = base + tid + 256u * k;
+                bx[k] = item < n_items ? fb.boxes[item] : make_uint2(1u, 1u);
+            }
+        }
+        __syncthreads();
+        if (tid == 0) sh.nc = 0;
+        __syncthreads();
+        uint64_t hm[CAND / 256];
+        uint32_t wtot = 0u;
+#pragma unroll
+        for (int k = 0; k < CAND / 256; ++k) {
+            const int gx0 = lo16(bx[k].x), gx1 = hi16(bx[k].x), gy0 = lo16(bx[k].y), gy1 = hi16(bx[k].y);
+            hm[k] = __ballot(gx0 <= gx1 && gy0 <= gy1 && gx1 >= GX0 && gx0 <= GX1 && gy1 >= GY0 && gy0 <= GY1);
+            wtot += (uint32_t)__popcll(hm[k]);
+        }
+        uint32_t basew = 0;
+        if (lane == 0 && wtot) basew = atomicAdd(&sh.nc, wtot);
+        basew = __shfl(basew, 0);
+#pragma unroll
+        for (int k = 0; k < CAND / 256; ++k) {
+            if ((hm[k] >> lane) & 1ull) sh.cand[basew + lanes_below(hm[k])] = base + tid + 256u * k;
+            basew += (uint32_t)__popcll(hm[k]);
+        }
+        __syncthreads();
+        tl_mark(tl, tls, 1);
+        const uint32_t nc = sh.nc;
+        single = single && nc <= (uint32_t)RCHUNK;
+        for (uint32_t c = 0; c < nc; c += RCHUNK) {
+            const int m = (int)min((uint32_t)RCHUNK, nc - c);
+            if (c > 0) __syncthreads();
+            // stage the records, float bboxes and (single-pass groups) shade records: one round trip
+            if (tid < m) sh.id[tid] = sh.cand[c + tid];
+            {
+                constexpr int NQ = (RCHUNK * 4 + 255) / 256, NS = (RCHUNK * 5 + 255) / 256;
+                float4 q[NQ], s[NS], e = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+                for (int k = 0; k < NQ; ++k) {
+                    const int f = tid + 256 * k;
+                    const int ci = f >> 2;
+                    q[k] = f < 4 * m ? reinterpret_cast<const float4 *>(&fb.recs[sh.cand[c + min(ci, m - 1)]])[f & 3]
+                                     : make_float4(0.f, 0.f, 0.f, 0.f);
+                }
+                if (tid < m) e = fb.rext[sh.cand[c + tid]];
+#pragma unroll
+                for (int k = 0; k < NS; ++k) {
+                    const int f = tid + 256 * k;
+                    const int ci = f / 5;
+                    s[k] = single && f < 5 * m ? reinterpret_cast<const float4 *>(&fb.shade[sh.cand[min(ci, m - 1)]])[f - 5 * ci]
+                                               : make_float4(0.f, 0.f, 0.f, 0.f);
+                }
+#pragma unroll
+                for (int k = 0; k < NQ; ++k) {
+                    const int f = tid + 256 * k;
+                    if (f < 4 * m) sh.rec[f] = q[k];
+                }
+                if (tid < m) sh.ext[tid] = e;
+#pragma unroll
+                for (int k = 0; k < NS; ++k) {
+                    const int f = tid + 256 * k;
+                    if (single && f < 5 * m) sh.srec[f] = s[k];
+                }
+            }
+            __syncthreads();
+            tl_mark(tl, tls, 2);
+            for (uint32_t bm = bmask; bm; bm &= bm - 1u) {
+                const int t = __ffs((int)bm) - 1;
+                const int X0 = GX0 + (t % GX) * RTW, Y0 = GY0 + (t / GX) * RTH;
+                const int X1 = X0 + RTW - 1, Y1 = Y0 + RTH - 1;
+                unsigned long long *bits = pb ? gs.bits : sh.bits;
+                uint16_t *wown = pb ? gs.wown : sh.wown;
+                uint4 *pinfo = pb ? gs.pinfo : sh.pinfo;
+                if (wave == 0) {
+                    // raster_tile's pair prefix over the candidates with pixels in this tile
+                    for (int i = lane; i < m * (RTW * RTH / 64); i += 64) bits[i] = 0ull;
+                    wave_lds_sync();
+                    int area = 0, bx0 = 0, by0 = 0, bw = 1;
+                    if (lane < m) {
+                        const uint4 bb = reinterpret_cast<const uint4 *>(&sh.rec[lane * 4])[3];   // z2 word gbx gby
+                        const int x0 = max(lo16(bb.z), X0), x1 = min(hi16(bb.z), X1);
+                        const int y0 = max(lo16(bb.w), Y0), y1 = min(hi16(bb.w), Y1);
+                        if (x0 <= x1 && y0 <= y1) { area = (x1 - x0 + 1) * (y1 - y0 + 1); bx0 = x0; by0 = y0; bw = x1 - x0 + 1; }
+                    }
+                    const uint32_t rank = lanes_below(__ballot(area > 0));
+                    int incl = area;
+#pragma unroll
+                    for (int o = 1; o < 64; o <<= 1) {
+                        const int v = __shfl_up(incl, o);
+                        if (lane >= o) incl += v;
+                    }
+                    const int start = incl - area;
+                    if (area > 0) {
+                        pinfo[rank] = make_uint4((uint32_t)start, (uint32_t)bx0 | ((uint32_t)by0 << 16), (uint32_t)bw | ((uint32_t)lane << 8),
+                                                 (65536u + (uint32_t)bw - 1u) / (uint32_t)bw);
+                        atomicOr(&bits[start >> 6], 1ull << (start & 63));
+                        for (int wd = (start + 63) >> 6; wd * 64 < incl; ++wd) wown[wd] = (uint16_t)rank;
+                    }
+                    if (lane == 63) gs.npairs[pb] = (uint32_t)incl;
+                }
+                __syncthreads();
+                const int total = SHS_DBG(fp, DBG_SKIP_PAIRS) ? 0 : (int)gs.npairs[pb];
+                if (t == t_first) pairs += total;
+                unsigned long long *key = t ? &gs.key[(t - 1) * (RTW * RTH)] : sh.key;
+                for (int k0 = 64 * wave; k0 < total; k0 += 256) {
+                    const int k = k0 + lane;
+                    if (k < total) {
+                        const unsigned long long wb = bits[k0 >> 6];
+                        const unsigned long long upto = ((2ull << lane) - 1ull) & ~1ull;   // bits 1..lane
+                        const uint4 pi = pinfo[(int)wown[k0 >> 6] + __popcll(wb & upto)];
+                        const int o = (int)(pi.z >> 8), bw = (int)(pi.z & 0xffu);
+                        const int local = k - (int)pi.x;
+                        const int ly = (int)(((uint32_t)local * pi.w) >> 16), lx = local - ly * bw;
+                        const int px = (int)(pi.y & 0xffffu) + lx, py = (int)(pi.y >> 16) + ly;
+                        const TriRec r = rec_from_hot(fp, &sh.rec[o * 4], &sh.ext[o]);
+                        float z;
+                        if (pixel_test(fp, r, px, py, z))
+                            atomicMin(&key[(py - Y0) * RTW + (px - X0)], cand_key(z, sh.id[o], slot_keys, single ? (uint32_t)o : SLOT_NONE));
+                    }
+                }
+                pb ^= 1;
+            }
+            seq += (uint32_t)m;
+        }
+    }
+    tl_mark(tl, tls, 3);
+    // tile-clamp pixels of unbounded slivers outside their bbox that passed, into their tile's keys
+    for (uint32_t f = tid; f < n_frag; f += 256) {
+        const GhostFrag g = fb.frags[f];
+        const int gx = (int)(g.xy & 0xffffu), gy = (int)(g.xy >> 16);
+        if (g.frame == (uint32_t)frame && gx >= GX0 && gx <= GX1 && gy >= GY0 && gy <= GY1) {
+            const int tx = (gx - GX0) / RTW, ty = (gy - GY0) / RTH, t = ty * GX + tx;
+            unsigned long long *key = t ? &gs.key[(t - 1) * (RTW * RTH)] : sh.key;
+            if ((bmask >> t) & 1u)
+                atomicMin(&key[(gy - GY0 - ty * RTH) * RTW + (gx - GX0 - tx * RTW)], cand_key(g.z, g.id, slot_keys, SLOT_NONE));
+        }
+    }
+    __syncthreads();
+
+    // each busy tile: one pixel per thread -- resolve, shade the winner, write (raster_tile's)
+    uint32_t ncov = 0u;
+    for (uint32_t bm = bmask; bm; bm &= bm - 1u) {
+        const int t = __ffs((int)bm) - 1;
+        const int px = GX0 + (t % GX) * RTW + (tid & 31), py = GY0 + (t / GX) * RTH + (tid >> 5);
+        unsigned long long *kp = t ? &gs.key[(t - 1) * (RTW * RTH) + tid] : &sh.key[tid];
+        const unsigned long long key = *kp;
+        *kp = KEY_EMPTY;   // clean for the next item (read above, by this thread only)
+        uint32_t rgba = fp.clear_rgba;
+        float depth = FLT_MAX;
+        float4 pq = make_float4(0.f, 0.f, 0.f, 0.f);
+        const bool covered = key != KEY_EMPTY && px < fp.W && py < fp.H;
+        if (covered) {
+            const uint32_t lo = (uint32_t)key;
+            const uint32_t id = slot_keys ? lo >> 7 : lo, slot = slot_keys ? lo & SLOT_NONE : SLOT_NONE;
+            TriRec r;
+            ShadeRec sr;
+            {
+                float4 h4[4];   // the winner's stored record (its float bbox is not read here)
+                float4 *e4 = reinterpret_cast<float4 *>(&sr);
+                if (slot != SLOT_NONE) {   // only single-pass groups encode a slot: the staged copies
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) h4[k] = sh.rec[slot * 4 + k];
+#pragma unroll
+                    for (int k = 0; k < 5; ++k) e4[k] = sh.srec[slot * 5 + k];
+                } else {
+                    const float4 *s4 = reinterpret_cast<const float4 *>(&fb.recs[id]);
+                    const float4 *g4 = reinterpret_cast<const float4 *>(&fb.shade[id]);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) h4[k] = s4[k];
+#pragma unroll
+                    for (int k = 0; k < 5; ++k) e4[k] = g4[k];
+                }
+                r = rec_from_hot(fp, h4[0], h4[1], h4[2], h4[3], make_float4(0.f, 0.f, 0.f, 0.f));
+            }
+            float u, v, w;
+            bary_pass(r, (float)px + 0.5f, (float)py + 0.5f, u, v, w);   // the winner's own values
+            depth = (u * r.z0 + v * r.z1) + w * r.z2;
+            if (!SHS_DBG(fp, DBG_SKIP_SHADE)) {
+                const int wd = dbase + r.draw;   // the frame's draw (ShadeRec::draw is frame 0's when shared)
+                const float4 *du = wd < LDS_DRAWS ? &sh.du[wd * 4] : reinterpret_cast<const float4 *>(draws[wd].light);
+                float pre[3];
+                shade_winner(du, sr, u, v, w, pre);
+                const uint32_t cr = (uint32_t)(uint8_t)pre[0], cg = (uint32_t)(uint8_t)pre[1], cb = (uint32_t)(uint8_t)pre[2];
+                rgba = cr | (cg << 8) | (cb << 16) | (255u << 24);
+                pq = make_float4(pre[0], pre[1], pre[2], 1.0f);
+            }
+        }
+        if (t == t_first) tl_mark(tl, tls, 4);
+        ncov += (uint32_t)__popcll(__ballot(covered));
+        const bool dbg_nost = SHS_DBG(fp, DBG_SKIP_TILE_STORES) && !(rgba == 0x12345678u && depth == -1.0f);
+        if (px < fp.W && py < fp.H && !dbg_nost) {
+            LEGACY_STORE(rgba, &reinterpret_cast<uint32_t *>(fb.color)[(size_t)(fp.H - 1 - py) * fp.W + px]);
+            LEGACY_STORE(depth, &fb.depth[(size_t)py * fp.W + px]);
+            if (fb.prequant) fb.prequant[(size_t)(fp.H - 1 - py) * fp.W + px] = pq;
+            if (fb.present) LEGACY_STORE(rgba, &fb.present[(size_t)py * fp.W + px]);
+        }
+        // the tile no longer holds the clear values: a later batch that leaves it idle clears it
+        if (tid == 0) fb.stale[rt0 + (t / GX) * fp.tiles_x + t % GX] = 1u;
+        if (t == t_first) tl_mark(tl, tls, 5);
+    }
+    if (lane == 0 && ncov) atomicAdd(&sh.cov, ncov);
+    if (tl && tid == 0) {
+        tl[TL_STRIDE * tls + 8] = seq;
+        tl[TL_STRIDE * tls + 9] = (uint64_t)pairs;
+        tl[TL_STRIDE * tls + 12] = (uint64_t)__popc(bmask);
+    }
+}
+
 // A tile with no candidates: the clear, one pixel per thread (rows of 32 px: 128-B segments).
 __device__ __forceinline__ void clear_tile(const FrameParams &fp, const FrameBuffers &fb, int rt) {
     const int tid = threadIdx.x;
@@ -1839,7 +2132,7 @@ __device__ __forceinline__ uint32_t clear_item(const FrameParams &fp, const Fram
 constexpr int STRIP_RT = SHS_STRIP_RT;
 
 // Persistent raster over the whole batch.  Work items are the busy tiles (the busy list k_setup /
-// k_ghost built: latency-bound raster) and the clear strips (one raster-tile row of one frame:
+// k_ghost built: latency-bound raster; RF_TILE_GROUPS: the busy 2x2 groups of tiles) and the clear strips (one raster-tile row of one frame:
 // streaming stores), interleaved in proportion so that every CU mixes both kinds at all times.
 // Workgroup b's first item is b (no atomic: a single frame needs none); the rest come from N_WORKQ
 // ticket queues -- queue q deals items G + q + N_WORKQ * j to the workgroups b = q (mod N_WORKQ) --
@@ -1849,9 +2142,12 @@ constexpr int STRIP_RT = SHS_STRIP_RT;
 #ifndef SHS_LEGACY_RASTER_WAVES
 #define SHS_LEGACY_RASTER_WAVES 4   // minimum waves per SIMD (-D...: timing experiments)
 #endif
-template <bool KARG, bool NO_RECS, bool SPANS, bool PIX, int SCAN>
+// GROUPS (RF_TILE_GROUPS, the scan-mode pair kernel only): the busy list holds tile groups (raster_group).
+template <bool KARG, bool NO_RECS, bool SPANS, bool PIX, int SCAN, bool GROUPS = false>
 __global__ __launch_bounds__(256, SHS_LEGACY_RASTER_WAVES) void k_raster(FrameParams fp, FrameBuffers fb, KArgDraws ka) {
+    static_assert(!GROUPS || (SCAN == SCAN_ALL && !NO_RECS && !SPANS && !PIX), "tile groups: the scan-mode pair kernel");
     __shared__ RasterShared sh;
+    __shared__ typename std::conditional<GROUPS, GroupShared, NoGroupShared>::type gs;
     const int tid = threadIdx.x;
     uint32_t *cnt = fb.counters + fp.parity * CSET;
     const DrawGPU *draws = draw_table<KARG>(fb, ka);
@@ -1860,6 +2156,10 @@ __global__ __launch_bounds__(256, SHS_LEGACY_RASTER_WAVES) void k_raster(FramePa
     const uint64_t c_start = fb.timeline ? __builtin_amdgcn_s_memtime() : 0ull;
     if (tid == 0) { sh.cov = 0; sh.maxbin = 0; sh.nclr = 0; }
     sh.key[tid] = KEY_EMPTY;
+    if constexpr (GROUPS) {
+#pragma unroll
+        for (int t = 0; t < GX * GY - 1; ++t) gs.key[t * (RTW * RTH) + tid] = KEY_EMPTY;
+    }
     // Every independent first-touch load is issued up front so their round trips overlap: the
     // busy-list length, the ghost-fragment count and the draws' shading uniforms.  (A single-frame
     // scan-mode scene's bin boxes held in registers from the start -- rounds 1-4 -- cost the batch
@@ -1905,6 +2205,11 @@ __global__ __launch_bounds__(256, SHS_LEGACY_RASTER_WAVES) void k_raster(FramePa
             } else if (SHS_DBG(fp, DBG_CLEAR_ONLY)) {
                 __syncthreads();
                 clear_tile(fp, fv, rt);
+            } else if constexpr (GROUPS) {   // (rt: the group's top-left tile)
+                if (SHS_DBG(fp, DBG_TWICE)) raster_group(fp, fv, draws, n_frag, f, rt, sh, gs, nullptr);   // warm run
+                tl_mark(first ? fb.timeline : nullptr, fp.setup_grid + (int)blockIdx.x, 0);
+                raster_group(fp, fv, draws, n_frag, f, rt, sh, gs, first ? fb.timeline : nullptr);
+                first = false;
             } else {
                 if (SHS_DBG(fp, DBG_TWICE)) raster_tile<NO_RECS, SPANS, PIX, SCAN>(fp, fv, draws, cnt, n_frag, f, rt, sh, nullptr);   // warm run
                 tl_mark(first ? fb.timeline : nullptr, fp.setup_grid + (int)blockIdx.x, 0);
@@ -2040,10 +2345,10 @@ hipError_t launch_raster(const FrameParams &fp, const FrameBuffers &fb, const KA
     // binned frames test conservative row spans, scan-mode frames whole boxes (raster_tile); the
     // per-pixel loop (SHS_OPT_RASTER_LOOP 0) has kernels of its own, so the pair kernels carry none of
     // its registers
-#define SHS_RASTER(NR, SP, PX, SC)                                                                          \
-    do {                                                                                                   \
-        if (karg) hipLaunchKernelGGL((k_raster<true, NR, SP, PX, SC>), g, dim3(256), 0, s, fp, fb, ka);      \
-        else hipLaunchKernelGGL((k_raster<false, NR, SP, PX, SC>), g, dim3(256), 0, s, fp, fb, ka);          \
+#define SHS_RASTER(NR, SP, PX, SC, ...)                                                                              \
+    do {                                                                                                           \
+        if (karg) hipLaunchKernelGGL((k_raster<true, NR, SP, PX, SC, ##__VA_ARGS__>), g, dim3(256), 0, s, fp, fb, ka);  \
+        else hipLaunchKernelGGL((k_raster<false, NR, SP, PX, SC, ##__VA_ARGS__>), g, dim3(256), 0, s, fp, fb, ka);      \
     } while (0)
     const bool pix = (fp.flags & RF_PER_PIXEL) != 0u;
     if (DBG_BUILD && (fp.flags & RF_NO_RECS)) {   // binned frames, records recomputed (either loop; experiments build)
@@ -2055,6 +2360,7 @@ hipError_t launch_raster(const FrameParams &fp, const FrameBuffers &fb, const KA
 #ifdef SHS_SCAN_SPANS   // (timing experiments: scan-mode frames on row spans)
     else SHS_RASTER(false, true, false, SCAN_ALL);
 #else
+    else if (fp.flags & RF_TILE_GROUPS) SHS_RASTER(false, false, false, SCAN_ALL, true);   // busy groups (raster_group)
     else SHS_RASTER(false, false, false, SCAN_ALL);
 #endif
 #undef SHS_RASTER

@@ -602,6 +602,11 @@ class Context:
         (default on); off: every batch clears every idle tile.  Images identical either way."""
         self._check(self._lib.shs_set_option(self._h, _abi.OPT_LEGACY_STALE_CLEAR, 1 if on else 0))
 
+    def set_tile_groups(self, on: bool):
+        """SHS_OPT_LEGACY_TILE_GROUPS: scan-mode legacy batches raster their busy tiles in 2x2 groups that
+        share one box scan and staging (default on); off: a work item per busy tile.  Images identical."""
+        self._check(self._lib.shs_set_option(self._h, _abi.OPT_LEGACY_TILE_GROUPS, 1 if on else 0))
+
     def cleared_tiles(self) -> int:
         """shs_legacy_cleared_tiles: the 32x8 raster tiles the last legacy batch's clear strips cleared."""
         n = ctypes.c_uint64(0)

@@ -39,6 +39,7 @@ OPT_SHARD_ROOT_SHARE = 10
 OPT_SHADOW_FOOTPRINT = 11
 OPT_LEGACY_PIPELINE = 12
 OPT_LEGACY_STALE_CLEAR = 13
+OPT_LEGACY_TILE_GROUPS = 14
 
 
 class LegacyDraw(ctypes.Structure):

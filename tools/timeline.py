@@ -44,6 +44,15 @@ def phases(se, names, label):
         print(f"  {label} median of {len(ran)} wgs: " + " ".join("%s=%.2f" % (n, m) for n, m in zip(names, med)))
 
 
+def group_tiles(r):
+    """Tile groups (slot 12: busy tiles of each raster workgroup's first group; the phase marks are then
+    the group's shared scan and staging and its first busy tile's pairs and shading)."""
+    if r.shape[1] > 12 and (r[:, 12] != 0).any():
+        g = r[:, 12][r[:, 12] != 0].astype(np.int64)
+        print(f"  raster first group of {len(g)} wgs: busy tiles mean {g.mean():.2f}  " +
+              " ".join(f"{k}:{int((g == k).sum())}" for k in range(1, int(g.max()) + 1)))
+
+
 def main():
     cfg = sys.argv[1] if len(sys.argv) > 1 else "c2"
     flags = int(sys.argv[2], 0) if len(sys.argv) > 2 else 0
@@ -68,6 +77,7 @@ def main():
         summarize("raster", r, t0)
         phases(s[:sb], ["draw", "setup_tri", "busy", "bins", "make_rec"], "setup")
         phases(r, ["busy_list", "gather", "staged", "rastered", "shaded", "written"], "raster")
+        group_tiles(r)
         busy = r[r[:, 7] != 0]
         if len(busy):
             k = int(np.argmax(r[:, 1].astype(np.int64) - r[:, 0].astype(np.int64)))

@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, "leisure-software-renderer_amd"), ROOT, os.path.join(ROOT, "tools")]
 import shs_gpu  # noqa: E402
 import bench  # noqa: E402
-from timeline import phases, summarize  # noqa: E402
+from timeline import group_tiles, phases, summarize  # noqa: E402
 
 
 def main():
@@ -37,6 +37,7 @@ def main():
         summarize("raster", r, t0)
         phases(s, ["draw", "setup_tri", "busy", "bins", "make_rec", "stats"], "setup")
         phases(r, ["busy_list", "gather", "staged", "rastered", "shaded", "written"], "raster first tile")
+        group_tiles(r)
         st = (s[:, 0].astype(np.int64) - t0) / 100.0
         en = (s[:, 1].astype(np.int64) - t0) / 100.0
         for q in (0.25, 0.5, 0.75, 0.9, 1.0):
