@@ -1182,6 +1182,7 @@ __device__ __forceinline__ bool pixel_test(const FrameParams &fp, const TriRec &
 constexpr int RCHUNK = 64;         // candidate records staged per pass (one wave scans their areas)
 constexpr int LDS_DRAWS = 64;      // draws whose shading uniforms are kept in LDS
 constexpr int PAIR_WORDS = RCHUNK * RTW * RTH / 64;   // pair-start bitmap words (a box is <= 256 px)
+constexpr int PAIR_CAP = PAIR_WORDS * 64;             // pairs one pass lays out (groups: the rest in further passes)
 constexpr uint32_t SLOT_NONE = 127u;                  // key slot field: winner not staged in LDS
 
 // Candidate key: z_key with the low word (id << 7 | staging slot) when ids fit in 25 bits.  The order
@@ -1199,7 +1200,7 @@ struct RasterShared {
     unsigned long long bits[PAIR_WORDS]; // bit k: a staged candidate's pairs start at pair k (2 KB)
     uint32_t seg[RCHUNK * RTH];       // spans: per nonempty row span, first pair | x0 << 14 | row << 19 | candidate << 22
     uint4 pinfo[RCHUNK];              // boxes: per staged candidate first pair, x0 | y0 << 16, box width, 2^16/width
-                                      // (groups: per candidate with pairs in the tile; width | candidate << 8)
+                                      // (groups: per candidate with pairs in the pass, its box clipped to the group; width | candidate << 8)
     uint32_t wtot[4];                 // per wave: pairs << 11 | segments (the staging pass's block prefix)
     uint32_t id[RCHUNK];
     uint32_t cand[CAND];
@@ -1210,16 +1211,14 @@ struct RasterShared {
     uint16_t wown[PAIR_WORDS];        // segment (boxes: staged candidate) owning each bitmap word's first pair
 };
 
-// Tile groups (raster_group), on top of RasterShared (+9.5 KB: 35.3 KB, four workgroups per CU): the keys
-// of the group's tiles after the first, and a second copy of the pair prefix's outputs -- wave 0 lays
-// out the next tile's pairs while the other waves may still walk this one's.  Only the group kernel
-// declares it (k_pipe's and the other rasters' LDS stays what it was).
+// Tile groups (raster_group), on top of RasterShared (+6 KB, four workgroups per CU): the keys of the
+// group's tiles after the first, and the pair prefix's scalars.  Only the group kernel declares it
+// (k_pipe's and the other rasters' LDS stays what it was).
 struct GroupShared {
     unsigned long long key[(GX * GY - 1) * RTH * RTW];
-    unsigned long long bits[PAIR_WORDS];
-    uint4 pinfo[RCHUNK];
-    uint16_t wown[PAIR_WORDS];
-    uint32_t npairs[2];               // the tile's pairs, per prefix copy
+    uint32_t npairs;                  // the pair pass's pairs
+    uint32_t next;                    // the first staged candidate the pair pass left out (all fit: >= the staged count)
+    uint32_t seq, pairs;              // the group's candidates and pairs so far (timeline)
 };
 struct NoGroupShared {};
 
@@ -1746,12 +1745,12 @@ __device__ __forceinline__ void raster_tile(const FrameParams &fp, const FrameBu
 // from tile rt0 that exist on the grid.  What a tile's own item repeats for each of them is done once:
 // the group's busy flags travel with the box scan, the boxes are tested against the group rectangle (one
 // compaction atomic per wave), and the candidates' records, float bboxes and shade records are staged
-// once.  Each busy tile of the group then runs raster_tile's pair tasks over the staged candidates
-// clipped to it -- a candidate that misses the tile has no pairs there, so the prefix ranks only the
-// ones that hit and keeps their staging slot beside the box width -- into its own key array, and after
-// the ghost fragments its resolve, shading and stores.  Wave 0 lays out a tile's pairs into one of two
-// copies of the prefix outputs while the other waves may still walk the previous tile's: one barrier
-// per tile and staging pass.  The keys and values are raster_tile's, so the images are the same bits.
+// once.  One pair pass then runs raster_tile's pair tasks over the staged candidates' boxes clipped to
+// the group rectangle (one prefix by wave 0, one barrier): a pair finds its tile from its pixel, is
+// dropped when that tile is not busy, and otherwise goes into that tile's key array -- the same
+// (candidate, pixel) tests as the busy tiles' own passes, whose atomicMins commute.  After the ghost
+// fragments each busy tile is resolved, shaded and stored.  The keys and values are raster_tile's, so
+// the images are the same bits.
 // Idle tiles of the group (not marked, or another shard's) are not touched: the clear items own them.
 __device__ __forceinline__ void raster_group(const FrameParams &fp, const FrameBuffers &fb, const DrawGPU *draws,
                                              uint32_t n_frag, int frame, int rt0, RasterShared &sh, GroupShared &gs, uint64_t *tl) {
@@ -1781,11 +1780,10 @@ __device__ __forceinline__ void raster_group(const FrameParams &fp, const FrameB
     }
     // the previous item's key resets precede every shared write of this one (raster_tile)
     if (n_items == 0u) __syncthreads();
-    uint32_t seq = 0;   // candidates processed (profiling)
-    int pairs = 0;      // (candidate, pixel) tasks of the group's first busy tile (profiling)
+    // profiling, kept in LDS by wave 0: the candidates processed and the group's (candidate, pixel) tasks
+    if (tl && tid == 0) { gs.seq = 0u; gs.pairs = 0u; }
     const bool slot_keys = fp.n_tris < (1 << 25);
     bool single = n_items <= (uint32_t)CAND;   // one gather round and one staging pass: winners in LDS
-    int pb = 0;         // the prefix copy the next tile's pairs are laid out in
     const uint32_t bmask = (uint32_t)__ballot(flag == fp.epoch) & ((1u << (GX * GY)) - 1u);   // (epoch != 0)
     const int t_first = __ffs((int)bmask) - 1;
 
@@ -1821,6 +1819,7 @@ __device__ __forceinline__ void raster_group(const FrameParams &fp, const FrameB
         tl_mark(tl, tls, 1);
         const uint32_t nc = sh.nc;
         single = single && nc <= (uint32_t)RCHUNK;
+        if (tl && tid == 0) gs.seq += nc;
         for (uint32_t c = 0; c < nc; c += RCHUNK) {
             const int m = (int)min((uint32_t)RCHUNK, nc - c);
             if (c > 0) __syncthreads();
@@ -1829,9 +1828,13 @@ __device__ __forceinline__ void raster_group(const FrameParams &fp, const FrameB
             {
                 constexpr int NQ = (RCHUNK * 4 + 255) / 256, NS = (RCHUNK * 5 + 255) / 256;
                 float4 q[NQ], s[NS], e = make_float4(0.f, 0.f, 0.f, 0.f);
+                // (the thread's staging indices are computed here, per pass: hoisted out of the item loop
+                // they are registers held across the whole kernel, which then spills)
+                int stid = tid;
+                asm volatile("" : "+v"(stid));
 #pragma unroll
                 for (int k = 0; k < NQ; ++k) {
-                    const int f = tid + 256 * k;
+                    const int f = stid + 256 * k;
                     const int ci = f >> 2;
                     q[k] = f < 4 * m ? reinterpret_cast<const float4 *>(&fb.recs[sh.cand[c + min(ci, m - 1)]])[f & 3]
                                      : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -1839,7 +1842,7 @@ __device__ __forceinline__ void raster_group(const FrameParams &fp, const FrameB
                 if (tid < m) e = fb.rext[sh.cand[c + tid]];
 #pragma unroll
                 for (int k = 0; k < NS; ++k) {
-                    const int f = tid + 256 * k;
+                    const int f = stid + 256 * k;
                     const int ci = f / 5;
                     s[k] = single && f < 5 * m ? reinterpret_cast<const float4 *>(&fb.shade[sh.cand[min(ci, m - 1)]])[f - 5 * ci]
                                                : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -1858,63 +1861,75 @@ __device__ __forceinline__ void raster_group(const FrameParams &fp, const FrameB
             }
             __syncthreads();
             tl_mark(tl, tls, 2);
-            for (uint32_t bm = bmask; bm; bm &= bm - 1u) {
-                const int t = __ffs((int)bm) - 1;
-                const int X0 = GX0 + (t % GX) * RTW, Y0 = GY0 + (t / GX) * RTH;
-                const int X1 = X0 + RTW - 1, Y1 = Y0 + RTH - 1;
-                unsigned long long *bits = pb ? gs.bits : sh.bits;
-                uint16_t *wown = pb ? gs.wown : sh.wown;
-                uint4 *pinfo = pb ? gs.pinfo : sh.pinfo;
+            // one pair pass over the group: the staged candidates' bin boxes clipped to the group rectangle
+            // (<= 64 wide, <= 1024 px).  The bitmap holds PAIR_CAP pairs: a pass lays out the leading
+            // candidates whose pairs fit -- one always does -- and the rest follow in further passes.
+            for (int c0 = 0;;) {
                 if (wave == 0) {
-                    // raster_tile's pair prefix over the candidates with pixels in this tile
-                    for (int i = lane; i < m * (RTW * RTH / 64); i += 64) bits[i] = 0ull;
-                    wave_lds_sync();
+                    // raster_tile's pair prefix over the candidates from c0 with pixels in the group
                     int area = 0, bx0 = 0, by0 = 0, bw = 1;
-                    if (lane < m) {
+                    if (lane >= c0 && lane < m) {
                         const uint4 bb = reinterpret_cast<const uint4 *>(&sh.rec[lane * 4])[3];   // z2 word gbx gby
-                        const int x0 = max(lo16(bb.z), X0), x1 = min(hi16(bb.z), X1);
-                        const int y0 = max(lo16(bb.w), Y0), y1 = min(hi16(bb.w), Y1);
+                        const int x0 = max(lo16(bb.z), GX0), x1 = min(hi16(bb.z), GX1);
+                        const int y0 = max(lo16(bb.w), GY0), y1 = min(hi16(bb.w), GY1);
                         if (x0 <= x1 && y0 <= y1) { area = (x1 - x0 + 1) * (y1 - y0 + 1); bx0 = x0; by0 = y0; bw = x1 - x0 + 1; }
                     }
-                    const uint32_t rank = lanes_below(__ballot(area > 0));
                     int incl = area;
 #pragma unroll
                     for (int o = 1; o < 64; o <<= 1) {
                         const int v = __shfl_up(incl, o);
                         if (lane >= o) incl += v;
                     }
-                    const int start = incl - area;
-                    if (area > 0) {
-                        pinfo[rank] = make_uint4((uint32_t)start, (uint32_t)bx0 | ((uint32_t)by0 << 16), (uint32_t)bw | ((uint32_t)lane << 8),
-                                                 (65536u + (uint32_t)bw - 1u) / (uint32_t)bw);
-                        atomicOr(&bits[start >> 6], 1ull << (start & 63));
-                        for (int wd = (start + 63) >> 6; wd * 64 < incl; ++wd) wown[wd] = (uint16_t)rank;
+                    // the prefix grows with the lane: the candidates that fit are the leading lanes
+                    const bool fit = incl <= PAIR_CAP;
+                    const int nfit = __popcll(__ballot(fit));   // (>= c0 + 1: one box is <= 1024 pairs)
+                    const int total = __shfl(incl, nfit - 1);
+                    for (int i = lane; i * 64 < total; i += 64) sh.bits[i] = 0ull;
+                    wave_lds_sync();
+                    const bool on = area > 0 && fit;
+                    const uint32_t rank = lanes_below(__ballot(on));
+                    if (on) {
+                        const int start = incl - area;
+                        sh.pinfo[rank] = make_uint4((uint32_t)start, (uint32_t)bx0 | ((uint32_t)by0 << 16), (uint32_t)bw | ((uint32_t)lane << 8),
+                                                    (65536u + (uint32_t)bw - 1u) / (uint32_t)bw);
+                        atomicOr(&sh.bits[start >> 6], 1ull << (start & 63));
+                        for (int wd = (start + 63) >> 6; wd * 64 < incl; ++wd) sh.wown[wd] = (uint16_t)rank;
                     }
-                    if (lane == 63) gs.npairs[pb] = (uint32_t)incl;
+                    if (lane == 0) {
+                        gs.npairs = (uint32_t)total;
+                        gs.next = (uint32_t)nfit;
+                        if (tl) gs.pairs += (uint32_t)total;
+                    }
                 }
                 __syncthreads();
-                const int total = SHS_DBG(fp, DBG_SKIP_PAIRS) ? 0 : (int)gs.npairs[pb];
-                if (t == t_first) pairs += total;
-                unsigned long long *key = t ? &gs.key[(t - 1) * (RTW * RTH)] : sh.key;
+                const int total = SHS_DBG(fp, DBG_SKIP_PAIRS) ? 0 : __builtin_amdgcn_readfirstlane((int)gs.npairs);
+                c0 = __builtin_amdgcn_readfirstlane((int)gs.next);
                 for (int k0 = 64 * wave; k0 < total; k0 += 256) {
                     const int k = k0 + lane;
                     if (k < total) {
-                        const unsigned long long wb = bits[k0 >> 6];
+                        const unsigned long long wb = sh.bits[k0 >> 6];
                         const unsigned long long upto = ((2ull << lane) - 1ull) & ~1ull;   // bits 1..lane
-                        const uint4 pi = pinfo[(int)wown[k0 >> 6] + __popcll(wb & upto)];
+                        const uint4 pi = sh.pinfo[(int)sh.wown[k0 >> 6] + __popcll(wb & upto)];
                         const int o = (int)(pi.z >> 8), bw = (int)(pi.z & 0xffu);
-                        const int local = k - (int)pi.x;
+                        const int local = k - (int)pi.x;   // (< 16 * bw: the reciprocal is exact for bw <= 64)
                         const int ly = (int)(((uint32_t)local * pi.w) >> 16), lx = local - ly * bw;
                         const int px = (int)(pi.y & 0xffffu) + lx, py = (int)(pi.y >> 16) + ly;
-                        const TriRec r = rec_from_hot(fp, &sh.rec[o * 4], &sh.ext[o]);
-                        float z;
-                        if (pixel_test(fp, r, px, py, z))
-                            atomicMin(&key[(py - Y0) * RTW + (px - X0)], cand_key(z, sh.id[o], slot_keys, single ? (uint32_t)o : SLOT_NONE));
+                        // the pixel's tile: only the group's busy tiles are drawn (a sharded frame's
+                        // group holds tiles of other shards, which setup never marks)
+                        const int tx = (px - GX0) / RTW, ty = (py - GY0) / RTH, t = ty * GX + tx;
+                        if ((bmask >> t) & 1u) {
+                            const TriRec r = rec_from_hot(fp, &sh.rec[o * 4], &sh.ext[o]);
+                            unsigned long long *key = t ? &gs.key[(t - 1) * (RTW * RTH)] : sh.key;
+                            float z;
+                            if (pixel_test(fp, r, px, py, z))
+                                atomicMin(&key[(py - GY0 - ty * RTH) * RTW + (px - GX0 - tx * RTW)],
+                                          cand_key(z, sh.id[o], slot_keys, single ? (uint32_t)o : SLOT_NONE));
+                        }
                     }
                 }
-                pb ^= 1;
+                if (c0 >= m) break;
+                __syncthreads();   // the pass's pairs are walked before wave 0 lays out the next one's
             }
-            seq += (uint32_t)m;
         }
     }
     tl_mark(tl, tls, 3);
@@ -1994,8 +2009,8 @@ __device__ __forceinline__ void raster_group(const FrameParams &fp, const FrameB
     }
     if (lane == 0 && ncov) atomicAdd(&sh.cov, ncov);
     if (tl && tid == 0) {
-        tl[TL_STRIDE * tls + 8] = seq;
-        tl[TL_STRIDE * tls + 9] = (uint64_t)pairs;
+        tl[TL_STRIDE * tls + 8] = gs.seq;
+        tl[TL_STRIDE * tls + 9] = (uint64_t)gs.pairs;
         tl[TL_STRIDE * tls + 12] = (uint64_t)__popc(bmask);
     }
 }

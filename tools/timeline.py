@@ -46,7 +46,8 @@ def phases(se, names, label):
 
 def group_tiles(r):
     """Tile groups (slot 12: busy tiles of each raster workgroup's first group; the phase marks are then
-    the group's shared scan and staging and its first busy tile's pairs and shading)."""
+    the group's shared scan and staging, its one pair pass over all its busy tiles, and its first busy
+    tile's shading and stores; slot 9 is the group's pair count)."""
     if r.shape[1] > 12 and (r[:, 12] != 0).any():
         g = r[:, 12][r[:, 12] != 0].astype(np.int64)
         print(f"  raster first group of {len(g)} wgs: busy tiles mean {g.mean():.2f}  " +
@@ -81,7 +82,7 @@ def main():
         busy = r[r[:, 7] != 0]
         if len(busy):
             k = int(np.argmax(r[:, 1].astype(np.int64) - r[:, 0].astype(np.int64)))
-            print(f"  raster first-tile candidates: median {np.median(busy[:, 8]):.0f} max {busy[:, 8].max()} | pair tasks "
+            print(f"  raster first tile / group candidates: median {np.median(busy[:, 8]):.0f} max {busy[:, 8].max()} | pair tasks "
                   f"median {np.median(busy[:, 9]):.0f} max {busy[:, 9].max()} | slowest wg: cand {r[k, 8]} hits {r[k, 9]}")
         for nm, arr in (("setup", s), ("raster", r)):
             dt = arr[:, 1].astype(np.int64) - arr[:, 0].astype(np.int64)

@@ -36,8 +36,12 @@ def main():
         summarize("setup", s, t0)
         summarize("raster", r, t0)
         phases(s, ["draw", "setup_tri", "busy", "bins", "make_rec", "stats"], "setup")
-        phases(r, ["busy_list", "gather", "staged", "rastered", "shaded", "written"], "raster first tile")
+        phases(r, ["busy_list", "gather", "staged", "rastered", "shaded", "written"], "raster first tile / group")
         group_tiles(r)
+        busy = r[r[:, 7] != 0]
+        if len(busy):   # (groups: the candidates and the pairs of the whole group)
+            print(f"  raster first tile / group candidates: median {np.median(busy[:, 8]):.0f} max {busy[:, 8].max()} | pair tasks "
+                  f"median {np.median(busy[:, 9]):.0f} max {busy[:, 9].max()}")
         st = (s[:, 0].astype(np.int64) - t0) / 100.0
         en = (s[:, 1].astype(np.int64) - t0) / 100.0
         for q in (0.25, 0.5, 0.75, 0.9, 1.0):
