@@ -469,6 +469,43 @@ int shs_light_cull(shs_ctx *ctx, const shs_light_cull_desc *desc);
 int shs_resolve_light_lists(shs_ctx *ctx, uint32_t *counts, uint32_t *indices, float *ranges);
 #define SHS_PROGRAM_FORWARD_PLUS 5  /* per-pixel point lights from the tile lists (light_runtime.hpp:321-333) */
 
+/* ---- typed local lights: spot, rect-area and tube-area shading ----------------------------------
+ * LightProperties (lighting/light_runtime.hpp:53-72) with its LightType: what the four
+ * ILightModel::sample functions (:321-333, :376-402, :445-471, :514-534) read.  The packed
+ * shs_culling_light cannot stand in for it (other angle clamps, inflated rect extents, a negated rect
+ * direction).  128 B. */
+#define SHS_LIGHT_POINT 1
+#define SHS_LIGHT_SPOT 2
+#define SHS_LIGHT_RECT_AREA 3
+#define SHS_LIGHT_TUBE_AREA 4
+typedef struct shs_light_props {
+    uint32_t type;                /* SHS_LIGHT_* (LightType 1-4)                                   */
+    uint32_t attenuation_model;   /* LightAttenuationModel: 0 linear, 1 smooth, 2 inverse square   */
+    uint32_t flags;               /* LightFlags* (bit 0 enabled: read by the culling only)         */
+    float range;
+    float position_ws[3], intensity;
+    float color[3], inner_angle_rad;
+    float direction_ws[3], outer_angle_rad;
+    float right_ws[3], tube_half_length;
+    float up_ws[3], tube_radius;
+    float rect_half_extents[2], attenuation_power, attenuation_bias;
+    float attenuation_cutoff, reserved[3];
+} shs_light_props;
+
+/* ILightModel::pack_for_culling of each record's type (light_runtime.hpp:309-314, 357-367, 425-436,
+ * 494-502 through make_*_culling_light, lighting/light_types.hpp:251-435).  Host only, no device.
+ * SHS_ERR_INVALID for a type outside 1-4. */
+int shs_light_pack_culling(const shs_light_props *props, int32_t n_lights, shs_culling_light *out);
+/* Upload the light set for SHS_PROGRAM_FORWARD_PLUS_TYPED: `cull` feeds shs_light_cull as after
+ * shs_lights_upload, `props` the per-pixel shading.  SHS_ERR_INVALID (with a message) for a type outside
+ * 1-4 and for a rect-area light whose up_ws is parallel to its forward direction (the reference's basis
+ * is NaN there). */
+int shs_lights_upload_typed(shs_ctx *ctx, const shs_culling_light *cull, const shs_light_props *props, int32_t n_lights);
+/* As SHS_PROGRAM_FORWARD_PLUS, each listed light through the sample function of its own type
+ * (hello_light_types_culling_sw.cpp:366-418).  Needs shs_lights_upload_typed and a shs_light_cull run
+ * after it; program 5 lights any uploaded set as points. */
+#define SHS_PROGRAM_FORWARD_PLUS_TYPED 6
+
 /* ---- the software library's CPU light binning -----------------------------
  * build_light_bin_culling (shs-renderer-lib/include/shs/lighting/light_culling_runtime.hpp:266-371):
  * cull_lights_tiled / cull_lights_tiled_view_depth_range / cull_lights_clustered
@@ -687,6 +724,7 @@ int shs_group_mesh_upload(shs_group *g, const float *positions, int32_t n_verts,
 int shs_group_mesh_upload_soup(shs_group *g, const float *positions, const float *normals, int32_t n_tris, int32_t *mesh_id);
 int shs_group_texture_upload(shs_group *g, const uint8_t *rgba, int32_t w, int32_t h, int32_t *tex_id);
 int shs_group_lights_upload(shs_group *g, const shs_culling_light *lights, int32_t n_lights);
+int shs_group_lights_upload_typed(shs_group *g, const shs_culling_light *cull, const shs_light_props *props, int32_t n_lights);
 /* shs_set_option on every rank's context (e.g. SHS_OPT_SHARD_LAYOUT). */
 int shs_group_set_option(shs_group *g, int option, int64_t value);
 int shs_group_lib_fuse_tonemap(shs_group *g, const shs_tonemap_desc *desc);

@@ -422,4 +422,38 @@ inline void register_gpu_passes(shs::PassFactoryRegistry &reg, std::shared_ptr<G
 }
 
 }  // namespace shs_gpu_seams
+
+// ---- typed local lights (SHS_PROGRAM_FORWARD_PLUS_TYPED) ------------------------------------------
+#include "shs/lighting/light_runtime.hpp"
+
+namespace shs_gpu_seams {
+
+// LightProperties (lighting/light_runtime.hpp:53-72) of a light of `type` as the record
+// shs_light_pack_culling / shs_lights_upload_typed take (exp-plumbing/hello_light_types_culling_sw.cpp:
+// one per LightInstance, type = light.model->type()).
+inline shs_light_props to_shs_light_props(const shs::LightProperties &p, shs::LightType type) {
+    shs_light_props o{};
+    o.type = static_cast<uint32_t>(type);
+    o.attenuation_model = static_cast<uint32_t>(p.attenuation_model);
+    o.flags = p.flags;
+    o.range = p.range;
+    std::memcpy(o.position_ws, glm::value_ptr(p.position_ws), 12);
+    o.intensity = p.intensity;
+    std::memcpy(o.color, glm::value_ptr(p.color), 12);
+    o.inner_angle_rad = p.inner_angle_rad;
+    std::memcpy(o.direction_ws, glm::value_ptr(p.direction_ws), 12);
+    o.outer_angle_rad = p.outer_angle_rad;
+    std::memcpy(o.right_ws, glm::value_ptr(p.right_ws), 12);
+    o.tube_half_length = p.tube_half_length;
+    std::memcpy(o.up_ws, glm::value_ptr(p.up_ws), 12);
+    o.tube_radius = p.tube_radius;
+    o.rect_half_extents[0] = p.rect_half_extents.x;
+    o.rect_half_extents[1] = p.rect_half_extents.y;
+    o.attenuation_power = p.attenuation_power;
+    o.attenuation_bias = p.attenuation_bias;
+    o.attenuation_cutoff = p.attenuation_cutoff;
+    return o;
+}
+
+}  // namespace shs_gpu_seams
 #endif

@@ -268,6 +268,11 @@ int shs_group_lights_upload(shs_group *g, const shs_culling_light *lights, int32
     return for_ranks(g, [&](int, shs_ctx *c) { return shs_lights_upload(c, lights, n_lights); });
 }
 
+int shs_group_lights_upload_typed(shs_group *g, const shs_culling_light *cull, const shs_light_props *props, int32_t n_lights) {
+    if (!g) return SHS_ERR_INVALID;
+    return for_ranks(g, [&](int, shs_ctx *c) { return shs_lights_upload_typed(c, cull, props, n_lights); });
+}
+
 int shs_group_lib_fuse_tonemap(shs_group *g, const shs_tonemap_desc *desc) {
     if (!g) return SHS_ERR_INVALID;
     return for_ranks(g, [&](int, shs_ctx *c) { return shs_lib_fuse_tonemap(c, desc); });

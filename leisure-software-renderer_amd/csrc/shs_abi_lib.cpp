@@ -516,6 +516,7 @@ int enqueue_pass(shs_ctx *ctx, Work &w, bool shadow) {
         }
         fb.shadow_map = ctx->have_shadow ? ctx->shadow_map.p : nullptr;
         fb.lights = ctx->lights.p;
+        fb.tlights = ctx->lights_typed ? ctx->tlights.p : nullptr;
         fb.tile_counts = ctx->list_counts.p;
         fb.tile_indices = ctx->list_indices.p;
         if (ctx->want_timeline && !ctx->timeline_shadow) {
@@ -564,8 +565,10 @@ int enqueue_pass(shs_ctx *ctx, Work &w, bool shadow) {
         for (const auto &d : w.last_draws)
             if (d.program != prog) prog = -1;
         if (prog != 5 && prog != 0) prog = -1;
+        for (const auto &d : w.last_draws)   // any typed Forward+ draw: the kernel with the light models
+            if (d.program == SHS_PROGRAM_FORWARD_PLUS_TYPED) prog = SHS_PROGRAM_FORWARD_PLUS_TYPED;
         const bool wide = fp.count <= 1;   // the whole frame's build (PBR: 5 waves) or a sharded rank's
-        int &res = ctx->lib_resolve_resident[(prog == 5 ? 0 : prog == 0 ? 1 : 2) * 2 + wide];
+        int &res = ctx->lib_resolve_resident[(prog == 5 ? 0 : prog == 0 ? 1 : prog == 6 ? 3 : 2) * 2 + wide];
         if (res <= 0) res = shs_internal::lib_resolve_resident_blocks(ctx->device, prog, wide);
         const int rgrid = std::max(1, std::min(fp.n_owned_rt, res));
         HIP_TRY(ctx, shs_internal::launch_lib_resolve(fp, fb, prog, wide, rgrid, ctx->stream));
@@ -678,7 +681,7 @@ void shs_lib_release(shs_ctx *ctx) {
     ctx->textures.clear();
     release(ctx->srgb_lut);
     release(ctx->lib_hdr); release(ctx->lib_keys); release(ctx->lib_blkcov); ctx->blkcov_zero_at = nullptr; release(ctx->tm_thr_dev); ctx->tm_thr_dev_gamma = -1.0f; release(ctx->lib_depth); release(ctx->lib_motion); release(ctx->shadow_map);
-    release(ctx->lights); release(ctx->depth_ranges);
+    release(ctx->lights); release(ctx->tlights); release(ctx->depth_ranges);
     release(ctx->list_counts); release(ctx->list_indices); release(ctx->lib_timeline); release(ctx->lib_stimeline);
     release(ctx->lib_ldr); release(ctx->lib_present); release(ctx->lib_mb); release(ctx->lib_mb_present);
     release(ctx->lb_lights); release(ctx->lb_ndc); release(ctx->lb_counts); release(ctx->lb_indices);
@@ -1086,10 +1089,14 @@ int shs_render_pbr_forward(shs_ctx *ctx, const shs_lib_frame *frame, const shs_l
     if (f.shard_count <= 0 || f.shard_rank < 0 || f.shard_rank >= f.shard_count) { ctx->err = "bad shard"; return SHS_ERR_INVALID; }
     for (int i = 0; i < n_draws; ++i) {
         if (check_lib_mesh(ctx, draws[i].mesh_id)) return SHS_ERR_INVALID;
-        if (draws[i].program < SHS_PROGRAM_PBR_MR || draws[i].program > SHS_PROGRAM_FORWARD_PLUS) { ctx->err = "bad program"; return SHS_ERR_INVALID; }
-        if (draws[i].program == SHS_PROGRAM_FORWARD_PLUS &&
+        if (draws[i].program < SHS_PROGRAM_PBR_MR || draws[i].program > SHS_PROGRAM_FORWARD_PLUS_TYPED) { ctx->err = "bad program"; return SHS_ERR_INVALID; }
+        if ((draws[i].program == SHS_PROGRAM_FORWARD_PLUS || draws[i].program == SHS_PROGRAM_FORWARD_PLUS_TYPED) &&
             (!ctx->have_cull || ctx->cull.W != f.width || ctx->cull.H != f.height)) {
             ctx->err = "Forward+ draw needs shs_light_cull for this frame size";
+            return SHS_ERR_INVALID;
+        }
+        if (draws[i].program == SHS_PROGRAM_FORWARD_PLUS_TYPED && !(ctx->lights_typed && ctx->cull_typed)) {
+            ctx->err = "typed Forward+ draw needs shs_lights_upload_typed and a shs_light_cull after it";
             return SHS_ERR_INVALID;
         }
         if (draws[i].cull_mode < SHS_CULL_NONE || draws[i].cull_mode > SHS_CULL_FRONT) { ctx->err = "bad cull mode"; return SHS_ERR_INVALID; }
@@ -1371,6 +1378,7 @@ int shs_lights_upload(shs_ctx *ctx, const shs_culling_light *lights, int32_t n) 
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // the previous set may still be read
     if (n > 0) HIP_TRY(ctx, hipMemcpy(ctx->lights.p, lights, (size_t)n * sizeof(shs_dev::CullLight), hipMemcpyHostToDevice));
     ctx->n_lights = n;
+    ctx->lights_typed = ctx->cull_typed = false;   // (shs_lights_upload_typed sets the first after this call)
     return SHS_OK;
 }
 
@@ -1453,6 +1461,7 @@ int shs_light_cull(shs_ctx *ctx, const shs_light_cull_desc *d) {
                                                  ctx->list_counts.p, ctx->list_indices.p, ctx->stream));
     ctx->cull = p;
     ctx->have_cull = true;
+    ctx->cull_typed = ctx->lights_typed;
     return SHS_OK;
 }
 

@@ -271,8 +271,8 @@ struct shs_ctx {
     const uint32_t *blkcov_zero_at = nullptr;
     size_t blkcov_zero_cap = 0;
     uint64_t blkcov_zero_key = 0;
-    int lib_resolve_resident[6] = {};   // resident k_lib_resolve workgroups ((Forward+, PBR, mixed) x (sharded
-                                        // rank's build, whole frame's build))
+    int lib_resolve_resident[8] = {};   // resident k_lib_resolve workgroups ((Forward+, PBR, mixed, typed) x
+                                        // (sharded rank's build, whole frame's build))
     DevBuf<float> srgb_lut;               // srgb_to_linear_rgb table (texture sampling)
     DevBuf<float> lib_depth;
     DevBuf<float2> lib_motion;
@@ -285,6 +285,9 @@ struct shs_ctx {
     // Forward+ light lists (shs_light.hip)
     DevBuf<shs_dev::CullLight> lights;
     int32_t n_lights = 0;
+    DevBuf<shs_dev::TLight> tlights;      // shs_lights_upload_typed: the set's shading records
+    bool lights_typed = false;            // the current set has them ...
+    bool cull_typed = false;              // ... and the last shs_light_cull ran over that set
     DevBuf<float2> depth_ranges;
     DevBuf<uint32_t> list_counts, list_indices;
     shs_dev::LightCullParams cull{};

@@ -1438,6 +1438,9 @@ struct PLight {
 };
 constexpr int LIB_LDS_LIGHTS = 256;                  // lights staged in LDS by the camera pass
 __shared__ float4 lib_lds_lights[LIB_LDS_LIGHTS * 4];  // per light: pr, ci, sa, (model bits, 0, 0, 0)
+// typed Forward+ kernel only: per light its bounding sphere (cull_wave_list); the shading records
+// themselves (128 B) are not staged -- uniform lists read them with scalar loads, the rest from global memory
+__shared__ float4 lib_lds_bounds[LIB_LDS_LIGHTS];
 
 __device__ __forceinline__ PLight plight_global(const CullLight &L) {
     PLight p;
@@ -1471,25 +1474,29 @@ __device__ __forceinline__ PLight plight_lds(uint32_t i) {
     return p;
 }
 
-// eval_distance_attenuation (lighting/light_runtime.hpp:182-210) on a CullingLightGPU
-__device__ __forceinline__ float distance_attenuation(const PLight &L, float distance) {
-    const float range = s_max(L.pr.w, 0.001f);
+// eval_distance_attenuation (lighting/light_runtime.hpp:182-210)
+__device__ __forceinline__ float distance_attenuation(float prange, uint32_t model, float power, float bias, float cutoff,
+                                                      float distance) {
+    const float range = s_max(prange, 0.001f);
     if (distance >= range) return 0.0f;
     const float norm = s_clamp(1.0f - distance / range, 0.0f, 1.0f);
     float falloff = 0.0f;
-    const uint32_t model = L.model;
     if (model == 0u) {
         falloff = norm;
     } else if (model == 1u) {
         falloff = (norm * norm) * (3.0f - 2.0f * norm);
     } else if (model == 2u) {
-        const float inv = 1.0f / s_max(distance * distance, L.sa.z);
+        const float inv = 1.0f / s_max(distance * distance, bias);
         falloff = s_min(1.0f, inv * (range * range)) * (norm * norm);
     }
-    const float fpow = s_max(L.sa.y, 0.001f);
+    const float fpow = s_max(power, 0.001f);
     falloff = fpow == 1.0f ? s_max(falloff, 0.0f) : powf(s_max(falloff, 0.0f), fpow);   // pow(x, 1) == x exactly
-    if (L.sa.w > 0.0f && falloff < L.sa.w) return 0.0f;
+    if (cutoff > 0.0f && falloff < cutoff) return 0.0f;
     return s_max(falloff, 0.0f);
+}
+// ... on a CullingLightGPU
+__device__ __forceinline__ float distance_attenuation(const PLight &L, float distance) {
+    return distance_attenuation(L.pr.w, L.model, L.sa.y, L.sa.z, L.sa.w, distance);
 }
 
 // PointLightModel::sample + eval_local_light_brdf (light_runtime.hpp:212-237, 321-333), accumulated
@@ -1516,6 +1523,86 @@ __device__ __forceinline__ void point_light(const PLight &L, f3 world, f3 N, f3 
     // pow(x, 36) by squaring (x^32 * x^4, <= 6 ulp): well inside the shaded-float tolerance
     const float x1 = s_max(dot3(N, h), 0.0f), x2 = x1 * x1, x4 = x2 * x2, x8 = x4 * x4, x16 = x8 * x8, x32 = x16 * x16;
     const float spec = 0.30f * (x32 * x4);
+    lit = add3(lit, add3(mul3(base, sc3(rad, ndotl)), sc3(rad, spec)));
+}
+
+// A typed light's shading record (TLight), a float4 at a time -- a light model reads only the quads of
+// its own type: from global memory, or, at a wave-uniform index, through the constant address space
+// (scalar loads, as plight_uniform; the type branch is then scalar too).
+struct TLoadGlobal {
+    const TLight *p;
+    __device__ __forceinline__ float4 operator()(int k) const { return reinterpret_cast<const float4 *>(p)[k]; }
+};
+struct TLoadUniform {
+    ConstF *p;
+    __device__ __forceinline__ float4 operator()(int k) const { return make_float4(p[4 * k], p[4 * k + 1], p[4 * k + 2], p[4 * k + 3]); }
+};
+
+// ILightModel::sample of the light's type (light_runtime.hpp: Point :321-333, Spot :376-402, RectArea
+// :445-471, TubeArea :514-534): each model yields (to_light, shaping, specular power and scale) and
+// falls into the one eval_local_light_brdf / eval_distance_attenuation tail (:182-237), accumulated as
+// point_light does.  The pixel-independent values come from the record (computed on the host with
+// the reference's expressions).  Only Point and Spot emit from position_ws, so only they take
+// point_light's early exit on the squared distance; for the area lights the range applies to the
+// distance from the clamped emitter point.
+template <class LD>
+__device__ __forceinline__ void typed_light(const LD &ld, f3 world, f3 N, f3 V, f3 base, f3 &lit) {
+    const float4 pr = ld(0), sh = ld(3);
+    const uint32_t type = __float_as_uint(sh.x);
+    const f3 pos = {pr.x, pr.y, pr.z};
+    f3 tl, fwd = {0.0f, 0.0f, 0.0f};
+    if (type == 3u) {   // clamped projection onto the emitter rectangle
+        const float4 f4v = ld(4), r4 = ld(5), u4 = ld(6);
+        const f3 right = {r4.x, r4.y, r4.z}, up = {u4.x, u4.y, u4.z};
+        fwd = f3{f4v.x, f4v.y, f4v.z};
+        const f3 d = sub3(world, pos);
+        const float ux = s_clamp(dot3(d, right), -f4v.w, f4v.w);
+        const float uy = s_clamp(dot3(d, up), -r4.w, r4.w);
+        tl = sub3(add3(add3(pos, sc3(right, ux)), sc3(up, uy)), world);
+    } else if (type == 4u) {   // closest_point_on_segment (:254-261)
+        const float4 a4 = ld(4), ab4 = ld(5);
+        const f3 a = {a4.x, a4.y, a4.z}, ab = {ab4.x, ab4.y, ab4.z};
+        f3 emit = a;
+        if (!(a4.w <= 1e-8f)) emit = add3(a, sc3(ab, s_clamp(dot3(sub3(world, a), ab) / a4.w, 0.0f, 1.0f)));
+        tl = sub3(emit, world);
+    } else {
+        tl = sub3(pos, world);
+        if (dot3(tl, tl) > (pr.w * pr.w) * (1.0f + 0x1p-20f)) return;   // as point_light
+    }
+    const float dist = sqrtf(dot3(tl, tl));
+    if (dist <= 1e-4f || dist > pr.w) return;
+    const f3 Ld = {tl.x / dist, tl.y / dist, tl.z / dist};
+    float shaping = 1.0f;
+    if (type == 2u) {   // smoothstep of the cone term
+        const float4 d4 = ld(4);
+        const float cos_theta = dot3(neg3(Ld), f3{d4.x, d4.y, d4.z});
+        if (cos_theta <= sh.z) return;
+        const float t = s_clamp((cos_theta - sh.z) / sh.w, 0.0f, 1.0f);
+        shaping = (t * t) * (3.0f - 2.0f * t);
+    } else if (type == 3u) {
+        const float facing = s_max(dot3(fwd, neg3(Ld)), 0.0f);
+        if (facing <= 0.0f) return;
+        shaping = 0.65f + 0.55f * facing;
+    } else if (type == 4u) {
+        shaping = 0.75f + 0.35f * s_clamp(1.0f - dist / s_max(pr.w, 0.1f), 0.0f, 1.0f);
+    }
+    const float ndotl = s_max(dot3(N, Ld), 0.0f);
+    if (ndotl <= 0.0f) return;
+    const float4 at = ld(2);
+    const float att = distance_attenuation(pr.w, __float_as_uint(at.w), at.x, at.y, at.z, dist) * s_max(shaping, 0.0f);
+    if (att <= 0.0f) return;
+    const float4 ci4 = ld(1);
+    const float ci = s_max(ci4.w, 0.0f);
+    const f3 rad = {(s_max(ci4.x, 0.0f) * ci) * att, (s_max(ci4.y, 0.0f) * ci) * att, (s_max(ci4.z, 0.0f) * ci) * att};
+    f3 h = add3(Ld, V);
+    const float len2 = dot3(h, h);
+    h = len2 <= 1e-10f ? Ld : sc3(h, 1.0f / sqrtf(len2));
+    // the integer specular powers by squaring, as point_light's: 36 = 32 + 4, 34 = 32 + 2, 26 = 16 + 8 + 2,
+    // 22 = 16 + 4 + 2 -- at most 35 roundings of 2^-24 each (< 18 ulp, 2.1e-6 relative) on a term of
+    // at most 0.32 x radiance: well inside the shaded-float tolerance
+    const float x1 = s_max(dot3(N, h), 0.0f), x2 = x1 * x1, x4 = x2 * x2, x8 = x4 * x4, x16 = x8 * x8, x32 = x16 * x16;
+    const float spec = type == 1u ? 0.30f * (x32 * x4) : type == 2u ? 0.32f * (x32 * x2)
+                     : type == 3u ? 0.26f * ((x16 * x8) * x2) : 0.20f * ((x16 * x4) * x2);
     lit = add3(lit, add3(mul3(base, sc3(rad, ndotl)), sc3(rad, spec)));
 }
 
@@ -1549,6 +1636,18 @@ __device__ __forceinline__ float ord2f(uint32_t o) { return __uint_as_float((o &
 // range^2 * (1 + 2^-10): a culled light is out of every lane's range with a wide margin, so the
 // survivors in list order give bit-identical sums.  Lanes with a non-finite world position keep the
 // whole list (their sums depend on every light).  Returns the culled count; ids -> lw.fids.
+// TYPED (typed_light): the sphere is the record's bounding sphere (position_ws, shape[1]), staged in
+// lib_lds_bounds.  Point and Spot emit from position_ws, and typed_light's tests are point_light's, so
+// the argument above holds with radius = range.  A Rect or Tube light emits from a point e of its
+// rectangle or segment: |e - position_ws| <= extent (1 + 2^-21), extent = |clamped half extents| or the
+// clamped half length (right, up and the tube axis are unit vectors to 2^-22, right and up orthogonal
+// to the same order), and the float e differs from it by a few roundings of coordinates no larger than
+// |position_ws| + extent.  typed_light returns before touching `lit` when sqrt(float |e - world|^2) >
+// range, and that float distance is at least (|position_ws - world| - extent)(1 - 2^-21) minus those
+// roundings; the host's radius, (extent + range)(1 + 2^-10) + 2^-18 (|position_ws|_1 + extent) rounded up,
+// exceeds extent + range by far more than both.  So a culled light of any type is out of every lane's
+// range and contributes exactly nothing; survivors stay in list order.
+template <bool TYPED = false>
 __device__ __forceinline__ uint32_t cull_wave_list(const LibFrameParams &fp, const LibBuffers &fb, const LtWave &lw, f3 world,
                                                    bool lds) {
     const uint64_t ex = __ballot(1);
@@ -1580,7 +1679,7 @@ __device__ __forceinline__ uint32_t cull_wave_list(const LibFrameParams &fp, con
         if (i < lw.count) {
             idx = lw.ids[i];
             if (idx < fp.n_lights) {
-                const float4 pr = lib_lds_lights[4 * idx];
+                const float4 pr = TYPED ? lib_lds_bounds[idx] : lib_lds_lights[4 * idx];
                 // (fmaxf, not s_max: ROCm 7.2's instruction selection crashes on the select form here;
                 // a NaN difference gives gap 0 -- kept -- and an infinite light position an infinite gap,
                 // which point_light's d2 test rejects as well)
@@ -1610,7 +1709,9 @@ __device__ __forceinline__ uint32_t lt_tile_list(const LibFrameParams &fp, int p
 // Forward+ program: the pixel's light list (fp_stress_scene.frag:644-685 selection: a saturated list
 // falls back to every light) through PointLightModel::sample, combined as the software light-culling
 // demo does (hello_light_types_culling_sw.cpp:404-416): ambient hemisphere + sum, clamped to [0,1].
-template <bool CULL>
+// TYPED (SHS_PROGRAM_FORWARD_PLUS_TYPED): the same selection and combination, each light through the
+// sample function of its own type (typed_light over fb.tlights, :366-418 of the demo).
+template <bool CULL, bool TYPED = false>
 __device__ f3 forward_plus(const LibFrameParams &fp, const LibBuffers &fb, const LibDrawGPU &dr, f3 world, f3 nrm, int px, int py,
                            const LtWave &lw) {
     const f3 N = normalize3(nrm);
@@ -1636,18 +1737,22 @@ __device__ f3 forward_plus(const LibFrameParams &fp, const LibBuffers &fb, const
     const bool uni = lw.list != 0xffffffffu;   // wave-uniform: every lane's list is lw.list
     const uint32_t count = uni ? lw.count : fp.lt_mode == 0u ? maxp : min(fb.tile_counts[list], maxp);
     if (count >= maxp) {
-        for (uint32_t i = 0; i < fp.n_lights; ++i)
-            point_light(lds ? plight_lds(i) : plight_global(fb.lights[i]), world, N, V, base, lit);
+        for (uint32_t i = 0; i < fp.n_lights; ++i) {
+            if (TYPED) typed_light(TLoadGlobal{fb.tlights + i}, world, N, V, base, lit);
+            else point_light(lds ? plight_lds(i) : plight_global(fb.lights[i]), world, N, V, base, lit);
+        }
     } else if (uni) {   // the list in the wave's LDS slice: one broadcast index per light
         const uint32_t *ids = lw.ids;
         uint32_t n = count;
         if (CULL && lw.fids) {   // culled by the wave's world box (exact: cull_wave_list)
-            const uint32_t nc = (uint32_t)__builtin_amdgcn_readfirstlane((int)cull_wave_list(fp, fb, lw, world, lds));
+            const uint32_t nc = (uint32_t)__builtin_amdgcn_readfirstlane((int)cull_wave_list<TYPED>(fp, fb, lw, world, lds));
             if (nc != 0xffffffffu) { ids = lw.fids; n = nc; }
         }
         for (uint32_t i = 0; i < n; ++i) {   // C4 0.828 -> 0.815 ms against LDS-staged lights
             const uint32_t idx = (uint32_t)__builtin_amdgcn_readfirstlane((int)ids[i]);   // uniform
-            if (idx < fp.n_lights) point_light(plight_uniform(fb.lights, idx), world, N, V, base, lit);
+            if (idx >= fp.n_lights) continue;
+            if (TYPED) typed_light(TLoadUniform{(ConstF *)(fb.tlights + idx)}, world, N, V, base, lit);
+            else point_light(plight_uniform(fb.lights, idx), world, N, V, base, lit);
         }
     } else {
         // the next index is loaded while the current light is evaluated
@@ -1656,7 +1761,9 @@ __device__ f3 forward_plus(const LibFrameParams &fp, const LibBuffers &fb, const
         for (uint32_t i = 0; i < count; ++i) {
             const uint32_t idx = next;
             if (i + 1 < count) next = ids[i + 1];
-            if (idx < fp.n_lights) point_light(lds ? plight_lds(idx) : plight_global(fb.lights[idx]), world, N, V, base, lit);
+            if (idx >= fp.n_lights) continue;
+            if (TYPED) typed_light(TLoadGlobal{fb.tlights + idx}, world, N, V, base, lit);
+            else point_light(lds ? plight_lds(idx) : plight_global(fb.lights[idx]), world, N, V, base, lit);
         }
     }
     return f3{g_clamp(lit.x, 0.0f, 1.0f), g_clamp(lit.y, 0.0f, 1.0f), g_clamp(lit.z, 0.0f, 1.0f)};
@@ -1690,12 +1797,13 @@ __device__ __noinline__ f3 sample_base_color(const LibBuffers &fb, const LibDraw
 // The builtin fragment programs (builtin_shaders.hpp:105-245); tex = the base_color_tex sample
 // (vec3(1) without a texture, :35).
 // PROG >= 0: every draw of the pass runs that program (k_lib_resolve specialisations: only its
-// registers are live); -1: per draw.
+// registers are live); -1: per draw; 6: per draw, the typed Forward+ program included.
 template <int PROG>
 __device__ f3 lib_fragment(const LibFrameParams &fp, const LibBuffers &fb, const LibDrawGPU &dr, f3 world, f3 nrm, float depth01,
                            int px, int py, const LtWave &st, f3 tex = f3{1.0f, 1.0f, 1.0f}) {
     const f3 bc = {dr.base[0], dr.base[1], dr.base[2]};
-    const int program = PROG >= 0 ? PROG : dr.program;
+    const int program = (PROG >= 0 && PROG != 6) ? PROG : dr.program;
+    if (PROG == 6 && program == 6) return forward_plus<true, true>(fp, fb, dr, world, nrm, px, py, st);
     if (program == 5) return forward_plus<true>(fp, fb, dr, world, nrm, px, py, st);
     if (program == 2) return bc;                                                   // debug albedo
     if (program == 3) return add3(sc3(normalize3(nrm), 0.5f), f3{0.5f, 0.5f, 0.5f});  // debug normal
@@ -2800,6 +2908,9 @@ void k_lib_raster(LibFrameParams fp, LibBuffers fb) {
 #ifndef SHS_RESOLVE_WAVES_PBR_SHARD
 #define SHS_RESOLVE_WAVES_PBR_SHARD 3
 #endif
+#ifndef SHS_RESOLVE_WAVES_TYPED
+#define SHS_RESOLVE_WAVES_TYPED 3
+#endif
 // Minimum waves per SIMD: 4 for the Forward+ kernel (no spills; 5 measured +2.3 % per C4 frame), 3 for
 // the mixed one, and for the PBR one two builds: WIDE at 5 waves (96 VGPRs with 24 spilled) for a whole
 // frame's pass -- C5 0.350 -> 0.341 ms per frame in three A/B pairs -- and 3 waves (no spills) for a
@@ -2808,7 +2919,8 @@ void k_lib_raster(LibFrameParams fp, LibBuffers fb) {
 // timing experiments; the Forward+ kernel has one build unless _FP_SHARD differs.)
 template <int PROG, bool WIDE = false>
 __global__ __launch_bounds__(256, PROG == 5 ? (WIDE ? SHS_RESOLVE_WAVES_FP : SHS_RESOLVE_WAVES_FP_SHARD)
-                                  : PROG == 0 ? (WIDE ? SHS_RESOLVE_WAVES_PBR : SHS_RESOLVE_WAVES_PBR_SHARD) : 3)
+                                  : PROG == 0 ? (WIDE ? SHS_RESOLVE_WAVES_PBR : SHS_RESOLVE_WAVES_PBR_SHARD)
+                                  : PROG == 6 ? SHS_RESOLVE_WAVES_TYPED : 3)
 void k_lib_resolve(LibFrameParams fp, LibBuffers fb) {
     __shared__ float tm_thr[256];
     __shared__ uint32_t wlist[PROG == 0 ? 1 : 4][128];   // per wave: its block's light list (LtWave)
@@ -2826,6 +2938,11 @@ void k_lib_resolve(LibFrameParams fp, LibBuffers fb) {
             lib_lds_lights[4 * i + 2] = p.sa;
             lib_lds_lights[4 * i + 3] = make_float4(__uint_as_float(p.model), 0.0f, 0.0f, 0.0f);
         }
+    }
+    if (PROG == 6 && fb.tlights && fp.n_lights <= LIB_LDS_LIGHTS) {   // typed lights: their bounding spheres
+        for (int i = tid; i < (int)fp.n_lights; i += 256)
+            lib_lds_bounds[i] = make_float4(fb.tlights[i].pos_range[0], fb.tlights[i].pos_range[1], fb.tlights[i].pos_range[2],
+                                            fb.tlights[i].shape[1]);
     }
     __syncthreads();
     // tiled Forward+ lists can be wave-uniform (LtWave); clustered ones depend on the pixel's depth
@@ -2939,14 +3056,16 @@ int lib_raster_resident_blocks(int device, bool shadow, bool shallow) {
     return cus * per_cu;
 }
 
-// k_lib_resolve per program class: 5 (Forward+ only), 0 (PBR metallic-roughness only), -1 (any mix)
+// k_lib_resolve per program class: 5 (Forward+ only), 0 (PBR metallic-roughness only), -1 (any mix of
+// programs 0-5), 6 (any mix with a typed Forward+ draw)
 #if SHS_RESOLVE_WAVES_FP_SHARD != SHS_RESOLVE_WAVES_FP
 #define SHS_RESOLVE_FP(wide) ((wide) ? k_lib_resolve<5, true> : k_lib_resolve<5>)
 #else
 #define SHS_RESOLVE_FP(wide) k_lib_resolve<5, true>
 #endif
 #define SHS_RESOLVE_KERNEL(prog, wide) \
-    (prog == 5 ? SHS_RESOLVE_FP(wide) : prog == 0 ? ((wide) ? k_lib_resolve<0, true> : k_lib_resolve<0>) : k_lib_resolve<-1>)
+    (prog == 5 ? SHS_RESOLVE_FP(wide) : prog == 0 ? ((wide) ? k_lib_resolve<0, true> : k_lib_resolve<0>) \
+     : prog == 6 ? k_lib_resolve<6> : k_lib_resolve<-1>)
 
 int lib_resolve_resident_blocks(int device, int prog, bool wide) {
     int cus = 0, per_cu = 0;

@@ -75,6 +75,24 @@ struct alignas(16) CullLight {
 };
 static_assert(sizeof(CullLight) == 160, "CullingLightGPU is 160 B");
 
+// Shading record of one typed light (SHS_PROGRAM_FORWARD_PLUS_TYPED), 128 B: the LightProperties fields
+// ILightModel::sample reads (lighting/light_runtime.hpp:53-72), unclamped as it reads them, and the
+// pixel-independent values the reference recomputes in every sample call, derived once on the host
+// with its expressions (shs_abi_light_types.cpp).  Eight float4 so that a wave-uniform light is read
+// with scalar loads, a quad at a time, and only the quads its type needs.
+struct alignas(16) TLight {
+    float pos_range[4];      // position_ws, range
+    float color_int[4];      // color, intensity
+    float atten[4];          // attenuation_power, _bias, _cutoff, attenuation_model (bits)
+    float shape[4];          // type (bits), bounding radius (cull_wave_list), spot cos_outer,
+                             //   spot max(cos_inner - cos_outer, 1e-5f)
+    float v0[4];             // spot safe_forward | rect fwd, half_ext.x | tube a, dot(ab, ab)
+    float v1[4];             // rect right, half_ext.y | tube ab
+    float v2[4];             // rect up
+    float pad[4];
+};
+static_assert(sizeof(TLight) == 128, "TLight is 8 float4");
+
 // The light-list binning's view of the frame (CameraUBO fields of fp_stress_light_cull.comp).
 struct LightCullParams {
     int32_t W, H;
@@ -194,6 +212,7 @@ struct LibBuffers {
                                      // bounded) of its chunk bounds, mapped host memory (the region balancer's input)
     uint32_t *hsq;                   // camera pass with fp.hsort: the bin tiles k_lib_hsort sorts (k_lib_dyn)
     uint2 *hsr;                      // ... per bin tile: the depth-bound range (lo, hi) its list was bucketed over
+    const TLight *tlights;           // typed Forward+ program: per light of `lights` its shading record, or null
 };
 
 // k_lib_hsort: one 512-thread workgroup per listed bin tile, LIB_HSORT_PER entries per thread in registers (a

@@ -780,6 +780,22 @@ class Context:
         self._check(self._lib.shs_lights_upload(self._h, arr.ctypes.data_as(ctypes.POINTER(CullingLightC)), arr.shape[0]))
         self._n_lights = arr.shape[0]
 
+    def upload_lights_typed(self, props):
+        """props: numpy LIGHT_PROPS_DTYPE array (shs_light_props).  Packs the culling records
+        (shs_light_pack_culling), uploads both (shs_lights_upload_typed: PROGRAM_FORWARD_PLUS_TYPED shades
+        each light with the model of its type) and returns the culling records (LIGHT_DTYPE)."""
+        from ._abi import CullingLightC, LightPropsC
+        from .lib_path import LIGHT_PROPS_DTYPE, pack_culling
+        arr = np.ascontiguousarray(props, dtype=LIGHT_PROPS_DTYPE)
+        try:
+            cull = pack_culling(arr)
+        except ValueError as e:   # a type outside 1-4: what shs_lights_upload_typed itself answers
+            raise ShsError(_abi.SHS_ERR_INVALID, str(e)) from None
+        self._check(self._lib.shs_lights_upload_typed(self._h, cull.ctypes.data_as(ctypes.POINTER(CullingLightC)),
+                                                      arr.ctypes.data_as(ctypes.POINTER(LightPropsC)), arr.shape[0]))
+        self._n_lights = arr.shape[0]
+        return cull
+
     def light_cull(self, cull):
         """fp_stress_light_cull.comp (+ depth reduce for mode 2) into the context's tile lists."""
         self._cull = cull

@@ -198,6 +198,24 @@ class CullingLightC(ctypes.Structure):
                 ("cull_sphere", _F4), ("cull_aabb_min", _F4), ("cull_aabb_max", _F4)]
 
 
+PROGRAM_FORWARD_PLUS_TYPED = 6
+LIGHT_POINT, LIGHT_SPOT, LIGHT_RECT_AREA, LIGHT_TUBE_AREA = 1, 2, 3, 4
+
+
+class LightPropsC(ctypes.Structure):
+    """shs_light_props: LightProperties (lighting/light_runtime.hpp:53-72) + its LightType, 128 B."""
+    _fields_ = [("type", ctypes.c_uint32), ("attenuation_model", ctypes.c_uint32), ("flags", ctypes.c_uint32),
+                ("range", ctypes.c_float),
+                ("position_ws", _F3), ("intensity", ctypes.c_float),
+                ("color", _F3), ("inner_angle_rad", ctypes.c_float),
+                ("direction_ws", _F3), ("outer_angle_rad", ctypes.c_float),
+                ("right_ws", _F3), ("tube_half_length", ctypes.c_float),
+                ("up_ws", _F3), ("tube_radius", ctypes.c_float),
+                ("rect_half_extents", ctypes.c_float * 2), ("attenuation_power", ctypes.c_float),
+                ("attenuation_bias", ctypes.c_float),
+                ("attenuation_cutoff", ctypes.c_float), ("reserved", _F3)]
+
+
 class LightCullDescC(ctypes.Structure):
     _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("tile_size", ctypes.c_uint32),
                 ("max_per_tile", ctypes.c_uint32), ("mode", ctypes.c_uint32), ("z_slices", ctypes.c_uint32),
@@ -296,6 +314,8 @@ SIGNATURES = [
     ("shs_tiles_unpack", ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int32, ctypes.c_int32, _P]),
     ("shs_tiles_unpack_ranks", ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p)]),
     ("shs_lights_upload", ctypes.c_int, [_P, ctypes.POINTER(CullingLightC), ctypes.c_int32]),
+    ("shs_light_pack_culling", ctypes.c_int, [ctypes.POINTER(LightPropsC), ctypes.c_int32, ctypes.POINTER(CullingLightC)]),
+    ("shs_lights_upload_typed", ctypes.c_int, [_P, ctypes.POINTER(CullingLightC), ctypes.POINTER(LightPropsC), ctypes.c_int32]),
     ("shs_light_cull", ctypes.c_int, [_P, ctypes.POINTER(LightCullDescC)]),
     ("shs_light_bin_culling", ctypes.c_int, [_P, ctypes.POINTER(LightBinDescC), _P, ctypes.c_int32, _P, _P, _P]),
     ("shs_resolve_light_lists", ctypes.c_int, [_P, _P, _P, _P]),
@@ -314,6 +334,8 @@ SIGNATURES = [
     ("shs_group_mesh_upload_soup", ctypes.c_int, [_P, _F, _F, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)]),
     ("shs_group_texture_upload", ctypes.c_int, [_P, _P, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)]),
     ("shs_group_lights_upload", ctypes.c_int, [_P, ctypes.POINTER(CullingLightC), ctypes.c_int32]),
+    ("shs_group_lights_upload_typed", ctypes.c_int, [_P, ctypes.POINTER(CullingLightC), ctypes.POINTER(LightPropsC),
+                                                     ctypes.c_int32]),
     ("shs_group_set_option", ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int64]),
     ("shs_group_lib_fuse_tonemap", ctypes.c_int, [_P, ctypes.POINTER(TonemapDescC)]),
     ("shs_group_light_cull", ctypes.c_int, [_P, ctypes.POINTER(LightCullDescC)]),

@@ -119,6 +119,19 @@ class Group:
         self._check(self._lib.shs_group_lights_upload(self._h, arr.ctypes.data_as(ctypes.POINTER(_abi.CullingLightC)),
                                                       arr.shape[0]))
 
+    def upload_lights_typed(self, props):
+        """Context.upload_lights_typed on every rank (shs_group_lights_upload_typed) -> the culling records."""
+        from .lib_path import LIGHT_PROPS_DTYPE, pack_culling
+        arr = np.ascontiguousarray(props, dtype=LIGHT_PROPS_DTYPE)
+        try:
+            cull = pack_culling(arr)
+        except ValueError as e:   # a type outside 1-4: what shs_lights_upload_typed itself answers
+            raise ShsError(_abi.SHS_ERR_INVALID, str(e)) from None
+        self._check(self._lib.shs_group_lights_upload_typed(self._h, cull.ctypes.data_as(ctypes.POINTER(_abi.CullingLightC)),
+                                                            arr.ctypes.data_as(ctypes.POINTER(_abi.LightPropsC)),
+                                                            arr.shape[0]))
+        return cull
+
     def fuse_tonemap(self, exposure=1.0, gamma=2.2, ldr=True, present=True):
         d = _abi.TonemapDescC()
         d.exposure, d.gamma = float(exposure), float(gamma)

@@ -14,7 +14,7 @@ import numpy as np
 from . import _abi
 from ._abi import (CULL_BACK, CULL_FRONT, CULL_NONE, LIB_BG_GRADIENT, LIB_DEPTH_MOTION, LIGHT_CULL_CLUSTERED,
                    LIGHT_CULL_NONE, LIGHT_CULL_TILED, LIGHT_CULL_TILED_DEPTH, PROGRAM_BLINN_PHONG, PROGRAM_DEBUG_ALBEDO,
-                   PROGRAM_DEBUG_DEPTH, PROGRAM_DEBUG_NORMAL, PROGRAM_FORWARD_PLUS, PROGRAM_PBR_MR)
+                   PROGRAM_DEBUG_DEPTH, PROGRAM_DEBUG_NORMAL, PROGRAM_FORWARD_PLUS, PROGRAM_FORWARD_PLUS_TYPED, PROGRAM_PBR_MR)
 
 __all__ = [
     "LibMesh", "LibDraw", "Texture2D", "LibFrame", "ShadowCaster", "PROGRAM_PBR_MR", "PROGRAM_BLINN_PHONG", "PROGRAM_DEBUG_ALBEDO",
@@ -135,7 +135,7 @@ def make_point_lights(pos, rng_range, color, intensity, attenuation_model=ATTEN_
     out["axis_spot_outer"] = (1.0, 0.0, 0.0, 0.0)
     out["up_shape_x"] = (0.0, 1.0, 0.0, 0.0)
     out["shape_attenuation"] = (0.0, max(power, 0.001), max(bias, 1e-5), max(cutoff, 0.0))
-    out["type_shape_flags"] = (1, 0, flags, attenuation_model)     # Point, Sphere
+    out["type_shape_flags"] = (1, 1, flags, attenuation_model)     # LightType::Point, LightCullingShape::Sphere
     r = np.maximum(rng_range, f(0.0))                               # point_light_culling_sphere
     out["cull_sphere"][:, :3] = pos
     out["cull_sphere"][:, 3] = r
@@ -143,6 +143,53 @@ def make_point_lights(pos, rng_range, color, intensity, attenuation_model=ATTEN_
     out["cull_aabb_max"][:, :3] = pos + r[:, None]
     out["cull_aabb_min"][:, 3] = 1.0
     out["cull_aabb_max"][:, 3] = 1.0
+    return out
+
+
+# shs_light_props: LightProperties (lighting/light_runtime.hpp:53-72) + its LightType as a numpy record (128 B)
+LIGHT_PROPS_DTYPE = np.dtype([("type", "<u4"), ("attenuation_model", "<u4"), ("flags", "<u4"), ("range", "<f4"),
+                              ("position_ws", "<f4", 3), ("intensity", "<f4"), ("color", "<f4", 3),
+                              ("inner_angle_rad", "<f4"), ("direction_ws", "<f4", 3), ("outer_angle_rad", "<f4"),
+                              ("right_ws", "<f4", 3), ("tube_half_length", "<f4"), ("up_ws", "<f4", 3),
+                              ("tube_radius", "<f4"), ("rect_half_extents", "<f4", 2), ("attenuation_power", "<f4"),
+                              ("attenuation_bias", "<f4"), ("attenuation_cutoff", "<f4"), ("reserved", "<f4", 3)])
+assert LIGHT_PROPS_DTYPE.itemsize == ctypes.sizeof(_abi.LightPropsC) == 128
+LIGHT_POINT, LIGHT_SPOT, LIGHT_RECT_AREA, LIGHT_TUBE_AREA = 1, 2, 3, 4
+
+
+def light_props(n, light_type=LIGHT_POINT):
+    """n shs_light_props records holding the LightProperties defaults (light_runtime.hpp:55-71)."""
+    p = np.zeros(n, LIGHT_PROPS_DTYPE)
+    p["type"], p["attenuation_model"], p["flags"] = light_type, ATTEN_SMOOTH, LIGHT_FLAGS_DEFAULT
+    p["color"], p["intensity"], p["range"] = 1.0, 1.0, 8.0
+    p["direction_ws"], p["right_ws"], p["up_ws"] = (0.0, -1.0, 0.0), (1.0, 0.0, 0.0), (0.0, 1.0, 0.0)
+    p["inner_angle_rad"], p["outer_angle_rad"] = np.float32(np.deg2rad(16.0)), np.float32(np.deg2rad(28.0))
+    p["rect_half_extents"], p["tube_half_length"], p["tube_radius"] = (0.8, 0.5), 1.0, 0.25
+    p["attenuation_power"], p["attenuation_bias"], p["attenuation_cutoff"] = 1.0, 0.05, 0.0
+    return p
+
+
+def make_point_props(pos, rng_range, color, intensity, attenuation_model=ATTEN_SMOOTH, power=1.0, bias=0.05, cutoff=0.0,
+                     flags=LIGHT_FLAGS_DEFAULT):
+    """make_point_lights' arguments as LIGHT_PROPS_DTYPE [n] point lights (pack_culling of them gives
+    make_point_lights' records)."""
+    pos = np.asarray(pos, np.float32).reshape(-1, 3)
+    p = light_props(pos.shape[0], LIGHT_POINT)
+    p["position_ws"], p["range"], p["color"], p["intensity"] = pos, rng_range, np.asarray(color).reshape(-1, 3), intensity
+    p["attenuation_model"], p["flags"] = attenuation_model, flags
+    p["attenuation_power"], p["attenuation_bias"], p["attenuation_cutoff"] = power, bias, cutoff
+    return p
+
+
+def pack_culling(props):
+    """ILightModel::pack_for_culling per record (shs_light_pack_culling, host only): LIGHT_PROPS_DTYPE [n]
+    -> LIGHT_DTYPE [n]."""
+    props = np.ascontiguousarray(props, dtype=LIGHT_PROPS_DTYPE)
+    out = np.zeros(props.shape[0], LIGHT_DTYPE)
+    rc = _abi.lib().shs_light_pack_culling(props.ctypes.data_as(ctypes.POINTER(_abi.LightPropsC)), props.shape[0],
+                                           out.ctypes.data_as(ctypes.POINTER(_abi.CullingLightC)))
+    if rc != 0:
+        raise ValueError("shs_light_pack_culling: a light type outside 1-4")
     return out
 
 

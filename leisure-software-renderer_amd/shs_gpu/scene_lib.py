@@ -181,6 +181,41 @@ def c4_lights(n_lights=256, seed=0x11A7):
                              rng.uniform(0.5, 2.0, n_lights))
 
 
+C4_CENTER = (0.0, 4.0, 40.0)     # c4_scene's look-at point
+
+
+def c4_lights_typed(n_lights=256, seed=0x11A7):
+    """c4_lights' positions, ranges, colours and intensities (the same draws) as LIGHT_PROPS_DTYPE records
+    with the types assigned round-robin (point, spot, rect, tube): directions aim at the scene centre,
+    right_ws (the tube axis) is a seeded direction, up_ws its cross product with the aim (perpendicular
+    to it, so no rect basis degenerates), and angles, half extents and tube sizes are drawn from
+    fixed-seed ranges around the LightProperties defaults (light_runtime.hpp:55-71)."""
+    from .lib_path import light_props
+    rng = np.random.default_rng(seed)
+    p = light_props(n_lights)
+    p["position_ws"] = rng.uniform(C4_BOX_MIN, C4_BOX_MAX, size=(n_lights, 3))
+    p["range"] = rng.uniform(2.0, 8.0, n_lights)
+    p["color"] = rng.uniform(0.2, 1.0, (n_lights, 3))
+    p["intensity"] = rng.uniform(0.5, 2.0, n_lights)
+    p["type"] = 1 + np.arange(n_lights) % 4
+    aim = np.asarray(C4_CENTER, np.float64) - p["position_ws"].astype(np.float64)
+    aim /= np.maximum(np.linalg.norm(aim, axis=1, keepdims=True), 1e-6)
+    p["direction_ws"] = aim
+    side = rng.normal(size=(n_lights, 3))
+    side /= np.linalg.norm(side, axis=1, keepdims=True)
+    p["right_ws"] = side
+    up = np.cross(aim, side)
+    up /= np.maximum(np.linalg.norm(up, axis=1, keepdims=True), 1e-6)
+    p["up_ws"] = up
+    inner = rng.uniform(np.deg2rad(10.0), np.deg2rad(22.0), n_lights)
+    p["inner_angle_rad"] = inner
+    p["outer_angle_rad"] = inner + rng.uniform(np.deg2rad(6.0), np.deg2rad(16.0), n_lights)
+    p["rect_half_extents"] = rng.uniform((0.4, 0.25), (1.2, 0.75), (n_lights, 2))
+    p["tube_half_length"] = rng.uniform(0.5, 1.5, n_lights)
+    p["tube_radius"] = rng.uniform(0.1, 0.4, n_lights)
+    return p
+
+
 def c4_scene(width=3840, height=2160, n_objects=1000, tris_per_object=1000, n_draws=16, n_lights=256, mode=1,
              tile_size=16, max_per_tile=128, yaw=0.0):
     """-> (frame, draws, lights, cull).  Forward+ program (SHS_PROGRAM_FORWARD_PLUS), no culling."""
