@@ -616,7 +616,8 @@ typedef struct shs_occluder {
     float aabb_min[3], aabb_max[3];   /* world AABB (SceneElement::geometry.world_aabb()) */
 } shs_occluder;
 typedef struct shs_occlusion_desc {
-    int32_t width, height;      /* occlusion buffer (OCC_W x OCC_H) */
+    int32_t width, height;      /* occlusion buffer (OCC_W x OCC_H): 1 .. 65535 per side, width * height
+                                 * <= 2^31 - 2^16 (SHS_ERR_INVALID beyond either limit, nothing allocated) */
     float view[16], view_proj[16];
     float depth_epsilon;        /* 1e-4 in the reference */
     int32_t enable;             /* 0: every frustum-visible object is visible */

@@ -31,6 +31,12 @@ extern "C" int shs_occlusion_pass(shs_ctx *ctx, const shs_occlusion_desc *desc, 
         ctx->err = "occlusion buffer size: 1 .. 65535 per side";
         return SHS_ERR_INVALID;
     }
+    // k_occlusion indexes a triangle's (triangle, pixel) pairs and a rect's pixels with 32-bit ints, and
+    // its strided loops step up to 8192 past the pixel count before they stop
+    if ((uint64_t)desc->width * (uint64_t)desc->height > (1ull << 31) - (1ull << 16)) {
+        ctx->err = "occlusion buffer size: at most 2^31 - 2^16 pixels";
+        return SHS_ERR_INVALID;
+    }
     std::memset(occluded, 0, (size_t)n_objects);
     // the frustum-visible objects, sorted by view depth (std::sort's strict '<'; equal keys keep the
     // input order here), out-of-range indices dropped as the reference's comparator pushes them last
@@ -89,7 +95,9 @@ extern "C" int shs_occlusion_pass(shs_ctx *ctx, const shs_occlusion_desc *desc, 
     p.H = desc->height;
     std::memcpy(p.vp, desc->view_proj, sizeof p.vp);
     p.eps = desc->depth_epsilon;
-    p.chunk = (int32_t)std::min<uint64_t>(1024, 0xffffffffull / npx);
+    // a chunk's pair total stays at 2^32 - 2^17 or less: the window loop adds a window (2^17 pairs) to
+    // a pair index below the total, which must not wrap
+    p.chunk = (int32_t)std::min<uint64_t>(1024, 0xfffe0000ull / npx);
     p.depth = ctx->occ_depth.p;
     p.occluded = ctx->occ_flags.p;
     p.visible = ctx->occ_visible.p + 1;

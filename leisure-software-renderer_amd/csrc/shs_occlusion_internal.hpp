@@ -49,7 +49,7 @@ struct OccParams {
     uint8_t *occluded;       // per caller object index
     uint32_t *visible;       // visible object indices in visit order
     uint32_t *n_visible;     // [1]
-    int32_t chunk;           // triangles per raster chunk: <= 1024 with chunk * W * H < 2^32
+    int32_t chunk;           // triangles per raster chunk: 1 .. 1024 with chunk * W * H <= 2^32 - 2^17
     int prof;                // SHS_OCC_PROF: print per-phase wall-clock totals
 };
 

@@ -214,7 +214,7 @@ int ora_occlusion_pass(const ora_occ_object *objs, int n_objects, const uint32_t
     for (int i = 0; i < n_objects; ++i) occluded[i] = 0;
     if (!enable) {
         for (int k = 0; k < n_fv; ++k)
-            if ((int)frustum_visible[k] < n_objects) visible_out[n_vis++] = frustum_visible[k];
+            if (frustum_visible[k] < (uint32_t)n_objects) visible_out[n_vis++] = frustum_visible[k];
         return n_vis;
     }
     for (size_t i = 0; i < (size_t)W * H; ++i) depth[i] = 1.0f;
@@ -224,7 +224,7 @@ int ora_occlusion_pass(const ora_occ_object *objs, int n_objects, const uint32_t
     int n = 0;
     for (int k = 0; k < n_fv; ++k) {
         const uint32_t idx = frustum_visible[k];
-        if ((int)idx >= n_objects) continue;
+        if (idx >= (uint32_t)n_objects) continue;   /* idx >= objects.size(): unsigned, as the reference */
         const ora_occ_object *o = &objs[idx];
         const float c[4] = {0.5f * (o->aabb_min[0] + o->aabb_max[0]), 0.5f * (o->aabb_min[1] + o->aabb_max[1]),
                             0.5f * (o->aabb_min[2] + o->aabb_max[2]), 1.0f};
@@ -260,7 +260,7 @@ int ora_occlusion_pass(const ora_occ_object *objs, int n_objects, const uint32_t
             int ok = 1;
             for (int k = 0; k < 3 && ok; ++k) {
                 const uint32_t vi = o->idx[t + k];
-                if ((int)vi >= o->n_verts) { ok = 0; break; }
+                if (vi >= (uint32_t)o->n_verts) { ok = 0; break; }
                 const float lp[4] = {o->pos[3 * vi], o->pos[3 * vi + 1], o->pos[3 * vi + 2], 1.0f};
                 float wp[4];
                 m4v_(o->model, lp, wp);
