@@ -270,6 +270,11 @@ int shs_debug_records(shs_ctx *ctx, void *out, int64_t capacity, int64_t *n_out)
  * frames (fewer busy tiles than raster workgroups: latency, not throughput), for bin-mode batches, under SHS_OPT_LEGACY_PIPELINE for the batches it pipelines, and with SHS_OPT_RASTER_LOOP 0.
  * 0 = every busy tile is its own work item.  Images and statistics are identical either way. */
 #define SHS_OPT_LEGACY_TILE_GROUPS 14
+/* SHS_OPT_LEGACY_GROUP_SPANS: 1 (default) = a tile group's pair pass (SHS_OPT_LEGACY_TILE_GROUPS, wherever
+ * that applies) tests only the pixels inside a conservative span of each row of a candidate's box clipped
+ * to the group, instead of the whole clipped box.  0 = whole boxes.  Images and statistics are identical
+ * either way. */
+#define SHS_OPT_LEGACY_GROUP_SPANS 15
 int shs_set_option(shs_ctx *ctx, int option, int64_t value);
 /* The regions of the last region-sharded camera pass: rects[4 r .. 4 r + 3] = (bx0, by0, bx1, by1) of
  * rank r, bin tiles, inclusive (bx1 < bx0: rank r owns nothing). */

@@ -429,7 +429,7 @@ static int enqueue_frame(shs_ctx *ctx) {
     fp.n_tris = n_tris; fp.n_draws = n_draws;
     fp.clear_rgba = (uint32_t)f.clear_color[0] | ((uint32_t)f.clear_color[1] << 8) | ((uint32_t)f.clear_color[2] << 16) |
                     ((uint32_t)f.clear_color[3] << 24);
-    fp.flags = (f.flags & (SHS_EXPERIMENTS ? ~0u : ~shs_dev::DBG_MASK) & ~(shs_dev::RF_PER_PIXEL | shs_dev::RF_NO_RECS | shs_dev::RF_SHARED_VARY | shs_dev::RF_GHOST_INLINE | shs_dev::RF_XCD_ROWS | shs_dev::RF_FULL_CLEAR | shs_dev::RF_TILE_GROUPS)) | (ctx->pair_loop ? 0u : shs_dev::RF_PER_PIXEL) |
+    fp.flags = (f.flags & (SHS_EXPERIMENTS ? ~0u : ~shs_dev::DBG_MASK) & ~(shs_dev::RF_PER_PIXEL | shs_dev::RF_NO_RECS | shs_dev::RF_SHARED_VARY | shs_dev::RF_GHOST_INLINE | shs_dev::RF_XCD_ROWS | shs_dev::RF_FULL_CLEAR | shs_dev::RF_TILE_GROUPS | shs_dev::RF_GROUP_SPANS)) | (ctx->pair_loop ? 0u : shs_dev::RF_PER_PIXEL) |
                (full_clear ? shs_dev::RF_FULL_CLEAR : 0u);
     fp.bin_cap = ctx->bin_cap;
     fp.spill_cap = (uint32_t)std::min<size_t>(ws.spill.cap, 0xffffffffu);
@@ -485,7 +485,7 @@ static int enqueue_frame(shs_ctx *ctx) {
 #ifndef SHS_SCAN_SPANS   // (timing experiments: scan-mode frames on row spans keep tile lists)
     if (ctx->tile_groups && fp.scan_mode && n_frames > 1 && !pipe && ctx->pair_loop &&
         !(SHS_EXPERIMENTS && (f.flags & shs_dev::DBG_CLEAR_ONLY)))
-        fp.flags |= shs_dev::RF_TILE_GROUPS;
+        fp.flags |= shs_dev::RF_TILE_GROUPS | (ctx->group_spans ? shs_dev::RF_GROUP_SPANS : 0u);   // (spans: SHS_OPT_LEGACY_GROUP_SPANS)
 #endif
     const int owned_bt = (n_tiles - f.shard_rank + f.shard_count - 1) / f.shard_count;
     const int n_groups = (n_tris + 15) / 16;
@@ -949,6 +949,11 @@ int shs_set_option(shs_ctx *ctx, int option, int64_t value) {
     if (option == SHS_OPT_LEGACY_TILE_GROUPS) {
         if (value < 0 || value > 1) return SHS_ERR_INVALID;
         ctx->tile_groups = value != 0;
+        return SHS_OK;
+    }
+    if (option == SHS_OPT_LEGACY_GROUP_SPANS) {
+        if (value < 0 || value > 1) return SHS_ERR_INVALID;
+        ctx->group_spans = value != 0;
         return SHS_OK;
     }
     if (option == SHS_OPT_SHADOW_FOOTPRINT) {

@@ -139,6 +139,7 @@ struct shs_ctx {
     bool stale_clear = true;         // SHS_OPT_LEGACY_STALE_CLEAR
     uint64_t last_cleared = 0;       // tiles the last batch's clear strips cleared
     bool tile_groups = true;         // SHS_OPT_LEGACY_TILE_GROUPS
+    bool group_spans = true;         // SHS_OPT_LEGACY_GROUP_SPANS
 
     uint32_t *h_counters = nullptr;  // pinned, C_NCOUNTERS
 

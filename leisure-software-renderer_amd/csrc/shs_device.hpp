@@ -164,6 +164,10 @@ constexpr uint32_t RF_FULL_CLEAR = 1u << 21;
 // k_raster scans the bin boxes and stages the records once per group, then runs the pairs, resolve and
 // stores of each busy tile of the group.  Idle tiles of a busy group are left to the clear items.
 constexpr uint32_t RF_TILE_GROUPS = 1u << 22;
+// Tile groups whose pair pass walks conservative row spans of the candidates' clipped boxes instead of
+// the whole boxes (frame flags bit 23, set by the host only with RF_TILE_GROUPS:
+// SHS_OPT_LEGACY_GROUP_SPANS).  The same keys: the images are the same bits.
+constexpr uint32_t RF_GROUP_SPANS = 1u << 23;
 #ifndef SHS_GROUP_X
 #define SHS_GROUP_X 2                // (-DSHS_GROUP_X=.. -DSHS_GROUP_Y=..: timing experiments)
 #endif
@@ -296,7 +300,8 @@ __device__ __forceinline__ FrameBuffers frame_view(const FrameParams &fp, const 
     return v;
 }
 
-constexpr int TL_STRIDE = 13;   // (slot 12: busy tiles of the first tile group, RF_TILE_GROUPS)
+constexpr int TL_STRIDE = 14;   // (slot 12: busy tiles of the first tile group, RF_TILE_GROUPS)
+constexpr int TL_SPANS = 13;    // (slot 13: the first group's last span pass done, RF_GROUP_SPANS; else 0)
 
 struct KArgDraws {
     DrawGPU d[KARG_DRAWS];

@@ -1221,6 +1221,18 @@ struct GroupShared {
     uint32_t seq, pairs;              // the group's candidates and pairs so far (timeline)
 };
 struct NoGroupShared {};
+// Row-span pair tasks of a group (RF_GROUP_SPANS): one segment per nonempty (staged candidate, group row)
+// span, +4 KB on the span kernel alone (still four workgroups per CU).
+constexpr int GROUP_SEGS = RCHUNK * GY * RTH;
+struct GroupSpanShared : GroupShared {
+    uint32_t seg[GROUP_SEGS];         // group_seg_pack's words, in pair order
+};
+// A segment: its first pair of the pass (< PAIR_CAP: 14 bits), its first pixel's group-relative x (6 bits),
+// its group row (4 bits) and its staged candidate (6 bits).  tests/test_group_spans.py restates the layout.
+static_assert(PAIR_CAP <= (1 << 14) && GX * RTW <= 64 && GY * RTH <= 16 && RCHUNK <= 64, "the segment word's fields");
+__device__ __forceinline__ uint32_t group_seg_pack(uint32_t first, uint32_t x0, uint32_t row, uint32_t cand) {
+    return first | (x0 << 14) | (row << 20) | (cand << 24);
+}
 
 // The record rebuilt from the screen corners with the stored flags and bin box: rec_from_screen's
 // float arithmetic (the Gram terms, z, float bbox, integer bbox) without danger_margin -- its only
@@ -1564,7 +1576,9 @@ __device__ __forceinline__ void raster_tile(const FrameParams &fp, const FrameBu
                 }
             } else {
                 // (scan-mode frames: whole clipped bin boxes -- C2's Suzanne triangles fill most of their boxes,
-                // and the spans measured slower there: 0.271 -> 0.278 ms per step)
+                // and the spans measured slower there: 0.271 -> 0.278 ms per step -- on a per-tile item, a
+                // median of 72 span tasks for ~600 pairs, in a kernel then bound by its clear strips; a tile
+                // group's span pass, raster_group, serves four tiles' pairs)
                 // Pair tasks, dealt evenly over the workgroup.  Wave 0 lays the staged candidates' clipped
                 // bin boxes end to end (prefix of the areas; every staged box holds >= 1 pixel of the tile,
                 // so the starts are distinct) and marks each start in a bitmap over the pairs, plus the
@@ -1752,8 +1766,15 @@ __device__ __forceinline__ void raster_tile(const FrameParams &fp, const FrameBu
 // fragments each busy tile is resolved, shaded and stored.  The keys and values are raster_tile's, so
 // the images are the same bits.
 // Idle tiles of the group (not marked, or another shard's) are not touched: the clear items own them.
+// SPANS (RF_GROUP_SPANS): the pair pass walks conservative row spans instead of whole clipped boxes.  A
+// span pass cuts every staged candidate's clipped box into its group rows (legacy_row_span: every pixel
+// of the row that can pass lies in the span, ghosts' expanded boxes included) and lays the nonempty spans
+// end to end as segments, as raster_tile's span path does per tile; the pairs tested are a superset of
+// the passing ones, so the keys are the box pass's.  A staging chunk whose spans hold more pairs than the
+// bitmap (many near-group-filling triangles, where spans cut nothing) takes the box passes, which split.
+template <bool SPANS, class GS>
 __device__ __forceinline__ void raster_group(const FrameParams &fp, const FrameBuffers &fb, const DrawGPU *draws,
-                                             uint32_t n_frag, int frame, int rt0, RasterShared &sh, GroupShared &gs, uint64_t *tl) {
+                                             uint32_t n_frag, int frame, int rt0, RasterShared &sh, GS &gs, uint64_t *tl) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int tls = fp.setup_grid + (int)blockIdx.x;
     const int col0 = rt0 % fp.tiles_x, row0 = rt0 / fp.tiles_x;
@@ -1861,10 +1882,104 @@ __device__ __forceinline__ void raster_group(const FrameParams &fp, const FrameB
             }
             __syncthreads();
             tl_mark(tl, tls, 2);
+            bool boxes = true;
+            if constexpr (SPANS) {
+                // Span tasks: thread (row = tid % 16, cj = tid / 16) takes group row `row` of the staged
+                // candidates cj, cj + 16, ...; one block prefix of (pairs << 11 | segments) lays the
+                // threads' spans end to end, each thread's in candidate order.
+                static_assert(PAIR_WORDS == 256 && GY * RTH == 16 && RCHUNK == 64, "the span pass's thread mapping");
+                constexpr uint32_t NO_SPAN = 0xffu;
+                sh.bits[tid] = 0ull;
+                // (the thread's task indices are computed here, per pass, and its spans wait in LDS for the
+                // prefix -- RasterShared::seg, the tile span path's, is free in this kernel: as registers
+                // held across the prefix, or across the item loop, they spill)
+                int stid = tid;
+                asm volatile("" : "+v"(stid));
+                const int row = stid & 15, cj = stid >> 4, py = GY0 + row;
+                uint16_t *spw = reinterpret_cast<uint16_t *>(sh.seg) + stid;   // [j * 256]: group-relative x0 | x1 << 8
+                static_assert(sizeof(sh.seg) >= (RCHUNK / 16) * 256 * sizeof(uint16_t), "the threads' spans");
+                uint32_t pk = 0u;
+#pragma unroll
+                for (int j = 0; j < RCHUNK / 16; ++j) {
+                    uint32_t sp = NO_SPAN;
+                    const int cc = cj + 16 * j;
+                    if (16 * j < m && cc < m) {   // (the first test is wave-uniform)
+                        const float4 *rc = &sh.rec[cc * 4];
+                        const uint4 bb = reinterpret_cast<const uint4 *>(rc)[3];   // z2 word gbx gby
+                        const int x0 = max(lo16(bb.z), GX0), x1 = min(hi16(bb.z), GX1);
+                        if (x0 <= x1 && py >= lo16(bb.w) && py <= hi16(bb.w) && py <= GY1) {
+                            int s0, s1;
+                            legacy_row_span(rc[0], rc[1], rc[2], py, x0, x1, s0, s1);
+                            if (s0 <= s1) {
+                                sp = (uint32_t)(s0 - GX0) | ((uint32_t)(s1 - GX0) << 8);
+                                pk += ((uint32_t)(s1 - s0 + 1) << 11) + 1u;
+                            }
+                        }
+                    }
+                    spw[j * 256] = (uint16_t)sp;
+                }
+                uint32_t incl = pk;
+#pragma unroll
+                for (int o = 1; o < 64; o <<= 1) {
+                    const uint32_t vv = (uint32_t)__shfl_up((int)incl, o);
+                    if (lane >= o) incl += vv;
+                }
+                if (lane == 63) sh.wtot[wave] = incl;
+                __syncthreads();
+                uint32_t pbase = 0u, ptot = 0u;
+#pragma unroll
+                for (int w2 = 0; w2 < 4; ++w2) {
+                    const uint32_t p2 = sh.wtot[w2];
+                    if (w2 < wave) pbase += p2;
+                    ptot += p2;
+                }
+                boxes = (ptot >> 11) > (uint32_t)PAIR_CAP;   // (block-uniform)
+                if (!boxes && pk) {
+                    const uint32_t ex = pbase + incl - pk;
+                    uint32_t ps = ex >> 11, sg = ex & 2047u;
+#pragma unroll
+                    for (int j = 0; j < RCHUNK / 16; ++j) {
+                        const uint32_t sp = spw[j * 256];
+                        if (sp == NO_SPAN) continue;
+                        const uint32_t s0 = sp & 0xffu, wdt = (sp >> 8) - s0 + 1u;
+                        gs.seg[sg] = group_seg_pack(ps, s0, (uint32_t)row, (uint32_t)(cj + 16 * j));
+                        atomicOr(&sh.bits[ps >> 6], 1ull << (ps & 63u));
+                        for (uint32_t wd = (ps + 63u) >> 6; wd * 64u < ps + wdt; ++wd) sh.wown[wd] = (uint16_t)sg;
+                        ps += wdt;
+                        ++sg;
+                    }
+                }
+                __syncthreads();
+                tl_mark(tl, tls, TL_SPANS - 2);
+                if (!boxes) {
+                    const int total = SHS_DBG(fp, DBG_SKIP_PAIRS) ? 0 : (int)(ptot >> 11);
+                    if (tl && tid == 0) gs.pairs += (uint32_t)total;
+                    for (int k0 = 64 * wave; k0 < total; k0 += 256) {
+                        const int k = k0 + lane;
+                        if (k < total) {
+                            const unsigned long long wb = sh.bits[k0 >> 6];
+                            const unsigned long long upto = ((2ull << lane) - 1ull) & ~1ull;   // bits 1..lane
+                            const uint32_t sgi = gs.seg[(int)sh.wown[k0 >> 6] + __popcll(wb & upto)];
+                            const int o = (int)(sgi >> 24);
+                            const int px = GX0 + (int)((sgi >> 14) & 63u) + (k - (int)(sgi & 0x3fffu)), py = GY0 + (int)((sgi >> 20) & 15u);
+                            // the pixel's tile: only the group's busy tiles are drawn (the box pass's test)
+                            const int tx = (px - GX0) / RTW, ty = (py - GY0) / RTH, t = ty * GX + tx;
+                            if ((bmask >> t) & 1u) {
+                                const TriRec r = rec_from_hot(fp, &sh.rec[o * 4], &sh.ext[o]);
+                                unsigned long long *key = t ? &gs.key[(t - 1) * (RTW * RTH)] : sh.key;
+                                float z;
+                                if (pixel_test(fp, r, px, py, z))
+                                    atomicMin(&key[(py - GY0 - ty * RTH) * RTW + (px - GX0 - tx * RTW)],
+                                              cand_key(z, sh.id[o], slot_keys, single ? (uint32_t)o : SLOT_NONE));
+                            }
+                        }
+                    }
+                }
+            }
             // one pair pass over the group: the staged candidates' bin boxes clipped to the group rectangle
             // (<= 64 wide, <= 1024 px).  The bitmap holds PAIR_CAP pairs: a pass lays out the leading
             // candidates whose pairs fit -- one always does -- and the rest follow in further passes.
-            for (int c0 = 0;;) {
+            if (boxes) for (int c0 = 0;;) {
                 if (wave == 0) {
                     // raster_tile's pair prefix over the candidates from c0 with pixels in the group
                     int area = 0, bx0 = 0, by0 = 0, bw = 1;
@@ -2157,12 +2272,14 @@ constexpr int STRIP_RT = SHS_STRIP_RT;
 #ifndef SHS_LEGACY_RASTER_WAVES
 #define SHS_LEGACY_RASTER_WAVES 4   // minimum waves per SIMD (-D...: timing experiments)
 #endif
-// GROUPS (RF_TILE_GROUPS, the scan-mode pair kernel only): the busy list holds tile groups (raster_group).
-template <bool KARG, bool NO_RECS, bool SPANS, bool PIX, int SCAN, bool GROUPS = false>
+// GROUPS (RF_TILE_GROUPS, the scan-mode pair kernel only): the busy list holds tile groups (raster_group);
+// GSPANS (RF_GROUP_SPANS): their pair pass walks row spans.
+template <bool KARG, bool NO_RECS, bool SPANS, bool PIX, int SCAN, bool GROUPS = false, bool GSPANS = false>
 __global__ __launch_bounds__(256, SHS_LEGACY_RASTER_WAVES) void k_raster(FrameParams fp, FrameBuffers fb, KArgDraws ka) {
     static_assert(!GROUPS || (SCAN == SCAN_ALL && !NO_RECS && !SPANS && !PIX), "tile groups: the scan-mode pair kernel");
+    static_assert(!GSPANS || GROUPS, "group spans: the group kernel");
     __shared__ RasterShared sh;
-    __shared__ typename std::conditional<GROUPS, GroupShared, NoGroupShared>::type gs;
+    __shared__ typename std::conditional<GSPANS, GroupSpanShared, typename std::conditional<GROUPS, GroupShared, NoGroupShared>::type>::type gs;
     const int tid = threadIdx.x;
     uint32_t *cnt = fb.counters + fp.parity * CSET;
     const DrawGPU *draws = draw_table<KARG>(fb, ka);
@@ -2221,9 +2338,9 @@ __global__ __launch_bounds__(256, SHS_LEGACY_RASTER_WAVES) void k_raster(FramePa
                 __syncthreads();
                 clear_tile(fp, fv, rt);
             } else if constexpr (GROUPS) {   // (rt: the group's top-left tile)
-                if (SHS_DBG(fp, DBG_TWICE)) raster_group(fp, fv, draws, n_frag, f, rt, sh, gs, nullptr);   // warm run
+                if (SHS_DBG(fp, DBG_TWICE)) raster_group<GSPANS>(fp, fv, draws, n_frag, f, rt, sh, gs, nullptr);   // warm run
                 tl_mark(first ? fb.timeline : nullptr, fp.setup_grid + (int)blockIdx.x, 0);
-                raster_group(fp, fv, draws, n_frag, f, rt, sh, gs, first ? fb.timeline : nullptr);
+                raster_group<GSPANS>(fp, fv, draws, n_frag, f, rt, sh, gs, first ? fb.timeline : nullptr);
                 first = false;
             } else {
                 if (SHS_DBG(fp, DBG_TWICE)) raster_tile<NO_RECS, SPANS, PIX, SCAN>(fp, fv, draws, cnt, n_frag, f, rt, sh, nullptr);   // warm run
@@ -2375,6 +2492,7 @@ hipError_t launch_raster(const FrameParams &fp, const FrameBuffers &fb, const KA
 #ifdef SHS_SCAN_SPANS   // (timing experiments: scan-mode frames on row spans)
     else SHS_RASTER(false, true, false, SCAN_ALL);
 #else
+    else if (fp.flags & RF_GROUP_SPANS) SHS_RASTER(false, false, false, SCAN_ALL, true, true);   // busy groups, row spans
     else if (fp.flags & RF_TILE_GROUPS) SHS_RASTER(false, false, false, SCAN_ALL, true);   // busy groups (raster_group)
     else SHS_RASTER(false, false, false, SCAN_ALL);
 #endif

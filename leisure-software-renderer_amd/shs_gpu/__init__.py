@@ -607,6 +607,11 @@ class Context:
         share one box scan and staging (default on); off: a work item per busy tile.  Images identical."""
         self._check(self._lib.shs_set_option(self._h, _abi.OPT_LEGACY_TILE_GROUPS, 1 if on else 0))
 
+    def set_group_spans(self, on: bool):
+        """SHS_OPT_LEGACY_GROUP_SPANS: a tile group's pair pass walks conservative row spans of the
+        candidates' clipped boxes (default on); off: the whole boxes.  Images identical."""
+        self._check(self._lib.shs_set_option(self._h, _abi.OPT_LEGACY_GROUP_SPANS, 1 if on else 0))
+
     def cleared_tiles(self) -> int:
         """shs_legacy_cleared_tiles: the 32x8 raster tiles the last legacy batch's clear strips cleared."""
         n = ctypes.c_uint64(0)

@@ -40,6 +40,7 @@ OPT_SHADOW_FOOTPRINT = 11
 OPT_LEGACY_PIPELINE = 12
 OPT_LEGACY_STALE_CLEAR = 13
 OPT_LEGACY_TILE_GROUPS = 14
+OPT_LEGACY_GROUP_SPANS = 15
 
 
 class LegacyDraw(ctypes.Structure):

@@ -42,6 +42,11 @@ def main():
         if len(busy):   # (groups: the candidates and the pairs of the whole group)
             print(f"  raster first tile / group candidates: median {np.median(busy[:, 8]):.0f} max {busy[:, 8].max()} | pair tasks "
                   f"median {np.median(busy[:, 9]):.0f} max {busy[:, 9].max()}")
+        sp = r[r[:, 13] != 0] if r.shape[1] > 13 else r[:0]
+        if len(sp):     # (group spans: slot 13 = the first group's last span pass done, slot 4 = its records staged)
+            d = (sp[:, 13].astype(np.int64) - sp[:, 4].astype(np.int64)) / 100.0
+            print(f"  raster first group span pass (staged -> segments laid out): median {np.median(d):.2f} us max {d.max():.2f} us "
+                  f"({len(sp)} workgroups)")
         st = (s[:, 0].astype(np.int64) - t0) / 100.0
         en = (s[:, 1].astype(np.int64) - t0) / 100.0
         for q in (0.25, 0.5, 0.75, 0.9, 1.0):
