@@ -201,8 +201,11 @@ __device__ __forceinline__ void vertex_screen(const FrameParams &fp, const float
     sz = nz;
 }
 
-__device__ __forceinline__ TriRec rec_from_screen(const FrameParams &fp, int draw, int local, const float (&sx)[3],
-                                                  const float (&sy)[3], const float (&sz)[3]) {
+// The part of a record that is plain float arithmetic on its screen corners: the per-triangle half of
+// barycentric_coordinate (anchor, edges, Gram terms, denominator), z and the float bbox.  The flags and
+// the integer / bin boxes are the caller's (rec_from_screen, rec_from_stored).
+__device__ __forceinline__ TriRec rec_geometry(int draw, int local, const float (&sx)[3], const float (&sy)[3],
+                                               const float (&sz)[3]) {
     TriRec r;
     r.ax = sx[0]; r.ay = sy[0];
     r.v0x = sx[1] - sx[0]; r.v0y = sy[1] - sy[0];
@@ -220,7 +223,12 @@ __device__ __forceinline__ TriRec rec_from_screen(const FrameParams &fp, int dra
     r.fmaxx = g_max(g_max(sx[0], sx[1]), sx[2]);
     r.fminy = g_min(g_min(sy[0], sy[1]), sy[2]);
     r.fmaxy = g_max(g_max(sy[0], sy[1]), sy[2]);
+    return r;
+}
 
+__device__ __forceinline__ TriRec rec_from_screen(const FrameParams &fp, int draw, int local, const float (&sx)[3],
+                                                  const float (&sy)[3], const float (&sz)[3]) {
+    TriRec r = rec_geometry(draw, local, sx, sy, sz);
     uint32_t flags = 0;
     bool finite = true;
 #pragma unroll
@@ -350,6 +358,26 @@ struct NewBusy {
     uint32_t e[NEW_BUSY_CAP];
 };
 
+// N consecutive entries: into the block's LDS list while it has room, else straight into the global list.
+template <int N>
+__device__ __forceinline__ void push_busy(NewBusy &nb, const FrameBuffers &fb, uint32_t *cnt, const uint32_t (&entry)[N]) {
+    static_assert(NEW_BUSY_CAP % N == 0, "a run of entries does not straddle the LDS list's end");
+    const uint32_t k = atomicAdd(&nb.n, (uint32_t)N);
+    if (k < (uint32_t)NEW_BUSY_CAP) {
+#pragma unroll
+        for (int i = 0; i < N; ++i) nb.e[k + i] = entry[i];
+    } else {
+        const uint32_t g = atomicAdd(&cnt[C_BUSY], (uint32_t)N);
+#pragma unroll
+        for (int i = 0; i < N; ++i) fb.busy_list[g + i] = entry[i];
+    }
+}
+
+__device__ __forceinline__ void push_busy(NewBusy &nb, const FrameBuffers &fb, uint32_t *cnt, uint32_t entry) {
+    const uint32_t one[1] = {entry};
+    push_busy(nb, fb, cnt, one);
+}
+
 // The tile's listing once its mark found it not yet busy (old != epoch).
 __device__ __forceinline__ void list_busy(const FrameParams &fp, const FrameBuffers &fb, uint32_t *cnt, int frame, int rx,
                                           int ry, NewBusy &nb) {
@@ -358,9 +386,7 @@ __device__ __forceinline__ void list_busy(const FrameParams &fp, const FrameBuff
         rt = group_entry_tile(fp, fb, rx, ry);
         if (rt < 0) return;
     }
-    const uint32_t k = atomicAdd(&nb.n, 1u);
-    if (k < (uint32_t)NEW_BUSY_CAP) nb.e[k] = busy_entry(fp, frame, rt);
-    else fb.busy_list[atomicAdd(&cnt[C_BUSY], 1u)] = busy_entry(fp, frame, rt);
+    push_busy(nb, fb, cnt, busy_entry(fp, frame, rt));
 }
 
 __device__ __forceinline__ void mark_busy(const FrameParams &fp, const FrameBuffers &fb, uint32_t *cnt, int frame, int rx,
@@ -376,15 +402,15 @@ __device__ __forceinline__ void mark_bin_rows(const FrameParams &fp, const Frame
                                               NewBusy &nb) {
     const int bx = t % fp.tiles_x, ry0 = (t / fp.tiles_x) * (TILE / RTH);
     if (fp.flags & RF_XCD_ROWS) {   // the rows as one 4-aligned group (every bin-mode append is 4 entries)
-        static_assert(TILE / RTH == 4 && NEW_BUSY_CAP % 4 == 0, "row groups of four");
-        const uint32_t k = atomicAdd(&nb.n, 4u);
-        uint32_t *dst = k < (uint32_t)NEW_BUSY_CAP ? &nb.e[k] : &fb.busy_list[atomicAdd(&cnt[C_BUSY], 4u)];
+        static_assert(TILE / RTH == 4, "row groups of four");
+        uint32_t rows[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int rt = (ry0 + r) * fp.tiles_x + bx;
             if (ry0 + r < fp.rtiles_y) fb.busy[rt] = fp.epoch;
-            dst[r] = ry0 + r < fp.rtiles_y ? busy_entry(fp, frame, rt) : BUSY_SKIP;
+            rows[r] = ry0 + r < fp.rtiles_y ? busy_entry(fp, frame, rt) : BUSY_SKIP;
         }
+        push_busy(nb, fb, cnt, rows);
         return;
     }
 #pragma unroll
@@ -393,9 +419,7 @@ __device__ __forceinline__ void mark_bin_rows(const FrameParams &fp, const Frame
         if (ry >= fp.rtiles_y) break;
         const int rt = ry * fp.tiles_x + bx;
         fb.busy[rt] = fp.epoch;
-        const uint32_t k = atomicAdd(&nb.n, 1u);
-        if (k < (uint32_t)NEW_BUSY_CAP) nb.e[k] = busy_entry(fp, frame, rt);
-        else fb.busy_list[atomicAdd(&cnt[C_BUSY], 1u)] = busy_entry(fp, frame, rt);
+        push_busy(nb, fb, cnt, busy_entry(fp, frame, rt));
     }
 }
 
@@ -1191,6 +1215,11 @@ constexpr uint32_t SLOT_NONE = 127u;                  // key slot field: winner 
 __device__ __forceinline__ unsigned long long cand_key(float z, uint32_t id, bool slot_keys, uint32_t slot) {
     return z_key(z, slot_keys ? (id << 7) | slot : id);
 }
+__device__ __forceinline__ void key_winner(unsigned long long key, bool slot_keys, uint32_t &id, uint32_t &slot) {
+    const uint32_t lo = (uint32_t)key;
+    id = slot_keys ? lo >> 7 : lo;
+    slot = slot_keys ? lo & SLOT_NONE : SLOT_NONE;
+}
 
 struct RasterShared {
     float4 rec[RCHUNK * 4];           // staged triangle records (TriHot, 4 KB)
@@ -1198,9 +1227,9 @@ struct RasterShared {
     float4 srec[RCHUNK * 5];          // staged shading records (single-pass tiles, 5 KB)
     unsigned long long key[RTH * RTW];// per-pixel (z, index) keys (2 KB)
     unsigned long long bits[PAIR_WORDS]; // bit k: a staged candidate's pairs start at pair k (2 KB)
-    uint32_t seg[RCHUNK * RTH];       // spans: per nonempty row span, first pair | x0 << 14 | row << 19 | candidate << 22
-    uint4 pinfo[RCHUNK];              // boxes: per staged candidate first pair, x0 | y0 << 16, box width, 2^16/width
-                                      // (groups: per candidate with pairs in the pass, its box clipped to the group; width | candidate << 8)
+    uint32_t seg[RCHUNK * RTH];       // spans: per nonempty row span, seg_pack's word (groups: the threads' spans before the prefix)
+    uint4 pinfo[RCHUNK];              // boxes: per staged candidate with pairs in the pass, its box clipped to the tile / group:
+                                      // first pair, x0 | y0 << 16, width | candidate << 8, 2^16/width
     uint32_t wtot[4];                 // per wave: pairs << 11 | segments (the staging pass's block prefix)
     uint32_t id[RCHUNK];
     uint32_t cand[CAND];
@@ -1225,38 +1254,29 @@ struct NoGroupShared {};
 // span, +4 KB on the span kernel alone (still four workgroups per CU).
 constexpr int GROUP_SEGS = RCHUNK * GY * RTH;
 struct GroupSpanShared : GroupShared {
-    uint32_t seg[GROUP_SEGS];         // group_seg_pack's words, in pair order
+    uint32_t seg[GROUP_SEGS];         // seg_pack's words, in pair order
 };
-// A segment: its first pair of the pass (< PAIR_CAP: 14 bits), its first pixel's group-relative x (6 bits),
-// its group row (4 bits) and its staged candidate (6 bits).  tests/test_group_spans.py restates the layout.
+// A segment (a tile's or a group's): its first pair of the pass (< PAIR_CAP: 14 bits), its first pixel's x
+// relative to the tile / group (6 bits), its row there (4 bits) and its staged candidate (6 bits).
+// tests/test_group_spans.py restates the layout.
 static_assert(PAIR_CAP <= (1 << 14) && GX * RTW <= 64 && GY * RTH <= 16 && RCHUNK <= 64, "the segment word's fields");
-__device__ __forceinline__ uint32_t group_seg_pack(uint32_t first, uint32_t x0, uint32_t row, uint32_t cand) {
+__device__ __forceinline__ uint32_t seg_pack(uint32_t first, uint32_t x0, uint32_t row, uint32_t cand) {
     return first | (x0 << 14) | (row << 20) | (cand << 24);
+}
+// Pair k of the pass inside segment sgi of the tile / group at (X0, Y0): its staged candidate and pixel.
+__device__ __forceinline__ int seg_pixel(uint32_t sgi, int k, int X0, int Y0, int &px, int &py) {
+    px = X0 + (int)((sgi >> 14) & 63u) + (k - (int)(sgi & 0x3fffu));
+    py = Y0 + (int)((sgi >> 20) & 15u);
+    return (int)(sgi >> 24);
 }
 
 // The record rebuilt from the screen corners with the stored flags and bin box: rec_from_screen's
-// float arithmetic (the Gram terms, z, float bbox, integer bbox) without danger_margin -- its only
+// float arithmetic (rec_geometry, and the integer bbox) without danger_margin -- its only
 // outputs, the flags and the bin box, come from k_setup.  Candidates are never culled (their bin box
 // is non-empty), so the integer bbox is always the clamped floor.
 __device__ __forceinline__ TriRec rec_from_stored(const FrameParams &fp, int draw, int local, const float (&sx)[3],
                                                   const float (&sy)[3], const float (&sz)[3], uint32_t flags, uint2 gbox) {
-    TriRec r;
-    r.ax = sx[0]; r.ay = sy[0];
-    r.v0x = sx[1] - sx[0]; r.v0y = sy[1] - sy[0];
-    r.v1x = sx[2] - sx[0]; r.v1y = sy[2] - sy[0];
-    {
-        const float a = r.v0x * r.v0x, b = r.v0y * r.v0y; r.d00 = a + b;
-        const float c = r.v0x * r.v1x, d = r.v0y * r.v1y; r.d01 = c + d;
-        const float e = r.v1x * r.v1x, f = r.v1y * r.v1y; r.d11 = e + f;
-    }
-    r.denom = r.d00 * r.d11 - r.d01 * r.d01;
-    r.z0 = sz[0]; r.z1 = sz[1]; r.z2 = sz[2];
-    r.draw = draw;
-    r.local = local;
-    r.fminx = g_min(g_min(sx[0], sx[1]), sx[2]);
-    r.fmaxx = g_max(g_max(sx[0], sx[1]), sx[2]);
-    r.fminy = g_min(g_min(sy[0], sy[1]), sy[2]);
-    r.fmaxy = g_max(g_max(sy[0], sy[1]), sy[2]);
+    TriRec r = rec_geometry(draw, local, sx, sy, sz);
     r.flags = flags;
     r.ibx = pack16(floor_clamped(r.fminx, 0, fp.W), floor_clamped(r.fmaxx, -1, fp.W - 1));
     r.iby = pack16(floor_clamped(r.fminy, 0, fp.H), floor_clamped(r.fmaxy, -1, fp.H - 1));
@@ -1335,6 +1355,261 @@ __device__ __forceinline__ void resolve_from_mesh(const FrameParams &fp, const F
     shading = dr.shading;
 }
 
+// ---- the phases raster_tile and raster_group share ---------------------------------------------
+// Each is written once: its keys and values are the same bits on every path that runs it.
+
+// Stage the stored records of candidates sh.cand[c .. c + m): TriHot, float bbox and (single-pass items:
+// so the resolve reads no HBM) shade records.  Consecutive lanes load consecutive float4s of one record;
+// all loads in one round trip, then the LDS stores.  all_ext: every candidate's float bbox is stored (scan
+// mode); otherwise only the ghosts', whose bin entries carry BIN_GHOST (a tile group's candidates carry
+// no tag: masking them is a no-op).
+// PIN: the thread's staging indices are computed here, per pass -- hoisted out of the item loop they are
+// registers held across the whole kernel, which then spills (the group kernels; the experiments build's
+// per-pixel kernel).  Not pinned in the tile span kernels: pinned, the bin-mode one measured 0.005 ms per
+// C3 step slower.
+template <bool PIN>
+__device__ __forceinline__ void stage_stored(const FrameBuffers &fb, RasterShared &sh, uint32_t c, int m, bool single,
+                                             bool all_ext) {
+    const int tid = threadIdx.x;
+    constexpr int NQ = (RCHUNK * 4 + 255) / 256, NS = (RCHUNK * 5 + 255) / 256;
+    float4 q[NQ], s[NS], e = make_float4(0.f, 0.f, 0.f, 0.f);
+    int stid = tid;
+    if constexpr (PIN) asm volatile("" : "+v"(stid));
+#pragma unroll
+    for (int k = 0; k < NQ; ++k) {
+        const int f = stid + 256 * k;
+        const int ci = f >> 2;
+        q[k] = f < 4 * m ? reinterpret_cast<const float4 *>(&fb.recs[sh.cand[c + min(ci, m - 1)] & ~BIN_GHOST])[f & 3]
+                         : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    {
+        const uint32_t ce = tid < m ? sh.cand[c + tid] : 0u;
+        if (tid < m && (all_ext || (ce & BIN_GHOST))) e = fb.rext[ce & ~BIN_GHOST];
+    }
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {   // (single: one staging pass, c == 0)
+        const int f = stid + 256 * k;
+        const int ci = f / 5;
+        s[k] = single && f < 5 * m ? reinterpret_cast<const float4 *>(&fb.shade[sh.cand[min(ci, m - 1)] & ~BIN_GHOST])[f - 5 * ci]
+                                   : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+#pragma unroll
+    for (int k = 0; k < NQ; ++k) {
+        const int f = tid + 256 * k;
+        if (f < 4 * m) sh.rec[f] = q[k];
+    }
+    if (tid < m) sh.ext[tid] = e;
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+        const int f = tid + 256 * k;
+        if (single && f < 5 * m) sh.srec[f] = s[k];
+    }
+}
+
+// A run of len pairs from pair `start` of the pass belongs to `owner` (a segment or a pinfo entry): its
+// start bit in the bitmap over the pairs, and the owner of every bitmap word whose first pair is in the run.
+__device__ __forceinline__ void mark_run(RasterShared &sh, uint32_t start, uint32_t len, uint32_t owner) {
+    atomicOr(&sh.bits[start >> 6], 1ull << (start & 63u));
+    for (uint32_t wd = (start + 63u) >> 6; wd * 64u < start + len; ++wd) sh.wown[wd] = (uint16_t)owner;
+}
+
+// Span tasks.  A thread's spans are x0 | x1 << 8 relative to the tile / group, NO_SPAN when empty; pk
+// counts them as pairs << 11 | segments.
+constexpr uint32_t NO_SPAN = 0xffu;
+static_assert(RCHUNK * GX * RTW * GY * RTH < (1 << 21) && GROUP_SEGS < 2048, "the prefix word's fields");
+
+// Block prefix of the threads' pk words through sh.wtot (one barrier): the thread's exclusive prefix; the
+// block's total in ptot.  (lane, wave: the caller's -- recomputed here they cost the experiments build's
+// NO_RECS kernel eight more spilled registers.)
+__device__ __forceinline__ uint32_t block_span_prefix(RasterShared &sh, uint32_t pk, int lane, int wave, uint32_t &ptot) {
+    const uint32_t incl = wave_incl_sum(pk);
+    if (lane == 63) sh.wtot[wave] = incl;
+    __syncthreads();
+    uint32_t pbase = 0u;
+    ptot = 0u;
+#pragma unroll
+    for (int w2 = 0; w2 < 4; ++w2) {
+        const uint32_t p2 = sh.wtot[w2];
+        if (w2 < wave) pbase += p2;
+        ptot += p2;
+    }
+    return pbase + incl - pk;
+}
+
+// Segment write-out: the thread's N spans (span(j)) laid end to end from its exclusive prefix ex, each as
+// word(j, first pair, x0) in seg[] with its run marked.
+template <int N, class Span, class Word>
+__device__ __forceinline__ void write_segments(RasterShared &sh, uint32_t *seg, uint32_t ex, Span span, Word word) {
+    uint32_t ps = ex >> 11, sg = ex & 2047u;
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+        const uint32_t sp = span(j);
+        if (sp == NO_SPAN) continue;
+        const uint32_t s0 = sp & 0xffu, wdt = (sp >> 8) - s0 + 1u;
+        seg[sg] = word(j, ps, s0);
+        mark_run(sh, ps, wdt, sg);
+        ps += wdt;
+        ++sg;
+    }
+}
+
+// Box tasks.  Wave 0 lays the bin boxes of the staged candidates c0 .. m - 1, clipped to the rectangle
+// [X0, X1] x [Y0, Y1], end to end (prefix of the areas) as pinfo entries, and marks their runs.  Returns
+// the pass's pairs; next = the first candidate left out.
+// SPLIT (tile groups: a clipped box is <= 1024 px, and some candidates have no pixel in the group): the
+// bitmap holds PAIR_CAP pairs, so a pass takes the leading candidates whose pairs fit -- the prefix grows
+// with the lane; one always does -- and the entries are compacted by rank; the pass clears its own bitmap
+// words.  Otherwise (a tile: every staged box holds >= 1 pixel of it, so the starts are distinct, and 64
+// boxes of <= 256 px fit) entry = candidate, and the caller has cleared the bitmap.
+template <bool SPLIT>
+__device__ __forceinline__ int layout_boxes(RasterShared &sh, int c0, int m, int X0, int Y0, int X1, int Y1, int &next) {
+    const int lane = __lane_id();
+    int area = 0, bx0 = 0, by0 = 0, bw = 1;
+    if (lane >= c0 && lane < m) {
+        const uint4 bb = reinterpret_cast<const uint4 *>(&sh.rec[lane * 4])[3];   // z2 word gbx gby
+        const int x0 = max(lo16(bb.z), X0), x1 = min(hi16(bb.z), X1);
+        const int y0 = max(lo16(bb.w), Y0), y1 = min(hi16(bb.w), Y1);
+        if (x0 <= x1 && y0 <= y1) { area = (x1 - x0 + 1) * (y1 - y0 + 1); bx0 = x0; by0 = y0; bw = x1 - x0 + 1; }
+    }
+    const int incl = (int)wave_incl_sum((uint32_t)area);
+    bool on = area > 0;
+    uint32_t entry = (uint32_t)lane;
+    int total;
+    next = m;
+    if constexpr (SPLIT) {
+        const bool fit = incl <= PAIR_CAP;
+        next = __popcll(__ballot(fit));   // (>= c0 + 1)
+        total = __shfl(incl, next - 1);
+        for (int i = lane; i * 64 < total; i += 64) sh.bits[i] = 0ull;
+        wave_lds_sync();
+        on = on && fit;
+        entry = lanes_below(__ballot(on));
+    } else {
+        total = __shfl(incl, 63);
+    }
+    if (on) {
+        // 2^16 / width rounded up: (local * magic) >> 16 == local / width for local < 16 * width, width <= 64
+        sh.pinfo[entry] = make_uint4((uint32_t)(incl - area), (uint32_t)bx0 | ((uint32_t)by0 << 16), (uint32_t)bw | ((uint32_t)lane << 8),
+                                     (65536u + (uint32_t)bw - 1u) / (uint32_t)bw);
+        mark_run(sh, (uint32_t)(incl - area), (uint32_t)area, entry);
+    }
+    return total;
+}
+
+// Pair k of the pass inside pinfo entry pi: its staged candidate and pixel.
+__device__ __forceinline__ int pinfo_pixel(const uint4 pi, int k, int &px, int &py) {
+    const int bw = (int)(pi.z & 0xffu), local = k - (int)pi.x;
+    const int ly = (int)(((uint32_t)local * pi.w) >> 16), lx = local - ly * bw;
+    px = (int)(pi.y & 0xffffu) + lx;
+    py = (int)(pi.y >> 16) + ly;
+    return (int)(pi.z >> 8);
+}
+
+// The owner (segment or pinfo entry) of lane `lane`'s pair in the 64-pair window from pair k0: the
+// window's bitmap word's first owner + the starts in the word up to the pair.
+__device__ __forceinline__ int pair_owner(const RasterShared &sh, int k0, int lane) {
+    const unsigned long long wb = sh.bits[k0 >> 6];
+    const unsigned long long upto = ((2ull << lane) - 1ull) & ~1ull;   // bits 1..lane
+    return (int)sh.wown[k0 >> 6] + __popcll(wb & upto);
+}
+
+// Staged candidate o at pixel (px, py): whether the pixel passes, and then its key.
+__device__ __forceinline__ bool staged_key(const FrameParams &fp, const RasterShared &sh, int o, int px, int py, bool slot_keys,
+                                           bool single, unsigned long long &key) {
+    const TriRec r = rec_from_hot(fp, &sh.rec[o * 4], &sh.ext[o]);
+    float z;
+    if (!pixel_test(fp, r, px, py, z)) return false;
+    key = cand_key(z, sh.id[o], slot_keys, single ? (uint32_t)o : SLOT_NONE);
+    return true;
+}
+
+// One (candidate, pixel) pair task: a passing pixel's key into its key slot.
+__device__ __forceinline__ void test_pair(const FrameParams &fp, RasterShared &sh, int o, int px, int py,
+                                          unsigned long long *key_slot, bool slot_keys, bool single) {
+    unsigned long long key;
+    if (staged_key(fp, sh, o, px, py, slot_keys, single, key)) atomicMin(key_slot, key);
+}
+
+// The pair loop: wave w takes the 64-pair windows w, w + 4, ... of the pass's pairs.  pair(owner, k, px,
+// py) decodes pair k to its staged candidate and pixel; key_slot(px, py) is the pixel's key, or null where
+// the pixel is not drawn.
+template <class Pair, class KeySlot>
+__device__ __forceinline__ void walk_pairs(const FrameParams &fp, RasterShared &sh, int total, bool slot_keys, bool single,
+                                           Pair pair, KeySlot key_slot) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int k0 = 64 * wave; k0 < total; k0 += 256) {
+        const int k = k0 + lane;
+        if (k < total) {
+            int px, py;
+            const int o = pair(pair_owner(sh, k0, lane), k, px, py);
+            unsigned long long *slot = key_slot(px, py);
+            if (slot) test_pair(fp, sh, o, px, py, slot, slot_keys, single);
+        }
+    }
+}
+
+// The winner's records for the resolve: the staged copies when its key carries a slot (only single-pass
+// items encode one), else HBM.  Returns the raster record (its float bbox is not read here); sr: the shade
+// record.
+__device__ __forceinline__ TriRec winner_records(const FrameParams &fp, const FrameBuffers &fb, const RasterShared &sh, uint32_t id,
+                                                 uint32_t slot, ShadeRec &sr) {
+    float4 h4[4];
+    float4 *e4 = reinterpret_cast<float4 *>(&sr);
+    if (slot != SLOT_NONE) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) h4[k] = sh.rec[slot * 4 + k];
+#pragma unroll
+        for (int k = 0; k < 5; ++k) e4[k] = sh.srec[slot * 5 + k];
+    } else {
+        const float4 *s4 = reinterpret_cast<const float4 *>(&fb.recs[id]);
+        const float4 *g4 = reinterpret_cast<const float4 *>(&fb.shade[id]);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) h4[k] = s4[k];
+#pragma unroll
+        for (int k = 0; k < 5; ++k) e4[k] = g4[k];
+    }
+    return rec_from_hot(fp, h4[0], h4[1], h4[2], h4[3], make_float4(0.f, 0.f, 0.f, 0.f));
+}
+
+// The shaded floats as the pixel's colour (truncated to uint8 like the reference) and prequant value.
+__device__ __forceinline__ void pack_pixel(const float (&pre)[3], uint32_t &rgba, float4 &pq) {
+    const uint32_t cr = (uint32_t)(uint8_t)pre[0], cg = (uint32_t)(uint8_t)pre[1], cb = (uint32_t)(uint8_t)pre[2];
+    rgba = cr | (cg << 8) | (cb << 16) | (255u << 24);
+    pq = make_float4(pre[0], pre[1], pre[2], 1.0f);
+}
+
+// A covered pixel whose winner has stored records: (u, v, w) recomputed with the pair test's arithmetic,
+// the depth, and the winner shaded.  dbase: the frame's slice of the batch's draw table `draws`.
+__device__ __forceinline__ void shade_stored_winner(const FrameParams &fp, const FrameBuffers &fb, const DrawGPU *draws, int dbase,
+                                                    const RasterShared &sh, uint32_t id, uint32_t slot, int px, int py,
+                                                    float &depth, uint32_t &rgba, float4 &pq) {
+    ShadeRec sr;
+    const TriRec r = winner_records(fp, fb, sh, id, slot, sr);
+    float u, v, w;
+    bary_pass(r, (float)px + 0.5f, (float)py + 0.5f, u, v, w);   // the winner's own values
+    depth = (u * r.z0 + v * r.z1) + w * r.z2;
+    if (SHS_DBG(fp, DBG_SKIP_SHADE)) return;
+    const int wd = dbase + r.draw;   // the frame's draw (ShadeRec::draw is frame 0's when shared)
+    const float4 *du = wd < LDS_DRAWS ? &sh.du[wd * 4] : reinterpret_cast<const float4 *>(draws[wd].light);
+    float pre[3];
+    shade_winner(du, sr, u, v, w, pre);
+    pack_pixel(pre, rgba, pq);
+}
+
+// A resolved pixel of a busy tile into every enabled plane: colour and prequant in canvas rows, depth and
+// present in screen rows (copy_to_SDLSurface: surface row h-1-y takes canvas row y, i.e. the screen row).
+__device__ __forceinline__ void store_pixel(const FrameParams &fp, const FrameBuffers &fb, int px, int py, uint32_t rgba, float depth,
+                                            float4 pq) {
+    // (DBG_SKIP_TILE_STORES, timing experiments: the busy tile's stores dropped, its values kept live)
+    const bool dbg_nost = SHS_DBG(fp, DBG_SKIP_TILE_STORES) && !(rgba == 0x12345678u && depth == -1.0f);
+    if (px < fp.W && py < fp.H && !dbg_nost) {
+        LEGACY_STORE(rgba, &reinterpret_cast<uint32_t *>(fb.color)[(size_t)(fp.H - 1 - py) * fp.W + px]);
+        LEGACY_STORE(depth, &fb.depth[(size_t)py * fp.W + px]);
+        if (fb.prequant) fb.prequant[(size_t)(fp.H - 1 - py) * fp.W + px] = pq;
+        if (fb.present) LEGACY_STORE(rgba, &fb.present[(size_t)py * fp.W + px]);
+    }
+}
+
 // One busy raster tile.  Candidates (bin box overlaps the tile) are staged in LDS; every (candidate,
 // pixel of its clipped bin box) pair is one lane-task, dealt evenly over the workgroup by a prefix
 // sum of the box areas; passing pairs atomic-min their key into the tile's LDS key array.  Then
@@ -1380,6 +1655,7 @@ __device__ __forceinline__ void raster_tile(const FrameParams &fp, const FrameBu
     unsigned long long kmin = KEY_EMPTY;   // per-pixel loop: this thread's pixel key
     const bool slot_keys = fp.n_tris < (1 << 25);
     bool single = n_items <= (uint32_t)CAND;   // one gather round and one staging pass: winners in LDS
+    auto key_slot = [&](int px, int py) { return &sh.key[(py - Y0) * RTW + (px - X0)]; };   // a pixel of the tile
 
     for (uint32_t base = 0; base < n_items; base += CAND) {
         __syncthreads();
@@ -1426,8 +1702,7 @@ __device__ __forceinline__ void raster_tile(const FrameParams &fp, const FrameBu
         for (uint32_t c = 0; c < nc; c += RCHUNK) {
             const int m = (int)min((uint32_t)RCHUNK, nc - c);
             if (c > 0) __syncthreads();
-            // stage records (single-pass tiles: the shading records too, so the resolve reads no HBM):
-            // consecutive lanes load consecutive float4s of one record; all loads in one round trip
+            // stage the records (the float bbox only for ghosts -- tagged entries -- or every candidate in scan mode)
             if (tid < m) sh.id[tid] = sh.cand[c + tid] & ~BIN_GHOST;
             for (int i = tid; i < m * (RTW * RTH / 64); i += 256) sh.bits[i] = 0ull;
             if constexpr (no_recs) {   // a quad of lanes per candidate (RCHUNK * 4 == 256)
@@ -1436,38 +1711,7 @@ __device__ __forceinline__ void raster_tile(const FrameParams &fp, const FrameBu
                     stage_from_mesh(fp, fb, draws + dbase, dbase, sh.cand[c + ci] & ~BIN_GHOST, single, &sh.rec[ci * 4], &sh.ext[ci],
                                     &sh.srec[ci * 5]);
             } else {
-                // (the float bbox only for ghosts -- tagged entries -- or every candidate in scan mode)
-                constexpr int NQ = (RCHUNK * 4 + 255) / 256, NS = (RCHUNK * 5 + 255) / 256;
-                float4 q[NQ], s[NS], e = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-                for (int k = 0; k < NQ; ++k) {
-                    const int f = tid + 256 * k;
-                    const int ci = f >> 2;
-                    q[k] = f < 4 * m ? reinterpret_cast<const float4 *>(&fb.recs[sh.cand[c + min(ci, m - 1)] & ~BIN_GHOST])[f & 3]
-                                     : make_float4(0.f, 0.f, 0.f, 0.f);
-                }
-                {
-                    const uint32_t ce = tid < m ? sh.cand[c + tid] : 0u;
-                    if (tid < m && (scan || (ce & BIN_GHOST))) e = fb.rext[ce & ~BIN_GHOST];
-                }
-#pragma unroll
-                for (int k = 0; k < NS; ++k) {
-                    const int f = tid + 256 * k;
-                    const int ci = f / 5;
-                    s[k] = single && f < 5 * m ? reinterpret_cast<const float4 *>(&fb.shade[sh.cand[min(ci, m - 1)] & ~BIN_GHOST])[f - 5 * ci]
-                                               : make_float4(0.f, 0.f, 0.f, 0.f);
-                }
-#pragma unroll
-                for (int k = 0; k < NQ; ++k) {
-                    const int f = tid + 256 * k;
-                    if (f < 4 * m) sh.rec[f] = q[k];
-                }
-                if (tid < m) sh.ext[tid] = e;
-#pragma unroll
-                for (int k = 0; k < NS; ++k) {
-                    const int f = tid + 256 * k;
-                    if (single && f < 5 * m) sh.srec[f] = s[k];
-                }
+                stage_stored<!SPANS>(fb, sh, c, m, single, scan);
             }
             __syncthreads();
             tl_mark(tl, tls, 2);
@@ -1482,12 +1726,8 @@ __device__ __forceinline__ void raster_tile(const FrameParams &fp, const FrameBu
                     const int x0 = lo16(bb.z), x1 = hi16(bb.z), y0 = lo16(bb.w), y1 = hi16(bb.w);
                     if (y1 < wy0 || y0 > wy1) continue;                                     // wave-uniform
                     if (px < x0 || px > x1 || py < y0 || py > y1) continue;
-                    const TriRec r = rec_from_hot(fp, &sh.rec[cc * 4], &sh.ext[cc]);
-                    float z;
-                    if (pixel_test(fp, r, px, py, z)) {
-                        const unsigned long long k = cand_key(z, sh.id[cc], slot_keys, single ? (uint32_t)cc : SLOT_NONE);
-                        kmin = k < kmin ? k : kmin;
-                    }
+                    unsigned long long k;
+                    if (staged_key(fp, sh, cc, px, py, slot_keys, single, k)) kmin = k < kmin ? k : kmin;
                 }
                 seq += (uint32_t)m;
                 continue;
@@ -1504,8 +1744,8 @@ __device__ __forceinline__ void raster_tile(const FrameParams &fp, const FrameBu
                 uint32_t ptot = 0u;
                 {
                     const int ci = tid >> 2, q = tid & 3;
-                    uint32_t spw[2] = {0x1fu, 0x1fu};   // tile-relative x0 | x1 << 8; 0x1f: empty
-                    uint32_t pk = 0u;                   // pairs << 11 | segments
+                    uint32_t spw[2] = {NO_SPAN, NO_SPAN};
+                    uint32_t pk = 0u;
                     if (ci < m) {
                         const float4 *rc = &sh.rec[ci * 4];
                         const uint4 bb = reinterpret_cast<const uint4 *>(rc)[3];   // z2 word gbx gby
@@ -1525,122 +1765,48 @@ __device__ __forceinline__ void raster_tile(const FrameParams &fp, const FrameBu
                             }
                         }
                     }
-                    uint32_t incl = pk;
-    #pragma unroll
-                    for (int o = 1; o < 64; o <<= 1) {
-                        const uint32_t vv = (uint32_t)__shfl_up((int)incl, o);
-                        if (lane >= o) incl += vv;
-                    }
-                    if (lane == 63) sh.wtot[wave] = incl;
-                    __syncthreads();
-                    uint32_t pbase = 0u;
-    #pragma unroll
-                    for (int w2 = 0; w2 < 4; ++w2) {
-                        const uint32_t p2 = sh.wtot[w2];
-                        if (w2 < wave) pbase += p2;
-                        ptot += p2;
-                    }
-                    if (pk) {
-                        const uint32_t ex = pbase + incl - pk;
-                        uint32_t ps = ex >> 11, sg = ex & 2047u;
-    #pragma unroll
-                        for (int j = 0; j < 2; ++j) {
-                            if (spw[j] == 0x1fu) continue;
-                            const uint32_t s0 = spw[j] & 0xffu, wdt = (spw[j] >> 8) - s0 + 1u;
-                            sh.seg[sg] = ps | (s0 << 14) | ((uint32_t)(2 * q + j) << 19) | ((uint32_t)ci << 22);
-                            atomicOr(&sh.bits[ps >> 6], 1ull << (ps & 63u));
-                            for (uint32_t wd = (ps + 63u) >> 6; wd * 64u < ps + wdt; ++wd) sh.wown[wd] = (uint16_t)sg;
-                            ps += wdt;
-                            ++sg;
-                        }
-                    }
+                    const uint32_t ex = block_span_prefix(sh, pk, lane, wave, ptot);
+                    if (pk)
+                        write_segments<2>(sh, sh.seg, ex, [&](int j) { return spw[j]; },
+                                          [&](int j, uint32_t ps, uint32_t s0) { return seg_pack(ps, s0, (uint32_t)(2 * q + j), (uint32_t)ci); });
                 }
                 __syncthreads();
                 const int total = SHS_DBG(fp, DBG_SKIP_PAIRS) ? 0 : (int)(ptot >> 11);
                 pairs += total;
-                for (int k0 = 64 * wave; k0 < total; k0 += 256) {
-                    const int k = k0 + lane;
-                    if (k < total) {
-                        const unsigned long long wb = sh.bits[k0 >> 6];
-                        const unsigned long long upto = ((2ull << lane) - 1ull) & ~1ull;   // bits 1..lane
-                        const int o = (int)sh.wown[k0 >> 6] + __popcll(wb & upto);
-                        const uint32_t sgi = sh.seg[o];
-                        const int cc = (int)(sgi >> 22);
-                        const int px = X0 + (int)((sgi >> 14) & 31u) + (k - (int)(sgi & 0x3fffu)), py = Y0 + (int)((sgi >> 19) & 7u);
-                        const TriRec r = rec_from_hot(fp, &sh.rec[cc * 4], &sh.ext[cc]);
-                        float z;
-                        if (pixel_test(fp, r, px, py, z))
-                            atomicMin(&sh.key[(py - Y0) * RTW + (px - X0)],
-                                      cand_key(z, sh.id[cc], slot_keys, single ? (uint32_t)cc : SLOT_NONE));
-                    }
-                }
+                walk_pairs(fp, sh, total, slot_keys, single,
+                           [&](int seg, int k, int &px, int &py) { return seg_pixel(sh.seg[seg], k, X0, Y0, px, py); }, key_slot);
             } else {
                 // (scan-mode frames: whole clipped bin boxes -- C2's Suzanne triangles fill most of their boxes,
                 // and the spans measured slower there: 0.271 -> 0.278 ms per step -- on a per-tile item, a
                 // median of 72 span tasks for ~600 pairs, in a kernel then bound by its clear strips; a tile
                 // group's span pass, raster_group, serves four tiles' pairs)
                 // Pair tasks, dealt evenly over the workgroup.  Wave 0 lays the staged candidates' clipped
-                // bin boxes end to end (prefix of the areas; every staged box holds >= 1 pixel of the tile,
-                // so the starts are distinct) and marks each start in a bitmap over the pairs, plus the
-                // owner of every bitmap word's first pair.  Wave w then takes the 64-pair windows w, w + 4,
+                // bin boxes end to end (layout_boxes) and marks each start in a bitmap over the pairs, plus
+                // the owner of every bitmap word's first pair.  Wave w then takes the 64-pair windows w, w + 4,
                 // ...: a pair's owner = that word's first owner + the starts in the word up to it.
                 if (wave == 0) {
-                    int area = 0, bx0 = 0, by0 = 0, bw = 1;
-                    if (lane < m) {
-                        const uint4 bb = reinterpret_cast<const uint4 *>(&sh.rec[lane * 4])[3];   // z2 word gbx gby
-                        const int x0 = max(lo16(bb.z), X0), x1 = min(hi16(bb.z), X1);
-                        const int y0 = max(lo16(bb.w), Y0), y1 = min(hi16(bb.w), Y1);
-                        if (x0 <= x1 && y0 <= y1) { area = (x1 - x0 + 1) * (y1 - y0 + 1); bx0 = x0; by0 = y0; bw = x1 - x0 + 1; }
-                    }
-                    int incl = area;
-    #pragma unroll
-                    for (int o = 1; o < 64; o <<= 1) {
-                        const int v = __shfl_up(incl, o);
-                        if (lane >= o) incl += v;
-                    }
-                    const int start = incl - area;
-                    if (area > 0) {
-                        // 2^16 / width rounded up: (local * magic) >> 16 == local / width for local < 256
-                        sh.pinfo[lane] = make_uint4((uint32_t)start, (uint32_t)bx0 | ((uint32_t)by0 << 16), (uint32_t)bw,
-                                                    (65536u + (uint32_t)bw - 1u) / (uint32_t)bw);
-                        atomicOr(&sh.bits[start >> 6], 1ull << (start & 63));
-                        for (int wd = (start + 63) >> 6; wd * 64 < incl; ++wd) sh.wown[wd] = (uint16_t)lane;
-                    }
-                    if (lane == 63) sh.npairs = (uint32_t)incl;
+                    int next;
+                    const int total = layout_boxes<false>(sh, 0, m, X0, Y0, X1, Y1, next);
+                    if (lane == 0) sh.npairs = (uint32_t)total;
                 }
                 __syncthreads();
                 const int total = SHS_DBG(fp, DBG_SKIP_PAIRS) ? 0 : (int)sh.npairs;
                 pairs += total;
-                for (int k0 = 64 * wave; k0 < total; k0 += 256) {
-                    const int k = k0 + lane;
-                    if (k < total) {
-                        const unsigned long long wb = sh.bits[k0 >> 6];
-                        const unsigned long long upto = ((2ull << lane) - 1ull) & ~1ull;   // bits 1..lane
-                        const int o = (int)sh.wown[k0 >> 6] + __popcll(wb & upto);
-                        const uint4 pi = sh.pinfo[o];
-                        const int local = k - (int)pi.x;
-                        const int ly = (int)(((uint32_t)local * pi.w) >> 16), lx = local - ly * (int)pi.z;
-                        const int px = (int)(pi.y & 0xffffu) + lx, py = (int)(pi.y >> 16) + ly;
-                        const TriRec r = rec_from_hot(fp, &sh.rec[o * 4], &sh.ext[o]);
-                        float z;
-                        if (pixel_test(fp, r, px, py, z))
-                            atomicMin(&sh.key[(py - Y0) * RTW + (px - X0)],
-                                      cand_key(z, sh.id[o], slot_keys, single ? (uint32_t)o : SLOT_NONE));
-                    }
-                }
+                walk_pairs(fp, sh, total, slot_keys, single,
+                           [&](int e, int k, int &px, int &py) { return pinfo_pixel(sh.pinfo[e], k, px, py); }, key_slot);
             }
             seq += (uint32_t)m;
         }
     }
     tl_mark(tl, tls, 3);
-    // tile-clamp pixels of unbounded slivers outside their bbox that passed (k_setup ghost waves)
-    {
-        for (uint32_t f = tid; f < n_frag; f += 256) {
-            const GhostFrag g = fb.frags[f];
-            const int gx = (int)(g.xy & 0xffffu), gy = (int)(g.xy >> 16);
-            if (g.frame == (uint32_t)frame && gx >= X0 && gx <= X1 && gy >= Y0 && gy <= Y1)
-                atomicMin(&sh.key[(gy - Y0) * RTW + (gx - X0)], cand_key(g.z, g.id, slot_keys, SLOT_NONE));
-        }
+    // tile-clamp pixels of unbounded slivers outside their bbox that passed (k_setup's ghost waves, k_ghost).
+    // (This loop and raster_group's are left as two copies: as one helper over key_slot the bin-mode span
+    // kernel measured 0.003 ms per C3 step slower, the group kernels 0.002 ms per C1 and 0.003 per C2 step.)
+    for (uint32_t f = tid; f < n_frag; f += 256) {
+        const GhostFrag g = fb.frags[f];
+        const int gx = (int)(g.xy & 0xffffu), gy = (int)(g.xy >> 16);
+        if (g.frame == (uint32_t)frame && gx >= X0 && gx <= X1 && gy >= Y0 && gy <= Y1)
+            atomicMin(&sh.key[(gy - Y0) * RTW + (gx - X0)], cand_key(g.z, g.id, slot_keys, SLOT_NONE));
     }
     __syncthreads();
 
@@ -1654,69 +1820,20 @@ __device__ __forceinline__ void raster_tile(const FrameParams &fp, const FrameBu
     float4 pq = make_float4(0.f, 0.f, 0.f, 0.f);
     const bool covered = key != KEY_EMPTY && px < fp.W && py < fp.H;
     if (covered) {
-        const uint32_t lo = (uint32_t)key;
-        const uint32_t id = slot_keys ? lo >> 7 : lo, slot = slot_keys ? lo & SLOT_NONE : SLOT_NONE;
-        if constexpr (!no_recs) {   // stored records: the staged copies (single-pass tiles) or HBM
-            TriRec r;
-            ShadeRec sr;
-            {
-                float4 h4[4];   // the winner's stored record (its float bbox is not read here)
-                float4 *e4 = reinterpret_cast<float4 *>(&sr);
-                if (slot != SLOT_NONE) {   // only single-pass tiles encode a slot: the staged copies
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) h4[k] = sh.rec[slot * 4 + k];
-#pragma unroll
-                    for (int k = 0; k < 5; ++k) e4[k] = sh.srec[slot * 5 + k];
-                } else {
-                    const float4 *s4 = reinterpret_cast<const float4 *>(&fb.recs[id]);
-                    const float4 *g4 = reinterpret_cast<const float4 *>(&fb.shade[id]);
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) h4[k] = s4[k];
-#pragma unroll
-                    for (int k = 0; k < 5; ++k) e4[k] = g4[k];
-                }
-                r = rec_from_hot(fp, h4[0], h4[1], h4[2], h4[3], make_float4(0.f, 0.f, 0.f, 0.f));
-            }
-            float u, v, w;
-            bary_pass(r, (float)px + 0.5f, (float)py + 0.5f, u, v, w);   // the winner's own values
-            depth = (u * r.z0 + v * r.z1) + w * r.z2;
-            if (!SHS_DBG(fp, DBG_SKIP_SHADE)) {
-                const int wd = dbase + r.draw;   // the frame's draw (ShadeRec::draw is frame 0's when shared)
-                const float4 *du = wd < LDS_DRAWS ? &sh.du[wd * 4] : reinterpret_cast<const float4 *>(draws[wd].light);
-                float pre[3];
-                shade_winner(du, sr, u, v, w, pre);
-                const uint32_t cr = (uint32_t)(uint8_t)pre[0], cg = (uint32_t)(uint8_t)pre[1], cb = (uint32_t)(uint8_t)pre[2];
-                rgba = cr | (cg << 8) | (cb << 16) | (255u << 24);
-                pq = make_float4(pre[0], pre[1], pre[2], 1.0f);
-            }
+        uint32_t id, slot;
+        key_winner(key, slot_keys, id, slot);
+        if constexpr (!no_recs) {
+            shade_stored_winner(fp, fb, draws, dbase, sh, id, slot, px, py, depth, rgba, pq);
         } else {
             const bool shade = !SHS_DBG(fp, DBG_SKIP_SHADE);
             f3 A = {0.f, 0.f, 0.f}, N = {0.f, 0.f, 0.f};   // interpolated varyings (shade_interp's inputs)
             int shading = 0;
             float4 du[4];
-            if (no_recs && slot == SLOT_NONE) {   // binned frame, winner not staged: recomputed from the mesh
+            if (slot == SLOT_NONE) {   // binned frame, winner not staged: recomputed from the mesh
                 resolve_from_mesh(fp, fb, draws, dbase, id, px, py, sh.du, shade, depth, A, N, shading, du);
-            } else {
-                TriRec r;
+            } else {   // the staged copies stage_from_mesh made
                 ShadeRec sr;
-                {
-                    float4 h4[4];   // the winner's stored record (its float bbox is not read here)
-                    float4 *e4 = reinterpret_cast<float4 *>(&sr);
-                    if (slot != SLOT_NONE) {   // only single-pass tiles encode a slot: the staged copies
-    #pragma unroll
-                        for (int k = 0; k < 4; ++k) h4[k] = sh.rec[slot * 4 + k];
-    #pragma unroll
-                        for (int k = 0; k < 5; ++k) e4[k] = sh.srec[slot * 5 + k];
-                    } else {
-                        const float4 *s4 = reinterpret_cast<const float4 *>(&fb.recs[id]);
-                        const float4 *g4 = reinterpret_cast<const float4 *>(&fb.shade[id]);
-    #pragma unroll
-                        for (int k = 0; k < 4; ++k) h4[k] = s4[k];
-    #pragma unroll
-                        for (int k = 0; k < 5; ++k) e4[k] = g4[k];
-                    }
-                    r = rec_from_hot(fp, h4[0], h4[1], h4[2], h4[3], make_float4(0.f, 0.f, 0.f, 0.f));
-                }
+                const TriRec r = winner_records(fp, fb, sh, id, slot, sr);
                 float u, v, w;
                 bary_pass(r, (float)px + 0.5f, (float)py + 0.5f, u, v, w);   // the winner's own values
                 depth = (u * r.z0 + v * r.z1) + w * r.z2;
@@ -1731,25 +1848,15 @@ __device__ __forceinline__ void raster_tile(const FrameParams &fp, const FrameBu
             if (shade) {
                 float pre[3];
                 shade_interp(du, shading, A, N, pre);
-                const uint32_t cr = (uint32_t)(uint8_t)pre[0], cg = (uint32_t)(uint8_t)pre[1], cb = (uint32_t)(uint8_t)pre[2];
-                rgba = cr | (cg << 8) | (cb << 16) | (255u << 24);
-                pq = make_float4(pre[0], pre[1], pre[2], 1.0f);
+                pack_pixel(pre, rgba, pq);
             }
         }
-        }
+    }
     tl_mark(tl, tls, 4);
     if (tl && tid == 0) { tl[TL_STRIDE * tls + 8] = seq; tl[TL_STRIDE * tls + 9] = (uint64_t)pairs; }
     const uint64_t cm = __ballot(covered);
     if (lane == 0 && cm) atomicAdd(&sh.cov, (uint32_t)__popcll(cm));
-    // (DBG_SKIP_TILE_STORES, timing experiments: the busy tile's stores dropped, its values kept live)
-    const bool dbg_nost = SHS_DBG(fp, DBG_SKIP_TILE_STORES) && !(rgba == 0x12345678u && depth == -1.0f);
-    if (px < fp.W && py < fp.H && !dbg_nost) {
-        LEGACY_STORE(rgba, &reinterpret_cast<uint32_t *>(fb.color)[(size_t)(fp.H - 1 - py) * fp.W + px]);
-        LEGACY_STORE(depth, &fb.depth[(size_t)py * fp.W + px]);
-        if (fb.prequant) fb.prequant[(size_t)(fp.H - 1 - py) * fp.W + px] = pq;
-        // copy_to_SDLSurface: surface row h-1-y takes canvas row y, i.e. the screen row
-        if (fb.present) LEGACY_STORE(rgba, &fb.present[(size_t)py * fp.W + px]);
-    }
+    store_pixel(fp, fb, px, py, rgba, depth, pq);
     // the tile no longer holds the clear values: a later batch that leaves it idle clears it
     if (tid == 0) fb.stale[rt] = 1u;
     tl_mark(tl, tls, 5);
@@ -1807,6 +1914,15 @@ __device__ __forceinline__ void raster_group(const FrameParams &fp, const FrameB
     bool single = n_items <= (uint32_t)CAND;   // one gather round and one staging pass: winners in LDS
     const uint32_t bmask = (uint32_t)__ballot(flag == fp.epoch) & ((1u << (GX * GY)) - 1u);   // (epoch != 0)
     const int t_first = __ffs((int)bmask) - 1;
+    // A pixel of the group: its key in its tile's key array (tile 0: RasterShared's, the others GroupShared's),
+    // or null when the tile is not busy -- only the group's busy tiles are drawn (a sharded frame's group
+    // holds tiles of other shards, which setup never marks).
+    auto key_slot = [&](int px, int py) -> unsigned long long * {
+        const int tx = (px - GX0) / RTW, ty = (py - GY0) / RTH, t = ty * GX + tx;
+        if (!((bmask >> t) & 1u)) return nullptr;
+        unsigned long long *key = t ? &gs.key[(t - 1) * (RTW * RTH)] : sh.key;
+        return &key[(py - GY0 - ty * RTH) * RTW + (px - GX0 - tx * RTW)];
+    };
 
     for (uint32_t base = 0; base < n_items; base += CAND) {
         // every bin box of the round against the group rectangle (4 independent loads per thread)
@@ -1846,40 +1962,7 @@ __device__ __forceinline__ void raster_group(const FrameParams &fp, const FrameB
             if (c > 0) __syncthreads();
             // stage the records, float bboxes and (single-pass groups) shade records: one round trip
             if (tid < m) sh.id[tid] = sh.cand[c + tid];
-            {
-                constexpr int NQ = (RCHUNK * 4 + 255) / 256, NS = (RCHUNK * 5 + 255) / 256;
-                float4 q[NQ], s[NS], e = make_float4(0.f, 0.f, 0.f, 0.f);
-                // (the thread's staging indices are computed here, per pass: hoisted out of the item loop
-                // they are registers held across the whole kernel, which then spills)
-                int stid = tid;
-                asm volatile("" : "+v"(stid));
-#pragma unroll
-                for (int k = 0; k < NQ; ++k) {
-                    const int f = stid + 256 * k;
-                    const int ci = f >> 2;
-                    q[k] = f < 4 * m ? reinterpret_cast<const float4 *>(&fb.recs[sh.cand[c + min(ci, m - 1)]])[f & 3]
-                                     : make_float4(0.f, 0.f, 0.f, 0.f);
-                }
-                if (tid < m) e = fb.rext[sh.cand[c + tid]];
-#pragma unroll
-                for (int k = 0; k < NS; ++k) {
-                    const int f = stid + 256 * k;
-                    const int ci = f / 5;
-                    s[k] = single && f < 5 * m ? reinterpret_cast<const float4 *>(&fb.shade[sh.cand[min(ci, m - 1)]])[f - 5 * ci]
-                                               : make_float4(0.f, 0.f, 0.f, 0.f);
-                }
-#pragma unroll
-                for (int k = 0; k < NQ; ++k) {
-                    const int f = tid + 256 * k;
-                    if (f < 4 * m) sh.rec[f] = q[k];
-                }
-                if (tid < m) sh.ext[tid] = e;
-#pragma unroll
-                for (int k = 0; k < NS; ++k) {
-                    const int f = tid + 256 * k;
-                    if (single && f < 5 * m) sh.srec[f] = s[k];
-                }
-            }
+            stage_stored<true>(fb, sh, c, m, single, true);
             __syncthreads();
             tl_mark(tl, tls, 2);
             bool boxes = true;
@@ -1888,7 +1971,6 @@ __device__ __forceinline__ void raster_group(const FrameParams &fp, const FrameB
                 // candidates cj, cj + 16, ...; one block prefix of (pairs << 11 | segments) lays the
                 // threads' spans end to end, each thread's in candidate order.
                 static_assert(PAIR_WORDS == 256 && GY * RTH == 16 && RCHUNK == 64, "the span pass's thread mapping");
-                constexpr uint32_t NO_SPAN = 0xffu;
                 sh.bits[tid] = 0ull;
                 // (the thread's task indices are computed here, per pass, and its spans wait in LDS for the
                 // prefix -- RasterShared::seg, the tile span path's, is free in this kernel: as registers
@@ -1918,62 +2000,19 @@ __device__ __forceinline__ void raster_group(const FrameParams &fp, const FrameB
                     }
                     spw[j * 256] = (uint16_t)sp;
                 }
-                uint32_t incl = pk;
-#pragma unroll
-                for (int o = 1; o < 64; o <<= 1) {
-                    const uint32_t vv = (uint32_t)__shfl_up((int)incl, o);
-                    if (lane >= o) incl += vv;
-                }
-                if (lane == 63) sh.wtot[wave] = incl;
-                __syncthreads();
-                uint32_t pbase = 0u, ptot = 0u;
-#pragma unroll
-                for (int w2 = 0; w2 < 4; ++w2) {
-                    const uint32_t p2 = sh.wtot[w2];
-                    if (w2 < wave) pbase += p2;
-                    ptot += p2;
-                }
+                uint32_t ptot;
+                const uint32_t ex = block_span_prefix(sh, pk, lane, wave, ptot);
                 boxes = (ptot >> 11) > (uint32_t)PAIR_CAP;   // (block-uniform)
-                if (!boxes && pk) {
-                    const uint32_t ex = pbase + incl - pk;
-                    uint32_t ps = ex >> 11, sg = ex & 2047u;
-#pragma unroll
-                    for (int j = 0; j < RCHUNK / 16; ++j) {
-                        const uint32_t sp = spw[j * 256];
-                        if (sp == NO_SPAN) continue;
-                        const uint32_t s0 = sp & 0xffu, wdt = (sp >> 8) - s0 + 1u;
-                        gs.seg[sg] = group_seg_pack(ps, s0, (uint32_t)row, (uint32_t)(cj + 16 * j));
-                        atomicOr(&sh.bits[ps >> 6], 1ull << (ps & 63u));
-                        for (uint32_t wd = (ps + 63u) >> 6; wd * 64u < ps + wdt; ++wd) sh.wown[wd] = (uint16_t)sg;
-                        ps += wdt;
-                        ++sg;
-                    }
-                }
+                if (!boxes && pk)
+                    write_segments<RCHUNK / 16>(sh, gs.seg, ex, [&](int j) { return (uint32_t)spw[j * 256]; },
+                                                [&](int j, uint32_t ps, uint32_t s0) { return seg_pack(ps, s0, (uint32_t)row, (uint32_t)(cj + 16 * j)); });
                 __syncthreads();
                 tl_mark(tl, tls, TL_SPANS - 2);
                 if (!boxes) {
                     const int total = SHS_DBG(fp, DBG_SKIP_PAIRS) ? 0 : (int)(ptot >> 11);
                     if (tl && tid == 0) gs.pairs += (uint32_t)total;
-                    for (int k0 = 64 * wave; k0 < total; k0 += 256) {
-                        const int k = k0 + lane;
-                        if (k < total) {
-                            const unsigned long long wb = sh.bits[k0 >> 6];
-                            const unsigned long long upto = ((2ull << lane) - 1ull) & ~1ull;   // bits 1..lane
-                            const uint32_t sgi = gs.seg[(int)sh.wown[k0 >> 6] + __popcll(wb & upto)];
-                            const int o = (int)(sgi >> 24);
-                            const int px = GX0 + (int)((sgi >> 14) & 63u) + (k - (int)(sgi & 0x3fffu)), py = GY0 + (int)((sgi >> 20) & 15u);
-                            // the pixel's tile: only the group's busy tiles are drawn (the box pass's test)
-                            const int tx = (px - GX0) / RTW, ty = (py - GY0) / RTH, t = ty * GX + tx;
-                            if ((bmask >> t) & 1u) {
-                                const TriRec r = rec_from_hot(fp, &sh.rec[o * 4], &sh.ext[o]);
-                                unsigned long long *key = t ? &gs.key[(t - 1) * (RTW * RTH)] : sh.key;
-                                float z;
-                                if (pixel_test(fp, r, px, py, z))
-                                    atomicMin(&key[(py - GY0 - ty * RTH) * RTW + (px - GX0 - tx * RTW)],
-                                              cand_key(z, sh.id[o], slot_keys, single ? (uint32_t)o : SLOT_NONE));
-                            }
-                        }
-                    }
+                    walk_pairs(fp, sh, total, slot_keys, single,
+                               [&](int seg, int k, int &px, int &py) { return seg_pixel(gs.seg[seg], k, GX0, GY0, px, py); }, key_slot);
                 }
             }
             // one pair pass over the group: the staged candidates' bin boxes clipped to the group rectangle
@@ -1981,67 +2020,19 @@ __device__ __forceinline__ void raster_group(const FrameParams &fp, const FrameB
             // candidates whose pairs fit -- one always does -- and the rest follow in further passes.
             if (boxes) for (int c0 = 0;;) {
                 if (wave == 0) {
-                    // raster_tile's pair prefix over the candidates from c0 with pixels in the group
-                    int area = 0, bx0 = 0, by0 = 0, bw = 1;
-                    if (lane >= c0 && lane < m) {
-                        const uint4 bb = reinterpret_cast<const uint4 *>(&sh.rec[lane * 4])[3];   // z2 word gbx gby
-                        const int x0 = max(lo16(bb.z), GX0), x1 = min(hi16(bb.z), GX1);
-                        const int y0 = max(lo16(bb.w), GY0), y1 = min(hi16(bb.w), GY1);
-                        if (x0 <= x1 && y0 <= y1) { area = (x1 - x0 + 1) * (y1 - y0 + 1); bx0 = x0; by0 = y0; bw = x1 - x0 + 1; }
-                    }
-                    int incl = area;
-#pragma unroll
-                    for (int o = 1; o < 64; o <<= 1) {
-                        const int v = __shfl_up(incl, o);
-                        if (lane >= o) incl += v;
-                    }
-                    // the prefix grows with the lane: the candidates that fit are the leading lanes
-                    const bool fit = incl <= PAIR_CAP;
-                    const int nfit = __popcll(__ballot(fit));   // (>= c0 + 1: one box is <= 1024 pairs)
-                    const int total = __shfl(incl, nfit - 1);
-                    for (int i = lane; i * 64 < total; i += 64) sh.bits[i] = 0ull;
-                    wave_lds_sync();
-                    const bool on = area > 0 && fit;
-                    const uint32_t rank = lanes_below(__ballot(on));
-                    if (on) {
-                        const int start = incl - area;
-                        sh.pinfo[rank] = make_uint4((uint32_t)start, (uint32_t)bx0 | ((uint32_t)by0 << 16), (uint32_t)bw | ((uint32_t)lane << 8),
-                                                    (65536u + (uint32_t)bw - 1u) / (uint32_t)bw);
-                        atomicOr(&sh.bits[start >> 6], 1ull << (start & 63));
-                        for (int wd = (start + 63) >> 6; wd * 64 < incl; ++wd) sh.wown[wd] = (uint16_t)rank;
-                    }
+                    int next;
+                    const int total = layout_boxes<true>(sh, c0, m, GX0, GY0, GX1, GY1, next);
                     if (lane == 0) {
                         gs.npairs = (uint32_t)total;
-                        gs.next = (uint32_t)nfit;
+                        gs.next = (uint32_t)next;
                         if (tl) gs.pairs += (uint32_t)total;
                     }
                 }
                 __syncthreads();
                 const int total = SHS_DBG(fp, DBG_SKIP_PAIRS) ? 0 : __builtin_amdgcn_readfirstlane((int)gs.npairs);
                 c0 = __builtin_amdgcn_readfirstlane((int)gs.next);
-                for (int k0 = 64 * wave; k0 < total; k0 += 256) {
-                    const int k = k0 + lane;
-                    if (k < total) {
-                        const unsigned long long wb = sh.bits[k0 >> 6];
-                        const unsigned long long upto = ((2ull << lane) - 1ull) & ~1ull;   // bits 1..lane
-                        const uint4 pi = sh.pinfo[(int)sh.wown[k0 >> 6] + __popcll(wb & upto)];
-                        const int o = (int)(pi.z >> 8), bw = (int)(pi.z & 0xffu);
-                        const int local = k - (int)pi.x;   // (< 16 * bw: the reciprocal is exact for bw <= 64)
-                        const int ly = (int)(((uint32_t)local * pi.w) >> 16), lx = local - ly * bw;
-                        const int px = (int)(pi.y & 0xffffu) + lx, py = (int)(pi.y >> 16) + ly;
-                        // the pixel's tile: only the group's busy tiles are drawn (a sharded frame's
-                        // group holds tiles of other shards, which setup never marks)
-                        const int tx = (px - GX0) / RTW, ty = (py - GY0) / RTH, t = ty * GX + tx;
-                        if ((bmask >> t) & 1u) {
-                            const TriRec r = rec_from_hot(fp, &sh.rec[o * 4], &sh.ext[o]);
-                            unsigned long long *key = t ? &gs.key[(t - 1) * (RTW * RTH)] : sh.key;
-                            float z;
-                            if (pixel_test(fp, r, px, py, z))
-                                atomicMin(&key[(py - GY0 - ty * RTH) * RTW + (px - GX0 - tx * RTW)],
-                                          cand_key(z, sh.id[o], slot_keys, single ? (uint32_t)o : SLOT_NONE));
-                        }
-                    }
-                }
+                walk_pairs(fp, sh, total, slot_keys, single,
+                           [&](int e, int k, int &px, int &py) { return pinfo_pixel(sh.pinfo[e], k, px, py); }, key_slot);
                 if (c0 >= m) break;
                 __syncthreads();   // the pass's pairs are walked before wave 0 lays out the next one's
             }
@@ -2049,6 +2040,7 @@ __device__ __forceinline__ void raster_group(const FrameParams &fp, const FrameB
     }
     tl_mark(tl, tls, 3);
     // tile-clamp pixels of unbounded slivers outside their bbox that passed, into their tile's keys
+    // (raster_tile's loop, left duplicated: see there)
     for (uint32_t f = tid; f < n_frag; f += 256) {
         const GhostFrag g = fb.frags[f];
         const int gx = (int)(g.xy & 0xffffu), gy = (int)(g.xy >> 16);
@@ -2074,50 +2066,13 @@ __device__ __forceinline__ void raster_group(const FrameParams &fp, const FrameB
         float4 pq = make_float4(0.f, 0.f, 0.f, 0.f);
         const bool covered = key != KEY_EMPTY && px < fp.W && py < fp.H;
         if (covered) {
-            const uint32_t lo = (uint32_t)key;
-            const uint32_t id = slot_keys ? lo >> 7 : lo, slot = slot_keys ? lo & SLOT_NONE : SLOT_NONE;
-            TriRec r;
-            ShadeRec sr;
-            {
-                float4 h4[4];   // the winner's stored record (its float bbox is not read here)
-                float4 *e4 = reinterpret_cast<float4 *>(&sr);
-                if (slot != SLOT_NONE) {   // only single-pass groups encode a slot: the staged copies
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) h4[k] = sh.rec[slot * 4 + k];
-#pragma unroll
-                    for (int k = 0; k < 5; ++k) e4[k] = sh.srec[slot * 5 + k];
-                } else {
-                    const float4 *s4 = reinterpret_cast<const float4 *>(&fb.recs[id]);
-                    const float4 *g4 = reinterpret_cast<const float4 *>(&fb.shade[id]);
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) h4[k] = s4[k];
-#pragma unroll
-                    for (int k = 0; k < 5; ++k) e4[k] = g4[k];
-                }
-                r = rec_from_hot(fp, h4[0], h4[1], h4[2], h4[3], make_float4(0.f, 0.f, 0.f, 0.f));
-            }
-            float u, v, w;
-            bary_pass(r, (float)px + 0.5f, (float)py + 0.5f, u, v, w);   // the winner's own values
-            depth = (u * r.z0 + v * r.z1) + w * r.z2;
-            if (!SHS_DBG(fp, DBG_SKIP_SHADE)) {
-                const int wd = dbase + r.draw;   // the frame's draw (ShadeRec::draw is frame 0's when shared)
-                const float4 *du = wd < LDS_DRAWS ? &sh.du[wd * 4] : reinterpret_cast<const float4 *>(draws[wd].light);
-                float pre[3];
-                shade_winner(du, sr, u, v, w, pre);
-                const uint32_t cr = (uint32_t)(uint8_t)pre[0], cg = (uint32_t)(uint8_t)pre[1], cb = (uint32_t)(uint8_t)pre[2];
-                rgba = cr | (cg << 8) | (cb << 16) | (255u << 24);
-                pq = make_float4(pre[0], pre[1], pre[2], 1.0f);
-            }
+            uint32_t id, slot;
+            key_winner(key, slot_keys, id, slot);
+            shade_stored_winner(fp, fb, draws, dbase, sh, id, slot, px, py, depth, rgba, pq);
         }
         if (t == t_first) tl_mark(tl, tls, 4);
         ncov += (uint32_t)__popcll(__ballot(covered));
-        const bool dbg_nost = SHS_DBG(fp, DBG_SKIP_TILE_STORES) && !(rgba == 0x12345678u && depth == -1.0f);
-        if (px < fp.W && py < fp.H && !dbg_nost) {
-            LEGACY_STORE(rgba, &reinterpret_cast<uint32_t *>(fb.color)[(size_t)(fp.H - 1 - py) * fp.W + px]);
-            LEGACY_STORE(depth, &fb.depth[(size_t)py * fp.W + px]);
-            if (fb.prequant) fb.prequant[(size_t)(fp.H - 1 - py) * fp.W + px] = pq;
-            if (fb.present) LEGACY_STORE(rgba, &fb.present[(size_t)py * fp.W + px]);
-        }
+        store_pixel(fp, fb, px, py, rgba, depth, pq);
         // the tile no longer holds the clear values: a later batch that leaves it idle clears it
         if (tid == 0) fb.stale[rt0 + (t / GX) * fp.tiles_x + t % GX] = 1u;
         if (t == t_first) tl_mark(tl, tls, 5);

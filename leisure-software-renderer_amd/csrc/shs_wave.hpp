@@ -1,5 +1,5 @@
 // shs_wave.hpp -- wavefront (64-lane) helpers shared by the legacy and library raster kernels:
-// in-wave LDS hand-off, ballot-based appends and the order-preserving 64-bit depth key.
+// in-wave LDS hand-off, the wave prefix sum, ballot-based appends and the order-preserving 64-bit depth key.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -15,6 +15,17 @@ __device__ __forceinline__ void wave_lds_sync() {
 
 __device__ __forceinline__ uint32_t lanes_below(uint64_t m) {
     return (uint32_t)__popcll(m & ((1ull << __lane_id()) - 1ull));
+}
+
+// Inclusive prefix sum over the wave's 64 lanes (converged wave): lane l gets v[0] + ... + v[l].
+__device__ __forceinline__ uint32_t wave_incl_sum(uint32_t v) {
+    const int lane = __lane_id();
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t up = (uint32_t)__shfl_up((int)v, o);
+        if (lane >= o) v += up;
+    }
+    return v;
 }
 
 // Wave-aggregated appends to NK per-key counters (call with the whole wave converged).  Lanes with

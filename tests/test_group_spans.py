@@ -302,7 +302,7 @@ def test_group_row_spans_hold_every_passing_pixel():
 
 
 def _seg_pack(first, x0, row, cand):
-    """group_seg_pack (shs_legacy.hip): first pair | x0 << 14 | row << 20 | candidate << 24."""
+    """seg_pack (shs_legacy.hip): first pair | x0 << 14 | row << 20 | candidate << 24."""
     return first | (x0 << 14) | (row << 20) | (cand << 24)
 
 
