@@ -542,23 +542,50 @@ __device__ __forceinline__ TriRec quad_record(const FrameParams &fp, const DrawG
 // more covers the conversion to pixel indices.  Non-finite records keep the whole box row.  The bound
 // holds outside the triangle's bbox too (the 80x80 tile clamp's ghost pixels, section 5 of DESIGN.md).
 // tests/test_legacy_row_spans.py restates this in numpy and checks it against the per-pixel test.
-__device__ __forceinline__ void legacy_row_span(const float4 r0, const float4 r1, const float4 r2, int py, int bx0, int bx1,
-                                                int &x0, int &x1) {
-    x0 = bx0; x1 = bx1;
-    // r0, r1, r2: the record's first three float4s: ax ay v0x v0y | v1x v1y d00 d01 | d11 denom ...
+//
+// The evaluation is in two halves.  span_terms: what depends on the record and the box alone -- the
+// finiteness of the record, 1 / denom, av, aw, the coefficients of Y in cv and cw, and the |v x| T
+// products of the magnitudes.  span_row: one row from those terms and the record.  legacy_row_span is
+// their composition; the group span pass (raster_group) computes the terms once per staged candidate and
+// the rows from them, every operation with the same operands in the same association: the same bits.
+struct SpanTerms {
+    bool ok;                // false: the record is not finite (or denom is 0) and rows keep the whole box
+    float idn;              // 1 / denom
+    float av, aw, kv, kw;   // cv = kv Y, cw = kw Y
+    float p0, p1;           // |v0x| T, |v1x| T with T = the box's largest |t|
+};
+// r0, r1, r2: the record's first three float4s: ax ay v0x v0y | v1x v1y d00 d01 | d11 denom ...
+__device__ __forceinline__ SpanTerms span_terms(const float4 r0, const float4 r1, const float4 r2, int bx0, int bx1) {
     const float ax = r0.x, ay = r0.y, v0x = r0.z, v0y = r0.w, v1x = r1.x, v1y = r1.y, d00 = r1.z, d01 = r1.w;
     const float d11 = r2.x, den = r2.y;
+    SpanTerms s;
+    s.ok = false;
+    s.idn = s.av = s.aw = s.kv = s.kw = s.p0 = s.p1 = 0.0f;
     if (!(isfinite(ax) && isfinite(ay) && isfinite(v0x) && isfinite(v0y) && isfinite(v1x) && isfinite(v1y) && isfinite(d00) &&
           isfinite(d01) && isfinite(d11) && isfinite(den) && fabsf(den) > 0.0f))
-        return;
+        return s;
+    const float T = fmaxf(fabsf(((float)bx0 + 0.5f) - ax), fabsf(((float)bx1 + 0.5f) - ax));
+    const float idn = 1.0f / den;
+    s.ok = true;
+    s.idn = idn;
+    s.p0 = fabsf(v0x) * T; s.p1 = fabsf(v1x) * T;
+    s.av = (d11 * v0x - d01 * v1x) * idn; s.kv = (d11 * v0y - d01 * v1y) * idn;
+    s.aw = (d00 * v1x - d01 * v0x) * idn; s.kw = (d00 * v1y - d01 * v0y) * idn;
+    return s;
+}
+// Row py of the box [bx0, bx1] from the candidate's terms; of the record it reads ax ay . v0y | . v1y d00 d01 | d11.
+__device__ __forceinline__ void span_row(const SpanTerms &s, const float4 r0, const float4 r1, const float4 r2, int py, int bx0,
+                                         int bx1, int &x0, int &x1) {
+    x0 = bx0; x1 = bx1;
+    if (!s.ok) return;
+    const float ax = r0.x, ay = r0.y, v0y = r0.w, v1y = r1.y, d00 = r1.z, d01 = r1.w, d11 = r2.x;
     constexpr float E = 0x1p-18f;
     const float Y = ((float)py + 0.5f) - ay, aY = fabsf(Y);
-    const float T = fmaxf(fabsf(((float)bx0 + 0.5f) - ax), fabsf(((float)bx1 + 0.5f) - ax));
-    const float idn = 1.0f / den, aid = fabsf(idn);
-    const float s0 = fabsf(v0x) * T + fabsf(v0y) * aY, s1 = fabsf(v1x) * T + fabsf(v1y) * aY;
+    const float aid = fabsf(s.idn);
+    const float s0 = s.p0 + fabsf(v0y) * aY, s1 = s.p1 + fabsf(v1y) * aY;
     const float mv = aid * (fabsf(d11) * s0 + fabsf(d01) * s1), mw = aid * (fabsf(d00) * s1 + fabsf(d01) * s0);
-    const float av = (d11 * v0x - d01 * v1x) * idn, cv = ((d11 * v0y - d01 * v1y) * idn) * Y;
-    const float aw = (d00 * v1x - d01 * v0x) * idn, cw = ((d00 * v1y - d01 * v0y) * idn) * Y;
+    const float av = s.av, cv = s.kv * Y;
+    const float aw = s.aw, cw = s.kw * Y;
     float lo = -1e30f, hi = 1e30f;
     auto edge = [&](float a, float c, float e) {   // a t + c >= -e
         const float b = -e - c;
@@ -573,6 +600,10 @@ __device__ __forceinline__ void legacy_row_span(const float4 r0, const float4 r1
     const float slo = 0x1p-12f * ((fabsf(lo) + fabsf(ax)) + 1.0f), shi = 0x1p-12f * ((fabsf(hi) + fabsf(ax)) + 1.0f);
     x0 = max(bx0, (int)ceilf(fmaxf(fminf(flo - slo, 1e9f), -1e9f)));
     x1 = min(bx1, (int)floorf(fmaxf(fminf(fhi + shi, 1e9f), -1e9f)));
+}
+__device__ __forceinline__ void legacy_row_span(const float4 r0, const float4 r1, const float4 r2, int py, int bx0, int bx1,
+                                                int &x0, int &x1) {
+    span_row(span_terms(r0, r1, r2, bx0, bx1), r0, r1, r2, py, bx0, bx1, x0, x1);
 }
 
 // Every pixel sliver `tri` (record t) visits outside its ibox in the reference's tile jobs that can
@@ -1253,9 +1284,27 @@ struct NoGroupShared {};
 // Row-span pair tasks of a group (RF_GROUP_SPANS): one segment per nonempty (staged candidate, group row)
 // span, +4 KB on the span kernel alone (still four workgroups per CU).
 constexpr int GROUP_SEGS = RCHUNK * GY * RTH;
+// The span pass's tasks, one per (staged candidate, group row of its clipped box), are dealt over the
+// threads like the pairs: the candidates with rows (entries, by rank) lie end to end in a start bitmap
+// over the tasks with the entry owning each word's first task (+3.2 KB, 39,952 B in all; 40,960 is the limit
+// of four workgroups per CU).
+constexpr int SPAN_TASK_WORDS = GROUP_SEGS / 64;
 struct GroupSpanShared : GroupShared {
     uint32_t seg[GROUP_SEGS];         // seg_pack's words, in pair order
+    float4 term[RCHUNK];              // per entry: SpanTerms' kw p0 p1 | span_entry's word (idn av aw kv: RasterShared::pinfo,
+                                      // free while spans are walked)
+    uint16_t task[GROUP_SEGS];        // per task with a span: group row | staged candidate << 4 (the spans: RasterShared::seg)
+    unsigned long long tbits[SPAN_TASK_WORDS];   // bit t: an entry's tasks start at task t
+    uint16_t town[SPAN_TASK_WORDS];   // entry owning each word's first task
+    uint32_t ntasks;
 };
+// An entry's word: its first task (< GROUP_SEGS: 10 bits), its box's first row (4 bits) and x range (6 + 6
+// bits) relative to the group, and its staged candidate (6 bits).  tests/test_group_span_tasks.py restates
+// the dealing.
+static_assert(GROUP_SEGS <= (1 << 10) && GX * RTW <= 64 && GY * RTH <= 16 && RCHUNK <= 64, "the entry word's fields");
+__device__ __forceinline__ uint32_t span_entry(uint32_t first, uint32_t row0, uint32_t x0, uint32_t x1, uint32_t cand) {
+    return first | (row0 << 10) | (x0 << 14) | (x1 << 20) | (cand << 26);
+}
 // A segment (a tile's or a group's): its first pair of the pass (< PAIR_CAP: 14 bits), its first pixel's x
 // relative to the tile / group (6 bits), its row there (4 bits) and its staged candidate (6 bits).
 // tests/test_group_spans.py restates the layout.
@@ -1408,9 +1457,13 @@ __device__ __forceinline__ void stage_stored(const FrameBuffers &fb, RasterShare
 
 // A run of len pairs from pair `start` of the pass belongs to `owner` (a segment or a pinfo entry): its
 // start bit in the bitmap over the pairs, and the owner of every bitmap word whose first pair is in the run.
+// (bits, wown: the pass's bitmap and word owners -- RasterShared's for the pairs)
+__device__ __forceinline__ void mark_run(unsigned long long *bits, uint16_t *wown, uint32_t start, uint32_t len, uint32_t owner) {
+    atomicOr(&bits[start >> 6], 1ull << (start & 63u));
+    for (uint32_t wd = (start + 63u) >> 6; wd * 64u < start + len; ++wd) wown[wd] = (uint16_t)owner;
+}
 __device__ __forceinline__ void mark_run(RasterShared &sh, uint32_t start, uint32_t len, uint32_t owner) {
-    atomicOr(&sh.bits[start >> 6], 1ull << (start & 63u));
-    for (uint32_t wd = (start + 63u) >> 6; wd * 64u < start + len; ++wd) sh.wown[wd] = (uint16_t)owner;
+    mark_run(sh.bits, sh.wown, start, len, owner);
 }
 
 // Span tasks.  A thread's spans are x0 | x1 << 8 relative to the tile / group, NO_SPAN when empty; pk
@@ -1437,7 +1490,16 @@ __device__ __forceinline__ uint32_t block_span_prefix(RasterShared &sh, uint32_t
 }
 
 // Segment write-out: the thread's N spans (span(j)) laid end to end from its exclusive prefix ex, each as
-// word(j, first pair, x0) in seg[] with its run marked.
+// word(j, first pair, x0) in seg[] with its run marked.  (write_segment: one span, sp != NO_SPAN, as
+// segment sg from pair ps; both move on.)
+template <class Word>
+__device__ __forceinline__ void write_segment(RasterShared &sh, uint32_t *seg, uint32_t &ps, uint32_t &sg, uint32_t sp, Word word) {
+    const uint32_t s0 = sp & 0xffu, wdt = (sp >> 8) - s0 + 1u;
+    seg[sg] = word(ps, s0);
+    mark_run(sh, ps, wdt, sg);
+    ps += wdt;
+    ++sg;
+}
 template <int N, class Span, class Word>
 __device__ __forceinline__ void write_segments(RasterShared &sh, uint32_t *seg, uint32_t ex, Span span, Word word) {
     uint32_t ps = ex >> 11, sg = ex & 2047u;
@@ -1445,11 +1507,7 @@ __device__ __forceinline__ void write_segments(RasterShared &sh, uint32_t *seg, 
     for (int j = 0; j < N; ++j) {
         const uint32_t sp = span(j);
         if (sp == NO_SPAN) continue;
-        const uint32_t s0 = sp & 0xffu, wdt = (sp >> 8) - s0 + 1u;
-        seg[sg] = word(j, ps, s0);
-        mark_run(sh, ps, wdt, sg);
-        ps += wdt;
-        ++sg;
+        write_segment(sh, seg, ps, sg, sp, [&](uint32_t p, uint32_t s0) { return word(j, p, s0); });
     }
 }
 
@@ -1507,11 +1565,12 @@ __device__ __forceinline__ int pinfo_pixel(const uint4 pi, int k, int &px, int &
 
 // The owner (segment or pinfo entry) of lane `lane`'s pair in the 64-pair window from pair k0: the
 // window's bitmap word's first owner + the starts in the word up to the pair.
-__device__ __forceinline__ int pair_owner(const RasterShared &sh, int k0, int lane) {
-    const unsigned long long wb = sh.bits[k0 >> 6];
+__device__ __forceinline__ int pair_owner(const unsigned long long *bits, const uint16_t *wown, int k0, int lane) {
+    const unsigned long long wb = bits[k0 >> 6];
     const unsigned long long upto = ((2ull << lane) - 1ull) & ~1ull;   // bits 1..lane
-    return (int)sh.wown[k0 >> 6] + __popcll(wb & upto);
+    return (int)wown[k0 >> 6] + __popcll(wb & upto);
 }
+__device__ __forceinline__ int pair_owner(const RasterShared &sh, int k0, int lane) { return pair_owner(sh.bits, sh.wown, k0, lane); }
 
 // Staged candidate o at pixel (px, py): whether the pixel passes, and then its key.
 __device__ __forceinline__ bool staged_key(const FrameParams &fp, const RasterShared &sh, int o, int px, int py, bool slot_keys,
@@ -1967,45 +2026,87 @@ __device__ __forceinline__ void raster_group(const FrameParams &fp, const FrameB
             tl_mark(tl, tls, 2);
             bool boxes = true;
             if constexpr (SPANS) {
-                // Span tasks: thread (row = tid % 16, cj = tid / 16) takes group row `row` of the staged
-                // candidates cj, cj + 16, ...; one block prefix of (pairs << 11 | segments) lays the
-                // threads' spans end to end, each thread's in candidate order.
+                // Span tasks: one per (staged candidate, group row of its bin box clipped to the group), dealt
+                // over the threads in rounds of 256 -- task 256 r + tid; one round for most groups.  The lanes
+                // below m of waves 0 and 1 take a candidate each: its clipped box, and from it its rows (none
+                // when the x range is empty; rows past GY1 are cut).  The candidates with rows are the
+                // entries, in rank order.  Wave 0 lays their rows end to end (one wave prefix: <= 64 x 16
+                // tasks), each entry's start in the task bitmap plus the entry owning every word's first task
+                // (mark_run); wave 1 computes each entry's span_terms, once for all its rows.  After the
+                // barrier a task finds its entry as a pair finds its segment (pair_owner: a wave's 64 tasks are
+                // one bitmap word) and its row from the entry's first task, and span_row gives its span.  One
+                // block prefix of (pairs << 11 | segments) then lays the threads' spans end to end.
                 static_assert(PAIR_WORDS == 256 && GY * RTH == 16 && RCHUNK == 64, "the span pass's thread mapping");
                 sh.bits[tid] = 0ull;
+                if (wave < 2) {
+                    if (wave == 0 && lane < SPAN_TASK_WORDS) gs.tbits[lane] = 0ull;
+                    wave_lds_sync();
+                    const float4 *rc = &sh.rec[min(lane, m - 1) * 4];
+                    const uint4 bb = reinterpret_cast<const uint4 *>(rc)[3];   // z2 word gbx gby
+                    const int x0 = max(lo16(bb.z), GX0), x1 = min(hi16(bb.z), GX1);
+                    const int y0 = max(lo16(bb.w), GY0), y1 = min(hi16(bb.w), GY1);
+                    const uint32_t rows = lane < m && x0 <= x1 && y0 <= y1 ? (uint32_t)(y1 - y0 + 1) : 0u;
+                    const uint32_t e = lanes_below(__ballot(rows > 0u));
+                    if (wave == 0) {
+                        const uint32_t incl = wave_incl_sum(rows);
+                        if (rows) {
+                            gs.term[e].w = __uint_as_float(span_entry(incl - rows, (uint32_t)(y0 - GY0), (uint32_t)(x0 - GX0),
+                                                                      (uint32_t)(x1 - GX0), (uint32_t)lane));
+                            mark_run(gs.tbits, gs.town, incl - rows, rows, e);
+                        }
+                        if (lane == 63) gs.ntasks = incl;
+                    } else if (rows) {
+                        const SpanTerms st = span_terms(rc[0], rc[1], rc[2], x0, x1);
+                        // (ok travels as idn: the reciprocal of a finite nonzero denom is never NaN)
+                        reinterpret_cast<float4 *>(sh.pinfo)[e] = make_float4(st.ok ? st.idn : __builtin_nanf(""), st.av, st.aw, st.kv);
+                        float *tm = reinterpret_cast<float *>(&gs.term[e]);
+                        tm[0] = st.kw; tm[1] = st.p0; tm[2] = st.p1;
+                    }
+                }
+                __syncthreads();
+                const int ntasks = __builtin_amdgcn_readfirstlane((int)gs.ntasks);
                 // (the thread's task indices are computed here, per pass, and its spans wait in LDS for the
                 // prefix -- RasterShared::seg, the tile span path's, is free in this kernel: as registers
                 // held across the prefix, or across the item loop, they spill)
                 int stid = tid;
                 asm volatile("" : "+v"(stid));
-                const int row = stid & 15, cj = stid >> 4, py = GY0 + row;
-                uint16_t *spw = reinterpret_cast<uint16_t *>(sh.seg) + stid;   // [j * 256]: group-relative x0 | x1 << 8
-                static_assert(sizeof(sh.seg) >= (RCHUNK / 16) * 256 * sizeof(uint16_t), "the threads' spans");
+                uint16_t *spw = reinterpret_cast<uint16_t *>(sh.seg) + stid;   // [r * 256]: group-relative x0 | x1 << 8
+                static_assert(sizeof(sh.seg) >= GROUP_SEGS * sizeof(uint16_t), "the threads' spans");
                 uint32_t pk = 0u;
-#pragma unroll
-                for (int j = 0; j < RCHUNK / 16; ++j) {
+                for (int r = 0; 256 * r < ntasks; ++r) {
+                    const int t = 256 * r + stid;
                     uint32_t sp = NO_SPAN;
-                    const int cc = cj + 16 * j;
-                    if (16 * j < m && cc < m) {   // (the first test is wave-uniform)
+                    if (t < ntasks) {
+                        const int e = pair_owner(gs.tbits, gs.town, 256 * r + 64 * wave, lane);
+                        const float4 tb = gs.term[e], ta = reinterpret_cast<const float4 *>(sh.pinfo)[e];
+                        const uint32_t en = __float_as_uint(tb.w);
+                        const int row = t - (int)(en & 1023u) + (int)((en >> 10) & 15u), cc = (int)(en >> 26);
+                        const int x0 = GX0 + (int)((en >> 14) & 63u), x1 = GX0 + (int)((en >> 20) & 63u);
                         const float4 *rc = &sh.rec[cc * 4];
-                        const uint4 bb = reinterpret_cast<const uint4 *>(rc)[3];   // z2 word gbx gby
-                        const int x0 = max(lo16(bb.z), GX0), x1 = min(hi16(bb.z), GX1);
-                        if (x0 <= x1 && py >= lo16(bb.w) && py <= hi16(bb.w) && py <= GY1) {
-                            int s0, s1;
-                            legacy_row_span(rc[0], rc[1], rc[2], py, x0, x1, s0, s1);
-                            if (s0 <= s1) {
-                                sp = (uint32_t)(s0 - GX0) | ((uint32_t)(s1 - GX0) << 8);
-                                pk += ((uint32_t)(s1 - s0 + 1) << 11) + 1u;
-                            }
+                        const SpanTerms st = {!isnan(ta.x), ta.x, ta.y, ta.z, ta.w, tb.x, tb.y, tb.z};
+                        int s0, s1;
+                        span_row(st, rc[0], rc[1], rc[2], GY0 + row, x0, x1, s0, s1);
+                        if (s0 <= s1) {
+                            sp = (uint32_t)(s0 - GX0) | ((uint32_t)(s1 - GX0) << 8);
+                            pk += ((uint32_t)(s1 - s0 + 1) << 11) + 1u;
+                            gs.task[t] = (uint16_t)((uint32_t)row | ((uint32_t)cc << 4));
                         }
                     }
-                    spw[j * 256] = (uint16_t)sp;
+                    spw[r * 256] = (uint16_t)sp;
                 }
                 uint32_t ptot;
                 const uint32_t ex = block_span_prefix(sh, pk, lane, wave, ptot);
                 boxes = (ptot >> 11) > (uint32_t)PAIR_CAP;   // (block-uniform)
-                if (!boxes && pk)
-                    write_segments<RCHUNK / 16>(sh, gs.seg, ex, [&](int j) { return (uint32_t)spw[j * 256]; },
-                                                [&](int j, uint32_t ps, uint32_t s0) { return seg_pack(ps, s0, (uint32_t)row, (uint32_t)(cj + 16 * j)); });
+                if (!boxes && pk) {
+                    uint32_t ps = ex >> 11, sg = ex & 2047u;
+                    for (int r = 0; 256 * r < ntasks; ++r) {
+                        const uint32_t sp = spw[r * 256];
+                        if (sp == NO_SPAN) continue;
+                        const uint32_t tk = gs.task[256 * r + stid];
+                        write_segment(sh, gs.seg, ps, sg, sp,
+                                      [&](uint32_t p, uint32_t s0) { return seg_pack(p, s0, tk & 15u, tk >> 4); });
+                    }
+                }
                 __syncthreads();
                 tl_mark(tl, tls, TL_SPANS - 2);
                 if (!boxes) {

@@ -14,9 +14,9 @@ row = {}
 for line in sys.stdin:
     m = re.search(r'Function Name: (\S+)', line)
     if m: cur = m.group(1); continue
-    m = re.search(r'remark:\s+(VGPRs|TotalSGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]|VGPRs Spill): (\d+)', line)
+    m = re.search(r'remark:\s+(VGPRs|TotalSGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]|SGPRs Spill|VGPRs Spill): (\d+)', line)
     if m and cur and flt in cur:
-        row.setdefault(cur, []).append(f'{m.group(1).split()[0]}={m.group(2)}')
+        row.setdefault(cur, []).append(f\"{m.group(1).split(' [')[0].replace(' ', '_')}={m.group(2)}\")
 for k, v in row.items():
     print(f'{k[:70]:70s} ' + ' '.join(v))
 " "$FLT"
