@@ -1455,13 +1455,7 @@ __device__ __forceinline__ void stage_stored(const FrameBuffers &fb, RasterShare
     }
 }
 
-// A run of len pairs from pair `start` of the pass belongs to `owner` (a segment or a pinfo entry): its
-// start bit in the bitmap over the pairs, and the owner of every bitmap word whose first pair is in the run.
-// (bits, wown: the pass's bitmap and word owners -- RasterShared's for the pairs)
-__device__ __forceinline__ void mark_run(unsigned long long *bits, uint16_t *wown, uint32_t start, uint32_t len, uint32_t owner) {
-    atomicOr(&bits[start >> 6], 1ull << (start & 63u));
-    for (uint32_t wd = (start + 63u) >> 6; wd * 64u < start + len; ++wd) wown[wd] = (uint16_t)owner;
-}
+// mark_run / pair_owner (shs_wave.hpp) on RasterShared's bitmap and word owners for the pairs.
 __device__ __forceinline__ void mark_run(RasterShared &sh, uint32_t start, uint32_t len, uint32_t owner) {
     mark_run(sh.bits, sh.wown, start, len, owner);
 }
@@ -1473,7 +1467,8 @@ static_assert(RCHUNK * GX * RTW * GY * RTH < (1 << 21) && GROUP_SEGS < 2048, "th
 
 // Block prefix of the threads' pk words through sh.wtot (one barrier): the thread's exclusive prefix; the
 // block's total in ptot.  (lane, wave: the caller's -- recomputed here they cost the experiments build's
-// NO_RECS kernel eight more spilled registers.)
+// NO_RECS kernel eight more spilled registers.  shs_wave.hpp's block_excl_sum written out: through it, with
+// the caller's lane in the scan or not, the raster kernels' register allocation moves.)
 __device__ __forceinline__ uint32_t block_span_prefix(RasterShared &sh, uint32_t pk, int lane, int wave, uint32_t &ptot) {
     const uint32_t incl = wave_incl_sum(pk);
     if (lane == 63) sh.wtot[wave] = incl;
@@ -1563,13 +1558,6 @@ __device__ __forceinline__ int pinfo_pixel(const uint4 pi, int k, int &px, int &
     return (int)(pi.z >> 8);
 }
 
-// The owner (segment or pinfo entry) of lane `lane`'s pair in the 64-pair window from pair k0: the
-// window's bitmap word's first owner + the starts in the word up to the pair.
-__device__ __forceinline__ int pair_owner(const unsigned long long *bits, const uint16_t *wown, int k0, int lane) {
-    const unsigned long long wb = bits[k0 >> 6];
-    const unsigned long long upto = ((2ull << lane) - 1ull) & ~1ull;   // bits 1..lane
-    return (int)wown[k0 >> 6] + __popcll(wb & upto);
-}
 __device__ __forceinline__ int pair_owner(const RasterShared &sh, int k0, int lane) { return pair_owner(sh.bits, sh.wown, k0, lane); }
 
 // Staged candidate o at pixel (px, py): whether the pixel passes, and then its key.

@@ -20,10 +20,12 @@
 //   k_lib_bigmark the queued large primitives' (primitive, tile) marks / appends over the whole chip.
 //   k_lib_dyn     (camera pass) the raster's dynamic work items compacted per ticket queue, heavy
 //                 tiles first.
-//   k_lib_raster  persistent over the owned raster tiles: busy tiles stage their candidates'
-//                 records in LDS and deal every (primitive, pixel) pair to one lane; each passing
-//                 pair atomic-mins a 64-bit key (z01 bits, submission order) into LDS -- identical
-//                 to the reference's in-order strict-less test on a cleared buffer.  The shadow pass
+//   k_lib_raster  persistent over the owned raster tiles.  A busy tile (lib_raster_tile) takes rounds of
+//                 candidates (lib_gather, lib_write_list), stages their records in LDS (lib_deep_passes, or
+//                 lib_select / lib_stage_records / lib_box_pairs) and deals every (primitive, pixel) pair to
+//                 one lane; each passing pair (lib_pair) atomic-mins a 64-bit key (z01 bits, submission
+//                 order) into LDS -- identical to the reference's in-order strict-less test on a cleared
+//                 buffer -- and lib_finish writes the tile out.  The shadow pass
 //                 writes each texel's depth here (idle tiles get the clear depth); the camera pass
 //                 hands each 16x4 block's winners to k_lib_resolve as 4-B words, with a flag per block
 //                 that holds one.
@@ -1886,7 +1888,7 @@ struct LibShared {
     uint32_t sel[LIB_CHUNK];              // list positions staged by the current pass
     uint32_t hist[256];                   // depth buckets: counts, then first positions (the sort)
     uint32_t zlo, zhi;
-    uint32_t wtot[4][2];                  // per wave: surviving candidates, pairs
+    uint32_t wtot[4][2];                  // per wave: [0] bucket counts / surviving candidates, [1] pairs (slot stride 2)
     uint32_t wmax[4];                     // deep camera raster: per wave, the largest key z of its pixels after a pass
     uint32_t last;                        // split tile: this part finished last (it writes the merged keys)
     uint32_t colmax[2][LIB_RTW];          // per pixel column: max key z (orderable bits) over its rows, by chunk parity
@@ -2050,482 +2052,499 @@ __device__ __forceinline__ void lib_row_span(const float4 r0, const float4 r1, i
     x1 = min(bx1, (int)floorf(fmaxf(fminf(fhi + shi, 1e9f), -1e9f)));
 }
 
-// One work item: raster tile rt, or (k_lib_plan, camera pass) part `part` of `parts` of it: the list
-// positions [part n / parts, (part + 1) n / parts) over the whole tile, its keys merged with the other
-// parts' in fb.pkeys[sid] (plan_parts).  T0 = the tile origin (LDS key layout); X0..Y1 = the tile.
-template <bool SHADOW, int LIB_CAND>
-__device__ void lib_raster_tile(const LibFrameParams &fp, const LibBuffers &fb, const uint32_t *cnt, int rt, LibShared<LIB_CAND> &sh,
-                                uint32_t &chunk, uint32_t part = 0u, uint32_t parts = 1u, uint32_t sid = 0u) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const bool hiz = SHADOW || (fp.flags & LF_DEPTH);   // painter's order (no depth target): never
-    const int col = rt % fp.tiles_x, row = rt / fp.tiles_x;
-    const int TX0 = col * LIB_RTW, TY0 = row * LIB_RTH;
-    const int X0 = TX0, Y0 = TY0, X1 = TX0 + LIB_RTW - 1, Y1 = TY0 + LIB_RTH - 1;
-    // this thread's pixel (tile layout: wave w = 16x4 block w)
-    const int my_lx = 16 * (wave & 1) + (lane & 15), my_ly = 4 * (wave >> 1) + (lane >> 4);
-    const int bt = (row / (TILE / LIB_RTH)) * fp.tiles_x + col;
-    // (no barrier here: the previous tile ended with each thread resetting its own pixel's key, and
-    // every round below starts with one before any shared state is touched)
-    const bool tlon = fb.timeline != nullptr && tid == 0;
-    const uint64_t t_tile = tlon ? tl_now() : 0ull;
-    uint64_t t_gather = 0ull;
-    const uint32_t chunk0 = chunk;
-    uint32_t t_rounds = 0u, t_pairs = 0u, t_breaks = 0u;   // (timeline, thread 0: this tile's counts)
-    if (tlon) sh.tl_staged = 0u;
+// ---- lib_raster_tile's phases.  Each states the barriers it relies on and leaves: "complete" = written and a
+// barrier passed, "free" = read no more.  lane and wave are the caller's (recomputed they cost code and registers).
+struct LibThread { int tid, lane, wave; };
+struct LibBox { int x0 = 0, x1 = -1, y0 = 0, y1 = -1; };
 
-    uint32_t n_bin = 0, n_spill = 0, n_items;
-    bool gsorted = false;   // the bin list is depth-sorted whole (k_lib_hsort) over hsr's range
-    uint2 hsr = make_uint2(0u, 0u);
+// A work item's tile [TX0, TX0 + LIB_RTW) x [TY0, TY0 + LIB_RTH) (TX0, TY0: also the origin of the LDS key
+// layout) and its share of the candidate list: positions [lo, n_items) of the bin tile's n_bin entries
+// followed by n_spill spilled ones (scan mode: of every primitive).
+struct LibTile {
+    int TX0, TY0, bt;
+    const uint4 *bin;
+    uint32_t n_bin, n_spill, lo, n_items;
+    bool gsorted;   // the bin list is depth-sorted whole (k_lib_hsort) over hsr's range
+    uint2 hsr;
+    __device__ __forceinline__ LibBox clip(uint2 b) const {   // a bin box cut to the tile
+        return {max(lo16(b.x), TX0), min(hi16(b.x), TX0 + LIB_RTW - 1), max(lo16(b.y), TY0), min(hi16(b.y), TY0 + LIB_RTH - 1)};
+    }
+    __device__ __forceinline__ bool touches(uint2 b) const {
+        const int gx0 = lo16(b.x), gx1 = hi16(b.x), gy0 = lo16(b.y), gy1 = hi16(b.y);
+        return gx0 <= gx1 && gy0 <= gy1 && gx1 >= TX0 && gx0 <= TX0 + LIB_RTW - 1 && gy1 >= TY0 && gy0 <= TY0 + LIB_RTH - 1;
+    }
+};
+
+template <bool SHADOW, int LIB_CAND>
+__device__ __forceinline__ LibTile lib_tile(const LibFrameParams &fp, const LibBuffers &fb, const uint32_t *cnt, int rt, LibShared<LIB_CAND> &sh,
+                                            bool hiz, uint32_t part, uint32_t parts, int tid) {
+    LibTile t;
+    const int col = rt % fp.tiles_x, row = rt / fp.tiles_x;
+    t.TX0 = col * LIB_RTW; t.TY0 = row * LIB_RTH;
+    t.bt = (row / (TILE / LIB_RTH)) * fp.tiles_x + col;
+    t.n_bin = 0; t.n_spill = 0; t.gsorted = false; t.hsr = make_uint2(0u, 0u);
+    uint32_t n;
     if (fp.scan_mode) {
-        n_items = (uint32_t)fp.n_tris + (SHADOW ? 0u : min(cnt[LC_EXTRA], fp.extra_cap));
+        n = (uint32_t)fp.n_tris + (SHADOW ? 0u : min(cnt[LC_EXTRA], fp.extra_cap));
     } else {
-        const uint32_t n_bin_total = fb.tile_count[(size_t)fp.parity * fp.tiles_x * fp.tiles_y + bt];
-        n_bin = min(n_bin_total, fp.bin_cap);
-        if (n_bin_total > fp.bin_cap) n_spill = min(cnt[LC_SPILL], fp.spill_cap);
-        n_items = n_bin + n_spill;
+        const uint32_t n_bin_total = fb.tile_count[(size_t)fp.parity * fp.tiles_x * fp.tiles_y + t.bt];
+        t.n_bin = min(n_bin_total, fp.bin_cap);
+        if (n_bin_total > fp.bin_cap) t.n_spill = min(cnt[LC_SPILL], fp.spill_cap);
+        n = t.n_bin + t.n_spill;
         if (tid == 0) sh.maxbin = max(sh.maxbin, n_bin_total);
         // (the predicate k_lib_dyn listed the tile's bin list by; this tile is busy, so it was listed)
-        gsorted = !SHADOW && LIB_CAND == LIB_CAND_DEEP && hiz && fp.hsort && parts == 1u && n_bin_total > fp.hsort_min &&
-                  n_bin_total <= min(fp.bin_cap, (uint32_t)LIB_HSORT_MAX);
-        if (gsorted) hsr = fb.hsr[bt];
+        t.gsorted = !SHADOW && LIB_CAND == LIB_CAND_DEEP && hiz && fp.hsort && parts == 1u && n_bin_total > fp.hsort_min &&
+                    n_bin_total <= min(fp.bin_cap, (uint32_t)LIB_HSORT_MAX);
+        if (t.gsorted) t.hsr = fb.hsr[t.bt];
     }
-    const uint4 *bin = fb.bins + (size_t)bt * fp.bin_cap;
-    // a part's share of the list (positions [lo, n_items))
-    const uint32_t lo = (uint32_t)(((uint64_t)n_items * part) / parts);
-    n_items = (uint32_t)(((uint64_t)n_items * (part + 1u)) / parts);
+    t.bin = fb.bins + (size_t)t.bt * fp.bin_cap;
+    t.lo = (uint32_t)(((uint64_t)n * part) / parts);
+    t.n_items = (uint32_t)(((uint64_t)n * (part + 1u)) / parts);
+    return t;
+}
 
-    const uint32_t tl_items = n_items;
-    for (uint32_t base = lo; base < n_items; base += LIB_CAND) {
-        __syncthreads();
-        if (gsorted && base > lo && chunk != chunk0) {
-            // a sorted list: every entry from `base` on lies in hsr bucket >= the one of bin[base]; once the
-            // tile's largest key z (the waves' maxima after the last pass, stale only upwards) sorts into a
-            // lower bucket, or below the whole range, no later entry can beat any pixel -- the tile is done
-            const uint32_t om = max(max(sh.wmax[0], sh.wmax[1]), max(sh.wmax[2], sh.wmax[3]));
-            if (om < hsr.x || hs_bucket(hsr, om) < hs_bucket(hsr, bin[base].w)) break;
+// SHS_OPT_TIMELINE: one tile's clock and counts.  `on` for thread 0 of a pass with a timeline buffer; for
+// every other thread the stamps are 0 and nothing is accumulated.
+struct LibTileClock {
+    bool on;
+    uint64_t t_tile, t_gather, t_g0, t_a, t_b, t_res;
+    uint32_t rounds, pairs, breaks;   // this tile's counts
+    __device__ __forceinline__ uint64_t now() const { return on ? tl_now() : 0ull; }
+    // (sh by reference: with sh.tl as a pointer the shallow camera raster spills one more register)
+    template <class Sh>
+    __device__ __forceinline__ void begin(const LibBuffers &fb, Sh &sh, int tid) {
+        on = fb.timeline != nullptr && tid == 0;
+        t_tile = now();
+        t_gather = 0ull;
+        rounds = 0u; pairs = 0u; breaks = 0u;
+        if (on) sh.tl_staged = 0u;
+    }
+    template <class Sh>
+    __device__ __forceinline__ void gathered(Sh &sh, uint32_t nc) {   // a round's gather and list write-out, from t_g0
+        if (on) { t_gather += tl_now() - t_g0; sh.tl[LTL_NCAND] += nc; }
+    }
+    template <class Sh>
+    __device__ __forceinline__ void laid_out(Sh &sh, uint32_t total) {   // a deep pass at [C]: staged t_a..t_b, segments from t_b
+        if (!on) return;
+        const uint64_t t_c = tl_now();
+        pairs += total;
+        sh.tl[LTL_NPAIRS] += total;
+        sh.tl[LTL_STAGE] += t_b - t_a;
+        sh.tl[LTL_SEG] += t_c - t_b;
+    }
+    template <class Sh>
+    __device__ __forceinline__ void end(Sh &sh, int rt, uint32_t items, uint32_t passes) {
+        if (!on) return;
+        const uint64_t t_end = tl_now();
+        sh.tl[LTL_GATHER] += t_gather;
+        sh.tl[LTL_PAIRS] += (t_res - t_tile) - t_gather;
+        sh.tl[LTL_SHADE] += t_end - t_res;
+        sh.tl[LTL_NBUSY] += 1;
+        sh.tl[LTL_CHUNKS] += passes;
+        if (t_end - t_tile > sh.tl[LTL_MAXTILE]) {   // this workgroup's longest tile so far
+            sh.tl[LTL_MT_RT] = (uint64_t)rt; sh.tl[LTL_MT_ITEMS] = items; sh.tl[LTL_MT_ROUNDS] = rounds;
+            sh.tl[LTL_MT_PASSES] = passes; sh.tl[LTL_MT_STAGED] = sh.tl_staged; sh.tl[LTL_MT_PAIRS] = pairs;
+            sh.tl[LTL_MT_GATHER] = t_gather; sh.tl[LTL_MT_BREAKS] = breaks;
         }
-        ++t_rounds;
-        if (tid == 0) { sh.nc = 0; sh.zlo = 0xffffffffu; sh.zhi = 0u; }
-        sh.hist[tid] = 0u;
-        __syncthreads();
-        const uint64_t t_g0 = tlon ? tl_now() : 0ull;
-        // (1) gather up to LIB_CAND candidates (bin list or every primitive), their boxes and depth
-        //     bounds in one round trip; a candidate's box overlaps the tile
-        constexpr int NG = LIB_CAND / 256;
-        uint32_t ids[NG], zk[NG];
-        uint2 bx[NG];
-        bool hit[NG];
-        if (fp.scan_mode) {
-#pragma unroll
-            for (int k = 0; k < NG; ++k) {
-                const uint32_t item = base + tid + 256u * k;
-                ids[k] = item < n_items ? item : 0xffffffffu;
-            }
-#pragma unroll
-            for (int k = 0; k < NG; ++k) {
-                bx[k] = ids[k] != 0xffffffffu ? fb.boxes[ids[k]] : make_uint2(0u, 0u);
-                zk[k] = hiz && ids[k] != 0xffffffffu ? fb.zord[ids[k]] : 0u;
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < NG; ++k) {
-                const uint32_t item = base + tid + 256u * k;
-                uint4 e = make_uint4(0xffffffffu, 0u, 0u, 0u);
-                if (item < n_bin) {   // the entry carries the box and the depth bound
-                    e = bin[item];
-                } else if (item < n_items) {   // spilled entries hold the slot only (rare)
-                    const uint2 sp = fb.spill[item - n_bin];
-                    if ((int)sp.x == bt) {
-                        const uint2 b = fb.boxes[sp.y];
-                        e = make_uint4(sp.y, b.x, b.y, fb.zord[sp.y]);
-                    }
-                }
-                ids[k] = e.x;
-                bx[k] = e.x != 0xffffffffu ? make_uint2(e.y, e.z) : make_uint2(0u, 0u);
-                zk[k] = hiz && e.x != 0xffffffffu ? e.w : 0u;
-            }
-        }
-        uint32_t zlo = 0xffffffffu, zhi = 0u, nhit = 0u;
+        sh.tl[LTL_MAXTILE] = max(sh.tl[LTL_MAXTILE], t_end - t_tile);
+        sh.tl[LTL_TILES] += t_end - t_tile;
+        sh.tl[LTL_LAST] = t_end;
+    }
+};
+
+// One candidate round in registers: thread tid holds entries tid + 256 k of the round.
+template <int NG>
+struct LibRound {
+    uint32_t ids[NG], zk[NG];   // slot, depth bound (0 without a depth test)
+    uint2 bx[NG];               // bin box
+    bool hit[NG];               // a candidate: its box overlaps the tile
+    uint32_t basew;             // the wave's first position in gather order
+};
+
+// (1) Gather the round from list position `base`: the bin list or every primitive, their boxes and depth
+//     bounds in one round trip.  Entry: sh.nc, sh.zlo, sh.zhi reset and complete.  Exit (one barrier): they
+//     hold the round's candidate count and depth-bound range; returns sh.nc.
+template <int LIB_CAND>
+__device__ __forceinline__ uint32_t lib_gather(const LibFrameParams &fp, const LibBuffers &fb, const LibTile &t, LibShared<LIB_CAND> &sh,
+                                               uint32_t base, bool hiz, const LibThread &th, LibRound<LIB_CAND / 256> &g) {
+    constexpr int NG = LIB_CAND / 256;
+    const int tid = th.tid;
+    if (fp.scan_mode) {
 #pragma unroll
         for (int k = 0; k < NG; ++k) {
-            const int gx0 = lo16(bx[k].x), gx1 = hi16(bx[k].x), gy0 = lo16(bx[k].y), gy1 = hi16(bx[k].y);
-            hit[k] = ids[k] != 0xffffffffu && gx0 <= gx1 && gy0 <= gy1 && gx1 >= X0 && gx0 <= X1 && gy1 >= Y0 && gy0 <= Y1;
-            if (hit[k]) { zlo = min(zlo, zk[k]); zhi = max(zhi, zk[k]); }
-            nhit += (uint32_t)__popcll(__ballot(hit[k]));
+            const uint32_t item = base + tid + 256u * k;
+            g.ids[k] = item < t.n_items ? item : 0xffffffffu;
         }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            zlo = min(zlo, (uint32_t)__shfl_xor((int)zlo, off));
-            zhi = max(zhi, (uint32_t)__shfl_xor((int)zhi, off));
-        }
-        uint32_t basew = 0;   // this wave's first position in gather order
-        if (lane == 0 && nhit) { basew = atomicAdd(&sh.nc, nhit); atomicMin(&sh.zlo, zlo); atomicMax(&sh.zhi, zhi); }
-        basew = (uint32_t)__shfl((int)basew, 0);
-        __syncthreads();
-        const uint32_t nc = sh.nc;
-        // one staging pass holds every candidate (or painter's order): gather order, no sort
-        const bool sorted = hiz && nc > (uint32_t)LIB_CHUNK;
-        if (!sorted) {
-            uint32_t run = 0;
-#pragma unroll
-            for (int k = 0; k < NG; ++k) {
-                const uint64_t hm = __ballot(hit[k]);
-                if (hit[k]) {
-                    const uint32_t pos = basew + run + lanes_below(hm);
-                    sh.lid[pos] = ids[k];
-                    sh.lkey[pos] = zk[k];
-                    sh.lbox[pos] = bx[k];
-                }
-                run += (uint32_t)__popcll(hm);
-            }
-        }
-        // (2) the list, front to back: a 256-bucket counting sort by depth bound.  bucket(z) is
-        //     monotone in z, so the entries from position p on lie in buckets >= bucket(lkey[p]).
-        //     Order inside a tile is otherwise free -- the resolve is by (z, submission index) keys.
-        const uint32_t s_lo = sh.zlo, s_span = sh.zhi - sh.zlo;
-        const float s_scale = (hiz && s_span) ? 255.0f / (float)s_span : 0.0f;
-        auto bucket = [&](uint32_t z) { return min(255u, (uint32_t)((float)(z - s_lo) * s_scale)); };
-        uint32_t bk[NG], rk[NG];
 #pragma unroll
         for (int k = 0; k < NG; ++k) {
-            bk[k] = 0u; rk[k] = 0u;
-            if (sorted && hit[k]) { bk[k] = bucket(zk[k]); rk[k] = atomicAdd(&sh.hist[bk[k]], 1u); }
+            g.bx[k] = g.ids[k] != 0xffffffffu ? fb.boxes[g.ids[k]] : make_uint2(0u, 0u);
+            g.zk[k] = hiz && g.ids[k] != 0xffffffffu ? fb.zord[g.ids[k]] : 0u;
         }
-        if (sorted) {
-            __syncthreads();
-            const uint32_t cntb = sh.hist[tid];
-            uint32_t incl = cntb;
+    } else {
 #pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const uint32_t vv = (uint32_t)__shfl_up((int)incl, o);
-                if (lane >= o) incl += vv;
-            }
-            if (lane == 63) sh.wtot[wave][0] = incl;
-            __syncthreads();
-            uint32_t wbase = 0;
-#pragma unroll
-            for (int w2 = 0; w2 < 4; ++w2) wbase += w2 < wave ? sh.wtot[w2][0] : 0u;
-            sh.hist[tid] = wbase + incl - cntb;   // first position of bucket tid
-            __syncthreads();
-#pragma unroll
-            for (int k = 0; k < NG; ++k)
-                if (hit[k]) {
-                    const uint32_t pos = sh.hist[bk[k]] + rk[k];
-                    sh.lid[pos] = ids[k];
-                    sh.lkey[pos] = zk[k];
-                    sh.lbox[pos] = bx[k];
+        for (int k = 0; k < NG; ++k) {
+            const uint32_t item = base + tid + 256u * k;
+            uint4 e = make_uint4(0xffffffffu, 0u, 0u, 0u);
+            if (item < t.n_bin) {   // the entry carries the box and the depth bound
+                e = t.bin[item];
+            } else if (item < t.n_items) {   // spilled entries hold the slot only (rare)
+                const uint2 sp = fb.spill[item - t.n_bin];
+                if ((int)sp.x == t.bt) {
+                    const uint2 b = fb.boxes[sp.y];
+                    e = make_uint4(sp.y, b.x, b.y, fb.zord[sp.y]);
                 }
+            }
+            g.ids[k] = e.x;
+            g.bx[k] = e.x != 0xffffffffu ? make_uint2(e.y, e.z) : make_uint2(0u, 0u);
+            g.zk[k] = hiz && e.x != 0xffffffffu ? e.w : 0u;
         }
-        __syncthreads();
-        if (tlon) { t_gather += tl_now() - t_g0; sh.tl[LTL_NCAND] += nc; }
+    }
+    uint32_t zlo = 0xffffffffu, zhi = 0u, nhit = 0u;
+#pragma unroll
+    for (int k = 0; k < NG; ++k) {
+        g.hit[k] = g.ids[k] != 0xffffffffu && t.touches(g.bx[k]);
+        if (g.hit[k]) { zlo = min(zlo, g.zk[k]); zhi = max(zhi, g.zk[k]); }
+        nhit += (uint32_t)__popcll(__ballot(g.hit[k]));
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        zlo = min(zlo, (uint32_t)__shfl_xor((int)zlo, off));
+        zhi = max(zhi, (uint32_t)__shfl_xor((int)zhi, off));
+    }
+    g.basew = 0;
+    if (th.lane == 0 && nhit) { g.basew = atomicAdd(&sh.nc, nhit); atomicMin(&sh.zlo, zlo); atomicMax(&sh.zhi, zhi); }
+    g.basew = (uint32_t)__shfl((int)g.basew, 0);
+    __syncthreads();
+    return sh.nc;
+}
 
-        if constexpr (LIB_CAND == LIB_CAND_DEEP && !SHADOW) {
-            // (3) deep camera raster: passes over LIB_CHUNK list positions, a pair of threads per position
-            //     (position c = tid / 2; half h = tid & 1 takes the tile rows 4h .. 4h + 3), three barriers
-            //     per pass.  A position is staged when its depth bound can still beat the key z of some
-            //     pixel of its box (hierarchical z against the keys themselves: exact, never drops a
-            //     possible winner); its pair of threads loads the record, solves its row spans in
-            //     registers and lays its segments out after one block prefix.  In a sorted list, once the
-            //     item's largest key z (a per-wave maximum read after the previous pass, stale only
-            //     upwards) sorts into a lower bucket than the next position's bound, the rest is skipped.
-            static_assert(2 * LIB_CHUNK == 256 && LIB_PAIR_WORDS == 512, "a thread pair per staged position");
-            const int c = tid >> 1, h = tid & 1;
-            const uint32_t *keyhi = reinterpret_cast<const uint32_t *>(sh.key);   // [2 * pixel + 1]: key z
-            uint32_t p = 0;
-            while (p < nc) {
-                __syncthreads();   // [A] the previous pass's pairs are resolved; its bits, segments, records free
-                const uint64_t t_a = tlon ? tl_now() : 0ull;
-                const bool first = chunk == chunk0;   // no key of the tile written yet
-                const uint32_t ordmax = first ? 0xffffffffu : max(max(sh.wmax[0], sh.wmax[1]), max(sh.wmax[2], sh.wmax[3]));
-                // (the list is front to back only when sorted; the per-position test below holds either way)
-                if (sorted && ordmax != 0xffffffffu && (ordmax < s_lo || bucket(ordmax) < bucket(sh.lkey[p]))) {
-                    ++t_breaks;
-                    break;
-                }
-                ++chunk;
-                sh.bits[tid] = 0ull;
-                sh.bits[tid + 256] = 0ull;
-                const uint32_t q = p + (uint32_t)c;
-                bool alive = false;
-                int bx0 = 0, bx1 = -1, by0 = 0, by1 = -1;
-                uint32_t zk = 0u;
-                if (q < nc) {
-                    const uint2 b = sh.lbox[q];
-                    bx0 = max(lo16(b.x), X0); bx1 = min(hi16(b.x), X1);
-                    by0 = max(lo16(b.y), Y0); by1 = min(hi16(b.y), Y1);
-                    zk = sh.lkey[q];
-                    alive = bx0 <= bx1 && by0 <= by1;
-                    if (alive && hiz && !first) {
-                        if (zk > ordmax) {
-                            alive = false;
-                        } else if ((bx1 - bx0 + 1) * (by1 - by0 + 1) <= SHS_HIZ_BOX) {
-                            uint32_t mx = 0u;
-                            for (int y = by0; y <= by1; ++y)
-                                for (int x = bx0; x <= bx1; ++x) mx = max(mx, keyhi[2 * ((y - TY0) * LIB_RTW + (x - TX0)) + 1]);
-                            alive = zk <= mx;
-                        }
-                    }
-                }
-                if (fb.timeline) {   // (uniform) staged candidates of this tile
-                    const uint64_t am = __ballot(alive && h == 0);
-                    if (lane == 0 && am) atomicAdd(&sh.tl_staged, (uint32_t)__popcll(am));
-                }
-                // the record: half h loads and stages its two float4s; both need the first two (the spans)
-                float4 ra = make_float4(0.f, 0.f, 0.f, 0.f), rb = ra;
-                if (alive) {
-                    const float4 *src = reinterpret_cast<const float4 *>(&fb.recs[sh.lid[q]]) + 2 * h;
-                    ra = src[0];
-                    rb = src[1];
-                    sh.rec[c * 4 + 2 * h] = ra;
-                    sh.rec[c * 4 + 2 * h + 1] = rb;
-                    if (h == 0) sh.zord[c] = zk;
-                }
-                const float4 oa = make_float4(__shfl_xor(ra.x, 1), __shfl_xor(ra.y, 1), __shfl_xor(ra.z, 1), __shfl_xor(ra.w, 1));
-                const float4 ob = make_float4(__shfl_xor(rb.x, 1), __shfl_xor(rb.y, 1), __shfl_xor(rb.z, 1), __shfl_xor(rb.w, 1));
-                const float4 r0 = h ? oa : ra, r1 = h ? ob : rb;
-                // this half's four row spans (tile-relative x0 | x1 << 8; 0x1f: empty)
-                uint32_t spw[4];
-                uint32_t pk = 0u;   // pairs << 11 | segments
+// The depth buckets of a round's list: bucket(z) is monotone in z over the round's depth-bound range.
+struct LibBuckets {
+    uint32_t lo;
+    float scale;
+    __device__ __forceinline__ uint32_t bucket(uint32_t z) const { return min(255u, (uint32_t)((float)(z - lo) * scale)); }
+    // In a sorted list nothing from the entry with bound `key` on can win once the tile's largest key z is
+    // ordmax (0xffffffff: some pixel uncovered): it sorts into a lower bucket, or below the whole range.
+    __device__ __forceinline__ bool behind(uint32_t ordmax, const uint32_t &key) const {
+        return ordmax != 0xffffffffu && (ordmax < lo || bucket(ordmax) < bucket(key));
+    }
+};
+
+// (2) The round's list in sh.lid / lkey / lbox: gather order (one staging pass holds every candidate, or
+//     painter's order), or front to back by a 256-bucket counting sort on the depth bound -- the entries
+//     from position p on then lie in buckets >= bucket(lkey[p]).  Order inside a tile is otherwise free: the
+//     resolve is by (z, submission index) keys.  Entry: lib_gather's exit, sh.hist zeroed and complete.
+//     Exit (its last barrier): the list complete; sh.hist and sh.wtot[.][0] free.
+template <int LIB_CAND>
+__device__ __forceinline__ LibBuckets lib_write_list(LibShared<LIB_CAND> &sh, const LibRound<LIB_CAND / 256> &g, bool sorted, bool hiz,
+                                                     const LibThread &th) {
+    constexpr int NG = LIB_CAND / 256;
+    auto put = [&](uint32_t pos, int k) { sh.lid[pos] = g.ids[k]; sh.lkey[pos] = g.zk[k]; sh.lbox[pos] = g.bx[k]; };
+    if (!sorted) {
+        uint32_t run = 0;
 #pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const int py = TY0 + 4 * h + k;
-                    int s0 = 1, s1 = 0;
-                    if (alive && py >= by0 && py <= by1) lib_row_span(r0, r1, py, bx0, bx1, s0, s1);
-                    spw[k] = s1 >= s0 ? (uint32_t)(s0 - TX0) | ((uint32_t)(s1 - TX0) << 8) : 0x1fu;
-                    if (s1 >= s0) pk += ((uint32_t)(s1 - s0 + 1) << 11) + 1u;
-                }
-                uint32_t incl = pk;
-#pragma unroll
-                for (int o = 1; o < 64; o <<= 1) {
-                    const uint32_t vv = (uint32_t)__shfl_up((int)incl, o);
-                    if (lane >= o) incl += vv;
-                }
-                if (lane == 63) sh.wtot[wave][1] = incl;
-                __syncthreads();   // [B] every wave's total, the zeroed bits
-                const uint64_t t_b = tlon ? tl_now() : 0ull;
-                uint32_t pbase = 0, ptot = 0;
-#pragma unroll
-                for (int w2 = 0; w2 < 4; ++w2) {
-                    const uint32_t p2 = sh.wtot[w2][1];
-                    if (w2 < wave) pbase += p2;
-                    ptot += p2;
-                }
-                if (pk) {
-                    const uint32_t ex = pbase + incl - pk;
-                    uint32_t ps = ex >> 11, sg = ex & 2047u;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const int s0 = (int)(spw[k] & 0xffu), s1 = (int)(spw[k] >> 8);
-                        if (s1 < s0) continue;
-                        const uint32_t wdt = (uint32_t)(s1 - s0 + 1);
-                        sh.seg[sg] = ps | ((uint32_t)s0 << 16) | ((uint32_t)(4 * h + k) << 21) | ((uint32_t)c << 24);
-                        atomicOr(&sh.bits[ps >> 6], 1ull << (ps & 63u));
-                        for (uint32_t wd = (ps + 63u) >> 6; wd * 64u < ps + wdt; ++wd) sh.wown[wd] = (uint16_t)sg;
-                        ps += wdt;
-                        ++sg;
-                    }
-                }
-                __syncthreads();   // [C] segments, starts and staged records complete
-                const int total = (int)(ptot >> 11);
-                if (tlon) {
-                    const uint64_t t_c = tl_now();
-                    t_pairs += (uint32_t)total;
-                    sh.tl[LTL_NPAIRS] += (uint32_t)total;
-                    sh.tl[LTL_STAGE] += t_b - t_a;
-                    sh.tl[LTL_SEG] += t_c - t_b;
-                }
-                const unsigned long long upto = ((2ull << lane) - 1ull) & ~1ull;   // bits 1..lane
-                for (int k0 = 64 * wave; k0 < total; k0 += 256) {
-                    const int k = k0 + lane;
-                    if (k >= total) continue;
-                    const unsigned long long wb = sh.bits[k0 >> 6];
-                    const int o = (int)sh.wown[k0 >> 6] + __popcll(wb & upto);
-                    const uint32_t sgi = sh.seg[o];
-                    const int lx = (int)((sgi >> 16) & 31u) + (k - (int)(sgi & 0xffffu)), ly = (int)((sgi >> 21) & 7u);
-                    const int slot = (int)(sgi >> 24);
-                    const int kp = ly * LIB_RTW + lx;
-                    // per-pixel hierarchical z: the pixel's current key already beats the primitive's
-                    // depth bound (a stale, higher key only skips less)
-                    if (sh.zord[slot] > keyhi[2 * kp + 1]) continue;
-                    const LibRec r = lib_rec_from(&sh.rec[slot * 4]);
-                    float z01, u, v, w, idn;
-                    if (lib_test<SHADOW>(fp, r, TX0 + lx, TY0 + ly, z01, u, v, w, idn))
-                        atomicMin(&sh.key[kp], lib_key(fp, z01, r.seq, SHADOW));
-                }
-                // this wave's largest key z for the next pass (read under the other waves' atomics: stale
-                // only upwards, which selects more, never less); a part counts its own pixels only
-                {
-                    uint32_t o = keyhi[2 * tid + 1];
-#pragma unroll
-                    for (int off = 32; off > 0; off >>= 1) o = max(o, (uint32_t)__shfl_xor((int)o, off));
-                    if (lane == 0) sh.wmax[wave] = o;
-                }
-                p += LIB_CHUNK;
-            }
-            continue;   // the next candidate round
+        for (int k = 0; k < NG; ++k) {
+            const uint64_t hm = __ballot(g.hit[k]);
+            if (g.hit[k]) put(g.basew + run + lanes_below(hm), k);
+            run += (uint32_t)__popcll(hm);
         }
-        // (3) staging passes.  Each selects, in list order, the entries that can still win a pixel
-        //     -- depth bound <= the largest current key z over the pixel columns their box covers
-        //     (hierarchical z; 0xffffffff = an uncovered pixel) -- stages up to LIB_CHUNK of them and
-        //     expands their (primitive, pixel) pairs.  Once the whole tile's largest key z sorts into
-        //     a lower bucket than the next entry, the rest of the list is skipped.
-        uint32_t p = 0;
-        while (p < nc) {
-            if (p > 0) __syncthreads();   // the previous pass's pairs are resolved
-            uint32_t m = 0;
-            if (!sorted) {   // list order, LIB_CHUNK at a time (one pass unless painter's order)
-                m = min((uint32_t)LIB_CHUNK, nc - p);
-                for (int i = tid; i < (int)m; i += 256) sh.sel[i] = p + (uint32_t)i;
-                p += m;
-                ++chunk;
-                __syncthreads();
-            } else {
-                if (hiz) {   // per pixel column, the largest key z so far
-                    uint32_t o = (uint32_t)(sh.key[tid] >> 32);
-                    o = max(o, (uint32_t)__shfl_xor((int)o, 32));   // a wave holds two rows of the column
-                    if (lane < LIB_RTW) atomicMax(&sh.colmax[chunk & 1u][lane], o);
-                }
-                __syncthreads();
-                const uint32_t *colmax = sh.colmax[chunk & 1u];
-                uint32_t ordmax = colmax[lane & (LIB_RTW - 1)];   // the whole tile's max (every wave alike)
+    }
+    const uint32_t span = sh.zhi - sh.zlo;
+    const LibBuckets bk = {sh.zlo, (hiz && span) ? 255.0f / (float)span : 0.0f};
+    uint32_t b[NG], rk[NG];
 #pragma unroll
-                for (int off = LIB_RTW / 2; off > 0; off >>= 1) ordmax = max(ordmax, (uint32_t)__shfl_xor((int)ordmax, off));
-                if (tid < LIB_RTW) sh.colmax[(chunk + 1u) & 1u][tid] = 0u;   // next pass's maxima start here
-                ++chunk;
-                auto done_after = [&](uint32_t q) {   // nothing from list position q on can win (uniform)
-                    return hiz && ordmax != 0xffffffffu && (ordmax < s_lo || bucket(ordmax) < bucket(sh.lkey[q]));
-                };
-                if (done_after(p)) break;
-                // select the next survivors (at most LIB_CHUNK), skipping rejected runs
-                while (p < nc) {
-                    const uint32_t q = p + (uint32_t)tid;
-                    bool alive = false;
-                    if (tid < LIB_CHUNK && q < nc) {
-                        alive = true;
-                        if (hiz) {
-                            const uint2 b = sh.lbox[q];
-                            const int x0 = max(lo16(b.x), X0) - TX0, x1 = min(hi16(b.x), X1) - TX0;
-                            uint32_t cm = 0u;
-                            for (int x = x0; x <= x1; ++x) cm = max(cm, colmax[x]);
-                            alive = sh.lkey[q] <= cm;
-                        }
-                    }
-                    const uint64_t am = __ballot(alive);
-                    if (lane == 0) sh.wtot[wave][0] = (uint32_t)__popcll(am);
-                    __syncthreads();
-                    uint32_t wb = 0;
+    for (int k = 0; k < NG; ++k) {
+        b[k] = 0u; rk[k] = 0u;
+        if (sorted && g.hit[k]) { b[k] = bk.bucket(g.zk[k]); rk[k] = atomicAdd(&sh.hist[b[k]], 1u); }
+    }
+    if (sorted) {
+        __syncthreads();
+        uint32_t tot;
+        const uint32_t first = block_excl_sum<2>(&sh.wtot[0][0], sh.hist[th.tid], th.lane, th.wave, tot);
+        sh.hist[th.tid] = first;   // first position of bucket tid
+        __syncthreads();
 #pragma unroll
-                    for (int w2 = 0; w2 < 4; ++w2) {
-                        const uint32_t c2 = sh.wtot[w2][0];
-                        wb += w2 < wave ? c2 : 0u;
-                        m += c2;
-                    }
-                    if (alive) sh.sel[wb + lanes_below(am)] = q;
-                    p += LIB_CHUNK;
-                    __syncthreads();   // sel complete; wtot reusable
-                    if (m > 0 || p >= nc || done_after(p)) break;
-                }
-                if (m == 0) break;
-            }
-            // stage the survivors' records (consecutive lanes: consecutive float4s of one record)
-            for (int i = tid; i < (int)m * (LIB_RTW * LIB_RTH / 64); i += 256) sh.bits[i] = 0ull;
-            {
-                constexpr int NQ = LIB_CHUNK * 4 / 256;
-                float4 q4[NQ];
-#pragma unroll
-                for (int k = 0; k < NQ; ++k) {
-                    const int f = tid + 256 * k;
-                    const int ci = f >> 2;
-                    q4[k] = f < 4 * (int)m ? reinterpret_cast<const float4 *>(&fb.recs[sh.lid[sh.sel[min(ci, (int)m - 1)]]])[f & 3]
-                                           : make_float4(0.f, 0.f, 0.f, 0.f);
-                }
-#pragma unroll
-                for (int k = 0; k < NQ; ++k) {
-                    const int f = tid + 256 * k;
-                    if (f < 4 * (int)m) sh.rec[f] = q4[k];
-                }
-            }
-            __syncthreads();
-            // Pair tasks (shallow raster and shadow pass -- the deep camera raster takes its own passes
-            // above): the staged boxes laid end to end (C5: few, mostly large primitives; the span
-            // arithmetic would spill the shallow raster's 80 registers, and measured 10 % slower on C5's
-            // shadow map).  Every (primitive, pixel) pair is dealt to one lane, 64-pair windows
-            // round-robin over the waves (start bitmap + word owners, as in shs_legacy.hip).
-            {
-                uint4 *pinfo = reinterpret_cast<uint4 *>(sh.seg);   // per staged box: first pair, x0 | y0 << 16, width | slot << 16, 2^16/width
-                int area = 0, bx0 = 0, by0 = 0, bw = 1;
-                uint32_t zord = 0u;
-                if (tid < (int)m) {
-                    const uint32_t q = sh.sel[tid];
-                    const uint2 b = sh.lbox[q];
-                    const int x0 = max(lo16(b.x), X0), x1 = min(hi16(b.x), X1);
-                    const int y0 = max(lo16(b.y), Y0), y1 = min(hi16(b.y), Y1);
-                    area = (x1 - x0 + 1) * (y1 - y0 + 1); bx0 = x0; by0 = y0; bw = x1 - x0 + 1;
-                    zord = sh.lkey[q];
-                }
-                int incl = area;
-#pragma unroll
-                for (int o = 1; o < 64; o <<= 1) {
-                    const int vv = __shfl_up(incl, o);
-                    if (lane >= o) incl += vv;
-                }
-                if (lane == 63) sh.wtot[wave][1] = (uint32_t)incl;
-                __syncthreads();
-                uint32_t pbase = 0, ptot = 0;
-#pragma unroll
-                for (int w2 = 0; w2 < 4; ++w2) {
-                    const uint32_t p2 = sh.wtot[w2][1];
-                    if (w2 < wave) pbase += p2;
-                    ptot += p2;
-                }
-                if (area > 0) {
-                    const int start = (int)pbase + incl - area;
-                    pinfo[tid] = make_uint4((uint32_t)start, (uint32_t)bx0 | ((uint32_t)by0 << 16),
-                                               (uint32_t)bw | ((uint32_t)tid << 16), (65536u + (uint32_t)bw - 1u) / (uint32_t)bw);
-                    sh.zord[tid] = zord;
-                    atomicOr(&sh.bits[start >> 6], 1ull << (start & 63));
-                    for (int wd = (start + 63) >> 6; wd * 64 < start + area; ++wd) sh.wown[wd] = (uint8_t)tid;
-                }
-                __syncthreads();
-                const int total = (int)ptot;
-                if (tlon) sh.tl[LTL_NPAIRS] += ptot;
-                const unsigned long long upto = ((2ull << lane) - 1ull) & ~1ull;   // bits 1..lane
-                // one pair: its owner (word's first owner + starts up to it), pixel, then the test
-                auto pair = [&](int k0) {
-                    const int k = k0 + lane;
-                    if (k >= total) return;
-                    const unsigned long long wb = sh.bits[k0 >> 6];
-                    const int o = (int)sh.wown[k0 >> 6] + __popcll(wb & upto);
-                    const uint4 pi = pinfo[o];
-                    const int local = k - (int)pi.x, ow = (int)(pi.z & 0xffffu);
-                    const int ly = (int)(((uint32_t)local * pi.w) >> 16), lx = local - ly * ow;
-                    const int px = (int)(pi.y & 0xffffu) + lx, py = (int)(pi.y >> 16) + ly;
-                    const int kp = (py - TY0) * LIB_RTW + (px - TX0);
-                    // per-pixel hierarchical z: the pixel's current key already beats the
-                    // primitive's depth bound (a stale, higher key only skips less)
-                    if (sh.zord[o] > reinterpret_cast<const uint32_t *>(sh.key)[2 * kp + 1]) return;
-                    const LibRec r = lib_rec_from(&sh.rec[(pi.z >> 16) * 4]);
-                    float z01, u, v, w, idn;
-                    if (lib_test<SHADOW>(fp, r, px, py, z01, u, v, w, idn))
-                        atomicMin(&sh.key[kp], lib_key(fp, z01, r.seq, SHADOW));
-                };
-                for (int k0 = 64 * wave; k0 < total; k0 += 256) pair(k0);
-            }
-        }
+        for (int k = 0; k < NG; ++k)
+            if (g.hit[k]) put(sh.hist[b[k]] + rk[k], k);
     }
     __syncthreads();
-    const uint64_t t_res = tlon ? tl_now() : 0ull;
-    // a wave takes a 16x4 block of the tile (rows are 128-B key / 256-B HDR segments); the shadow pass
-    // resolves here, the camera pass hands its keys to k_lib_resolve
-    const int lx = my_lx, ly = my_ly;
-    const int px = TX0 + lx, py = TY0 + ly;
+    return bk;
+}
+
+// The tile's largest key z: the waves' maxima after the last deep pass (stale only upwards).
+template <int LIB_CAND>
+__device__ __forceinline__ uint32_t tile_ordmax(const LibShared<LIB_CAND> &sh) {
+    return max(max(sh.wmax[0], sh.wmax[1]), max(sh.wmax[2], sh.wmax[3]));
+}
+
+// One (primitive, pixel) pair: staged record `slot` (its depth bound in sh.zord[zi]) at pixel (px, py), key
+// kp of the tile.  Per-pixel hierarchical z first: the pixel's current key already beats the primitive's
+// depth bound (a stale, higher key only skips less).
+template <bool SHADOW, int LIB_CAND>
+__device__ __forceinline__ void lib_pair(const LibFrameParams &fp, LibShared<LIB_CAND> &sh, int zi, int slot, int px, int py, int kp) {
+    if (sh.zord[zi] > reinterpret_cast<const uint32_t *>(sh.key)[2 * kp + 1]) return;
+    const LibRec r = lib_rec_from(&sh.rec[slot * 4]);
+    float z01, u, v, w, idn;
+    if (lib_test<SHADOW>(fp, r, px, py, z01, u, v, w, idn)) atomicMin(&sh.key[kp], lib_key(fp, z01, r.seq, SHADOW));
+}
+
+// (3a) Deep camera raster: passes over LIB_CHUNK list positions, a pair of threads per position (position
+//      c = tid / 2; half h = tid & 1 takes the tile rows 4h .. 4h + 3), three barriers per pass.  A position
+//      is staged when its depth bound can still beat the key z of some pixel of its box (hierarchical z
+//      against the keys themselves: exact, never drops a possible winner); its pair of threads loads the
+//      record, solves its row spans in registers and lays its segments out after one block prefix; every
+//      pair of the segments is then dealt to one lane, 64-pair windows round-robin over the waves.  In a
+//      sorted list, once the item's largest key z sorts into a lower bucket than the next position's
+//      bound, the rest is skipped.  Entry: the list complete.  Exit: no barrier after the last pass's pairs
+//      and sh.wmax writes (the next round's, or the finish's, first barrier orders them).
+template <int LIB_CAND>
+__device__ __forceinline__ void lib_deep_passes(const LibFrameParams &fp, const LibBuffers &fb, const LibTile &t, LibShared<LIB_CAND> &sh,
+                                                const LibBuckets &bk, uint32_t nc, bool sorted, bool hiz, uint32_t &chunk, uint32_t chunk0,
+                                                LibTileClock &clk, const LibThread &th) {
+    static_assert(2 * LIB_CHUNK == 256 && LIB_PAIR_WORDS == 512, "a thread pair per staged position");
+    const int tid = th.tid, lane = th.lane, wave = th.wave;
+    const int c = tid >> 1, h = tid & 1;
+    const uint32_t *keyhi = reinterpret_cast<const uint32_t *>(sh.key);   // [2 * pixel + 1]: key z
+    for (uint32_t p = 0; p < nc; p += LIB_CHUNK) {
+        __syncthreads();   // [A] the previous pass's pairs are resolved; its bits, segments, records free
+        clk.t_a = clk.now();
+        const bool first = chunk == chunk0;   // no key of the tile written yet
+        const uint32_t ordmax = first ? 0xffffffffu : tile_ordmax(sh);
+        // (the list is front to back only when sorted; the per-position test below holds either way)
+        if (sorted && bk.behind(ordmax, sh.lkey[p])) { ++clk.breaks; break; }
+        ++chunk;
+        sh.bits[tid] = 0ull;
+        sh.bits[tid + 256] = 0ull;
+        const uint32_t q = p + (uint32_t)c;
+        bool alive = false;
+        LibBox b;
+        uint32_t zk = 0u;
+        if (q < nc) {
+            b = t.clip(sh.lbox[q]);
+            zk = sh.lkey[q];
+            alive = b.x0 <= b.x1 && b.y0 <= b.y1;
+            if (alive && hiz && !first) {
+                if (zk > ordmax) {
+                    alive = false;
+                } else if ((b.x1 - b.x0 + 1) * (b.y1 - b.y0 + 1) <= SHS_HIZ_BOX) {
+                    uint32_t mx = 0u;
+                    for (int y = b.y0; y <= b.y1; ++y)
+                        for (int x = b.x0; x <= b.x1; ++x) mx = max(mx, keyhi[2 * ((y - t.TY0) * LIB_RTW + (x - t.TX0)) + 1]);
+                    alive = zk <= mx;
+                }
+            }
+        }
+        if (fb.timeline) {   // (uniform) staged candidates of this tile
+            const uint64_t am = __ballot(alive && h == 0);
+            if (lane == 0 && am) atomicAdd(&sh.tl_staged, (uint32_t)__popcll(am));
+        }
+        // the record: half h loads and stages its two float4s; both need the first two (the spans)
+        float4 ra = make_float4(0.f, 0.f, 0.f, 0.f), rb = ra;
+        if (alive) {
+            const float4 *src = reinterpret_cast<const float4 *>(&fb.recs[sh.lid[q]]) + 2 * h;
+            ra = src[0];
+            rb = src[1];
+            sh.rec[c * 4 + 2 * h] = ra;
+            sh.rec[c * 4 + 2 * h + 1] = rb;
+            if (h == 0) sh.zord[c] = zk;
+        }
+        const float4 oa = make_float4(__shfl_xor(ra.x, 1), __shfl_xor(ra.y, 1), __shfl_xor(ra.z, 1), __shfl_xor(ra.w, 1));
+        const float4 ob = make_float4(__shfl_xor(rb.x, 1), __shfl_xor(rb.y, 1), __shfl_xor(rb.z, 1), __shfl_xor(rb.w, 1));
+        const float4 r0 = h ? oa : ra, r1 = h ? ob : rb;
+        // this half's four row spans (tile-relative x0 | x1 << 8; 0x1f: empty)
+        uint32_t spw[4];
+        uint32_t pk = 0u;   // pairs << 11 | segments
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int py = t.TY0 + 4 * h + k;
+            int s0 = 1, s1 = 0;
+            if (alive && py >= b.y0 && py <= b.y1) lib_row_span(r0, r1, py, b.x0, b.x1, s0, s1);
+            spw[k] = s1 >= s0 ? (uint32_t)(s0 - t.TX0) | ((uint32_t)(s1 - t.TX0) << 8) : 0x1fu;
+            if (s1 >= s0) pk += ((uint32_t)(s1 - s0 + 1) << 11) + 1u;
+        }
+        // (block_excl_sum in two halves: the timeline's stamp sits at the barrier)
+        const uint32_t incl = wave_incl_sum(pk, lane);
+        if (lane == 63) sh.wtot[wave][1] = incl;
+        __syncthreads();   // [B] every wave's total in sh.wtot[.][1], the zeroed bits
+        clk.t_b = clk.now();
+        uint32_t ptot;
+        const uint32_t pbase = wave_slots_before<2>(&sh.wtot[0][1], wave, ptot);
+        if (pk) {
+            const uint32_t ex = pbase + incl - pk;
+            uint32_t ps = ex >> 11, sg = ex & 2047u;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int s0 = (int)(spw[k] & 0xffu), s1 = (int)(spw[k] >> 8);
+                if (s1 < s0) continue;
+                const uint32_t wdt = (uint32_t)(s1 - s0 + 1);
+                sh.seg[sg] = ps | ((uint32_t)s0 << 16) | ((uint32_t)(4 * h + k) << 21) | ((uint32_t)c << 24);
+                mark_run(sh.bits, sh.wown, ps, wdt, sg);
+                ps += wdt;
+                ++sg;
+            }
+        }
+        __syncthreads();   // [C] segments, starts and staged records complete
+        const int total = (int)(ptot >> 11);
+        clk.laid_out(sh, (uint32_t)total);
+        for (int k0 = 64 * wave; k0 < total; k0 += 256) {
+            const int k = k0 + lane;
+            if (k >= total) continue;
+            const uint32_t sgi = sh.seg[pair_owner(sh.bits, sh.wown, k0, lane)];
+            const int lx = (int)((sgi >> 16) & 31u) + (k - (int)(sgi & 0xffffu)), ly = (int)((sgi >> 21) & 7u);
+            const int slot = (int)(sgi >> 24);
+            lib_pair<false>(fp, sh, slot, slot, t.TX0 + lx, t.TY0 + ly, ly * LIB_RTW + lx);
+        }
+        // this wave's largest key z for the next pass (read under the other waves' atomics: stale only
+        // upwards, which selects more, never less); a part counts its own pixels only
+        uint32_t o = keyhi[2 * tid + 1];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) o = max(o, (uint32_t)__shfl_xor((int)o, off));
+        if (lane == 0) sh.wmax[wave] = o;
+    }
+}
+
+// (3b) Shallow raster and shadow pass, survivor selection: in list order, the next entries (at most
+//      LIB_CHUNK) that can still win a pixel -- depth bound <= the largest current key z over the pixel
+//      columns their box covers (hierarchical z; 0xffffffff = an uncovered pixel) -- as list positions in
+//      sh.sel; an unsorted list is taken LIB_CHUNK at a time.  Moves p past the entries looked at and
+//      counts the pass in chunk.  Returns the number selected; 0: the rest of the list cannot win (the
+//      whole tile's largest key z sorts into a lower bucket than the next entry).
+//      Entry: the list complete, the previous pass's pairs resolved.  Exit: sh.sel complete; sh.wtot[.][0] free.
+template <int LIB_CAND>
+__device__ __forceinline__ uint32_t lib_select(const LibTile &t, LibShared<LIB_CAND> &sh, const LibBuckets &bk, uint32_t nc, bool sorted,
+                                               bool hiz, uint32_t &p, uint32_t &chunk, const LibThread &th) {
+    const int tid = th.tid, lane = th.lane, wave = th.wave;
+    uint32_t m = 0;
+    if (!sorted) {   // (one pass unless painter's order)
+        m = min((uint32_t)LIB_CHUNK, nc - p);
+        for (int i = tid; i < (int)m; i += 256) sh.sel[i] = p + (uint32_t)i;
+        p += m;
+        ++chunk;
+        __syncthreads();
+        return m;
+    }
+    if (hiz) {   // per pixel column, the largest key z so far
+        uint32_t o = (uint32_t)(sh.key[tid] >> 32);
+        o = max(o, (uint32_t)__shfl_xor((int)o, 32));   // a wave holds two rows of the column
+        if (lane < LIB_RTW) atomicMax(&sh.colmax[chunk & 1u][lane], o);
+    }
+    __syncthreads();
+    const uint32_t *colmax = sh.colmax[chunk & 1u];
+    uint32_t ordmax = colmax[lane & (LIB_RTW - 1)];   // the whole tile's max (every wave alike)
+#pragma unroll
+    for (int off = LIB_RTW / 2; off > 0; off >>= 1) ordmax = max(ordmax, (uint32_t)__shfl_xor((int)ordmax, off));
+    if (tid < LIB_RTW) sh.colmax[(chunk + 1u) & 1u][tid] = 0u;   // next pass's maxima start here
+    ++chunk;
+    if (hiz && bk.behind(ordmax, sh.lkey[p])) return 0u;
+    // select the next survivors, skipping rejected runs
+    while (p < nc) {
+        const uint32_t q = p + (uint32_t)tid;
+        bool alive = false;
+        if (tid < LIB_CHUNK && q < nc) {
+            alive = true;
+            if (hiz) {
+                const LibBox b = t.clip(sh.lbox[q]);
+                uint32_t cm = 0u;
+                for (int x = b.x0 - t.TX0; x <= b.x1 - t.TX0; ++x) cm = max(cm, colmax[x]);
+                alive = sh.lkey[q] <= cm;
+            }
+        }
+        const uint64_t am = __ballot(alive);
+        if (lane == 0) sh.wtot[wave][0] = (uint32_t)__popcll(am);
+        __syncthreads();
+        uint32_t got;
+        const uint32_t wb = wave_slots_before<2>(&sh.wtot[0][0], wave, got);
+        m += got;
+        if (alive) sh.sel[wb + lanes_below(am)] = q;
+        p += LIB_CHUNK;
+        __syncthreads();   // sel complete; wtot reusable
+        if (m > 0 || p >= nc || (hiz && bk.behind(ordmax, sh.lkey[p]))) break;
+    }
+    return m;
+}
+
+// (3b) Stage the m selected entries' records in sh.rec (consecutive lanes: consecutive float4s of one record)
+//      and zero the pair bitmap.  Entry: sh.sel complete; sh.rec and sh.bits free.  Exit (one barrier): complete.
+template <int LIB_CAND>
+__device__ __forceinline__ void lib_stage_records(const LibBuffers &fb, LibShared<LIB_CAND> &sh, uint32_t m, int tid) {
+    for (int i = tid; i < (int)m * (LIB_RTW * LIB_RTH / 64); i += 256) sh.bits[i] = 0ull;
+    constexpr int NQ = LIB_CHUNK * 4 / 256;
+    float4 q4[NQ];
+#pragma unroll
+    for (int k = 0; k < NQ; ++k) {
+        const int f = tid + 256 * k;
+        const int ci = f >> 2;
+        q4[k] = f < 4 * (int)m ? reinterpret_cast<const float4 *>(&fb.recs[sh.lid[sh.sel[min(ci, (int)m - 1)]]])[f & 3]
+                               : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+#pragma unroll
+    for (int k = 0; k < NQ; ++k) {
+        const int f = tid + 256 * k;
+        if (f < 4 * (int)m) sh.rec[f] = q4[k];
+    }
+    __syncthreads();
+}
+
+// (3b) Pair tasks: the m staged boxes laid end to end (C5: few, mostly large primitives; the span
+//      arithmetic would spill the shallow raster's 80 registers, and measured 10 % slower on C5's shadow
+//      map), one block prefix of the areas; every (primitive, pixel) pair is then dealt to one lane, 64-pair
+//      windows round-robin over the waves.  Per staged box, sh.seg holds a uint4: first pair, x0 | y0 << 16,
+//      width | slot << 16, 2^16 / width rounded up.
+//      Entry: lib_stage_records' exit; sh.seg, sh.zord, sh.wown, sh.wtot[.][1] free.  Two barriers (the prefix;
+//      boxes, starts and owners complete), none after the pairs.
+template <bool SHADOW, int LIB_CAND>
+__device__ __forceinline__ void lib_box_pairs(const LibFrameParams &fp, const LibTile &t, LibShared<LIB_CAND> &sh, uint32_t m,
+                                              const LibTileClock &clk, const LibThread &th) {
+    const int tid = th.tid, lane = th.lane, wave = th.wave;
+    uint4 *pinfo = reinterpret_cast<uint4 *>(sh.seg);
+    uint32_t area = 0u, zord = 0u;
+    LibBox b;
+    if (tid < (int)m) {
+        const uint32_t q = sh.sel[tid];
+        b = t.clip(sh.lbox[q]);
+        area = (uint32_t)((b.x1 - b.x0 + 1) * (b.y1 - b.y0 + 1));
+        zord = sh.lkey[q];
+    }
+    uint32_t ptot;
+    const uint32_t start = block_excl_sum<2>(&sh.wtot[0][1], area, lane, wave, ptot);
+    if (area > 0u) {
+        const uint32_t bw = (uint32_t)(b.x1 - b.x0 + 1);
+        pinfo[tid] = make_uint4(start, (uint32_t)b.x0 | ((uint32_t)b.y0 << 16), bw | ((uint32_t)tid << 16), (65536u + bw - 1u) / bw);
+        sh.zord[tid] = zord;
+        mark_run(sh.bits, sh.wown, start, area, (uint32_t)tid);
+    }
+    __syncthreads();
+    const int total = (int)ptot;
+    if (clk.on) sh.tl[LTL_NPAIRS] += ptot;
+    for (int k0 = 64 * wave; k0 < total; k0 += 256) {
+        const int k = k0 + lane;
+        if (k >= total) continue;
+        const int o = pair_owner(sh.bits, sh.wown, k0, lane);
+        const uint4 pi = pinfo[o];
+        const int local = k - (int)pi.x, ow = (int)(pi.z & 0xffffu);
+        const int ly = (int)(((uint32_t)local * pi.w) >> 16), lx = local - ly * ow;
+        const int px = (int)(pi.y & 0xffffu) + lx, py = (int)(pi.y >> 16) + ly;
+        lib_pair<SHADOW>(fp, sh, o, (int)(pi.z >> 16), px, py, (py - t.TY0) * LIB_RTW + (px - t.TX0));
+    }
+}
+
+// The finish: a wave takes a 16x4 block of the tile (rows are 128-B key / 256-B HDR segments); the shadow
+// pass resolves its texels here, the camera pass hands each block's winners to k_lib_resolve.  A split
+// tile's part first merges its keys into the tile's fb.pkeys slot; the part that finishes last takes the
+// merged keys (resetting the slot for the next pass) and writes the winners.
+// Entry: every pair resolved (sh.key complete).  Exit: each thread has reset its own pixel's key, so the next
+// tile needs no barrier before its first.
+template <bool SHADOW, int LIB_CAND>
+__device__ __forceinline__ void lib_finish(const LibFrameParams &fp, const LibBuffers &fb, const LibTile &t, LibShared<LIB_CAND> &sh, int rt,
+                                           uint32_t parts, uint32_t sid, const LibThread &th) {
+    const int tid = th.tid, lane = th.lane, wave = th.wave;
+    const int lx = 16 * (wave & 1) + (lane & 15), ly = 4 * (wave >> 1) + (lane >> 4);   // tile layout: wave w = 16x4 block w
+    const int px = t.TX0 + lx, py = t.TY0 + ly;
     unsigned long long key = sh.key[ly * LIB_RTW + lx];
     sh.key[ly * LIB_RTW + lx] = KEY_EMPTY;   // this thread's pixel only: clean for the next tile
     bool covered = false;
     bool write = true;
     if (!SHADOW && parts > 1u) {
-        // a split tile: merge this part's keys into the tile's pkeys slot; the part that finishes last
-        // takes the merged keys (resetting the slot for the next pass) and writes the winners
         unsigned long long *pk = fb.pkeys + (size_t)sid * (LIB_RTH * LIB_RTW) + ly * LIB_RTW + lx;
         if (key != KEY_EMPTY) atomicMin(pk, key);
         __threadfence();
@@ -2552,22 +2571,59 @@ __device__ void lib_raster_tile(const LibFrameParams &fp, const LibBuffers &fb, 
     const uint64_t cm = __ballot(covered);
     if (lane == 0 && cm) atomicAdd(&sh.cov, (uint32_t)__popcll(cm));
     if (SHADOW && tid == 0) fb.busy[rt] = 0u;   // camera pass: k_lib_resolve resets it (split tiles' parts)
-    if (tlon) {
-        const uint64_t t_end = tl_now();
-        sh.tl[LTL_GATHER] += t_gather;
-        sh.tl[LTL_PAIRS] += (t_res - t_tile) - t_gather;
-        sh.tl[LTL_SHADE] += t_end - t_res;
-        sh.tl[LTL_NBUSY] += 1;
-        sh.tl[LTL_CHUNKS] += chunk - chunk0;
-        if (t_end - t_tile > sh.tl[LTL_MAXTILE]) {   // this workgroup's longest tile so far
-            sh.tl[LTL_MT_RT] = (uint64_t)rt; sh.tl[LTL_MT_ITEMS] = tl_items; sh.tl[LTL_MT_ROUNDS] = t_rounds;
-            sh.tl[LTL_MT_PASSES] = chunk - chunk0; sh.tl[LTL_MT_STAGED] = sh.tl_staged; sh.tl[LTL_MT_PAIRS] = t_pairs;
-            sh.tl[LTL_MT_GATHER] = t_gather; sh.tl[LTL_MT_BREAKS] = t_breaks;
+}
+
+// One work item: raster tile rt, or (k_lib_plan, camera pass) part `part` of `parts` of it: the list
+// positions [part n / parts, (part + 1) n / parts) over the whole tile, its keys merged with the other
+// parts' in fb.pkeys[sid] (plan_parts).  Rounds of LIB_CAND list entries: lib_gather, lib_write_list, then
+// the round's staging passes (lib_deep_passes, or lib_select / lib_stage_records / lib_box_pairs); lib_finish.
+template <bool SHADOW, int LIB_CAND>
+__device__ void lib_raster_tile(const LibFrameParams &fp, const LibBuffers &fb, const uint32_t *cnt, int rt, LibShared<LIB_CAND> &sh,
+                                uint32_t &chunk, uint32_t part = 0u, uint32_t parts = 1u, uint32_t sid = 0u) {
+    const int tid = threadIdx.x;
+    const LibThread th = {tid, tid & 63, tid >> 6};
+    const bool hiz = SHADOW || (fp.flags & LF_DEPTH);   // painter's order (no depth target): never
+    // (no barrier here: the previous tile ended with each thread resetting its own pixel's key, and
+    // every round below starts with one before any shared state is touched)
+    LibTileClock clk;
+    clk.begin(fb, sh, tid);
+    const uint32_t chunk0 = chunk;
+    const LibTile t = lib_tile<SHADOW>(fp, fb, cnt, rt, sh, hiz, part, parts, tid);
+    for (uint32_t base = t.lo; base < t.n_items; base += LIB_CAND) {
+        __syncthreads();
+        // a sorted list: every entry from `base` on lies in hsr bucket >= the one of bin[base]; once the
+        // tile's largest key z sorts into a lower bucket, or below the whole range, no later entry can
+        // beat any pixel -- the tile is done
+        if (t.gsorted && base > t.lo && chunk != chunk0) {
+            const uint32_t om = tile_ordmax(sh);
+            if (om < t.hsr.x || hs_bucket(t.hsr, om) < hs_bucket(t.hsr, t.bin[base].w)) break;
         }
-        sh.tl[LTL_MAXTILE] = max(sh.tl[LTL_MAXTILE], t_end - t_tile);
-        sh.tl[LTL_TILES] += t_end - t_tile;
-        sh.tl[LTL_LAST] = t_end;
+        ++clk.rounds;
+        if (tid == 0) { sh.nc = 0; sh.zlo = 0xffffffffu; sh.zhi = 0u; }
+        sh.hist[tid] = 0u;
+        __syncthreads();
+        clk.t_g0 = clk.now();
+        LibRound<LIB_CAND / 256> g;
+        const uint32_t nc = lib_gather(fp, fb, t, sh, base, hiz, th, g);
+        const bool sorted = hiz && nc > (uint32_t)LIB_CHUNK;   // else one staging pass holds every candidate
+        const LibBuckets bk = lib_write_list(sh, g, sorted, hiz, th);
+        clk.gathered(sh, nc);
+        if constexpr (LIB_CAND == LIB_CAND_DEEP && !SHADOW) {
+            lib_deep_passes(fp, fb, t, sh, bk, nc, sorted, hiz, chunk, chunk0, clk, th);
+        } else {
+            for (uint32_t p = 0; p < nc;) {
+                if (p > 0) __syncthreads();   // the previous pass's pairs are resolved
+                const uint32_t m = lib_select(t, sh, bk, nc, sorted, hiz, p, chunk, th);
+                if (m == 0) break;
+                lib_stage_records(fb, sh, m, tid);
+                lib_box_pairs<SHADOW>(fp, t, sh, m, clk, th);
+            }
+        }
     }
+    __syncthreads();
+    clk.t_res = clk.now();
+    lib_finish<SHADOW>(fp, fb, t, sh, rt, parts, sid, th);
+    clk.end(sh, rt, t.n_items, chunk - chunk0);
 }
 
 // A shadow-map raster tile no primitive touches: its texels get the clear depth.
@@ -2722,12 +2778,7 @@ __global__ __launch_bounds__(LIB_HSORT_T) void k_lib_hsort(LibFrameParams fp, Li
         uint32_t c = 0u, incl = 0u;
         if (tid < 256) {   // exclusive prefix of the bucket counts (waves 0..3)
             c = s_hist[tid];
-            incl = c;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const uint32_t v = (uint32_t)__shfl_up((int)incl, o);
-                if (lane >= o) incl += v;
-            }
+            incl = wave_incl_sum(c, lane);
             if (lane == 63) s_wsum[wave] = incl;
         }
         __syncthreads();
@@ -2764,12 +2815,7 @@ __global__ __launch_bounds__(256) void k_lib_plan(LibFrameParams fp, LibBuffers 
     }
     const uint32_t kk = k > 1u ? k : 0u;
     // wave-aggregated reservation of this wave's parts
-    uint32_t incl = kk;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t a = (uint32_t)__shfl_up((int)incl, o);
-        if (lane >= o) incl += a;
-    }
+    const uint32_t incl = wave_incl_sum(kk, lane);
     const uint32_t tot = (uint32_t)__shfl((int)incl, 63);
     uint32_t base = 0u;
     if (lane == 63 && tot) base = atomicAdd(&cnt[LC_ITEMS], tot);

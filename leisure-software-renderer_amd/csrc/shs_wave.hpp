@@ -1,5 +1,6 @@
 // shs_wave.hpp -- wavefront (64-lane) helpers shared by the legacy and library raster kernels:
-// in-wave LDS hand-off, the wave prefix sum, ballot-based appends and the order-preserving 64-bit depth key.
+// in-wave LDS hand-off, the wave and block prefix sums, the pair-run bitmap, ballot-based appends and the
+// order-preserving 64-bit depth key.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -18,14 +19,57 @@ __device__ __forceinline__ uint32_t lanes_below(uint64_t m) {
 }
 
 // Inclusive prefix sum over the wave's 64 lanes (converged wave): lane l gets v[0] + ... + v[l].
-__device__ __forceinline__ uint32_t wave_incl_sum(uint32_t v) {
-    const int lane = __lane_id();
+// (lane: the caller's, where it has one -- recomputed here it costs the raster kernels code and registers.)
+__device__ __forceinline__ uint32_t wave_incl_sum(uint32_t v, int lane) {
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
         const uint32_t up = (uint32_t)__shfl_up((int)v, o);
         if (lane >= o) v += up;
     }
     return v;
+}
+__device__ __forceinline__ uint32_t wave_incl_sum(uint32_t v) { return wave_incl_sum(v, __lane_id()); }
+
+// A 256-thread block's four per-wave slots, slot[STRIDE * w] for wave w (complete: a barrier since they
+// were written): the sum of the slots before the calling wave's; the block's total in tot.
+template <int STRIDE>
+__device__ __forceinline__ uint32_t wave_slots_before(const uint32_t *slot, int wave, uint32_t &tot) {
+    uint32_t before = 0u;
+    tot = 0u;
+#pragma unroll
+    for (int w2 = 0; w2 < 4; ++w2) {
+        const uint32_t p2 = slot[STRIDE * w2];
+        if (w2 < wave) before += p2;
+        tot += p2;
+    }
+    return before;
+}
+
+// Block exclusive prefix of the 256 threads' v through four per-wave slots (one barrier; the slots are free
+// on entry, and again after the next barrier); the block's total in tot.
+template <int STRIDE>
+__device__ __forceinline__ uint32_t block_excl_sum(uint32_t *slot, uint32_t v, int lane, int wave, uint32_t &tot) {
+    const uint32_t incl = wave_incl_sum(v, lane);
+    if (lane == 63) slot[STRIDE * wave] = incl;
+    __syncthreads();
+    return wave_slots_before<STRIDE>(slot, wave, tot) + incl - v;
+}
+
+// Pair runs.  The (candidate, pixel) pairs of a pass are numbered end to end, and a run of len pairs from
+// pair `start` belongs to `owner` (a row segment or a staged box): mark_run sets its start bit in the
+// bitmap over the pairs and names it the owner of every bitmap word whose first pair is in the run;
+// pair_owner finds the owner of lane `lane`'s pair in the 64-pair window from pair k0 -- the window's
+// word's first owner + the starts in the word up to the pair.  Own: the owner word (the caller's LDS budget).
+template <class Own>
+__device__ __forceinline__ void mark_run(unsigned long long *bits, Own *wown, uint32_t start, uint32_t len, uint32_t owner) {
+    atomicOr(&bits[start >> 6], 1ull << (start & 63u));
+    for (uint32_t wd = (start + 63u) >> 6; wd * 64u < start + len; ++wd) wown[wd] = (Own)owner;
+}
+template <class Own>
+__device__ __forceinline__ int pair_owner(const unsigned long long *bits, const Own *wown, int k0, int lane) {
+    const unsigned long long wb = bits[k0 >> 6];
+    const unsigned long long upto = ((2ull << lane) - 1ull) & ~1ull;   // bits 1..lane
+    return (int)wown[k0 >> 6] + __popcll(wb & upto);
 }
 
 // Wave-aggregated appends to NK per-key counters (call with the whole wave converged).  Lanes with
