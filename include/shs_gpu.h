@@ -590,6 +590,31 @@ int shs_lib_fuse_tonemap(shs_ctx *ctx, const shs_tonemap_desc *desc);
 int shs_resolve_ldr(shs_ctx *ctx, uint8_t *ldr, uint8_t *present);
 /* Device pointers of the tonemap targets (the pass chain finished first, as shs_lib_device_targets). */
 int shs_ldr_device_targets(shs_ctx *ctx, void **ldr_dev, void **present_dev);
+/* PassLightShafts::execute (shs-renderer-lib/include/shs/passes/pass_light_shafts.hpp:44-215), the
+ * "light_shafts" pass of the standard chain between tonemap and motion blur
+ * (pipeline/pass_adapters.hpp:1184-1276), on the last tonemap's RT_ColorLDR (SHS_TONEMAP_LDR; the
+ * separate and the fused tonemap both count) IN PLACE, as the adapter runs it (input == output): after
+ * the call the shafted bytes are the frame's LDR for shs_resolve_ldr, shs_ldr_device_targets,
+ * shs_motion_blur and SHS_TARGET_LIB_PRESENT tile packs (the tonemap's present staging is rewritten
+ * too when it has one).  rt_depth_like is the camera pass's depth plane when it has one
+ * (SHS_LIB_DEPTH_MOTION) unless SHS_LIGHT_SHAFTS_NO_DEPTH.  The bytes are the reference's.  With
+ * enable = 0, or a sun that projects outside the screen (:78-106), the LDR is left untouched.
+ * Fields are FrameParams::pass.light_shafts (frame/frame_params.hpp:35-42) and the scene's camera / sun.
+ * SHS_ERR_INVALID: no such tonemap since the last camera pass; a second call on the same tonemap, or one
+ * after its shs_motion_blur (run shs_tonemap again first); non-finite floats; steps > 1024 (the
+ * reference has no upper bound -- an error rather than a clamp, so no accepted input differs from it);
+ * a tile-sharded frame (shard_count > 1: the taps cross tile ownership -- in a multi-GPU run the pass
+ * belongs after the gather).  A later shs_tonemap or camera pass starts over. */
+#define SHS_LIGHT_SHAFTS_NO_DEPTH 1u    /* rt_depth_like absent: s = luma only */
+typedef struct shs_light_shafts_desc {
+    int32_t enable;             /* FrameParams::pass.light_shafts.enable */
+    int32_t steps;              /* 48; the pass takes max(8, steps) */
+    float density, weight, decay;   /* 0.8, 0.9, 0.95; clamped as the pass does */
+    float cam_pos[3], sun_dir_ws[3];   /* scene.cam.pos, scene.sun.dir_ws */
+    float viewproj[16];         /* scene.cam.viewproj, column-major */
+    uint32_t flags;             /* SHS_LIGHT_SHAFTS_* */
+} shs_light_shafts_desc;
+int shs_light_shafts(shs_ctx *ctx, const shs_light_shafts_desc *desc);
 /* PassMotionBlur::execute (shs-renderer-lib/include/shs/passes/pass_motion_blur.hpp:38-170) on the
  * last tonemap's RT_ColorLDR (SHS_TONEMAP_LDR) with the camera pass's depth / motion planes
  * (SHS_LIB_DEPTH_MOTION), into a separate RT_ColorLDR (+ its present staging with
@@ -748,6 +773,10 @@ int shs_group_synchronize(shs_group *g);
 /* Host-only (no device): the byte thresholds for gamma (thr[0] = 0; +inf where a byte is never
  * reached).  Exposed for the parity tests. */
 int shs_tonemap_thresholds(float gamma, float thr[256]);
+/* Host-only: PassLightShafts' sun projection (pass_light_shafts.hpp:78-92) as shs_light_shafts runs it.
+ * sun_uv keeps the pass's initial (0.5, 0.2) when |clip.w| <= 1e-6.  Exposed for the parity tests. */
+int shs_light_shafts_sun_uv(const float cam_pos[3], const float sun_dir_ws[3], const float viewproj[16],
+                            float sun_uv[2], int32_t *valid);
 
 #ifdef __cplusplus
 }

@@ -683,7 +683,7 @@ void shs_lib_release(shs_ctx *ctx) {
     release(ctx->lib_hdr); release(ctx->lib_keys); release(ctx->lib_blkcov); ctx->blkcov_zero_at = nullptr; release(ctx->tm_thr_dev); ctx->tm_thr_dev_gamma = -1.0f; release(ctx->lib_depth); release(ctx->lib_motion); release(ctx->shadow_map);
     release(ctx->lights); release(ctx->tlights); release(ctx->depth_ranges);
     release(ctx->list_counts); release(ctx->list_indices); release(ctx->lib_timeline); release(ctx->lib_stimeline);
-    release(ctx->lib_ldr); release(ctx->lib_present); release(ctx->lib_mb); release(ctx->lib_mb_present);
+    release(ctx->lib_ldr); release(ctx->lib_present); release(ctx->lib_mb); release(ctx->lib_mb_present); release(ctx->lib_shaft_mask);
     release(ctx->lb_lights); release(ctx->lb_ndc); release(ctx->lb_counts); release(ctx->lb_indices);
     release(ctx->occ_depth); release(ctx->occ_visible); release(ctx->occ_flags); release(ctx->occ_objs); release(ctx->occ_rects); release(ctx->occ_tris);
     release(ctx->dd_objs); release(ctx->dd_tris); release(ctx->dd_depth0); release(ctx->dd_depth); release(ctx->dd_lit_b);
@@ -1236,6 +1236,7 @@ int shs_render_pbr_forward(shs_ctx *ctx, const shs_lib_frame *frame, const shs_l
     // a new camera pass: a tonemap (and motion blur) must follow it again, unless it ran fused
     ctx->have_ldr = wk.tm_fused;
     if (wk.tm_fused) ctx->tm_desc = wk.tm_desc;
+    ctx->have_ls = false;
     ctx->have_mb = false;
     return SHS_OK;
 }

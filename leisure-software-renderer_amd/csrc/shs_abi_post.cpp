@@ -1,10 +1,12 @@
 // shs_abi_post.cpp -- C ABI of the passes after the raster path (include/shs_gpu.h):
 // PassTonemap (shs-renderer-lib/include/shs/passes/pass_tonemap.hpp:36-83) and the SDL texture
-// staging upload_ldr_to_rgba8 (exp-plumbing/hello_pass_basics.cpp:102-119) and PassMotionBlur
+// staging upload_ldr_to_rgba8 (exp-plumbing/hello_pass_basics.cpp:102-119), PassLightShafts
+// (shs-renderer-lib/include/shs/passes/pass_light_shafts.hpp:44-215) and PassMotionBlur
 // (shs-renderer-lib/include/shs/passes/pass_motion_blur.hpp:38-170), paths relative to
 // /root/reference/cpp-folders/src/.
 #include <cmath>
 #include <cstdint>
+#include <cstdlib>
 #include <cstring>
 #include <limits>
 
@@ -111,10 +113,59 @@ int enqueue_motion_blur(shs_ctx *ctx) {
     return SHS_OK;
 }
 
+// PassLightShafts' sun on the screen (pass_light_shafts.hpp:78-92): cam.pos + (-sun.dir_ws) * 100 through
+// cam.viewproj in glm's order ((m0*x + m1*y) + (m2*z + m3*w), shs_glm.hpp), three divisions by clip.w.
+bool light_shafts_sun(const float cam_pos[3], const float sun_dir[3], const float m[16], float uv[2]) {
+    uv[0] = 0.5f;
+    uv[1] = 0.2f;
+    const float x = cam_pos[0] + (-sun_dir[0]) * 100.0f;
+    const float y = cam_pos[1] + (-sun_dir[1]) * 100.0f;
+    const float z = cam_pos[2] + (-sun_dir[2]) * 100.0f;
+    float clip[4];
+    for (int r = 0; r < 4; ++r) clip[r] = (m[r] * x + m[4 + r] * y) + (m[8 + r] * z + m[12 + r] * 1.0f);
+    if (!(std::abs(clip[3]) > 1e-6f)) return false;
+    const float nx = clip[0] / clip[3], ny = clip[1] / clip[3], nz = clip[2] / clip[3];
+    uv[0] = nx * 0.5f + 0.5f;
+    uv[1] = ny * 0.5f + 0.5f;
+    return (clip[3] > 0.0f) && (nz >= -1.0f && nz <= 1.0f) && (uv[0] >= 0.0f && uv[0] <= 1.0f) &&
+           (uv[1] >= 0.0f && uv[1] <= 1.0f);
+}
+
+int enqueue_light_shafts(shs_ctx *ctx) {
+    const shs_light_shafts_desc &d = ctx->ls_desc;
+    float uv[2];
+    // disabled, or the sun not on the screen: input == output is left as it is (:54-67, :95-106)
+    if (!d.enable || !light_shafts_sun(d.cam_pos, d.sun_dir_ws, d.viewproj, uv)) return SHS_OK;
+    const int W = ctx->lib_frame.width, H = ctx->lib_frame.height;
+    if (ensure(ctx, ctx->lib_shaft_mask, (size_t)W * H)) return SHS_ERR_HIP;
+    shs_dev::LightShaftsParams p{};
+    p.ldr = ctx->lib_ldr.p;
+    const bool depth = (ctx->lib_frame.flags & SHS_LIB_DEPTH_MOTION) && !(d.flags & SHS_LIGHT_SHAFTS_NO_DEPTH);
+    p.depth = depth ? ctx->lib_depth.p : nullptr;
+    p.mask = ctx->lib_shaft_mask.p;
+    p.present = (ctx->tm_desc.flags & SHS_TONEMAP_PRESENT) ? ctx->lib_present.p : nullptr;
+    p.W = W;
+    p.H = H;
+    // the pass's parameter clamps (:133-136), the same expressions
+    p.steps = std::max(8, d.steps);
+    p.density = std::max(0.0f, d.density);
+    p.weight = std::max(0.0f, d.weight);
+    p.decay = d.decay < 0.0f ? 0.0f : (1.0f < d.decay ? 1.0f : d.decay);   // std::clamp
+    p.sun_u = uv[0];
+    p.sun_v = uv[1];
+    int part = 3;   // timing experiments (tools/exp_light_shafts.py): one of the two kernels alone
+    if (const char *e = shs_exp_env("SHS_LS_PART")) part = std::atoi(e);
+    if (part & 1) HIP_TRY(ctx, shs_internal::launch_shaft_mask(p, ctx->stream));
+    if (part & 2) HIP_TRY(ctx, shs_internal::launch_light_shafts(p, ctx->stream));
+    return SHS_OK;
+}
+
 }  // namespace
 
+// The chain behind a re-issued camera pass, in the pass order: tonemap, light shafts, motion blur.
 int shs_tonemap_reissue(shs_ctx *ctx) {
-    const int rc = enqueue_tonemap(ctx);
+    int rc = enqueue_tonemap(ctx);
+    if (!rc && ctx->have_ls) rc = enqueue_light_shafts(ctx);
     if (rc || !ctx->have_mb) return rc;
     return enqueue_motion_blur(ctx);
 }
@@ -162,7 +213,43 @@ int shs_tonemap(shs_ctx *ctx, const shs_tonemap_desc *desc) {
     const int rc = enqueue_tonemap(ctx);
     if (rc) return rc;
     ctx->have_ldr = true;
+    ctx->have_ls = false;
     ctx->have_mb = false;
+    return SHS_OK;
+}
+
+int shs_light_shafts_sun_uv(const float cam_pos[3], const float sun_dir_ws[3], const float viewproj[16], float sun_uv[2],
+                            int32_t *valid) {
+    if (!cam_pos || !sun_dir_ws || !viewproj || !sun_uv || !valid) return SHS_ERR_INVALID;
+    *valid = light_shafts_sun(cam_pos, sun_dir_ws, viewproj, sun_uv) ? 1 : 0;
+    return SHS_OK;
+}
+
+int shs_light_shafts(shs_ctx *ctx, const shs_light_shafts_desc *desc) {
+    if (!ctx || !desc) return SHS_ERR_INVALID;
+    if (!ctx->have_ldr || !(ctx->tm_desc.flags & SHS_TONEMAP_LDR)) {
+        ctx->err = "light shafts need a tonemap with SHS_TONEMAP_LDR after the camera pass";
+        return SHS_ERR_INVALID;
+    }
+    if (ctx->lib_frame.shard_count > 1) {
+        ctx->err = "light shafts on a tile-sharded frame (the taps cross tile ownership: run them after the gather)";
+        return SHS_ERR_INVALID;
+    }
+    if (ctx->have_mb || (ctx->have_ls && !SHS_EXPERIMENTS)) {
+        ctx->err = "light shafts run once, between the tonemap and its motion blur (run shs_tonemap again first)";
+        return SHS_ERR_INVALID;
+    }
+    if (desc->flags & ~SHS_LIGHT_SHAFTS_NO_DEPTH) { ctx->err = "light shafts flags"; return SHS_ERR_INVALID; }
+    if (desc->steps > shs_dev::LIGHT_SHAFTS_MAX_STEPS) { ctx->err = "light shafts steps > 1024"; return SHS_ERR_INVALID; }
+    bool finite = std::isfinite(desc->density) && std::isfinite(desc->weight) && std::isfinite(desc->decay);
+    for (int i = 0; i < 3; ++i) finite = finite && std::isfinite(desc->cam_pos[i]) && std::isfinite(desc->sun_dir_ws[i]);
+    for (int i = 0; i < 16; ++i) finite = finite && std::isfinite(desc->viewproj[i]);
+    if (!finite) { ctx->err = "light shafts density / weight / decay / camera / sun must be finite"; return SHS_ERR_INVALID; }
+    if (set_dev(ctx)) return SHS_ERR_HIP;
+    ctx->ls_desc = *desc;
+    const int rc = enqueue_light_shafts(ctx);
+    if (rc) return rc;
+    ctx->have_ls = true;
     return SHS_OK;
 }
 

@@ -307,6 +307,10 @@ struct shs_ctx {
     DevBuf<uint32_t> lib_mb, lib_mb_present;
     shs_motion_blur_desc mb_desc{};
     bool have_mb = false;                 // a motion blur follows that tonemap
+    // PassLightShafts between the two (shs_abi_post.cpp): it rewrites lib_ldr / lib_present in place
+    DevBuf<float> lib_shaft_mask;         // the plane its taps sample (k_shaft_mask)
+    shs_light_shafts_desc ls_desc{};
+    bool have_ls = false;                 // light shafts ran on that tonemap's LDR (replayed by a re-issue)
     // CPU light binning on the GPU (shs_abi_lightbin.cpp)
     DevBuf<shs_dev::BinLight> lb_lights;
     DevBuf<float2> lb_ndc;

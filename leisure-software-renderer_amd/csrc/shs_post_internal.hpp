@@ -51,9 +51,29 @@ struct MotionBlurParams {
     float strength, max_vel, min_vel, depth_eps, dt_scale;
 };
 
+// PassLightShafts (passes/pass_light_shafts.hpp:44-215) with the pass's parameter clamps (:133-136) and
+// the sun's projection (:78-92) done on the host (identical float expressions).  k_shaft_mask writes the
+// plane every tap samples -- luma (:117-121), times clamp(depth, 0, 1) when the pass has a depth plane
+// (:161-168: the same texel as the luma tap, so the product is the tap's own fp32 multiply) -- and
+// k_light_shafts marches it towards the sun and adds the boost to the RT_ColorLDR in place (it reads
+// only its own pixel of it).
+struct LightShaftsParams {
+    uint32_t *ldr;          // RT_ColorLDR RGBA8, rows y up: read by k_shaft_mask, rewritten by k_light_shafts
+    const float *depth;     // RT_ColorDepthMotion depth, rows y up, or null (no rt_depth_like)
+    float *mask;            // W*H fp32 scratch
+    uint32_t *present;      // the tonemap's upload_ldr_to_rgba8 staging (rows top-down), or null
+    int W, H;
+    int steps;              // max(8, steps), <= LIGHT_SHAFTS_MAX_STEPS
+    float density, weight, decay;
+    float sun_u, sun_v;
+};
+constexpr int LIGHT_SHAFTS_MAX_STEPS = 1024;
+
 }  // namespace shs_dev
 
 namespace shs_internal {
 hipError_t launch_tonemap(const shs_dev::TonemapParams &p, hipStream_t s);
 hipError_t launch_motion_blur(const shs_dev::MotionBlurParams &p, hipStream_t s);
+hipError_t launch_shaft_mask(const shs_dev::LightShaftsParams &p, hipStream_t s);
+hipError_t launch_light_shafts(const shs_dev::LightShaftsParams &p, hipStream_t s);
 }  // namespace shs_internal

@@ -296,6 +296,33 @@ class Context:
                                               None if pre is None else pre.ctypes.data_as(ctypes.c_void_p)))
         return ldr, pre
 
+    def light_shafts(self, viewproj, cam_pos, sun_dir_ws, enable=True, steps=48, density=0.8, weight=0.9, decay=0.95,
+                     use_depth=True):
+        """PassLightShafts (pass_light_shafts.hpp:44-215) on the last tonemap's RT_ColorLDR in place (and
+        its present staging), with the camera pass's depth plane when it has one and use_depth
+        (defaults: LightShaftsPassParams).  viewproj: column-major float[16], as LibDraw.viewproj.
+        resolve_ldr() then returns the shafted bytes."""
+        d = _abi.LightShaftsDescC()
+        d.enable, d.steps = 1 if enable else 0, int(steps)
+        d.density, d.weight, d.decay = float(density), float(weight), float(decay)
+        d.cam_pos[:] = [float(v) for v in cam_pos]
+        d.sun_dir_ws[:] = [float(v) for v in sun_dir_ws]
+        d.viewproj[:] = [float(v) for v in np.asarray(viewproj, np.float32).reshape(16)]
+        d.flags = 0 if use_depth else _abi.LIGHT_SHAFTS_NO_DEPTH
+        self._check(self._lib.shs_light_shafts(self._h, ctypes.byref(d)))
+
+    @staticmethod
+    def light_shafts_sun_uv(viewproj, cam_pos, sun_dir_ws):
+        """PassLightShafts' sun projection (pass_light_shafts.hpp:78-92) -> (sun_uv float32[2], valid)."""
+        fp = ctypes.POINTER(ctypes.c_float)
+        a = [np.ascontiguousarray(np.asarray(v, np.float32).reshape(n)) for v, n in ((cam_pos, 3), (sun_dir_ws, 3), (viewproj, 16))]
+        uv = np.zeros(2, np.float32)
+        valid = ctypes.c_int32(0)
+        rc = lib().shs_light_shafts_sun_uv(*[v.ctypes.data_as(fp) for v in a], uv.ctypes.data_as(fp), ctypes.byref(valid))
+        if rc != 0:
+            raise ShsError(rc, "shs_light_shafts_sun_uv")
+        return uv, bool(valid.value)
+
     def motion_blur(self, enable=True, samples=10, strength=1.0, max_velocity_px=20.0, min_velocity_px=0.25,
                     depth_reject=0.08, dt=1.0 / 60.0, present=True):
         """PassMotionBlur (pass_motion_blur.hpp:38-170) over the last tonemap's RT_ColorLDR with the

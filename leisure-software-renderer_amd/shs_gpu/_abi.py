@@ -150,6 +150,15 @@ class MotionBlurDescC(ctypes.Structure):
                 ("depth_reject", ctypes.c_float), ("dt", ctypes.c_float), ("flags", ctypes.c_uint32)]
 
 
+LIGHT_SHAFTS_NO_DEPTH = 1
+
+
+class LightShaftsDescC(ctypes.Structure):
+    _fields_ = [("enable", ctypes.c_int32), ("steps", ctypes.c_int32), ("density", ctypes.c_float),
+                ("weight", ctypes.c_float), ("decay", ctypes.c_float), ("cam_pos", _F3), ("sun_dir_ws", _F3),
+                ("viewproj", _F16), ("flags", ctypes.c_uint32)]
+
+
 class OccluderC(ctypes.Structure):
     _fields_ = [("mesh_id", ctypes.c_int32), ("model", _F16), ("aabb_min", _F3), ("aabb_max", _F3)]
 
@@ -286,6 +295,8 @@ SIGNATURES = [
     ("shs_canvas_dof", ctypes.c_int, [_P, ctypes.POINTER(CanvasDofDescC), _P, _P, _P, _F, ctypes.c_uint32]),
     ("shs_motion_blur", ctypes.c_int, [_P, ctypes.POINTER(MotionBlurDescC)]),
     ("shs_resolve_motion_blur", ctypes.c_int, [_P, _P, _P]),
+    ("shs_light_shafts", ctypes.c_int, [_P, ctypes.POINTER(LightShaftsDescC)]),
+    ("shs_light_shafts_sun_uv", ctypes.c_int, [_F, _F, _F, _F, ctypes.POINTER(ctypes.c_int32)]),
     ("shs_camera3d", ctypes.c_int, [_F, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _F, _F]),
     ("shs_model_trs", ctypes.c_int, [_F, ctypes.c_float, _F, _F]),
     ("shs_mat4_mul", ctypes.c_int, [_F, _F, _F]),
