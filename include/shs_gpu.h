@@ -586,6 +586,41 @@ int shs_tonemap(shs_ctx *ctx, const shs_tonemap_desc *desc);
  * a shs_tonemap call.  NULL turns it off.  The reference runs PassTonemap as a separate pass
  * (pass_tonemap.hpp:36-83); this only fuses it into the producer. */
 int shs_lib_fuse_tonemap(shs_ctx *ctx, const shs_tonemap_desc *desc);
+/* The scene's sky model behind the meshes: the first branch of PassPBRForward's background
+ * (passes/pass_pbr_forward.hpp:64-73), render_skybox_to_hdr (sky/skybox_renderer.hpp:25-57) over
+ * ProceduralSky::sample (sky/procedural_sky.hpp:22-46) or CubemapSky::sample (sky/cubemap_sky.hpp:39-116).
+ * Every later shs_render_pbr_forward writes, for each pixel no primitive won, (sample(dir), 1) with
+ * dir = normalize(inverse(cam_viewproj) * (ndc, 1, 1) / w - cam_pos), or (0, 0, 0, 1) where |w| < 1e-8 --
+ * from its shading kernel, so the HDR target, a fused tonemap and the present staging hold the sky with no
+ * further pass.  Such a frame ignores SHS_LIB_BG_GRADIENT and clear_hdr; depth and motion clears are
+ * unchanged.  The HDR values are the reference's bit for bit (GLM's operation orders, IEEE / and sqrt, the
+ * cubemap's sRGB decode as the host's std::pow(c / 255, 2.2) values).
+ * Sticky, like shs_lib_fuse_tonemap: a moving camera calls it per frame (cam_viewproj / cam_pos are the
+ * frame's scene.cam); each enqueued camera pass keeps the descriptor it was enqueued with.  NULL or
+ * SHS_SKY_NONE: back to the gradient / clear_hdr.
+ * SHS_ERR_INVALID: an unknown model, a non-finite field, a cam_viewproj whose glm::inverse is not finite,
+ * a zero (or not normalisable) sun direction for SHS_SKY_PROCEDURAL, a face id of SHS_SKY_CUBEMAP that is
+ * 0 or no live shs_texture_upload id.  The reference's CubemapSky returns black when a face fails
+ * Texture2DData::valid(); such a cubemap is not uploaded (as shs_texture_upload): the caller sets no sky
+ * model and a clear_hdr of (0, 0, 0, 1).  Faces may differ in size.  Fields the model does not read
+ * (sun_dir_ws of a cubemap; face_tex, intensity of a procedural sky) are ignored.
+ * shs_texture_release of a face of the context's current sky fails with SHS_ERR_INVALID: set another sky
+ * (or none) first. */
+#define SHS_SKY_NONE 0
+#define SHS_SKY_PROCEDURAL 1
+#define SHS_SKY_CUBEMAP 2
+typedef struct shs_sky_desc {
+    int32_t model;                        /* SHS_SKY_* */
+    float cam_viewproj[16], cam_pos[3];   /* scene.cam.viewproj (column-major) / .pos */
+    float sun_dir_ws[3];                  /* ProceduralSky's constructor argument (normalised by the library) */
+    int32_t face_tex[6];                  /* shs_texture_upload ids: +X,-X,+Y,-Y,+Z,-Z */
+    float intensity;                      /* CubemapSky's intensity */
+} shs_sky_desc;
+int shs_lib_set_sky(shs_ctx *ctx, const shs_sky_desc *desc);
+/* ISkyModel::sample of desc's model for n directions (dirs3: n x 3 floats) into rgb3 (n x 3), through the
+ * sampler the camera pass uses; the camera fields of desc are not read.  The loop body of the reference's
+ * IBL precompute (resources/ibl.hpp:97-203).  Synchronous; the context's sticky sky is left alone. */
+int shs_sky_sample(shs_ctx *ctx, const shs_sky_desc *desc, const float *dirs3, int32_t n, float *rgb3);
 /* Copy the tonemapped targets into caller-owned W*H*4-byte buffers (either may be NULL). */
 int shs_resolve_ldr(shs_ctx *ctx, uint8_t *ldr, uint8_t *present);
 /* Device pointers of the tonemap targets (the pass chain finished first, as shs_lib_device_targets). */
@@ -759,6 +794,8 @@ int shs_group_lights_upload_typed(shs_group *g, const shs_culling_light *cull, c
 /* shs_set_option on every rank's context (e.g. SHS_OPT_SHARD_LAYOUT). */
 int shs_group_set_option(shs_group *g, int option, int64_t value);
 int shs_group_lib_fuse_tonemap(shs_group *g, const shs_tonemap_desc *desc);
+/* shs_lib_set_sky on every rank's context (face_tex: shs_group_texture_upload ids). */
+int shs_group_lib_set_sky(shs_group *g, const shs_sky_desc *desc);
 /* Sharded passes: rank r runs the call with shard_rank = r, shard_count = n (the frame's own shard
  * fields are ignored).  The shadow map is rendered whole on every rank (every rank's PCF reads all of it). */
 int shs_group_light_cull(shs_group *g, const shs_light_cull_desc *desc);

@@ -158,6 +158,7 @@ private:
 
 #if __has_include("shs/pipeline/pass_adapters.hpp")
 #include "shs/pipeline/pass_adapters.hpp"
+#include "shs/sky/cubemap_sky.hpp"
 
 namespace shs_gpu_seams {
 
@@ -204,14 +205,49 @@ private:
     std::unordered_map<const shs::Texture2DData *, int32_t> ids_;
 };
 
-// Shared by the passes of one pipeline: the device context, its meshes and textures, and whether the
-// device shadow map belongs to the current frame.
+// The scene's sky models (sky/sky_model.hpp).  ISkyModel exposes only sample(), and ProceduralSky and
+// CubemapSky keep their parameters private, so the host binds each model to the parameters it was built
+// with, where it creates it; PassPBRForwardGPU looks scene.sky up here and adds the frame's camera.
+class GpuSkies {
+public:
+    explicit GpuSkies(GpuTextures &textures) : textures_(textures) {}
+    // ProceduralSky(sun_dir_ws) (sky/procedural_sky.hpp:22-24); call again after set_sun_direction
+    void bind_procedural(const shs::ISkyModel *sky, const glm::vec3 &sun_dir_ws) {
+        shs_sky_desc d{};
+        d.model = SHS_SKY_PROCEDURAL;
+        std::memcpy(d.sun_dir_ws, glm::value_ptr(sun_dir_ws), 12);
+        skies_[sky] = d;
+    }
+    // CubemapSky(cubemap, intensity) (sky/cubemap_sky.hpp:76-78).  A cubemap that fails CubemapData::valid()
+    // samples black everywhere: the model is bound as SHS_SKY_NONE with a black clear.
+    void bind_cubemap(const shs::ISkyModel *sky, const shs::CubemapData &cubemap, float intensity) {
+        shs_sky_desc d{};
+        d.model = cubemap.valid() ? SHS_SKY_CUBEMAP : SHS_SKY_NONE;
+        for (int k = 0; k < 6 && cubemap.valid(); ++k) d.face_tex[k] = textures_.id(&cubemap.face[(size_t)k]);
+        d.intensity = intensity;
+        skies_[sky] = d;
+    }
+    void unbind(const shs::ISkyModel *sky) { skies_.erase(sky); }
+    const shs_sky_desc *find(const shs::ISkyModel *sky) const {
+        const auto it = skies_.find(sky);
+        return it == skies_.end() ? nullptr : &it->second;
+    }
+
+private:
+    GpuTextures &textures_;
+    std::unordered_map<const shs::ISkyModel *, shs_sky_desc> skies_;
+};
+
+// Shared by the passes of one pipeline: the device context, its meshes, textures and sky models, and
+// whether the device shadow map belongs to the current frame.
 struct GpuPassRuntime {
     Device device;
     GpuMeshes meshes;
     GpuTextures textures;
+    GpuSkies skies;
     bool resolve_shadow_to_host = false;   // also fill RT_ShadowDepth (for CPU consumers: shadow debug)
-    explicit GpuPassRuntime(int device_index = 0) : device(device_index), meshes(device.ctx), textures(device.ctx) {}
+    explicit GpuPassRuntime(int device_index = 0)
+        : device(device_index), meshes(device.ctx), textures(device.ctx), skies(textures) {}
 };
 
 // RenderItem transform, as both passes build it (pass_shadow_map.hpp:56-64, pass_pbr_forward.hpp:136-141).
@@ -304,8 +340,18 @@ public:
         auto *motion = rt_motion_.valid() ? static_cast<shs::RT_ColorDepthMotion *>(rtr.get(rt_motion_)) : nullptr;
         auto *shadow = rt_shadow_.valid() ? static_cast<shs::RT_ShadowDepth *>(rtr.get(rt_shadow_)) : nullptr;
         const bool depth_motion = motion && motion->w == hdr->w && motion->h == hdr->h;
-        // The GPU pass draws the no-sky gradient background (:64-85); a sky model is outside its scope.
-        if (scene.sky) unsupported("sky model backgrounds");
+        // The background (:64-85): render_skybox_to_hdr of the scene's sky model, bound in rt_->skies with
+        // the parameters it was created with, else the gradient.  A model nobody bound fails loudly.
+        shs_sky_desc sky{};
+        bool black_sky = false;   // an invalid cubemap: CubemapSky::sample returns vec3(0)
+        if (scene.sky) {
+            const shs_sky_desc *bound = rt_->skies.find(scene.sky);
+            if (!bound) unsupported("sky models not bound with GpuPassRuntime::skies");
+            sky = *bound;
+            black_sky = sky.model == SHS_SKY_NONE;
+            std::memcpy(sky.cam_viewproj, glm::value_ptr(scene.cam.viewproj), 64);
+            std::memcpy(sky.cam_pos, glm::value_ptr(scene.cam.pos), 12);
+        }
 
         int32_t program = SHS_PROGRAM_PBR_MR;
         if (fp.shading_model == shs::ShadingModel::BlinnPhong) program = SHS_PROGRAM_BLINN_PHONG;
@@ -377,10 +423,12 @@ public:
         f.height = hdr->h;
         f.shard_rank = 0;
         f.shard_count = 1;
-        f.flags = SHS_LIB_BG_GRADIENT | (depth_motion ? SHS_LIB_DEPTH_MOTION : 0u);
+        f.flags = (black_sky ? 0u : SHS_LIB_BG_GRADIENT) | (depth_motion ? SHS_LIB_DEPTH_MOTION : 0u);
+        f.clear_hdr[3] = 1.0f;   // black_sky: (0, 0, 0, 1)
         f.zn = depth_motion ? motion->zn : 0.1f;
         f.zf = depth_motion ? motion->zf : 1000.0f;
         shs_ctx *dctx = rt_->device.ctx;
+        check(dctx, shs_lib_set_sky(dctx, scene.sky ? &sky : nullptr));
         check(dctx, shs_render_pbr_forward(dctx, &f, draws_.data(), static_cast<int32_t>(draws_.size())));
         check(dctx, shs_resolve_lib(dctx, &hdr->color.data[0].r, depth_motion ? motion->depth.data.data() : nullptr,
                                     depth_motion ? &motion->motion.data[0].x : nullptr));

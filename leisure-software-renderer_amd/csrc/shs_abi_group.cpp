@@ -278,6 +278,11 @@ int shs_group_lib_fuse_tonemap(shs_group *g, const shs_tonemap_desc *desc) {
     return for_ranks(g, [&](int, shs_ctx *c) { return shs_lib_fuse_tonemap(c, desc); });
 }
 
+int shs_group_lib_set_sky(shs_group *g, const shs_sky_desc *desc) {
+    if (!g) return SHS_ERR_INVALID;
+    return for_ranks(g, [&](int, shs_ctx *c) { return shs_lib_set_sky(c, desc); });
+}
+
 int shs_group_light_cull(shs_group *g, const shs_light_cull_desc *desc) {
     if (!g || !desc) return SHS_ERR_INVALID;
     const int n = (int)g->ctx.size();

@@ -250,6 +250,60 @@ uint64_t region_key(const shs_dev::ShardRegion &g) {
            ((uint64_t)(uint16_t)g.y1 << 48);
 }
 
+// srgb_to_linear_rgb (builtin_shaders.hpp:25-31) and srgb_to_linear_approx (cubemap_sky.hpp:39-45) with the
+// host's std::pow: the table the texture and sky samplers read
+int ensure_srgb_lut(shs_ctx *ctx) {
+    if (ctx->srgb_lut.p) return SHS_OK;
+    float lut[256];
+    for (int i = 0; i < 256; ++i) lut[i] = std::pow((float)i / 255.0f, 2.2f);
+    if (ensure(ctx, ctx->srgb_lut, 256)) return SHS_ERR_HIP;
+    HIP_TRY(ctx, hipMemcpy(ctx->srgb_lut.p, lut, sizeof lut, hipMemcpyHostToDevice));
+    return SHS_OK;
+}
+
+// shs_sky_desc -> the kernels' SkyParams.  camera: with the unprojection's fields (shs_lib_set_sky), which
+// shs_sky_sample does not read.
+int build_sky(shs_ctx *ctx, const shs_sky_desc &d, bool camera, shs_dev::SkyParams &o) {
+    std::memset(&o, 0, sizeof o);
+    if (d.model != SHS_SKY_PROCEDURAL && d.model != SHS_SKY_CUBEMAP) { ctx->err = "sky model: SHS_SKY_PROCEDURAL or SHS_SKY_CUBEMAP"; return SHS_ERR_INVALID; }
+    o.model = d.model == SHS_SKY_PROCEDURAL ? shs_dev::SKY_PROCEDURAL : shs_dev::SKY_CUBEMAP;
+    if (camera) {
+        bool finite = true;
+        for (float v : d.cam_viewproj) finite = finite && std::isfinite(v);
+        for (float v : d.cam_pos) finite = finite && std::isfinite(v);
+        if (!finite) { ctx->err = "sky cam_viewproj / cam_pos must be finite"; return SHS_ERR_INVALID; }
+        shs_host::inverse(d.cam_viewproj, o.inv_vp);   // skybox_renderer.hpp:29
+        for (float v : o.inv_vp) finite = finite && std::isfinite(v);
+        if (!finite) { ctx->err = "sky cam_viewproj has no finite inverse"; return SHS_ERR_INVALID; }
+        for (int i = 0; i < 3; ++i) o.cam[i] = d.cam_pos[i];
+    }
+    if (d.model == SHS_SKY_PROCEDURAL) {
+        if (!(std::isfinite(d.sun_dir_ws[0]) && std::isfinite(d.sun_dir_ws[1]) && std::isfinite(d.sun_dir_ws[2]))) {
+            ctx->err = "sky sun_dir_ws must be finite";
+            return SHS_ERR_INVALID;
+        }
+        // procedural_sky.hpp:23
+        const shs_host::vec3 s = shs_host::gnormalize(shs_host::vec3{d.sun_dir_ws[0], d.sun_dir_ws[1], d.sun_dir_ws[2]});
+        if (!(std::isfinite(s.x) && std::isfinite(s.y) && std::isfinite(s.z))) { ctx->err = "sky sun_dir_ws cannot be normalised"; return SHS_ERR_INVALID; }
+        o.sun[0] = s.x; o.sun[1] = s.y; o.sun[2] = s.z;
+    } else {
+        if (!std::isfinite(d.intensity)) { ctx->err = "sky intensity must be finite"; return SHS_ERR_INVALID; }
+        o.intensity = d.intensity;
+        for (int k = 0; k < 6; ++k) {
+            const int32_t id = d.face_tex[k];
+            if (id <= 0 || id > (int32_t)ctx->textures.size() || !ctx->textures[(size_t)id - 1].live) {
+                ctx->err = "sky face_tex (not a live texture id)";
+                return SHS_ERR_INVALID;
+            }
+            const Texture &t = ctx->textures[(size_t)id - 1];
+            o.face[k] = t.texels;
+            o.fw[k] = t.w;
+            o.fh[k] = t.h;
+        }
+    }
+    return SHS_OK;
+}
+
 // Enqueue one pass (w.last_fp / w.last_draws describe it): workspace sizing, draw upload, the two
 // kernels.  shadow: PassShadowMap's depth pass into ctx->shadow_map.
 int enqueue_pass(shs_ctx *ctx, Work &w, bool shadow) {
@@ -293,12 +347,7 @@ int enqueue_pass(shs_ctx *ctx, Work &w, bool shadow) {
     for (const auto &d : w.last_draws) textured = textured || d.tex != nullptr;
     if (textured && !shadow) {
         if (ensure(ctx, w.uvw, 2 * n_slots)) return SHS_ERR_HIP;
-        if (!ctx->srgb_lut.p) {   // srgb_to_linear_rgb (builtin_shaders.hpp:25-31) with the host's std::pow
-            float lut[256];
-            for (int i = 0; i < 256; ++i) lut[i] = std::pow((float)i / 255.0f, 2.2f);
-            if (ensure(ctx, ctx->srgb_lut, 256)) return SHS_ERR_HIP;
-            HIP_TRY(ctx, hipMemcpy(ctx->srgb_lut.p, lut, sizeof lut, hipMemcpyHostToDevice));
-        }
+        if (ensure_srgb_lut(ctx)) return SHS_ERR_HIP;
     }
     // every slot enters the large-primitive queue at most once
     if (ensure(ctx, w.bigq, n_slots) || ensure(ctx, w.bigpre, n_slots)) return SHS_ERR_HIP;
@@ -568,8 +617,9 @@ int enqueue_pass(shs_ctx *ctx, Work &w, bool shadow) {
         for (const auto &d : w.last_draws)   // any typed Forward+ draw: the kernel with the light models
             if (d.program == SHS_PROGRAM_FORWARD_PLUS_TYPED) prog = SHS_PROGRAM_FORWARD_PLUS_TYPED;
         const bool wide = fp.count <= 1;   // the whole frame's build (PBR: 5 waves) or a sharded rank's
-        int &res = ctx->lib_resolve_resident[(prog == 5 ? 0 : prog == 0 ? 1 : prog == 6 ? 3 : 2) * 2 + wide];
-        if (res <= 0) res = shs_internal::lib_resolve_resident_blocks(ctx->device, prog, wide);
+        const bool sky = fp.sky.model != shs_dev::SKY_NONE;   // the kernel's sky builds
+        int &res = ctx->lib_resolve_resident[(sky ? 8 : 0) + (prog == 5 ? 0 : prog == 0 ? 1 : prog == 6 ? 3 : 2) * 2 + wide];
+        if (res <= 0) res = shs_internal::lib_resolve_resident_blocks(ctx->device, prog, wide, sky);
         const int rgrid = std::max(1, std::min(fp.n_owned_rt, res));
         HIP_TRY(ctx, shs_internal::launch_lib_resolve(fp, fb, prog, wide, rgrid, ctx->stream));
         HIP_TRY(ctx, hipEventRecord(w.resolve_ev, ctx->stream));
@@ -890,12 +940,56 @@ int shs_texture_upload(shs_ctx *ctx, const uint8_t *rgba, int32_t w, int32_t h, 
 int shs_texture_release(shs_ctx *ctx, int32_t tex_id) {
     if (!ctx || tex_id <= 0 || tex_id > (int32_t)ctx->textures.size() || !ctx->textures[(size_t)tex_id - 1].live)
         return SHS_ERR_INVALID;
+    if (ctx->sky.model == shs_dev::SKY_CUBEMAP)
+        for (int32_t id : ctx->sky_face_tex)
+            if (id == tex_id) { ctx->err = "texture is a face of the current sky (shs_lib_set_sky another first)"; return SHS_ERR_INVALID; }
     if (set_dev(ctx)) return SHS_ERR_HIP;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->setup_stream));
     Texture &t = ctx->textures[(size_t)tex_id - 1];
     HIP_TRY(ctx, hipFree(t.texels));
     t = Texture{};
+    return SHS_OK;
+}
+
+int shs_lib_set_sky(shs_ctx *ctx, const shs_sky_desc *desc) {
+    if (!ctx) return SHS_ERR_INVALID;
+    if (!desc || desc->model == SHS_SKY_NONE) {
+        ctx->sky = shs_dev::SkyParams{};
+        return SHS_OK;
+    }
+    shs_dev::SkyParams sk;
+    const int rc = build_sky(ctx, *desc, true, sk);
+    if (rc) return rc;
+    if (sk.model == shs_dev::SKY_CUBEMAP) {
+        if (set_dev(ctx)) return SHS_ERR_HIP;
+        if (ensure_srgb_lut(ctx)) return SHS_ERR_HIP;
+    }
+    ctx->sky = sk;
+    for (int k = 0; k < 6; ++k) ctx->sky_face_tex[k] = desc->face_tex[k];
+    return SHS_OK;
+}
+
+int shs_sky_sample(shs_ctx *ctx, const shs_sky_desc *desc, const float *dirs3, int32_t n, float *rgb3) {
+    if (!ctx || !desc || n < 0 || (n > 0 && (!dirs3 || !rgb3))) return SHS_ERR_INVALID;
+    shs_dev::SkyParams sk;
+    const int rc = build_sky(ctx, *desc, false, sk);
+    if (rc) return rc;
+    if (n == 0) return SHS_OK;
+    if (set_dev(ctx)) return SHS_ERR_HIP;
+    if (ensure_srgb_lut(ctx)) return SHS_ERR_HIP;
+    float *buf = nullptr;   // n directions, then n colours
+    const size_t bytes = (size_t)n * 3 * sizeof(float);
+    HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&buf), 2 * bytes));
+    hipError_t e = hipMemcpy(buf, dirs3, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = shs_internal::launch_sky_sample(sk, ctx->srgb_lut.p, buf, n, buf + (size_t)n * 3, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e == hipSuccess) e = hipMemcpy(rgb3, buf + (size_t)n * 3, bytes, hipMemcpyDeviceToHost);
+    (void)hipFree(buf);
+    if (e != hipSuccess) {
+        ctx->err = hipGetErrorString(e);
+        return SHS_ERR_HIP;
+    }
     return SHS_OK;
 }
 
@@ -1157,6 +1251,7 @@ int shs_render_pbr_forward(shs_ctx *ctx, const shs_lib_frame *frame, const shs_l
     }
     fp.zn = f.zn; fp.zf = f.zf; fp.zspan = f.zf - f.zn;
     for (int i = 0; i < 4; ++i) fp.clear[i] = f.clear_hdr[i];
+    fp.sky = ctx->sky;   // kept in wk.last_fp: a re-issue replays the sky this pass was enqueued with
     fp.sm_w = ctx->shadow_w; fp.sm_h = ctx->shadow_h;
     if (ctx->have_cull) {
         const shs_dev::LightCullParams &c = ctx->cull;

@@ -272,8 +272,12 @@ struct shs_ctx {
     const uint32_t *blkcov_zero_at = nullptr;
     size_t blkcov_zero_cap = 0;
     uint64_t blkcov_zero_key = 0;
-    int lib_resolve_resident[8] = {};   // resident k_lib_resolve workgroups ((Forward+, PBR, mixed, typed) x
-                                        // (sharded rank's build, whole frame's build))
+    int lib_resolve_resident[16] = {};  // resident k_lib_resolve workgroups ((Forward+, PBR, mixed, typed) x
+                                        // (sharded rank's build, whole frame's build)), then the sky builds'
+    // shs_lib_set_sky: the sky model later camera passes paint behind the meshes (model SKY_NONE: none; each
+    // pass's LibFrameParams keeps its own copy), and the texture ids of a cubemap's faces (shs_texture_release)
+    shs_dev::SkyParams sky{};
+    int32_t sky_face_tex[6] = {};
     DevBuf<float> srgb_lut;               // srgb_to_linear_rgb table (texture sampling)
     DevBuf<float> lib_depth;
     DevBuf<float2> lib_motion;

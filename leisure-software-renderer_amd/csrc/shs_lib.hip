@@ -31,8 +31,10 @@
 //                 that holds one.
 //   k_lib_resolve (camera pass) every owned pixel: the winner re-evaluated, its varyings interpolated,
 //                 the fragment program run (+ the fused PassTonemap), HDR colour, depth, motion written;
-//                 pixels without a winner get the clear values, so every output byte is written exactly
-//                 once per pass.
+//                 pixels without a winner get the clear values -- or, in the kernel's SKY builds, the scene's
+//                 sky model as render_skybox_to_hdr paints it (sky/skybox_renderer.hpp:25-57) -- so every
+//                 output byte is written exactly once per pass.
+// Beside the passes: k_sky_sample, ISkyModel::sample for an array of directions (shs_sky_sample).
 // Primitive order: input triangle t's fan triangle k has submission index t*16 + k (a clipped
 // triangle yields at most 7 fans in exact arithmetic, MAX_POLY - 2 with rounding); fan 0 lives in
 // slot t, fans >= 1 in extra slots from xbase[t].  t is the submission index (draw base + MeshData
@@ -1775,9 +1777,10 @@ __device__ f3 forward_plus(const LibFrameParams &fp, const LibBuffers &fb, const
 // srgb_to_linear_rgb (:25-31) texels; the sRGB decode is the host-computed table of the reference's
 // own std::pow values (bit-identical), the lerps glm::mix's x * (1 - a) + y * a.  Indices are clamped
 // into the texture, which only changes non-finite UVs (where the reference reads out of bounds).
-__device__ __forceinline__ f3 srgb_texel(const LibBuffers &fb, uint32_t c) {
-    return f3{fb.srgb_lut[c & 0xffu], fb.srgb_lut[(c >> 8) & 0xffu], fb.srgb_lut[(c >> 16) & 0xffu]};
+__device__ __forceinline__ f3 srgb_texel(const float *lut, uint32_t c) {
+    return f3{lut[c & 0xffu], lut[(c >> 8) & 0xffu], lut[(c >> 16) & 0xffu]};
 }
+__device__ __forceinline__ f3 srgb_texel(const LibBuffers &fb, uint32_t c) { return srgb_texel(fb.srgb_lut, c); }
 
 __device__ __noinline__ f3 sample_base_color(const LibBuffers &fb, const LibDrawGPU &dr, float uvx, float uvy) {
     const float u = uvx - floorf(uvx);
@@ -1870,6 +1873,91 @@ __device__ __forceinline__ float4 bg_color(const LibFrameParams &fp, int y) {
     return make_float4(0.06f + 0.08f * t, 0.08f + 0.10f * t, 0.12f + 0.12f * t, 1.0f);
 }
 
+// ---- the scene's sky model (sky/procedural_sky.hpp, cubemap_sky.hpp, skybox_renderer.hpp) ----
+// sample_face_bilinear_linear (cubemap_sky.hpp:47-71) on face k: clamp, (w - 1) scale, floor, min(x0 + 1, w - 1),
+// srgb_to_linear_approx (:39-45) as the host's std::pow table (the base-colour sampler's), three glm::mix.
+// The face's uniforms are picked by compares (k is per lane).  Indices are clamped into the face, which only
+// changes a non-finite u or v (where the reference reads out of bounds).
+__device__ __forceinline__ f3 sky_face_bilinear(const SkyParams &sk, const float *lut, int k, float u, float v) {
+    const uint32_t *tex = sk.face[0];
+    int w = sk.fw[0], h = sk.fh[0];
+#pragma unroll
+    for (int i = 1; i < 6; ++i)
+        if (k == i) { tex = sk.face[i]; w = sk.fw[i]; h = sk.fh[i]; }
+    u = g_clamp(u, 0.0f, 1.0f);
+    v = g_clamp(v, 0.0f, 1.0f);
+    const float fx = u * (float)(w - 1);
+    const float fy = v * (float)(h - 1);
+    const int x0 = min(max((int)floorf(fx), 0), w - 1);
+    const int y0 = min(max((int)floorf(fy), 0), h - 1);
+    const int x1 = min(x0 + 1, w - 1);
+    const int y1 = min(y0 + 1, h - 1);
+    const float tx = fx - (float)x0;
+    const float ty = fy - (float)y0;
+    const uint32_t *row0 = tex + (size_t)y0 * w, *row1 = tex + (size_t)y1 * w;
+    const uint32_t t00 = row0[x0], t10 = row0[x1], t01 = row1[x0], t11 = row1[x1];
+    return mix3(mix3(srgb_texel(lut, t00), srgb_texel(lut, t10), tx), mix3(srgb_texel(lut, t01), srgb_texel(lut, t11), tx), ty);
+}
+
+// ISkyModel::sample of the bound model: ProceduralSky (procedural_sky.hpp:26-46) or CubemapSky
+// (cubemap_sky.hpp:80-116; its cubemap is valid, shs_lib_set_sky rejects any other).
+__device__ __forceinline__ f3 sky_sample(const SkyParams &sk, const float *lut, f3 dir) {
+    if (sk.model == SKY_PROCEDURAL) {
+        const f3 d = normalize3(dir);
+        const float t = g_clamp(d.y * 0.5f + 0.5f, 0.0f, 1.0f);
+        f3 sky = mix3(f3{0.30f, 0.60f, 1.00f}, f3{0.05f, 0.20f, 0.50f}, t);   // horizon, zenith
+        const float sun_dot = dot3(d, f3{-sk.sun[0], -sk.sun[1], -sk.sun[2]});
+        if (sun_dot > 0.9998f) {
+            sky = f3{15.0f, 15.0f, 15.0f};
+        } else if (sun_dot > 0.9990f) {
+            const float glow = (sun_dot - 0.9990f) / (0.9998f - 0.9990f);
+            sky = mix3(sky, f3{10.0f, 8.0f, 4.0f}, glow);
+        }
+        return sky;
+    }
+    const float len = sqrtf(dot3(dir, dir));   // glm::length
+    if (len < 1e-8f) return f3{0.0f, 0.0f, 0.0f};
+    const f3 d = {dir.x / len, dir.y / len, dir.z / len};
+    const float ax = fabsf(d.x), ay = fabsf(d.y), az = fabsf(d.z);
+    int face;
+    float u, v;
+    if (ax >= ay && ax >= az) {
+        if (d.x > 0.0f) { face = 0; u = -d.z / ax; v = d.y / ax; }
+        else            { face = 1; u = d.z / ax; v = d.y / ax; }
+    } else if (ay >= ax && ay >= az) {
+        if (d.y > 0.0f) { face = 2; u = d.x / ay; v = -d.z / ay; }
+        else            { face = 3; u = d.x / ay; v = d.z / ay; }
+    } else {
+        if (d.z > 0.0f) { face = 4; u = d.x / az; v = d.y / az; }
+        else            { face = 5; u = -d.x / az; v = d.y / az; }
+    }
+    u = 0.5f * (u + 1.0f);
+    v = 0.5f * (v + 1.0f);
+    return sc3(sky_face_bilinear(sk, lut, face, u, v), sk.intensity);
+}
+
+// render_skybox_to_hdr's pixel (skybox_renderer.hpp:36-54); y is the HDR target's own row
+__device__ __forceinline__ float4 sky_pixel(const LibFrameParams &fp, const float *lut, int x, int y) {
+    const SkyParams &sk = fp.sky;
+    const float ndc_y = (2.0f * ((float)y + 0.5f) / (float)fp.H) - 1.0f;
+    const float ndc_x = (2.0f * ((float)x + 0.5f) / (float)fp.W) - 1.0f;
+    const f4 world = m4v(sk.inv_vp, f4{ndc_x, ndc_y, 1.0f, 1.0f});
+    if (fabsf(world.w) < 1e-8f) return make_float4(0.0f, 0.0f, 0.0f, 1.0f);
+    const f3 p = {world.x / world.w, world.y / world.w, world.z / world.w};
+    const f3 c = sky_sample(sk, lut, normalize3(sub3(p, f3{sk.cam[0], sk.cam[1], sk.cam[2]})));
+    return make_float4(c.x, c.y, c.z, 1.0f);
+}
+
+// shs_sky_sample: n directions through the model's sample()
+__global__ __launch_bounds__(256) void k_sky_sample(SkyParams sk, const float *lut, const float *dirs, int n, float *rgb) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const f3 c = sky_sample(sk, lut, f3{dirs[3 * (size_t)i], dirs[3 * (size_t)i + 1], dirs[3 * (size_t)i + 2]});
+    rgb[3 * (size_t)i] = c.x;
+    rgb[3 * (size_t)i + 1] = c.y;
+    rgb[3 * (size_t)i + 2] = c.z;
+}
+
 constexpr int LIB_PAIR_WORDS = LIB_CHUNK * LIB_RTW * LIB_RTH / 64;   // pair-start bitmap words
 constexpr int LIB_MAX_STATIC = 256;                                  // static work items per raster workgroup
 
@@ -1918,7 +2006,7 @@ __device__ __forceinline__ void shade_px(const LibFrameParams &fp, const LibBuff
 
 // Resolve one pixel of a tile (one thread): the winner of the key array is re-evaluated with the
 // identical arithmetic, shaded and written; pixels without a winner get the clear values.
-template <bool SHADOW, int PROG = -1>
+template <bool SHADOW, int PROG = -1, bool SKY = false>
 __device__ __forceinline__ float4 lib_resolve(const LibFrameParams &fp, const LibBuffers &fb, unsigned long long key, int px,
                                               int py, bool &covered, const LtWave &st = LtWave{}) {
     covered = key != KEY_EMPTY && px < fp.W && py < fp.H;
@@ -1928,7 +2016,8 @@ __device__ __forceinline__ float4 lib_resolve(const LibFrameParams &fp, const Li
         fb.depth[o] = covered ? __uint_as_float((uint32_t)(key >> 32) & 0x7fffffffu) : 1.0f;
         return make_float4(0.f, 0.f, 0.f, 0.f);
     }
-    float4 color = bg_color(fp, py);
+    float4 color = SKY ? make_float4(0.f, 0.f, 0.f, 0.f) : bg_color(fp, py);
+    if (SKY && !covered) color = sky_pixel(fp, fb.srgb_lut, px, py);   // (a covered pixel's colour is the winner's)
     float depth = 1.0f;
     float2 mv = make_float2(0.0f, 0.0f);
     if (covered) {
@@ -2963,7 +3052,7 @@ void k_lib_raster(LibFrameParams fp, LibBuffers fb) {
 // sharded rank's, where the 5-wave build measured +4 % per rank frame at 8 ranks and the 3-wave one -4 %
 // against 4 waves (profiles/r06_resolve_waves_ab.txt).  (-DSHS_RESOLVE_WAVES_FP / _PBR / _FP_SHARD / _PBR_SHARD override:
 // timing experiments; the Forward+ kernel has one build unless _FP_SHARD differs.)
-template <int PROG, bool WIDE = false>
+template <int PROG, bool WIDE = false, bool SKY = false>
 __global__ __launch_bounds__(256, PROG == 5 ? (WIDE ? SHS_RESOLVE_WAVES_FP : SHS_RESOLVE_WAVES_FP_SHARD)
                                   : PROG == 0 ? (WIDE ? SHS_RESOLVE_WAVES_PBR : SHS_RESOLVE_WAVES_PBR_SHARD)
                                   : PROG == 6 ? SHS_RESOLVE_WAVES_TYPED : 3)
@@ -3035,7 +3124,7 @@ void k_lib_resolve(LibFrameParams fp, LibBuffers fb) {
             }
         }
         bool covered;
-        const float4 c = lib_resolve<false, PROG>(fp, fb, key, px, py, covered, lw);
+        const float4 c = lib_resolve<false, PROG, SKY>(fp, fb, key, px, py, covered, lw);
         const uint64_t cm = __ballot(covered);
         if (lane == 0 && cm) atomicAdd(&s_cov, (uint32_t)__popcll(cm));
         if (fb.tm_thr && inb) {   // fused PassTonemap of this pixel's HDR value
@@ -3112,18 +3201,30 @@ int lib_raster_resident_blocks(int device, bool shadow, bool shallow) {
 #define SHS_RESOLVE_KERNEL(prog, wide) \
     (prog == 5 ? SHS_RESOLVE_FP(wide) : prog == 0 ? ((wide) ? k_lib_resolve<0, true> : k_lib_resolve<0>) \
      : prog == 6 ? k_lib_resolve<6> : k_lib_resolve<-1>)
+// ... and the same classes with a sky model behind the meshes (fp.sky)
+#define SHS_RESOLVE_SKY_KERNEL(prog, wide) \
+    (prog == 5 ? k_lib_resolve<5, true, true> : prog == 0 ? ((wide) ? k_lib_resolve<0, true, true> : k_lib_resolve<0, false, true>) \
+     : prog == 6 ? k_lib_resolve<6, false, true> : k_lib_resolve<-1, false, true>)
 
-int lib_resolve_resident_blocks(int device, int prog, bool wide) {
+int lib_resolve_resident_blocks(int device, int prog, bool wide, bool sky) {
     int cus = 0, per_cu = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) cus = 256;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, SHS_RESOLVE_KERNEL(prog, wide), 256, 0) != hipSuccess || per_cu <= 0)
+    const hipError_t e = sky ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, SHS_RESOLVE_SKY_KERNEL(prog, wide), 256, 0)
+                             : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, SHS_RESOLVE_KERNEL(prog, wide), 256, 0);
+    if (e != hipSuccess || per_cu <= 0)
         per_cu = 2;
     (void)hipGetLastError();
     return cus * per_cu;
 }
 
 hipError_t launch_lib_resolve(const LibFrameParams &fp, const LibBuffers &fb, int prog, bool wide, int grid, hipStream_t s) {
-    hipLaunchKernelGGL(SHS_RESOLVE_KERNEL(prog, wide), dim3(std::max(grid, 1)), dim3(256), 0, s, fp, fb);
+    if (fp.sky.model != SKY_NONE) hipLaunchKernelGGL(SHS_RESOLVE_SKY_KERNEL(prog, wide), dim3(std::max(grid, 1)), dim3(256), 0, s, fp, fb);
+    else hipLaunchKernelGGL(SHS_RESOLVE_KERNEL(prog, wide), dim3(std::max(grid, 1)), dim3(256), 0, s, fp, fb);
+    return hipGetLastError();
+}
+
+hipError_t launch_sky_sample(const SkyParams &sk, const float *lut, const float *dirs, int n, float *rgb, hipStream_t s) {
+    hipLaunchKernelGGL(k_sky_sample, dim3((n + 255) / 256), dim3(256), 0, s, sk, lut, dirs, n, rgb);
     return hipGetLastError();
 }
 

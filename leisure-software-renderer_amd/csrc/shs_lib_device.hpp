@@ -128,6 +128,19 @@ constexpr uint32_t LOV_SPILL = 1u, LOV_EXTRA = 2u;
 // Row spans of a footprint shadow pass (LibFrameParams::span): maps up to 64 bin tiles (2,048 texels) high.
 constexpr int LIB_SPAN_ROWS = 64;
 
+// The scene's sky model (shs_lib_set_sky): what render_skybox_to_hdr (sky/skybox_renderer.hpp:25-57) and
+// the model's sample() read.  Face k of a cubemap (+X,-X,+Y,-Y,+Z,-Z) is face[k], fw[k] x fh[k] RGBA8 texels.
+constexpr int SKY_NONE = 0, SKY_PROCEDURAL = 1, SKY_CUBEMAP = 2;
+struct SkyParams {
+    int32_t model;                   // SKY_*
+    float intensity;                 // CubemapSky
+    float inv_vp[16];                // glm::inverse(scene.cam.viewproj), computed on the host
+    float cam[3];                    // scene.cam.pos
+    float sun[3];                    // ProceduralSky's sun_direction_ws_ (normalised by the host)
+    int32_t fw[6], fh[6];
+    const uint32_t *face[6];
+};
+
 struct LibFrameParams {
     int32_t W, H;
     int32_t rank, count;             // shard ownership of 32x32 bin tiles (tile % count == rank, or reg)
@@ -160,6 +173,8 @@ struct LibFrameParams {
     ShardRegion reg;                 // count > 1 with reg.on: this rank's rectangle of bin tiles
     int32_t span_rows;               // shadow pass of a footprint (round 6): > 0 -- per bin-tile row y < span_rows
     uint32_t span[LIB_SPAN_ROWS];    //   the bin columns x0 | x1 << 16 it renders (x1 < x0: none); 0 -- all of reg
+    SkyParams sky;                   // camera pass: model != SKY_NONE -- the background of pixels without a winner
+                                     // (k_lib_resolve's SKY builds; flags' LF_GRADIENT and clear[] are ignored)
 };
 
 struct LibBuffers {

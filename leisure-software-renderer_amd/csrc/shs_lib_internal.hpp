@@ -17,8 +17,12 @@ hipError_t launch_lib_raster(const shs_dev::LibFrameParams &fp, const shs_dev::L
                              int grid, hipStream_t s);
 // The camera pass's shading: every owned pixel's winner (fb.keys) shaded into hdr / depth / motion.
 // prog: the program every draw of the pass runs (5 Forward+, 0 PBR: specialised kernels) or -1.
-// CUs x occupancy of k_lib_resolve<prog> (wide: the whole frame's build, else a sharded rank's)
-int lib_resolve_resident_blocks(int device, int prog, bool wide);
+// CUs x occupancy of k_lib_resolve<prog> (wide: the whole frame's build, else a sharded rank's; sky: the
+// builds launch_lib_resolve takes when fp.sky names a model)
+int lib_resolve_resident_blocks(int device, int prog, bool wide, bool sky);
 hipError_t launch_lib_resolve(const shs_dev::LibFrameParams &fp, const shs_dev::LibBuffers &fb, int prog, bool wide,
                               int grid, hipStream_t s);
+// shs_sky_sample: n directions (device, 3 floats each) through the model's sample() into rgb
+hipError_t launch_sky_sample(const shs_dev::SkyParams &sk, const float *lut, const float *dirs, int n, float *rgb,
+                             hipStream_t s);
 }  // namespace shs_internal

@@ -286,6 +286,29 @@ class Context:
         self._check(self._lib.shs_lib_fuse_tonemap(self._h, ctypes.byref(d)))
         self._tonemap_flags = d.flags
 
+    def _sky_desc(self, sky):
+        faces = sky.faces if sky.model == _abi.SKY_CUBEMAP and sky.faces is not None else None
+        return sky.desc(None if faces is None else [self.upload_texture(t) for t in faces])
+
+    def set_sky(self, sky=None):
+        """shs_lib_set_sky: later camera passes paint lib_path.LibSky `sky` behind the meshes (sticky; a moving
+        camera sets it per frame); None: back to the gradient / clear_hdr."""
+        if sky is None or sky.model == _abi.SKY_NONE:
+            self._check(self._lib.shs_lib_set_sky(self._h, None))
+            return
+        d = self._sky_desc(sky)
+        self._check(self._lib.shs_lib_set_sky(self._h, ctypes.byref(d)))
+
+    def sky_sample(self, sky, dirs):
+        """shs_sky_sample: ISkyModel::sample of `sky` for dirs float32 [n, 3] -> rgb float32 [n, 3]."""
+        dirs = np.ascontiguousarray(np.asarray(dirs, np.float32).reshape(-1, 3))
+        rgb = np.zeros_like(dirs)
+        d = self._sky_desc(sky)
+        fp = ctypes.POINTER(ctypes.c_float)
+        self._check(self._lib.shs_sky_sample(self._h, ctypes.byref(d), dirs.ctypes.data_as(fp), dirs.shape[0],
+                                             rgb.ctypes.data_as(fp)))
+        return rgb
+
     def resolve_ldr(self):
         """-> (ldr uint8 [H, W, 4] rows y up or None, present uint8 [H, W, 4] rows top-down or None)."""
         f = self._lib_frame

@@ -159,6 +159,14 @@ class LightShaftsDescC(ctypes.Structure):
                 ("viewproj", _F16), ("flags", ctypes.c_uint32)]
 
 
+SKY_NONE, SKY_PROCEDURAL, SKY_CUBEMAP = 0, 1, 2
+
+
+class SkyDescC(ctypes.Structure):
+    _fields_ = [("model", ctypes.c_int32), ("cam_viewproj", _F16), ("cam_pos", _F3), ("sun_dir_ws", _F3),
+                ("face_tex", ctypes.c_int32 * 6), ("intensity", ctypes.c_float)]
+
+
 class OccluderC(ctypes.Structure):
     _fields_ = [("mesh_id", ctypes.c_int32), ("model", _F16), ("aabb_min", _F3), ("aabb_max", _F3)]
 
@@ -281,6 +289,8 @@ SIGNATURES = [
     ("shs_lib_debug_setup_timeline", ctypes.c_int, [_P, _P, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),
     ("shs_tonemap", ctypes.c_int, [_P, ctypes.POINTER(TonemapDescC)]),
     ("shs_lib_fuse_tonemap", ctypes.c_int, [_P, ctypes.POINTER(TonemapDescC)]),
+    ("shs_lib_set_sky", ctypes.c_int, [_P, ctypes.POINTER(SkyDescC)]),
+    ("shs_sky_sample", ctypes.c_int, [_P, ctypes.POINTER(SkyDescC), _F, ctypes.c_int32, _F]),
     ("shs_resolve_ldr", ctypes.c_int, [_P, _P, _P]),
     ("shs_ldr_device_targets", ctypes.c_int, [_P, ctypes.POINTER(_P), ctypes.POINTER(_P)]),
     ("shs_tonemap_thresholds", ctypes.c_int, [ctypes.c_float, _F]),
@@ -350,6 +360,7 @@ SIGNATURES = [
                                                      ctypes.c_int32]),
     ("shs_group_set_option", ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int64]),
     ("shs_group_lib_fuse_tonemap", ctypes.c_int, [_P, ctypes.POINTER(TonemapDescC)]),
+    ("shs_group_lib_set_sky", ctypes.c_int, [_P, ctypes.POINTER(SkyDescC)]),
     ("shs_group_light_cull", ctypes.c_int, [_P, ctypes.POINTER(LightCullDescC)]),
     ("shs_group_render_shadow_map", ctypes.c_int, [_P, ctypes.c_int32, ctypes.c_int32, _F, ctypes.POINTER(ShadowCasterC),
                                                    ctypes.c_int32, _F]),

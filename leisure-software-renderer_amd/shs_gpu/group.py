@@ -140,6 +140,15 @@ class Group:
         for r in self.ranks:
             r._tonemap_flags = d.flags
 
+    def set_sky(self, sky=None):
+        """shs_group_lib_set_sky: Context.set_sky on every rank (a cubemap's faces go through upload_texture)."""
+        if sky is None or sky.model == _abi.SKY_NONE:
+            self._check(self._lib.shs_group_lib_set_sky(self._h, None))
+            return
+        faces = sky.faces if sky.model == _abi.SKY_CUBEMAP and sky.faces is not None else None
+        d = sky.desc(None if faces is None else [self.upload_texture(t) for t in faces])
+        self._check(self._lib.shs_group_lib_set_sky(self._h, ctypes.byref(d)))
+
     def set_option(self, option, value):
         """shs_group_set_option: shs_set_option on every rank's context."""
         self._check(self._lib.shs_group_set_option(self._h, int(option), int(value)))

@@ -17,7 +17,7 @@ from ._abi import (CULL_BACK, CULL_FRONT, CULL_NONE, LIB_BG_GRADIENT, LIB_DEPTH_
                    PROGRAM_DEBUG_DEPTH, PROGRAM_DEBUG_NORMAL, PROGRAM_FORWARD_PLUS, PROGRAM_FORWARD_PLUS_TYPED, PROGRAM_PBR_MR)
 
 __all__ = [
-    "LibMesh", "LibDraw", "Texture2D", "LibFrame", "ShadowCaster", "PROGRAM_PBR_MR", "PROGRAM_BLINN_PHONG", "PROGRAM_DEBUG_ALBEDO",
+    "LibMesh", "LibDraw", "Texture2D", "LibFrame", "LibSky", "ShadowCaster", "PROGRAM_PBR_MR", "PROGRAM_BLINN_PHONG", "PROGRAM_DEBUG_ALBEDO",
     "PROGRAM_DEBUG_NORMAL", "PROGRAM_DEBUG_DEPTH", "CULL_NONE", "CULL_BACK", "CULL_FRONT", "IDENTITY",
     "look_at_lh", "perspective_lh_no", "model_euler", "mat_mul", "dir_light_camera_aabb",
 ]
@@ -96,6 +96,30 @@ class LibFrame:
         d.zn, d.zf = self.zn, self.zf
         for i in range(4):
             d.clear_hdr[i] = self.clear_hdr[i]
+        return d
+
+
+@dataclass
+class LibSky:
+    """scene.sky for the camera pass (shs_sky_desc): a ProceduralSky (sky/procedural_sky.hpp; sun_dir_ws is its
+    constructor argument) or a CubemapSky (sky/cubemap_sky.hpp; faces: six Texture2D, +X,-X,+Y,-Y,+Z,-Z, which
+    may differ in size), unprojected per pixel as render_skybox_to_hdr does (sky/skybox_renderer.hpp:25-57)
+    with the frame's scene.cam.viewproj / .pos."""
+    model: int = _abi.SKY_PROCEDURAL
+    cam_viewproj: np.ndarray = field(default_factory=lambda: IDENTITY.copy())
+    cam_pos: tuple = (0.0, 0.0, 0.0)
+    sun_dir_ws: tuple = (0.4668, -0.3487, 0.8127)      # ProceduralSky's default argument
+    faces: Optional[list] = None
+    intensity: float = 1.0
+
+    def desc(self, face_ids=None):
+        d = _abi.SkyDescC()
+        d.model = int(self.model)
+        d.cam_viewproj[:] = [float(v) for v in np.asarray(self.cam_viewproj, np.float32).reshape(16)]
+        d.cam_pos[:] = [float(v) for v in self.cam_pos]
+        d.sun_dir_ws[:] = [float(v) for v in self.sun_dir_ws]
+        d.face_tex[:] = [int(v) for v in (face_ids if face_ids is not None else [0] * 6)]
+        d.intensity = float(self.intensity)
         return d
 
 
