@@ -307,6 +307,53 @@ struct KArgDraws {
     DrawGPU d[KARG_DRAWS];
 };
 
+// k_raster's explicit kernel arguments (FrameParams, FrameBuffers, KArgDraws by value) as they lie in the
+// kernel-argument segment: each at the next offset of its alignment, which is this struct's layout.  The
+// tile-group kernels read a field from there where a phase uses it instead of holding it from the
+// kernel's entry (kernel_args()).
+struct RasterArgs {
+    FrameParams fp;
+    FrameBuffers fb;
+    KArgDraws ka;
+};
+static_assert(offsetof(RasterArgs, fb) == (sizeof(FrameParams) + alignof(FrameBuffers) - 1) / alignof(FrameBuffers) * alignof(FrameBuffers) &&
+                  offsetof(RasterArgs, ka) == (offsetof(RasterArgs, fb) + sizeof(FrameBuffers) + alignof(KArgDraws) - 1) /
+                                                  alignof(KArgDraws) * alignof(KArgDraws),
+              "RasterArgs: k_raster's parameters in order, each at its alignment");
+
+// The running kernel's arguments, read in place: scalar loads from the kernel-argument segment (constant
+// address space, scalar cache) at the point of use.  Every call returns a pointer the compiler cannot
+// connect to an earlier one's, so what one phase of a kernel loads through it -- and the frame pointers
+// frame_view() derives from that -- is not kept in scalar registers (or, beyond the 102 there are, in
+// VGPR lanes: v_readlane / v_writelane, vector instructions) for a later phase.  Only a kernel whose
+// parameters are RasterArgs' members, in order, may call it.
+__device__ __forceinline__ const RasterArgs *kernel_args() {
+    auto p = __builtin_amdgcn_kernarg_segment_ptr();   // (a constant-address-space pointer)
+    asm volatile("" : "+s"(p));
+    return (const RasterArgs *)p;
+}
+
+// ... and their buffers.  A pointer the compiler sees arrive as a kernel argument is known to point to
+// global memory; one loaded through kernel_args() is not, and would be dereferenced with flat
+// instructions and 64-bit vector address arithmetic.  Every pointer of FrameBuffers is a device or
+// mapped host allocation, so the view says so (null stays null).
+template <class T>
+__device__ __forceinline__ T *global_ptr(T *p) {
+    return (T *)(__attribute__((address_space(1))) T *)p;
+}
+__device__ __forceinline__ FrameBuffers arg_buffers(const RasterArgs *a) {
+    FrameBuffers v = a->fb;
+#define SHS_GLOBAL(m) v.m = global_ptr(v.m)
+    SHS_GLOBAL(draws); SHS_GLOBAL(bdraw); SHS_GLOBAL(recs); SHS_GLOBAL(rext); SHS_GLOBAL(shade);
+    SHS_GLOBAL(tile_count); SHS_GLOBAL(bins); SHS_GLOBAL(spill); SHS_GLOBAL(frags); SHS_GLOBAL(slivers);
+    SHS_GLOBAL(boxes); SHS_GLOBAL(tdraw); SHS_GLOBAL(counters); SHS_GLOBAL(busy); SHS_GLOBAL(gbusy);
+    SHS_GLOBAL(busy_list); SHS_GLOBAL(stale); SHS_GLOBAL(blk_stat); SHS_GLOBAL(rstat); SHS_GLOBAL(timeline);
+    SHS_GLOBAL(color); SHS_GLOBAL(depth); SHS_GLOBAL(prequant); SHS_GLOBAL(present); SHS_GLOBAL(ov_host);
+#undef SHS_GLOBAL
+    return v;
+}
+static_assert(sizeof(FrameBuffers) == 25 * sizeof(void *), "arg_buffers names every pointer of FrameBuffers");
+
 // ---- GLM scalar semantics (glm/detail/func_common.inl) -------------------------------------
 __device__ __forceinline__ float g_min(float x, float y) { return (y < x) ? y : x; }
 __device__ __forceinline__ float g_max(float x, float y) { return (x < y) ? y : x; }

@@ -1280,7 +1280,6 @@ struct GroupShared {
     uint32_t next;                    // the first staged candidate the pair pass left out (all fit: >= the staged count)
     uint32_t seq, pairs;              // the group's candidates and pairs so far (timeline)
 };
-struct NoGroupShared {};
 // Row-span pair tasks of a group (RF_GROUP_SPANS): one segment per nonempty (staged candidate, group row)
 // span, +4 KB on the span kernel alone (still four workgroups per CU).
 constexpr int GROUP_SEGS = RCHUNK * GY * RTH;
@@ -1602,19 +1601,15 @@ __device__ __forceinline__ TriRec winner_records(const FrameParams &fp, const Fr
                                                  uint32_t slot, ShadeRec &sr) {
     float4 h4[4];
     float4 *e4 = reinterpret_cast<float4 *>(&sr);
-    if (slot != SLOT_NONE) {
+    // (one base pointer per record, LDS or HBM, and one set of loads through it: written as two branches
+    // the compiler may instead carry an address per field through the join)
+    const bool staged = slot != SLOT_NONE;
+    const float4 *s4 = staged ? &sh.rec[slot * 4] : reinterpret_cast<const float4 *>(&fb.recs[id]);
+    const float4 *g4 = staged ? &sh.srec[slot * 5] : reinterpret_cast<const float4 *>(&fb.shade[id]);
 #pragma unroll
-        for (int k = 0; k < 4; ++k) h4[k] = sh.rec[slot * 4 + k];
+    for (int k = 0; k < 4; ++k) h4[k] = s4[k];
 #pragma unroll
-        for (int k = 0; k < 5; ++k) e4[k] = sh.srec[slot * 5 + k];
-    } else {
-        const float4 *s4 = reinterpret_cast<const float4 *>(&fb.recs[id]);
-        const float4 *g4 = reinterpret_cast<const float4 *>(&fb.shade[id]);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) h4[k] = s4[k];
-#pragma unroll
-        for (int k = 0; k < 5; ++k) e4[k] = g4[k];
-    }
+    for (int k = 0; k < 5; ++k) e4[k] = g4[k];
     return rec_from_hot(fp, h4[0], h4[1], h4[2], h4[3], make_float4(0.f, 0.f, 0.f, 0.f));
 }
 
@@ -1926,17 +1921,33 @@ __device__ __forceinline__ void raster_tile(const FrameParams &fp, const FrameBu
 // end to end as segments, as raster_tile's span path does per tile; the pairs tested are a superset of
 // the passing ones, so the keys are the box pass's.  A staging chunk whose spans hold more pairs than the
 // bitmap (many near-group-filling triangles, where spans cut nothing) takes the box passes, which split.
-template <bool SPANS, class GS>
-__device__ __forceinline__ void raster_group(const FrameParams &fp, const FrameBuffers &fb, const DrawGPU *draws,
-                                             uint32_t n_frag, int frame, int rt0, RasterShared &sh, GS &gs, uint64_t *tl) {
+//
+// Scalar state.  The kernel's arguments and the frame's pointers are not parameters: each phase -- the
+// group's header and first boxes, a later scan round, a staging chunk with its pair passes, the ghost
+// fragments, the resolve loop -- reads the fields it uses from the kernel-argument segment and derives
+// the frame's view from them (kernel_args(), frame_view(): scalar loads and scalar arithmetic; what a
+// phase does not use is never computed), so that only the group's own scalars (its rectangle, busy mask,
+// frame and tile) live from one phase to the next.  Held across the whole item, as they were, they
+// exceeded the scalar registers and travelled through VGPR lanes, which costs vector instructions.
+// TL: the timeline's marks and counters are compiled in (the instantiation launched when a timeline
+// buffer is set); first: the workgroup's first group, the one the timeline records.
+template <bool KARG, bool SPANS, bool TL, class GS>
+__device__ __forceinline__ void raster_group(uint32_t n_frag, int frame, int rt0, RasterShared &sh, GS &gs, bool first) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int tls = fp.setup_grid + (int)blockIdx.x;
-    const int col0 = rt0 % fp.tiles_x, row0 = rt0 / fp.tiles_x;
-    const int ncol = min(GX, fp.tiles_x - col0), nrow = min(GY, fp.rtiles_y - row0);
+    uint64_t *tl = nullptr;
+    int tls = 0;
+    const RasterArgs *a = kernel_args();
+    if constexpr (TL) {
+        tl = first ? arg_buffers(a).timeline : nullptr;
+        tls = a->fp.setup_grid + (int)blockIdx.x;
+    }
+    const int tiles_x = a->fp.tiles_x;
+    const int col0 = rt0 % tiles_x, row0 = rt0 / tiles_x;
+    const int ncol = min(GX, tiles_x - col0), nrow = min(GY, a->fp.rtiles_y - row0);
     const int GX0 = col0 * RTW, GY0 = row0 * RTH;
     const int GX1 = GX0 + ncol * RTW - 1, GY1 = GY0 + nrow * RTH - 1;
-    const int dbase = frame * fp.n_draws;                       // the frame's slice of the draw table
-    const uint32_t n_items = (uint32_t)fp.n_tris;
+    const uint32_t n_items = (uint32_t)a->fp.n_tris;
+    const uint32_t epoch = a->fp.epoch;
     // The group's busy flags (lane t of every wave loads tile t's: bit ty * GX + tx of the wave-uniform
     // mask below) and the first round's boxes are vector loads issued before the round's barriers, which
     // they stay in flight across: one round trip for both.  (As scalar loads the flags were waited for at
@@ -1945,21 +1956,25 @@ __device__ __forceinline__ void raster_group(const FrameParams &fp, const FrameB
     uint32_t flag = 0u;
     {
         const int tx = lane % GX, ty = lane / GX;
-        if (tx < ncol && ty < nrow) flag = fb.busy[rt0 + ty * fp.tiles_x + tx];   // (ty < nrow <= GY: lanes < GX * GY)
+        const FrameBuffers fv = frame_view(a->fp, arg_buffers(a), frame);
+        if (tx < ncol && ty < nrow) flag = fv.busy[rt0 + ty * tiles_x + tx];   // (ty < nrow <= GY: lanes < GX * GY)
     }
     uint2 bx[CAND / 256];
+    {
+        const FrameBuffers fv = frame_view(a->fp, arg_buffers(a), frame);
 #pragma unroll
-    for (int k = 0; k < CAND / 256; ++k) {
-        const uint32_t item = tid + 256u * k;
-        bx[k] = item < n_items ? fb.boxes[item] : make_uint2(1u, 1u);   // ([1, 0]: empty)
+        for (int k = 0; k < CAND / 256; ++k) {
+            const uint32_t item = tid + 256u * k;
+            bx[k] = item < n_items ? fv.boxes[item] : make_uint2(1u, 1u);   // ([1, 0]: empty)
+        }
     }
     // the previous item's key resets precede every shared write of this one (raster_tile)
     if (n_items == 0u) __syncthreads();
     // profiling, kept in LDS by wave 0: the candidates processed and the group's (candidate, pixel) tasks
     if (tl && tid == 0) { gs.seq = 0u; gs.pairs = 0u; }
-    const bool slot_keys = fp.n_tris < (1 << 25);
+    const bool slot_keys = n_items < (1u << 25);
     bool single = n_items <= (uint32_t)CAND;   // one gather round and one staging pass: winners in LDS
-    const uint32_t bmask = (uint32_t)__ballot(flag == fp.epoch) & ((1u << (GX * GY)) - 1u);   // (epoch != 0)
+    const uint32_t bmask = (uint32_t)__ballot(flag == epoch) & ((1u << (GX * GY)) - 1u);   // (epoch != 0)
     const int t_first = __ffs((int)bmask) - 1;
     // A pixel of the group: its key in its tile's key array (tile 0: RasterShared's, the others GroupShared's),
     // or null when the tile is not busy -- only the group's busy tiles are drawn (a sharded frame's group
@@ -1974,10 +1989,12 @@ __device__ __forceinline__ void raster_group(const FrameParams &fp, const FrameB
     for (uint32_t base = 0; base < n_items; base += CAND) {
         // every bin box of the round against the group rectangle (4 independent loads per thread)
         if (base > 0u) {
+            const RasterArgs *ar = kernel_args();
+            const FrameBuffers fv = frame_view(ar->fp, arg_buffers(ar), frame);
 #pragma unroll
             for (int k = 0; k < CAND / 256; ++k) {
                 const uint32_t item = base + tid + 256u * k;
-                bx[k] = item < n_items ? fb.boxes[item] : make_uint2(1u, 1u);
+                bx[k] = item < n_items ? fv.boxes[item] : make_uint2(1u, 1u);
             }
         }
         __syncthreads();
@@ -2007,9 +2024,12 @@ __device__ __forceinline__ void raster_group(const FrameParams &fp, const FrameB
         for (uint32_t c = 0; c < nc; c += RCHUNK) {
             const int m = (int)min((uint32_t)RCHUNK, nc - c);
             if (c > 0) __syncthreads();
+            // the chunk's view: the records' pointers for the staging, the pair tests' frame terms
+            const RasterArgs *ac = kernel_args();
+            const FrameParams fp = ac->fp;
             // stage the records, float bboxes and (single-pass groups) shade records: one round trip
             if (tid < m) sh.id[tid] = sh.cand[c + tid];
-            stage_stored<true>(fb, sh, c, m, single, true);
+            stage_stored<true>(frame_view(fp, arg_buffers(ac), frame), sh, c, m, single, true);
             __syncthreads();
             tl_mark(tl, tls, 2);
             bool boxes = true;
@@ -2131,7 +2151,7 @@ __device__ __forceinline__ void raster_group(const FrameParams &fp, const FrameB
     // tile-clamp pixels of unbounded slivers outside their bbox that passed, into their tile's keys
     // (raster_tile's loop, left duplicated: see there)
     for (uint32_t f = tid; f < n_frag; f += 256) {
-        const GhostFrag g = fb.frags[f];
+        const GhostFrag g = arg_buffers(kernel_args()).frags[f];
         const int gx = (int)(g.xy & 0xffffu), gy = (int)(g.xy >> 16);
         if (g.frame == (uint32_t)frame && gx >= GX0 && gx <= GX1 && gy >= GY0 && gy <= GY1) {
             const int tx = (gx - GX0) / RTW, ty = (gy - GY0) / RTH, t = ty * GX + tx;
@@ -2142,7 +2162,13 @@ __device__ __forceinline__ void raster_group(const FrameParams &fp, const FrameB
     }
     __syncthreads();
 
-    // each busy tile: one pixel per thread -- resolve, shade the winner, write (raster_tile's)
+    // each busy tile: one pixel per thread -- resolve, shade the winner, write (raster_tile's); the
+    // view of the loop: the planes, the winners' records and the draw table
+    const RasterArgs *av = kernel_args();
+    const FrameParams fp = av->fp;
+    const FrameBuffers fb = frame_view(fp, arg_buffers(av), frame);
+    const DrawGPU *draws = draw_table<KARG>(fb, av->ka);
+    const int dbase = frame * fp.n_draws;                       // the frame's slice of the draw table
     uint32_t ncov = 0u;
     for (uint32_t bm = bmask; bm; bm &= bm - 1u) {
         const int t = __ffs((int)bm) - 1;
@@ -2316,86 +2342,86 @@ constexpr int STRIP_RT = SHS_STRIP_RT;
 #ifndef SHS_LEGACY_RASTER_WAVES
 #define SHS_LEGACY_RASTER_WAVES 4   // minimum waves per SIMD (-D...: timing experiments)
 #endif
-// GROUPS (RF_TILE_GROUPS, the scan-mode pair kernel only): the busy list holds tile groups (raster_group);
-// GSPANS (RF_GROUP_SPANS): their pair pass walks row spans.
-template <bool KARG, bool NO_RECS, bool SPANS, bool PIX, int SCAN, bool GROUPS = false, bool GSPANS = false>
-__global__ __launch_bounds__(256, SHS_LEGACY_RASTER_WAVES) void k_raster(FrameParams fp, FrameBuffers fb, KArgDraws ka) {
-    static_assert(!GROUPS || (SCAN == SCAN_ALL && !NO_RECS && !SPANS && !PIX), "tile groups: the scan-mode pair kernel");
-    static_assert(!GSPANS || GROUPS, "group spans: the group kernel");
-    __shared__ RasterShared sh;
-    __shared__ typename std::conditional<GSPANS, GroupSpanShared, typename std::conditional<GROUPS, GroupShared, NoGroupShared>::type>::type gs;
+// The item loop of the tile-group kernels (k_raster with GROUPS: the busy list holds tile groups).  The
+// same items in the same order as k_raster's loop below, but the kernel's arguments stay where they are:
+// the prologue, every item's fetch and every clear item read what they use through kernel_args(), and
+// raster_group does so per phase, so the loop itself carries only the item counts and the ticket.
+template <bool KARG, bool GSPANS, bool TL, class GS>
+__device__ __forceinline__ void group_items(RasterShared &sh, GS &gs) {
     const int tid = threadIdx.x;
-    uint32_t *cnt = fb.counters + fp.parity * CSET;
-    const DrawGPU *draws = draw_table<KARG>(fb, ka);
-    const int n_rt = fp.tiles_x * fp.rtiles_y;            // raster tiles per frame
-    const uint64_t t_start = fb.timeline ? __builtin_amdgcn_s_memrealtime() : 0ull;
-    const uint64_t c_start = fb.timeline ? __builtin_amdgcn_s_memtime() : 0ull;
+    uint64_t t_start = 0ull, c_start = 0ull;
+    if constexpr (TL) {
+        t_start = __builtin_amdgcn_s_memrealtime();
+        c_start = __builtin_amdgcn_s_memtime();
+    }
     if (tid == 0) { sh.cov = 0; sh.maxbin = 0; sh.nclr = 0; }
     sh.key[tid] = KEY_EMPTY;
-    if constexpr (GROUPS) {
 #pragma unroll
-        for (int t = 0; t < GX * GY - 1; ++t) gs.key[t * (RTW * RTH) + tid] = KEY_EMPTY;
+    for (int t = 0; t < GX * GY - 1; ++t) gs.key[t * (RTW * RTH) + tid] = KEY_EMPTY;
+    uint32_t n_busy, n_frag, n_strips;
+    {
+        // (every independent first-touch load is issued up front: k_raster's prologue)
+        const RasterArgs *a = kernel_args();
+        const FrameParams fp = a->fp;
+        const FrameBuffers fb = arg_buffers(a);
+        const uint32_t *cnt = fb.counters + fp.parity * CSET;
+        const DrawGPU *draws = draw_table<KARG>(fb, a->ka);
+        n_busy = min(cnt[C_BUSY], (uint32_t)(fp.tiles_x * fp.tiles_y * (TILE / RTH) * fp.n_frames));
+        n_frag = min(cnt[C_FRAG], fp.frag_cap);
+        const int n_draws_all = fp.n_draws * fp.n_frames;
+        const float4 du_first = tid < min(n_draws_all, LDS_DRAWS) * 4 ? reinterpret_cast<const float4 *>(draws[tid >> 2].light)[tid & 3]
+                                                                       : make_float4(0.f, 0.f, 0.f, 0.f);
+        if (tid < min(n_draws_all, LDS_DRAWS) * 4) sh.du[tid] = du_first;
+        n_strips = (uint32_t)(((fp.rtiles_y + STRIP_RT - 1) / STRIP_RT) * fp.n_frames);
     }
-    // Every independent first-touch load is issued up front so their round trips overlap: the
-    // busy-list length, the ghost-fragment count and the draws' shading uniforms.  (A single-frame
-    // scan-mode scene's bin boxes held in registers from the start -- rounds 1-4 -- cost the batch
-    // kernel two spilled registers and bought the single frame nothing measurable: C2 0.0361 ->
-    // 0.0356 ms per single frame without them.)
-    const uint32_t n_busy = min(cnt[C_BUSY], (uint32_t)(fp.tiles_x * fp.tiles_y * (TILE / RTH) * fp.n_frames));
-    const uint32_t n_frag = min(cnt[C_FRAG], fp.frag_cap);
-    static_assert(LDS_DRAWS * 4 == 256, "one per-draw uniform float4 per thread");
-    const int n_draws_all = fp.n_draws * fp.n_frames;
-    const float4 du_first = tid < min(n_draws_all, LDS_DRAWS) * 4 ? reinterpret_cast<const float4 *>(draws[tid >> 2].light)[tid & 3]
-                                                                   : make_float4(0.f, 0.f, 0.f, 0.f);
-    if (tid < min(n_draws_all, LDS_DRAWS) * 4) sh.du[tid] = du_first;
-    // a strip item clears STRIP_RT raster-tile rows of one frame (fewer items: fewer tickets and
-    // barriers per cleared byte)
-    const int strips_y = (fp.rtiles_y + STRIP_RT - 1) / STRIP_RT;
-    const uint32_t n_strips = (uint32_t)(strips_y * fp.n_frames);
     const uint64_t n_items = (uint64_t)n_strips + n_busy;
-    const uint32_t G = gridDim.x, q = blockIdx.x % (uint32_t)N_WORKQ;
-    uint32_t *queue = &cnt[C_WORK + WORKQ_STRIDE * q];
-    const bool queued = (uint64_t)G + q < n_items;        // this queue deals any item at all
+    const uint32_t q = blockIdx.x % (uint32_t)N_WORKQ;
+    const bool queued = (uint64_t)gridDim.x + q < n_items;        // this queue deals any item at all
+    // the interleave's quotients (below) in 32 bits when (item + 1) * n_strips cannot pass 2^32
+    const bool narrow = n_items * n_strips <= 0xffffffffull;
     uint32_t item = blockIdx.x, ticket = 0u;
     uint32_t nclr = 0;   // tiles this thread's clear items marked clean
     bool first = true;
     while ((uint64_t)item < n_items) {
-        if (tid == 0 && queued) ticket = atomicAdd(queue, 1u);   // the next item, in flight meanwhile
+        const RasterArgs *a = kernel_args();
+        if (tid == 0 && queued)   // the next item, in flight meanwhile
+            ticket = atomicAdd(&arg_buffers(a).counters[a->fp.parity * CSET + C_WORK + WORKQ_STRIDE * q], 1u);
         // interleave: item i is a strip when the count of strips among items < i + 1 grows
-        const uint32_t s_lo = (uint32_t)(((uint64_t)item * n_strips) / n_items);
-        const uint32_t s_hi = (uint32_t)(((uint64_t)(item + 1) * n_strips) / n_items);
+        uint32_t s_lo, s_hi;
+        if (narrow) {
+            s_lo = (item * n_strips) / (uint32_t)n_items;
+            s_hi = ((item + 1u) * n_strips) / (uint32_t)n_items;
+        } else {
+            s_lo = (uint32_t)(((uint64_t)item * n_strips) / n_items);
+            s_hi = (uint32_t)(((uint64_t)(item + 1) * n_strips) / n_items);
+        }
         if (s_hi > s_lo) {
+            const FrameParams fp = a->fp;
+            const FrameBuffers fb = arg_buffers(a);
+            const int strips_y = (fp.rtiles_y + STRIP_RT - 1) / STRIP_RT;
             const int f = (int)(s_lo / (uint32_t)strips_y);
             const int sy = (int)s_lo - f * strips_y;
             if (!SHS_DBG(fp, DBG_SKIP_CLEAR))   // (timing experiments: the busy tiles alone)
                 nclr += clear_item(fp, fb, f, sy, STRIP_RT, sh);
         } else {
-            uint32_t k = item - s_lo;
-            if ((fp.flags & RF_XCD_ROWS) && k < (n_busy & ~31u))   // busy item 32B + 8r + x <- entry 32B + 4x + r:
-                k = (k & ~31u) | ((k & 7u) << 2) | ((k >> 3) & 3u);  // a row group's items 8 apart (one queue)
-            const uint32_t g = fb.busy_list[k];
-            const int f = (int)(g / (uint32_t)n_rt), rt = (int)g - f * n_rt;
-            const FrameBuffers fv = frame_view(fp, fb, f);
+            const uint32_t g = arg_buffers(a).busy_list[item - s_lo];   // (RF_XCD_ROWS: bin-mode batches only)
+            const int n_rt = a->fp.tiles_x * a->fp.rtiles_y;            // raster tiles per frame
+            const int f = (int)(g / (uint32_t)n_rt), rt = (int)g - f * n_rt;   // (rt: the group's top-left tile)
             if (g == BUSY_SKIP) {
                 // padding of a row group (a bin tile's row below the screen): nothing to draw
-            } else if (SHS_DBG(fp, DBG_CLEAR_ONLY)) {
+            } else if (SHS_DBG(a->fp, DBG_CLEAR_ONLY)) {
                 __syncthreads();
-                clear_tile(fp, fv, rt);
-            } else if constexpr (GROUPS) {   // (rt: the group's top-left tile)
-                if (SHS_DBG(fp, DBG_TWICE)) raster_group<GSPANS>(fp, fv, draws, n_frag, f, rt, sh, gs, nullptr);   // warm run
-                tl_mark(first ? fb.timeline : nullptr, fp.setup_grid + (int)blockIdx.x, 0);
-                raster_group<GSPANS>(fp, fv, draws, n_frag, f, rt, sh, gs, first ? fb.timeline : nullptr);
-                first = false;
+                clear_tile(a->fp, frame_view(a->fp, arg_buffers(a), f), rt);
             } else {
-                if (SHS_DBG(fp, DBG_TWICE)) raster_tile<NO_RECS, SPANS, PIX, SCAN>(fp, fv, draws, cnt, n_frag, f, rt, sh, nullptr);   // warm run
-                tl_mark(first ? fb.timeline : nullptr, fp.setup_grid + (int)blockIdx.x, 0);
-                raster_tile<NO_RECS, SPANS, PIX, SCAN>(fp, fv, draws, cnt, n_frag, f, rt, sh, first ? fb.timeline : nullptr);
+                if (SHS_DBG(a->fp, DBG_TWICE)) raster_group<KARG, GSPANS, false>(n_frag, f, rt, sh, gs, false);   // warm run
+                if constexpr (TL) tl_mark(first ? arg_buffers(a).timeline : nullptr, a->fp.setup_grid + (int)blockIdx.x, 0);
+                raster_group<KARG, GSPANS, TL>(n_frag, f, rt, sh, gs, first);
                 first = false;
             }
         }
         if (!queued) break;
         __syncthreads();   // every thread is done with sh.item of the previous round
-        if (tid == 0) sh.item = G + q + (uint32_t)N_WORKQ * ticket;
+        if (tid == 0) sh.item = gridDim.x + q + (uint32_t)N_WORKQ * ticket;
         __syncthreads();
         item = sh.item;
     }
@@ -2403,12 +2429,113 @@ __global__ __launch_bounds__(256, SHS_LEGACY_RASTER_WAVES) void k_raster(FramePa
     if (nclr) atomicAdd(&sh.nclr, nclr);
     __syncthreads();
     if (tid == 0) {
+        const RasterArgs *a = kernel_args();
+        const FrameBuffers fb = arg_buffers(a);
         fb.rstat[blockIdx.x] = make_uint4(sh.cov, sh.maxbin, sh.nclr, 0u);
-        if (fb.timeline) {
-            fb.timeline[TL_STRIDE * (fp.setup_grid + blockIdx.x)] = t_start;
-            fb.timeline[TL_STRIDE * (fp.setup_grid + blockIdx.x) + 1] = __builtin_amdgcn_s_memrealtime();
-            fb.timeline[TL_STRIDE * (fp.setup_grid + blockIdx.x) + 10] = c_start;
-            fb.timeline[TL_STRIDE * (fp.setup_grid + blockIdx.x) + 11] = __builtin_amdgcn_s_memtime();
+        if constexpr (TL) {
+            if (uint64_t *tl = fb.timeline) {
+                tl += TL_STRIDE * (a->fp.setup_grid + blockIdx.x);
+                tl[0] = t_start;
+                tl[1] = __builtin_amdgcn_s_memrealtime();
+                tl[10] = c_start;
+                tl[11] = __builtin_amdgcn_s_memtime();
+            }
+        }
+    }
+}
+
+// GROUPS (RF_TILE_GROUPS, the scan-mode pair kernel only): the busy list holds tile groups (group_items,
+// raster_group); GSPANS (RF_GROUP_SPANS): their pair pass walks row spans; TL: with the timeline's marks
+// (launched only when a timeline buffer is set, so the product's group kernels carry none of them).
+// The group kernels do not touch their parameters: they read the argument segment in place (kernel_args(),
+// whose RasterArgs is this parameter list).
+template <bool KARG, bool NO_RECS, bool SPANS, bool PIX, int SCAN, bool GROUPS = false, bool GSPANS = false, bool TL = false>
+__global__ __launch_bounds__(256, SHS_LEGACY_RASTER_WAVES) void k_raster(FrameParams fp, FrameBuffers fb, KArgDraws ka) {
+    static_assert(!GROUPS || (SCAN == SCAN_ALL && !NO_RECS && !SPANS && !PIX), "tile groups: the scan-mode pair kernel");
+    static_assert(!GSPANS || GROUPS, "group spans: the group kernel");
+    static_assert(!TL || GROUPS, "the other kernels test the timeline pointer at run time");
+    __shared__ RasterShared sh;
+    if constexpr (GROUPS) {
+        __shared__ typename std::conditional<GSPANS, GroupSpanShared, GroupShared>::type gs;
+        group_items<KARG, GSPANS, TL>(sh, gs);
+    } else {
+        const int tid = threadIdx.x;
+        uint32_t *cnt = fb.counters + fp.parity * CSET;
+        const DrawGPU *draws = draw_table<KARG>(fb, ka);
+        const int n_rt = fp.tiles_x * fp.rtiles_y;            // raster tiles per frame
+        const uint64_t t_start = fb.timeline ? __builtin_amdgcn_s_memrealtime() : 0ull;
+        const uint64_t c_start = fb.timeline ? __builtin_amdgcn_s_memtime() : 0ull;
+        if (tid == 0) { sh.cov = 0; sh.maxbin = 0; sh.nclr = 0; }
+        sh.key[tid] = KEY_EMPTY;
+        // Every independent first-touch load is issued up front so their round trips overlap: the
+        // busy-list length, the ghost-fragment count and the draws' shading uniforms.  (A single-frame
+        // scan-mode scene's bin boxes held in registers from the start -- rounds 1-4 -- cost the batch
+        // kernel two spilled registers and bought the single frame nothing measurable: C2 0.0361 ->
+        // 0.0356 ms per single frame without them.)
+        const uint32_t n_busy = min(cnt[C_BUSY], (uint32_t)(fp.tiles_x * fp.tiles_y * (TILE / RTH) * fp.n_frames));
+        const uint32_t n_frag = min(cnt[C_FRAG], fp.frag_cap);
+        static_assert(LDS_DRAWS * 4 == 256, "one per-draw uniform float4 per thread");
+        const int n_draws_all = fp.n_draws * fp.n_frames;
+        const float4 du_first = tid < min(n_draws_all, LDS_DRAWS) * 4 ? reinterpret_cast<const float4 *>(draws[tid >> 2].light)[tid & 3]
+                                                                       : make_float4(0.f, 0.f, 0.f, 0.f);
+        if (tid < min(n_draws_all, LDS_DRAWS) * 4) sh.du[tid] = du_first;
+        // a strip item clears STRIP_RT raster-tile rows of one frame (fewer items: fewer tickets and
+        // barriers per cleared byte)
+        const int strips_y = (fp.rtiles_y + STRIP_RT - 1) / STRIP_RT;
+        const uint32_t n_strips = (uint32_t)(strips_y * fp.n_frames);
+        const uint64_t n_items = (uint64_t)n_strips + n_busy;
+        const uint32_t G = gridDim.x, q = blockIdx.x % (uint32_t)N_WORKQ;
+        uint32_t *queue = &cnt[C_WORK + WORKQ_STRIDE * q];
+        const bool queued = (uint64_t)G + q < n_items;        // this queue deals any item at all
+        uint32_t item = blockIdx.x, ticket = 0u;
+        uint32_t nclr = 0;   // tiles this thread's clear items marked clean
+        bool first = true;
+        while ((uint64_t)item < n_items) {
+            if (tid == 0 && queued) ticket = atomicAdd(queue, 1u);   // the next item, in flight meanwhile
+            // interleave: item i is a strip when the count of strips among items < i + 1 grows
+            const uint32_t s_lo = (uint32_t)(((uint64_t)item * n_strips) / n_items);
+            const uint32_t s_hi = (uint32_t)(((uint64_t)(item + 1) * n_strips) / n_items);
+            if (s_hi > s_lo) {
+                const int f = (int)(s_lo / (uint32_t)strips_y);
+                const int sy = (int)s_lo - f * strips_y;
+                if (!SHS_DBG(fp, DBG_SKIP_CLEAR))   // (timing experiments: the busy tiles alone)
+                    nclr += clear_item(fp, fb, f, sy, STRIP_RT, sh);
+            } else {
+                uint32_t k = item - s_lo;
+                if ((fp.flags & RF_XCD_ROWS) && k < (n_busy & ~31u))   // busy item 32B + 8r + x <- entry 32B + 4x + r:
+                    k = (k & ~31u) | ((k & 7u) << 2) | ((k >> 3) & 3u);  // a row group's items 8 apart (one queue)
+                const uint32_t g = fb.busy_list[k];
+                const int f = (int)(g / (uint32_t)n_rt), rt = (int)g - f * n_rt;
+                const FrameBuffers fv = frame_view(fp, fb, f);
+                if (g == BUSY_SKIP) {
+                    // padding of a row group (a bin tile's row below the screen): nothing to draw
+                } else if (SHS_DBG(fp, DBG_CLEAR_ONLY)) {
+                    __syncthreads();
+                    clear_tile(fp, fv, rt);
+                } else {
+                    if (SHS_DBG(fp, DBG_TWICE)) raster_tile<NO_RECS, SPANS, PIX, SCAN>(fp, fv, draws, cnt, n_frag, f, rt, sh, nullptr);   // warm run
+                    tl_mark(first ? fb.timeline : nullptr, fp.setup_grid + (int)blockIdx.x, 0);
+                    raster_tile<NO_RECS, SPANS, PIX, SCAN>(fp, fv, draws, cnt, n_frag, f, rt, sh, first ? fb.timeline : nullptr);
+                    first = false;
+                }
+            }
+            if (!queued) break;
+            __syncthreads();   // every thread is done with sh.item of the previous round
+            if (tid == 0) sh.item = G + q + (uint32_t)N_WORKQ * ticket;
+            __syncthreads();
+            item = sh.item;
+        }
+        __syncthreads();
+        if (nclr) atomicAdd(&sh.nclr, nclr);
+        __syncthreads();
+        if (tid == 0) {
+            fb.rstat[blockIdx.x] = make_uint4(sh.cov, sh.maxbin, sh.nclr, 0u);
+            if (fb.timeline) {
+                fb.timeline[TL_STRIDE * (fp.setup_grid + blockIdx.x)] = t_start;
+                fb.timeline[TL_STRIDE * (fp.setup_grid + blockIdx.x) + 1] = __builtin_amdgcn_s_memrealtime();
+                fb.timeline[TL_STRIDE * (fp.setup_grid + blockIdx.x) + 10] = c_start;
+                fb.timeline[TL_STRIDE * (fp.setup_grid + blockIdx.x) + 11] = __builtin_amdgcn_s_memtime();
+            }
         }
     }
 }
@@ -2536,7 +2663,10 @@ hipError_t launch_raster(const FrameParams &fp, const FrameBuffers &fb, const KA
 #ifdef SHS_SCAN_SPANS   // (timing experiments: scan-mode frames on row spans)
     else SHS_RASTER(false, true, false, SCAN_ALL);
 #else
+    // (the group kernels' timeline marks are an instantiation of their own, TL)
+    else if ((fp.flags & RF_GROUP_SPANS) && fb.timeline) SHS_RASTER(false, false, false, SCAN_ALL, true, true, true);
     else if (fp.flags & RF_GROUP_SPANS) SHS_RASTER(false, false, false, SCAN_ALL, true, true);   // busy groups, row spans
+    else if ((fp.flags & RF_TILE_GROUPS) && fb.timeline) SHS_RASTER(false, false, false, SCAN_ALL, true, false, true);
     else if (fp.flags & RF_TILE_GROUPS) SHS_RASTER(false, false, false, SCAN_ALL, true);   // busy groups (raster_group)
     else SHS_RASTER(false, false, false, SCAN_ALL);
 #endif
