@@ -109,6 +109,20 @@ __device__ __forceinline__ const DrawGPU *draw_table(const FrameBuffers &fb, con
     return KARG ? ka.d : fb.draws;
 }
 
+// A draw at a block-uniform index: its {light, cam, ocol, colf} and shading model.  No kernel writes a
+// draw while it runs, so the device table may be read through the constant address space: scalar loads,
+// whatever stores the kernel has issued before them.  (The kernel-argument copy already lies there.)
+typedef const __attribute__((address_space(4))) float *const_floats;
+typedef const __attribute__((address_space(4))) int32_t *const_ints;
+__device__ __forceinline__ void uniform_draw(const DrawGPU *draws, int d, float4 (&du)[4], int &shading) {
+    const DrawGPU *dr = draws + d;
+    const_floats u = (const_floats)dr->light;
+    asm volatile("" : "+s"(u));   // (loaded where it is called, per tile: not twelve scalars held over the loop)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) du[k] = make_float4(u[4 * k], u[4 * k + 1], u[4 * k + 2], u[4 * k + 3]);
+    shading = *(const_ints)((const_floats)u - (offsetof(DrawGPU, light) - offsetof(DrawGPU, shading)) / 4);
+}
+
 // floor of a finite float, clamped into [lo, hi] before the conversion
 __device__ __forceinline__ int floor_clamped(float x, int lo, int hi) {
     return (int)fminf(fmaxf(floorf(x), (float)lo), (float)hi);
@@ -1181,14 +1195,19 @@ __device__ __forceinline__ void shade_interp(const float4 (&du)[4], int shading,
 
 // The ShadeRec's varyings at barycentrics (u, v, w): A = (a0 u + a1 v) + a2 w, N likewise (Phong,
 // Blinn-Phong) -- blinn_phong_shading.cpp:235-236's operation order.
-__device__ __forceinline__ void interp_varyings(const ShadeRec &sr, float u, float v, float w, f3 &A, f3 &N) {
+// shading: the record's model (sr.shading), or the same value held as a scalar (raster_group's
+// single-draw frames).
+__device__ __forceinline__ void interp_varyings(const ShadeRec &sr, int shading, float u, float v, float w, f3 &A, f3 &N) {
     const f3 a0 = {sr.v[0], sr.v[1], sr.v[2]}, a1 = {sr.v[3], sr.v[4], sr.v[5]}, a2 = {sr.v[6], sr.v[7], sr.v[8]};
     A = add3(add3(sc3(a0, u), sc3(a1, v)), sc3(a2, w));
     N = f3{0.0f, 0.0f, 0.0f};
-    if (sr.shading >= 2) {
+    if (shading >= 2) {
         const f3 n0 = {sr.v[9], sr.v[10], sr.v[11]}, n1 = {sr.v[12], sr.v[13], sr.v[14]}, n2 = {sr.v[15], sr.v[16], sr.v[17]};
         N = add3(add3(sc3(n0, u), sc3(n1, v)), sc3(n2, w));
     }
+}
+__device__ __forceinline__ void interp_varyings(const ShadeRec &sr, float u, float v, float w, f3 &A, f3 &N) {
+    interp_varyings(sr, sr.shading, u, v, w, A, N);
 }
 
 __device__ __forceinline__ void shade_winner(const float4 *du, const ShadeRec &sr, float u, float v, float w, float pre[3]) {
@@ -1649,6 +1668,51 @@ __device__ __forceinline__ void store_pixel(const FrameParams &fp, const FrameBu
         LEGACY_STORE(depth, &fb.depth[(size_t)py * fp.W + px]);
         if (fb.prequant) fb.prequant[(size_t)(fp.H - 1 - py) * fp.W + px] = pq;
         if (fb.present) LEGACY_STORE(rgba, &fb.present[(size_t)py * fp.W + px]);
+    }
+}
+
+// ---- raster_group's own resolve paths ----------------------------------------------------------
+// (The tile kernels and k_pipe keep the helpers above; each of these computes the same bits as the
+// helper it stands in for.)
+
+// winner_records for a wave whose covered lanes' keys all carry a slot: both records straight from their
+// LDS copies (ds_read with an immediate offset; no base-pointer select, no 64-bit address, and no
+// vmcnt wait that would also wait for the previous tile's stores).
+__device__ __forceinline__ TriRec staged_records(const FrameParams &fp, const RasterShared &sh, uint32_t slot, ShadeRec &sr) {
+    // (whole 16-B vectors: copied field by field the loads are regrouped into 4-B-aligned pairs)
+    typedef float v4f __attribute__((ext_vector_type(4)));
+    const v4f *s4 = reinterpret_cast<const v4f *>(&sh.rec[slot * 4]), *g4 = reinterpret_cast<const v4f *>(&sh.srec[slot * 5]);
+    float4 h4[4];
+    float *e = reinterpret_cast<float *>(&sr);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { const v4f q = s4[k]; h4[k] = make_float4(q.x, q.y, q.z, q.w); }
+#pragma unroll
+    for (int k = 0; k < 5; ++k) { const v4f q = g4[k]; e[4 * k] = q.x; e[4 * k + 1] = q.y; e[4 * k + 2] = q.z; e[4 * k + 3] = q.w; }
+    return rec_from_hot(fp, h4[0], h4[1], h4[2], h4[3], make_float4(0.f, 0.f, 0.f, 0.f));
+}
+
+// store_pixel for the tile at (X0, Y0) without 64-bit vector addresses, at any frame size: each plane's
+// address is a scalar base -- the tile's first pixel in the plane's row order, computed once per tile in
+// scalar arithmetic -- plus the pixel's 32-bit byte offset from it (at most RTH rows of W <= 16384 pixels,
+// 16 B each: it fits).  Canvas rows run upwards, so their base is the tile's lowest screen row that
+// exists; the rows of a bottom tile below the screen give offsets that are never stored through.
+template <class T>
+__device__ __forceinline__ T *plane_at(T *base, uint32_t byte_off) {
+    return reinterpret_cast<T *>(reinterpret_cast<char *>(base) + byte_off);
+}
+__device__ __forceinline__ void store_tile_pixel(const FrameParams &fp, const FrameBuffers &fb, int X0, int Y0, int px, int py,
+                                                 uint32_t rgba, float depth, float4 pq) {
+    const bool dbg_nost = SHS_DBG(fp, DBG_SKIP_TILE_STORES) && !(rgba == 0x12345678u && depth == -1.0f);
+    const int yc = min(Y0 + RTH, fp.H) - 1;                                     // canvas row H-1-yc is the tile's first
+    const size_t cb = (size_t)(fp.H - 1 - yc) * fp.W + X0, sb = (size_t)Y0 * fp.W + X0;   // scalars
+    if (px < fp.W && py < fp.H && !dbg_nost) {
+        // (the pixel's index in the plane less the base's, not rows x W + columns of the tile: that is the same
+        // for every tile, and held over the loop it became a 64-bit address per plane in four registers)
+        const uint32_t ic = (uint32_t)((fp.H - 1 - py) * fp.W + px) - (uint32_t)cb, is = (uint32_t)(py * fp.W + px) - (uint32_t)sb;
+        LEGACY_STORE(rgba, plane_at(reinterpret_cast<uint32_t *>(fb.color) + cb, ic * 4u));
+        LEGACY_STORE(depth, plane_at(fb.depth + sb, is * 4u));
+        if (fb.prequant) *plane_at(fb.prequant + cb, ic * 16u) = pq;
+        if (fb.present) LEGACY_STORE(rgba, plane_at(fb.present + sb, is * 4u));
     }
 }
 
@@ -2167,12 +2231,17 @@ __device__ __forceinline__ void raster_group(uint32_t n_frag, int frame, int rt0
     const RasterArgs *av = kernel_args();
     const FrameParams fp = av->fp;
     const FrameBuffers fb = frame_view(fp, arg_buffers(av), frame);
+    // A single-draw frame: every winner's draw is draws[frame] -- its uniforms and its shading model
+    // (ShadeRec::shading is always the winner's draw's: setup_quad and stage_from_mesh store dr.shading,
+    // and shared varyings require the model to agree across frames) are the group's scalars, and the
+    // model a scalar branch.  Frames of several draws take shade_stored_winner as raster_tile does.
+    const bool one_draw = fp.n_draws == 1;
     const DrawGPU *draws = draw_table<KARG>(fb, av->ka);
-    const int dbase = frame * fp.n_draws;                       // the frame's slice of the draw table
     uint32_t ncov = 0u;
     for (uint32_t bm = bmask; bm; bm &= bm - 1u) {
         const int t = __ffs((int)bm) - 1;
-        const int px = GX0 + (t % GX) * RTW + (tid & 31), py = GY0 + (t / GX) * RTH + (tid >> 5);
+        const int X0 = GX0 + (t % GX) * RTW, Y0 = GY0 + (t / GX) * RTH;
+        const int px = X0 + (tid & 31), py = Y0 + (tid >> 5);
         unsigned long long *kp = t ? &gs.key[(t - 1) * (RTW * RTH) + tid] : &sh.key[tid];
         const unsigned long long key = *kp;
         *kp = KEY_EMPTY;   // clean for the next item (read above, by this thread only)
@@ -2180,14 +2249,41 @@ __device__ __forceinline__ void raster_group(uint32_t n_frag, int frame, int rt0
         float depth = FLT_MAX;
         float4 pq = make_float4(0.f, 0.f, 0.f, 0.f);
         const bool covered = key != KEY_EMPTY && px < fp.W && py < fp.H;
-        if (covered) {
-            uint32_t id, slot;
-            key_winner(key, slot_keys, id, slot);
-            shade_stored_winner(fp, fb, draws, dbase, sh, id, slot, px, py, depth, rgba, pq);
+        uint32_t id = 0u, slot = 0u;
+        if (covered) key_winner(key, slot_keys, id, slot);
+        // The wave's vote: every covered lane's winner is staged (single-pass groups; no ghost fragment
+        // won here).  Then, in a single-draw frame, shade_stored_winner with the records from LDS and the
+        // draw from scalars; a wave with any other lane takes shade_stored_winner itself, whole.  (Two
+        // whole bodies: with the records alone on two paths, their join cost a register move per field.)
+        const bool staged = one_draw && __ballot(covered && slot == SLOT_NONE) == 0ull;
+        if (staged) {
+            float4 sdu[4];
+            int sshading;
+            uniform_draw(draws, frame, sdu, sshading);
+            if (covered) {
+                ShadeRec sr;
+                const TriRec r = staged_records(fp, sh, slot, sr);
+                float u, v, w;
+                bary_pass(r, (float)px + 0.5f, (float)py + 0.5f, u, v, w);   // the winner's own values
+                depth = (u * r.z0 + v * r.z1) + w * r.z2;
+                if (!SHS_DBG(fp, DBG_SKIP_SHADE)) {
+                    f3 A, N;
+                    float pre[3];
+                    interp_varyings(sr, sshading, u, v, w, A, N);
+                    shade_interp(sdu, sshading, A, N, pre);
+                    pack_pixel(pre, rgba, pq);
+                }
+            }
+        } else {
+            // (its own view: the record arrays and the draw table are not held over the staged waves' loop)
+            const RasterArgs *aw = kernel_args();
+            const FrameBuffers fw = frame_view(fp, arg_buffers(aw), frame);
+            if (covered)
+                shade_stored_winner(fp, fw, draw_table<KARG>(fw, aw->ka), frame * fp.n_draws, sh, id, slot, px, py, depth, rgba, pq);
         }
         if (t == t_first) tl_mark(tl, tls, 4);
         ncov += (uint32_t)__popcll(__ballot(covered));
-        store_pixel(fp, fb, px, py, rgba, depth, pq);
+        store_tile_pixel(fp, fb, X0, Y0, px, py, rgba, depth, pq);
         // the tile no longer holds the clear values: a later batch that leaves it idle clears it
         if (tid == 0) fb.stale[rt0 + (t / GX) * fp.tiles_x + t % GX] = 1u;
         if (t == t_first) tl_mark(tl, tls, 5);

@@ -17,10 +17,11 @@ contains every FILTER word:
 Static counts: weigh them by trip counts before comparing.  --weights takes
 "FIRST-LAST=W,..." -- loops named by the instruction range the listing prints -- and prints
 sum(W * the loop's lane moves, inner loops included), the figure the rounds compare (the item loop x 1,
-the box-scan loop x 1, the resolve loop x 3.79 tiles per busy group).
+the box-scan loop x 1, the resolve loop x 3.79 tiles per busy group; the resolve loop holds two bodies, of which a
+wave runs one: read its listing before weighing its VALU count).
 
 usage: tools/kernel_valu_loops.py [--asm FILE.s] [--src csrc/shs_legacy.hip] [--extra "-DFLAG"]
-                                  [--weights "244-4376=1,743-999=1,2802-3408=3.79"] FILTER [FILTER ...]
+                                  [--weights "243-4974=1,713-969=1,2818-4002=3.79"] FILTER [FILTER ...]
 """
 import argparse
 import os
