@@ -38,6 +38,13 @@ extern "C" {
 #define SHS_SHADING_GOURAUD 1      /* hello_pipeline_gouraud_shading.cpp:46-89       */
 #define SHS_SHADING_PHONG 2        /* hello_pipeline_phong_shading.cpp:47-108        */
 #define SHS_SHADING_BLINN_PHONG 3  /* hello_pipeline_blinn_phong_shading.cpp:48-97   */
+/* The other fragment shaders the reference binds to the same draw_triangle_tile.  Their vertex shader
+ * and Uniforms are the Blinn-Phong pipeline's (model, world light_dir, camera_pos, color). */
+#define SHS_SHADING_TOON 4         /* hello_pipeline_toon_shading.cpp:56-90          */
+#define SHS_SHADING_GOOCH 5        /* hello_pipeline_gooch_shading.cpp:56-95         */
+#define SHS_SHADING_OREN_NAYAR 6   /* hello_pipeline_oren_nayar_shading.cpp:57-99    */
+#define SHS_SHADING_NORMAL_VIS 7   /* hello_pipeline_normal_zbuffer_debug.cpp:57-69  */
+#define SHS_SHADING_DEPTH_VIS 8    /* hello_pipeline_normal_zbuffer_debug.cpp:105-120 (reads the clip z) */
 
 typedef struct shs_ctx shs_ctx;
 
@@ -126,6 +133,17 @@ int shs_render_legacy(shs_ctx *ctx, const shs_frame_desc *frame, const shs_legac
 #define SHS_MAX_BATCH_FRAMES 1024
 int shs_render_legacy_batch(shs_ctx *ctx, const shs_frame_desc *frame, const shs_legacy_draw *draws, int32_t n_draws,
                             int32_t n_frames);
+
+/* The legacy fragment shaders alone, for n samples (synchronous): the kernel shades each sample with
+ * the function the rasters shade a winning pixel with.  uniforms: light_dir, camera_pos, color and
+ * shading are read (mesh_id and mvp are ignored); shading is any model but SHS_SHADING_FLAT and
+ * SHS_SHADING_GOURAUD, whose varyings differ (SHS_ERR_INVALID).  normal_sum[3n]: the barycentric sum of
+ * the corners' normals, before draw_triangle_tile normalises it; world_pos[3n]: the interpolated world
+ * position; clip_z[n]: the interpolated clip-space z (read by SHS_SHADING_DEPTH_VIS alone).  rgba[4n]:
+ * the colour bytes; prequant[4n]: the pre-truncation floats (r, g, b, 1) as SHS_FRAME_PREQUANT keeps
+ * them.  Either output may be NULL. */
+int shs_legacy_shade_samples(shs_ctx *ctx, const shs_legacy_draw *uniforms, int32_t n, const float *normal_sum,
+                             const float *world_pos, const float *clip_z, uint8_t *rgba, float *prequant);
 
 /* Copy the frame into caller-owned host buffers (blocking).  color: W*H*4 bytes, canvas rows
  * (Canvas::buffer() layout); depth: W*H floats, screen rows (ZBuffer::buffer() as the legacy

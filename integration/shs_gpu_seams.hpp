@@ -7,8 +7,9 @@
 // /root/reference/cpp-folders/src/.
 //
 //   Seam 1  LegacyRendererSystemGPU<SceneT, ObjectT, SHADING>: replaces RendererSystem of
-//           hello-3d-primitives/hello_pipeline_{blinn_phong,phong,gouraud,flat}_shading.cpp
-//           (the 80x80 tile-job loop of process(), :244-313 in the Blinn-Phong demo).
+//           hello-3d-primitives/hello_pipeline_{blinn_phong,phong,gouraud,flat,toon,gooch,oren_nayar}_shading.cpp
+//           (the 80x80 tile-job loop of process(), :244-313 in the Blinn-Phong demo), and with three
+//           draws per object the split-screen hello_pipeline_normal_zbuffer_debug.cpp.
 //   Seam 3  PassShadowMapGPU / PassPBRForwardGPU: IRenderPass implementations with the ids,
 //           contracts and resource I/O of PassShadowMapAdapter / PassPBRForwardAdapter
 //           (shs-renderer-lib/include/shs/pipeline/pass_adapters.hpp:356-394, 1005-1062), registered
@@ -53,7 +54,9 @@ struct Device {
 // demo): declare the member as `shs::AbstractSystem *renderer_system;` and construct
 //     this->renderer_system = new shs_gpu_seams::LegacyRendererSystemGPU<HelloScene, MonkeyObject,
 //                                                                      SHS_SHADING_BLINN_PHONG>(scene);
-// (SHS_SHADING_PHONG / _GOURAUD / _FLAT in the other three demos).  Everything else -- the scene,
+// (SHS_SHADING_PHONG / _GOURAUD / _FLAT in the other three demos; SHS_SHADING_TOON / _GOOCH /
+// _OREN_NAYAR in hello_pipeline_{toon,gooch,oren_nayar}_shading.cpp, whose Uniforms and vertex shader
+// are the Blinn-Phong demo's, as are SHS_SHADING_NORMAL_VIS / _DEPTH_VIS's).  Everything else -- the scene,
 // the LogicSystem / Viewer camera update, Canvas::fill_pixel, copy_to_SDLSurface and the SDL loop --
 // is unchanged.  The job system is no longer used for rendering.
 //
@@ -65,6 +68,7 @@ struct Device {
 template <class SceneT, class ObjectT, int SHADING>
 class LegacyRendererSystemGPU : public shs::AbstractSystem {
 public:
+    static_assert(SHADING >= SHS_SHADING_FLAT && SHADING <= SHS_SHADING_DEPTH_VIS, "a legacy shading model");
     static constexpr int kTileX = 80, kTileY = 80;   // TILE_SIZE_X / _Y (blinn_phong_shading.cpp:29-30)
 
     explicit LegacyRendererSystemGPU(SceneT *scene, int device_index = 0)
@@ -97,7 +101,8 @@ public:
                 std::memcpy(d.model, glm::value_ptr(mv), sizeof d.model);
                 std::memcpy(d.light_dir, glm::value_ptr(light_dir_view), sizeof d.light_dir);
             } else {
-                // Uniforms{model, mvp = proj * view * model, light_dir, camera_pos, color} (:277-282)
+                // Uniforms{model, mvp = proj * view * model, light_dir, camera_pos, color} (:277-282; the
+                // same block in the Toon, Gooch, Oren-Nayar and split-screen demos)
                 const glm::mat4 model = obj->get_world_matrix();
                 const glm::mat4 mvp = proj * view * model;
                 std::memcpy(d.mvp, glm::value_ptr(mvp), sizeof d.mvp);

@@ -429,7 +429,7 @@ static int enqueue_frame(shs_ctx *ctx) {
     fp.n_tris = n_tris; fp.n_draws = n_draws;
     fp.clear_rgba = (uint32_t)f.clear_color[0] | ((uint32_t)f.clear_color[1] << 8) | ((uint32_t)f.clear_color[2] << 16) |
                     ((uint32_t)f.clear_color[3] << 24);
-    fp.flags = (f.flags & (SHS_EXPERIMENTS ? ~0u : ~shs_dev::DBG_MASK) & ~(shs_dev::RF_PER_PIXEL | shs_dev::RF_NO_RECS | shs_dev::RF_SHARED_VARY | shs_dev::RF_GHOST_INLINE | shs_dev::RF_XCD_ROWS | shs_dev::RF_FULL_CLEAR | shs_dev::RF_TILE_GROUPS | shs_dev::RF_GROUP_SPANS)) | (ctx->pair_loop ? 0u : shs_dev::RF_PER_PIXEL) |
+    fp.flags = (f.flags & (SHS_EXPERIMENTS ? ~0u : ~shs_dev::DBG_MASK) & ~(shs_dev::RF_PER_PIXEL | shs_dev::RF_NO_RECS | shs_dev::RF_SHARED_VARY | shs_dev::RF_GHOST_INLINE | shs_dev::RF_XCD_ROWS | shs_dev::RF_FULL_CLEAR | shs_dev::RF_TILE_GROUPS | shs_dev::RF_GROUP_SPANS | shs_dev::RF_EXT_MODELS)) | (ctx->pair_loop ? 0u : shs_dev::RF_PER_PIXEL) |
                (full_clear ? shs_dev::RF_FULL_CLEAR : 0u);
     fp.bin_cap = ctx->bin_cap;
     fp.spill_cap = (uint32_t)std::min<size_t>(ws.spill.cap, 0xffffffffu);
@@ -466,7 +466,9 @@ static int enqueue_frame(shs_ctx *ctx) {
         bool share = true;
         for (int i = 0; i < n_draws && share; ++i) {
             const shs_legacy_draw &d0 = ctx->last_draws[i];
-            share = d0.shading == SHS_SHADING_PHONG || d0.shading == SHS_SHADING_BLINN_PHONG;
+            // (Toon .. the normal visualiser run the Blinn-Phong VS line for line; the depth visualiser's
+            // varying is the clip z, which the camera pose changes)
+            share = d0.shading >= SHS_SHADING_PHONG && d0.shading <= SHS_SHADING_NORMAL_VIS;
             for (int fr = 1; fr < n_frames && share; ++fr) {
                 const shs_legacy_draw &d = ctx->last_draws[(size_t)fr * n_draws + i];
                 share = d.mesh_id == d0.mesh_id && d.shading == d0.shading && std::memcmp(d.model, d0.model, sizeof d.model) == 0;
@@ -474,6 +476,10 @@ static int enqueue_frame(shs_ctx *ctx) {
         }
         if (share) fp.flags |= shs_dev::RF_SHARED_VARY;
     }
+    // A batch with an extended shading model runs the kernels compiled with their shaders (RF_EXT_MODELS);
+    // every other batch the ones without.
+    for (int i = 0; i < n_draws_all; ++i)
+        if (ctx->last_draws[i].shading > SHS_SHADING_BLINN_PHONG) fp.flags |= shs_dev::RF_EXT_MODELS;
     // Bin-mode row groups dealt to one XCD (RF_XCD_ROWS): SHS_LEGACY_XCD_ROWS=0 turns it off (timing
     // experiments).
     static const bool xcd_rows_env = [] { const char *e = shs_exp_env("SHS_LEGACY_XCD_ROWS"); return !e || std::atoi(e) != 0; }();
@@ -694,7 +700,7 @@ int shs_render_legacy_batch(shs_ctx *ctx, const shs_frame_desc *frame, const shs
             ctx->err = "bad mesh id (not a legacy soup mesh)";
             return SHS_ERR_INVALID;
         }
-        if (draws[i].shading < SHS_SHADING_FLAT || draws[i].shading > SHS_SHADING_BLINN_PHONG) {
+        if (draws[i].shading < SHS_SHADING_FLAT || draws[i].shading > SHS_SHADING_DEPTH_VIS) {
             ctx->err = "bad shading model";
             return SHS_ERR_INVALID;
         }
@@ -727,6 +733,38 @@ int shs_render_legacy_batch(shs_ctx *ctx, const shs_frame_desc *frame, const shs
 
 int shs_render_legacy(shs_ctx *ctx, const shs_frame_desc *frame, const shs_legacy_draw *draws, int32_t n_draws) {
     return shs_render_legacy_batch(ctx, frame, draws, n_draws, 1);
+}
+
+int shs_legacy_shade_samples(shs_ctx *ctx, const shs_legacy_draw *uniforms, int32_t n, const float *normal_sum,
+                             const float *world_pos, const float *clip_z, uint8_t *rgba, float *prequant) {
+    if (!ctx || !uniforms || n < 0 || (n > 0 && (!normal_sum || !world_pos || !clip_z))) return SHS_ERR_INVALID;
+    if (uniforms->shading < SHS_SHADING_PHONG || uniforms->shading > SHS_SHADING_DEPTH_VIS) {
+        ctx->err = "bad shading model";   // (Flat and Gouraud interpolate other varyings)
+        return SHS_ERR_INVALID;
+    }
+    if (n == 0) return SHS_OK;
+    DrawGPU d;
+    build_draw(*uniforms, Mesh{}, 0, d);   // normalize(-light_dir), camera_pos, color / 255 as a frame's draw
+    if (set_dev(ctx)) return SHS_ERR_HIP;
+    float *buf = nullptr;   // 3n normal sums, 3n world positions, n clip z; then 4n prequant floats, n colour words
+    const size_t N = (size_t)n;
+    const size_t pq_at = (7 * N + 3) / 4 * 4;   // (float4 stores: 16-B aligned)
+    HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&buf), (pq_at + 5 * N) * sizeof(float)));
+    float4 *pq = reinterpret_cast<float4 *>(buf + pq_at);
+    uint32_t *cw = reinterpret_cast<uint32_t *>(buf + pq_at + 4 * N);
+    hipError_t e = hipMemcpy(buf, normal_sum, 3 * N * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(buf + 3 * N, world_pos, 3 * N * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(buf + 6 * N, clip_z, N * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = shs_internal::ext::launch_fs_sample(d, n, buf, cw, pq, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e == hipSuccess && rgba) e = hipMemcpy(rgba, cw, N * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && prequant) e = hipMemcpy(prequant, pq, 4 * N * sizeof(float), hipMemcpyDeviceToHost);
+    (void)hipFree(buf);
+    if (e != hipSuccess) {
+        ctx->err = hipGetErrorString(e);
+        return SHS_ERR_HIP;
+    }
+    return SHS_OK;
 }
 
 int shs_synchronize(shs_ctx *ctx) {

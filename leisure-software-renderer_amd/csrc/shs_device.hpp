@@ -168,6 +168,10 @@ constexpr uint32_t RF_TILE_GROUPS = 1u << 22;
 // the whole boxes (frame flags bit 23, set by the host only with RF_TILE_GROUPS:
 // SHS_OPT_LEGACY_GROUP_SPANS).  The same keys: the images are the same bits.
 constexpr uint32_t RF_GROUP_SPANS = 1u << 23;
+// A draw of the batch has one of the extended shading models, SHS_SHADING_TOON .. SHS_SHADING_DEPTH_VIS
+// (frame flags bit 24, set by the host): the launch wrappers take the compilation that has their shaders
+// (shs_legacy_ext.hip).  No kernel reads it.
+constexpr uint32_t RF_EXT_MODELS = 1u << 24;
 #ifndef SHS_GROUP_X
 #define SHS_GROUP_X 2                // (-DSHS_GROUP_X=.. -DSHS_GROUP_Y=..: timing experiments)
 #endif

@@ -1,7 +1,10 @@
 // shs_legacy.hip -- gfx950 kernels for the shs_renderer legacy triangle scan-conversion path.
 //
 // Replaces RendererSystem::process + draw_triangle_tile + the four legacy shader pairs
-// (cpp-folders/src/hello-3d-primitives/hello_pipeline_{blinn_phong,phong,gouraud,flat}_shading.cpp).
+// (cpp-folders/src/hello-3d-primitives/hello_pipeline_{blinn_phong,phong,gouraud,flat}_shading.cpp); compiled
+// a second time as shs_legacy_ext.hip, also the Toon, Gooch, Oren-Nayar and normal / depth visualiser
+// fragment shaders of hello_pipeline_{toon,gooch,oren_nayar}_shading.cpp and
+// hello_pipeline_normal_zbuffer_debug.cpp.
 //
 // Pipeline per frame: two launches on one HIP stream, no memsets, no copies for <= 6 draws.
 //   k_setup   three block roles in one grid:
@@ -47,7 +50,21 @@ template <typename T> __device__ __forceinline__ void LEGACY_STORE(T v, T *p) { 
 #define LEGACY_STORE(v, p) __builtin_nontemporal_store(v, p)
 #endif
 
+// The extended shading models (SHS_SHADING_TOON .. SHS_SHADING_DEPTH_VIS) are a second compilation of
+// this file (shs_legacy_ext.hip defines SHS_LEGACY_EXT and includes it): the same kernels in namespace
+// shs_dev::ext with the five models' branches in corner_varyings / shade_interp, launched only for a
+// batch that draws one of them (RF_EXT_MODELS).  Without the macro none of their code is compiled, so
+// the kernels of the Flat .. Blinn-Phong batches are the same instructions and registers as before the
+// models existed.
 namespace shs_dev {
+#ifdef SHS_LEGACY_EXT
+namespace ext {
+using shs_dev::mark_run;     // (shs_wave.hpp's overloads, beside the ones declared below)
+using shs_dev::pair_owner;
+constexpr bool EXT_MODELS = true;
+#else
+constexpr bool EXT_MODELS = false;
+#endif
 
 // ---- k_setup --------------------------------------------------------------------------------
 
@@ -753,6 +770,16 @@ __device__ __forceinline__ void corner_varyings(const DrawGPU &dr, const float (
         return;
     }
     float x, y, z, ww;
+    if constexpr (EXT_MODELS) {
+        if (dr.shading == 8) {
+            // Depth visualiser (normal_zbuffer_debug.cpp:49, :246): the FS reads the interpolated clip-space
+            // position's z -- the corner's u.mvp * vec4(aPos, 1), the very m4p vertex_screen feeds to
+            // clip_to_screen -- carried in a.x as Gouraud carries its colour; no normals
+            m4p(dr.mvp, p3[0], p3[1], p3[2], x, y, z, ww);
+            a = f3{z, 0.0f, 0.0f};
+            return;
+        }
+    }
     m4p(dr.model, p3[0], p3[1], p3[2], x, y, z, ww);
     const f3 wp = {x, y, z};
     const f3 n = normalize3(m3v(dr.nmat, f3{n3[0], n3[1], n3[2]}));
@@ -768,7 +795,9 @@ __device__ __forceinline__ void corner_varyings(const DrawGPU &dr, const float (
         a = f3{g_clamp01(sum * dr.ocol[0]), g_clamp01(sum * dr.ocol[1]), g_clamp01(sum * dr.ocol[2])};
         return;
     }
-    // Phong / Blinn-Phong VS (blinn_phong_shading.cpp:48-57)
+    // Phong / Blinn-Phong VS (blinn_phong_shading.cpp:48-57); the Toon, Gooch, Oren-Nayar and normal
+    // visualiser VS are the same lines (toon_shading.cpp:45-53, gooch_shading.cpp:45-53,
+    // oren_nayar_shading.cpp:46-54, normal_zbuffer_debug.cpp:46-54)
     a = wp;
     nr = n;
 }
@@ -1089,7 +1118,8 @@ __global__ __launch_bounds__(256, BIN ? SHS_BIN_SETUP_WAVES : SHS_SCAN_SETUP_WAV
 constexpr int GHOST_LIST_BLOCKS = SHS_GHOST_BLOCKS;
 
 // A wave's items are known up front: lane j loads the sliver entry of its j-th next item in one round
-// trip.
+// trip.  (It shades nothing: one compilation serves every batch.)
+#ifndef SHS_LEGACY_EXT
 __global__ __launch_bounds__(256) void k_ghost(FrameParams fp, FrameBuffers fb_all) {
     uint32_t *cnt = fb_all.counters + fp.parity * CSET;
     const int n = (int)min(cnt[C_SLIVER], (uint32_t)fp.n_tris * (uint32_t)fp.n_frames);
@@ -1128,6 +1158,7 @@ __global__ __launch_bounds__(256) void k_ghost(FrameParams fp, FrameBuffers fb_a
         }
     }
 }
+#endif
 
 // ---- k_raster ---------------------------------------------------------------------------------
 
@@ -1138,6 +1169,118 @@ __global__ __launch_bounds__(256) void k_ghost(FrameParams fp, FrameBuffers fb_a
 // vectors (world position / Gouraud colour / Flat normal), N = the same of the normals (Phong,
 // Blinn-Phong).  Split from the interpolation so a winner's varyings can be accumulated corner by
 // corner in the same operation order (recs_from_mesh's caller).
+#ifdef SHS_LEGACY_EXT
+// sin and cos of an angle in [0, pi/2] (an acosf of a value in [0, 1]; float(pi/2) lies 4.4e-8 above pi/2),
+// in double: the Taylor series through x^19 / x^20, whose first dropped terms are below 2.6e-16 / 1.8e-17
+// there.  Oren-Nayar's std::sin / std::tan (oren_nayar_shading.cpp:84) never see another argument, so
+// the general sinf / tanf -- with their large-argument reduction and its tables -- stay out of the
+// kernels.  |cos| >= 4.4e-8 at a float, so tan = s / c carries <= 3e-9 relative: like sin it equals the
+// host libm's float except within that of a rounding boundary (one ulp, inside the 1e-5 tolerance).
+// NaN (acosf of a dot product above 1) goes through as NaN.
+__device__ __forceinline__ void sincos_quadrant(float xf, double &s, double &c) {
+    const double x = (double)xf, x2 = x * x;
+    double ps = -1.0 / 121645100408832000.0;           // -1/19!
+    ps = ps * x2 + 1.0 / 355687428096000.0;              // 1/17!
+    ps = ps * x2 - 1.0 / 1307674368000.0;                // 1/15!
+    ps = ps * x2 + 1.0 / 6227020800.0;                   // 1/13!
+    ps = ps * x2 - 1.0 / 39916800.0;                     // 1/11!
+    ps = ps * x2 + 1.0 / 362880.0;                       // 1/9!
+    ps = ps * x2 - 1.0 / 5040.0;
+    ps = ps * x2 + 1.0 / 120.0;
+    ps = ps * x2 - 1.0 / 6.0;
+    s = x + x * (x2 * ps);
+    double pc = 1.0 / 2432902008176640000.0;             // 1/20!
+    pc = pc * x2 - 1.0 / 6402373705728000.0;             // 1/18!
+    pc = pc * x2 + 1.0 / 20922789888000.0;               // 1/16!
+    pc = pc * x2 - 1.0 / 87178291200.0;                  // 1/14!
+    pc = pc * x2 + 1.0 / 479001600.0;                    // 1/12!
+    pc = pc * x2 - 1.0 / 3628800.0;                      // 1/10!
+    pc = pc * x2 + 1.0 / 40320.0;
+    pc = pc * x2 - 1.0 / 720.0;
+    pc = pc * x2 + 1.0 / 24.0;
+    pc = pc * x2 - 0.5;
+    c = 1.0 + x2 * pc;
+}
+
+// The Toon, Gooch, Oren-Nayar and normal-visualiser FS from shade_interp's common head: norm =
+// normalize(in.normal) (already normalised once by draw_triangle_tile), L = normalize(-u.light_dir),
+// viewDir = normalize(u.camera_pos - in.world_pos), oc = vec3(u.color) / 255.0f.
+// Each model's terms that do not need the halfway vector are written ahead of it (they are independent
+// of it in the reference too), so that no more vectors are live at once than in Blinn-Phong.
+__device__ __forceinline__ void shade_ext(int shading, f3 norm, f3 L, f3 viewDir, f3 oc, float pre[3]) {
+    f3 result;
+    if (shading == 7) {
+        // Normal visualiser (normal_zbuffer_debug.cpp:57-69): (norm + 1.0f) * 0.5f, no clamp; a zero
+        // normal sum normalises to NaN, which the byte conversion turns into 0 (pack_pixel)
+        pre[0] = ((norm.x + 1.0f) * 0.5f) * 255.0f;
+        pre[1] = ((norm.y + 1.0f) * 0.5f) * 255.0f;
+        pre[2] = ((norm.z + 1.0f) * 0.5f) * 255.0f;
+        return;
+    } else if (shading == 6) {
+        // Oren-Nayar (oren_nayar_shading.cpp:57-99), roughness 0.9: A and B are float constant
+        // expressions (the compiler folds them in float, as the reference's does)
+        const float roughness = 0.9f;
+        const float sigma2 = roughness * roughness;
+        const float Ac = 1.0f - 0.5f * (sigma2 / (sigma2 + 0.33f));
+        const float Bc = 0.45f * (sigma2 / (sigma2 + 0.09f));
+        const float NdotL = g_max(dot3(norm, L), 0.0f);
+        const float NdotV = g_max(dot3(norm, viewDir), 0.0f);
+        // V parallel to N: V - N * NdotV = 0 and normalize gives 0 * inf = NaN, which glm::max(NaN, 0)
+        // = (NaN < 0) ? 0 : NaN keeps, as does the clamp: the pixel's floats are NaN and its bytes 0.
+        // (Written ahead of the angles, which it does not depend on: the three vectors are dead by then.)
+        const f3 V_plane = normalize3(sub3(viewDir, sc3(norm, NdotV)));
+        const f3 L_plane = normalize3(sub3(L, sc3(norm, NdotL)));
+        const float cos_phi_diff = g_max(dot3(V_plane, L_plane), 0.0f);
+        const float thetaL = acosf(NdotL), thetaV = acosf(NdotV);   // std::acos(float)
+        const float alpha = g_max(thetaL, thetaV);
+        const float beta = g_min(thetaL, thetaV);
+        double sa, ca, sb, cb;
+        sincos_quadrant(alpha, sa, ca);
+        sincos_quadrant(beta, sb, cb);
+        const float sin_alpha = (float)sa, tan_beta = (float)(sb / cb);
+        const float oren_nayar = NdotL * (Ac + (((Bc * cos_phi_diff) * sin_alpha) * tan_beta));
+        const float intensity = 0.15f + oren_nayar;
+        result = sc3(oc, intensity);
+    } else if (shading == 4) {
+        // Toon (toon_shading.cpp:56-90).  The bands and the rim come from IEEE operations alone:
+        // they are the reference's decisions exactly.  The unqualified pow(NdotH, 32.0f) is the
+        // float overload: SDL.h includes <math.h>, whose C++ wrapper brings std::pow(float, float)
+        // into the global namespace beside ::pow(double, double) -- an exact match, i.e. powf; the
+        // squaring chain can differ from it only where the power is within an ulp of 0.5
+        const float NdotL = g_max(dot3(norm, L), 0.0f);
+        float intensity;
+        if (NdotL > 0.95f) intensity = 1.0f;
+        else if (NdotL > 0.5f) intensity = 0.7f;
+        else if (NdotL > 0.25f) intensity = 0.4f;
+        else intensity = 0.2f;
+        const float rimDot = 1.0f - g_max(dot3(viewDir, norm), 0.0f);
+        const float rimIntensity = (rimDot > 0.7f && NdotL > 0.3f) ? 0.5f : 0.0f;
+        const f3 base = sc3(oc, intensity);
+        const f3 half = normalize3(add3(L, viewDir));
+        const float NdotH = g_max(dot3(norm, half), 0.0f);
+        const float specular = (pow2k<5>(NdotH) > 0.5f) ? 0.8f : 0.0f;
+        result = f3{(base.x + specular) + rimIntensity, (base.y + specular) + rimIntensity,
+                    (base.z + specular) + rimIntensity};
+    } else {
+        // Gooch (gooch_shading.cpp:56-95): NdotL unclamped, t = (NdotL + 1) / 2, cool to warm, and
+        // glm::pow(x, 32.0f) specular (powf) times 0.7
+        const float NdotL = dot3(norm, L);
+        const float t = (NdotL + 1.0f) / 2.0f;
+        const f3 k_cool = {0.0f + 0.25f * oc.x, 0.0f + 0.25f * oc.y, 0.55f + 0.25f * oc.z};
+        const f3 k_warm = {0.6f + 0.25f * oc.x, 0.6f + 0.25f * oc.y, 0.1f + 0.25f * oc.z};
+        const float ct = 1.0f - t;
+        const f3 mix = {t * k_warm.x + ct * k_cool.x, t * k_warm.y + ct * k_cool.y, t * k_warm.z + ct * k_cool.z};
+        const f3 half = normalize3(add3(L, viewDir));
+        const float spec = pow2k<5>(g_max(dot3(norm, half), 0.0f));
+        const float add = (1.0f * spec) * 0.7f;
+        result = f3{mix.x + add, mix.y + add, mix.z + add};
+    }
+    pre[0] = g_clamp01(result.x) * 255.0f;
+    pre[1] = g_clamp01(result.y) * 255.0f;
+    pre[2] = g_clamp01(result.z) * 255.0f;
+}
+#endif
+
 __device__ __forceinline__ void shade_interp(const float4 (&du)[4], int shading, f3 A, f3 N, float pre[3]) {
     const float4 dl = du[0], dc = du[1], doc = du[2], dcf = du[3];
     if (shading == 0) {
@@ -1162,6 +1305,15 @@ __device__ __forceinline__ void shade_interp(const float4 (&du)[4], int shading,
         pre[2] = c.z * 255.0f;
         return;
     }
+#ifdef SHS_LEGACY_EXT
+    if (shading == 8) {
+        // Depth visualiser (normal_zbuffer_debug.cpp:105-120): the interpolated clip z (A.x) over 40,
+        // glm::clamp'ed (NaN stays NaN: byte 0), 1 - that to r, g and b
+        const float visibility = 1.0f - g_clamp01(A.x / 40.0f);
+        pre[0] = pre[1] = pre[2] = visibility * 255.0f;
+        return;
+    }
+#endif
     // Phong / Blinn-Phong: normal and world position interpolated (blinn_phong_shading.cpp:235-236)
     const f3 in_n = normalize3(N);
     const f3 in_w = A;
@@ -1169,6 +1321,12 @@ __device__ __forceinline__ void shade_interp(const float4 (&du)[4], int shading,
     const f3 cam = {dc.x, dc.y, dc.z};
     const f3 norm = normalize3(in_n);
     const f3 viewDir = normalize3(sub3(cam, in_w));
+#ifdef SHS_LEGACY_EXT
+    if (shading >= 4) {
+        shade_ext(shading, norm, L, viewDir, f3{doc.x, doc.y, doc.z}, pre);
+        return;
+    }
+#endif
     const float diff = g_max(dot3(norm, L), 0.0f);
     float specular;
     if (shading == 2) {
@@ -1633,8 +1791,19 @@ __device__ __forceinline__ TriRec winner_records(const FrameParams &fp, const Fr
 }
 
 // The shaded floats as the pixel's colour (truncated to uint8 like the reference) and prequant value.
+#ifdef SHS_LEGACY_EXT
+// (uint8_t)x as the reference's x86-64 build converts it: cvttss2si to a 32-bit integer, whose low byte
+// is kept.  The extended models reach it with NaN (Oren-Nayar's V parallel to N, a zero normal sum, a
+// NaN clip z): the "integer indefinite" 0x80000000, i.e. byte 0 -- spelled out, since the conversion of a
+// NaN is undefined in C++.  Every other value the shaders produce lies in (-1, 256).
+__device__ __forceinline__ uint32_t byte_x86(float x) { return x == x ? (uint32_t)(int32_t)x & 0xffu : 0u; }
+#endif
 __device__ __forceinline__ void pack_pixel(const float (&pre)[3], uint32_t &rgba, float4 &pq) {
+#ifdef SHS_LEGACY_EXT
+    const uint32_t cr = byte_x86(pre[0]), cg = byte_x86(pre[1]), cb = byte_x86(pre[2]);
+#else
     const uint32_t cr = (uint32_t)(uint8_t)pre[0], cg = (uint32_t)(uint8_t)pre[1], cb = (uint32_t)(uint8_t)pre[2];
+#endif
     rgba = cr | (cg << 8) | (cb << 16) | (255u << 24);
     pq = make_float4(pre[0], pre[1], pre[2], 1.0f);
 }
@@ -2707,13 +2876,48 @@ __global__ __launch_bounds__(256, SHS_LEGACY_RASTER_WAVES) void k_pipe(FramePara
     if (tid == 0) fb.rstat[blockIdx.x] = make_uint4(sh.cov, sh.maxbin, sh.nclr, 0u);
 }
 
+#ifdef SHS_LEGACY_EXT
+// shs_legacy_shade_samples: one sample per lane through the rasters' own shade_interp and pack_pixel --
+// N = the barycentric normal sum (shade_interp normalises it as draw_triangle_tile does, then as the FS
+// does), A = the interpolated world position, or for the depth visualiser the interpolated clip z in A.x
+// as interp_varyings leaves it.  in: n normal sums, n world positions (3 floats each), n clip z.
+__global__ __launch_bounds__(256) void k_legacy_fs_sample(float4 u0, float4 u1, float4 u2, float4 u3, int shading, int n,
+                                                          const float *in, uint32_t *rgba, float4 *prequant) {
+    const int i = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (i >= n) return;
+    const float *nsum = in + 3 * (size_t)i, *wpos = in + 3 * (size_t)n + 3 * (size_t)i;
+    f3 A = {wpos[0], wpos[1], wpos[2]}, N = {nsum[0], nsum[1], nsum[2]};
+    if (shading == 8) { A = f3{in[6 * (size_t)n + i], 0.0f, 0.0f}; N = f3{0.0f, 0.0f, 0.0f}; }
+    const float4 du[4] = {u0, u1, u2, u3};
+    float pre[3];
+    shade_interp(du, shading, A, N, pre);
+    uint32_t c;
+    float4 q;
+    pack_pixel(pre, c, q);
+    rgba[i] = c;
+    prequant[i] = q;
+}
+
+}  // namespace ext
+#endif
 }  // namespace shs_dev
 
 // ---- launch wrappers (called by shs_abi.cpp) -----------------------------------------------
+// A batch with an extended shading model (RF_EXT_MODELS) takes the wrappers of the second compilation
+// (shs_internal::ext: the same code over namespace shs_dev::ext's kernels).
 namespace shs_internal {
 using namespace shs_dev;
+#ifdef SHS_LEGACY_EXT
+namespace ext {
+using namespace shs_dev::ext;
+#define SHS_EXT_DISPATCH(flags, call)
+#else
+#define SHS_EXT_DISPATCH(flags, call) \
+    if ((flags) & RF_EXT_MODELS) return ext::call
+#endif
 
 hipError_t launch_setup(const FrameParams &fp, const FrameBuffers &fb, const KArgDraws &ka, hipStream_t s) {
+    SHS_EXT_DISPATCH(fp.flags, launch_setup(fp, fb, ka, s));
     const int grid = fp.setup_grid;   // n_frames * frame_blocks
     const bool karg = fp.n_draws * fp.n_frames <= KARG_DRAWS;   // the whole batch's draws as kernel arguments
     const dim3 g(grid > 0 ? grid : 1);
@@ -2727,18 +2931,22 @@ hipError_t launch_setup(const FrameParams &fp, const FrameBuffers &fb, const KAr
     return hipGetLastError();
 }
 
+#ifndef SHS_LEGACY_EXT
 hipError_t launch_ghost(const FrameParams &fp, const FrameBuffers &fb, hipStream_t s) {
     hipLaunchKernelGGL(k_ghost, dim3(GHOST_LIST_BLOCKS), dim3(256), 0, s, fp, fb);
     return hipGetLastError();
 }
+#endif
 
 hipError_t launch_pipe(const FrameParams &fpR, const FrameBuffers &fbR, int grid, const FrameParams &fpS, const FrameBuffers &fbS,
                        hipStream_t s) {
+    SHS_EXT_DISPATCH(fpR.flags | fpS.flags, launch_pipe(fpR, fbR, grid, fpS, fbS, s));
     hipLaunchKernelGGL(k_pipe, dim3(grid > 0 ? grid : 1), dim3(256), 0, s, fpR, fbR, fpS, fbS);
     return hipGetLastError();
 }
 
 hipError_t launch_raster(const FrameParams &fp, const FrameBuffers &fb, const KArgDraws &ka, int grid, hipStream_t s) {
+    SHS_EXT_DISPATCH(fp.flags, launch_raster(fp, fb, ka, grid, s));
     const dim3 g(grid > 0 ? grid : 1);
     const bool karg = fp.n_draws * fp.n_frames <= KARG_DRAWS;   // the whole batch's draws as kernel arguments
     // binned frames test conservative row spans, scan-mode frames whole boxes (raster_tile); the
@@ -2769,5 +2977,16 @@ hipError_t launch_raster(const FrameParams &fp, const FrameBuffers &fb, const KA
 #undef SHS_RASTER
     return hipGetLastError();
 }
+#undef SHS_EXT_DISPATCH
+
+#ifdef SHS_LEGACY_EXT
+hipError_t launch_fs_sample(const DrawGPU &d, int n, const float *in, uint32_t *rgba, float4 *prequant, hipStream_t s) {
+    const float4 *u = reinterpret_cast<const float4 *>(d.light);
+    hipLaunchKernelGGL(k_legacy_fs_sample, dim3((n + 255) / 256), dim3(256), 0, s, u[0], u[1], u[2], u[3], d.shading, n, in, rgba,
+                       prequant);
+    return hipGetLastError();
+}
+}  // namespace ext
+#endif
 
 }  // namespace shs_internal

@@ -13,12 +13,14 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _abi
-from ._abi import (FRAME_PREQUANT, FRAME_PRESENT, SHADING_BLINN_PHONG, SHADING_FLAT, SHADING_GOURAUD, SHADING_NAMES,
-                   SHADING_PHONG, FrameDesc, LegacyDraw, RasterStats)
+from ._abi import (FRAME_PREQUANT, FRAME_PRESENT, SHADING_BLINN_PHONG, SHADING_DEPTH_VIS, SHADING_FLAT, SHADING_GOOCH,
+                   SHADING_GOURAUD, SHADING_NAMES, SHADING_NORMAL_VIS, SHADING_OREN_NAYAR, SHADING_PHONG, SHADING_TOON,
+                   FrameDesc, LegacyDraw, RasterStats)
 
 __all__ = [
     "ShsError", "Context", "Frame", "Draw", "SHADING_FLAT", "SHADING_GOURAUD", "SHADING_PHONG",
-    "SHADING_BLINN_PHONG", "SHADING_NAMES", "FRAME_PREQUANT", "lib",
+    "SHADING_BLINN_PHONG", "SHADING_TOON", "SHADING_GOOCH", "SHADING_OREN_NAYAR", "SHADING_NORMAL_VIS",
+    "SHADING_DEPTH_VIS", "SHADING_NAMES", "FRAME_PREQUANT", "lib",
 ]
 
 lib = _abi.lib
@@ -164,6 +166,30 @@ class Context:
     def render_batch(self, frame: Frame, frames_draws):
         """shs_render_legacy_batch: one k_setup + k_raster pair renders every frame of the batch."""
         self.render_batch_prepared(self.prepare_batch(frame, frames_draws))
+
+    def legacy_shade_samples(self, shading, light_dir, camera_pos, color, normal_sum, world_pos, clip_z):
+        """shs_legacy_shade_samples: the legacy fragment shader `shading` (any model but Flat and Gouraud) for n
+        samples of interpolated varyings -- normal_sum [n, 3] (before draw_triangle_tile's normalise), world_pos
+        [n, 3], clip_z [n] -- under the uniforms light_dir, camera_pos, color
+        -> (rgba uint8 [n, 4], pre-truncation floats float32 [n, 4])."""
+        ns = np.ascontiguousarray(np.asarray(normal_sum, np.float32).reshape(-1, 3))
+        wp = np.ascontiguousarray(np.asarray(world_pos, np.float32).reshape(-1, 3))
+        cz = np.ascontiguousarray(np.asarray(clip_z, np.float32).reshape(-1))
+        n = ns.shape[0]
+        assert wp.shape[0] == n and cz.shape[0] == n
+        u = LegacyDraw()
+        u.mesh_id, u.shading = -1, int(shading)
+        for k in range(3):
+            u.light_dir[k] = float(light_dir[k])
+            u.camera_pos[k] = float(camera_pos[k])
+        for k in range(4):
+            u.color[k] = int(color[k])
+        rgba = np.zeros((n, 4), np.uint8)
+        pq = np.zeros((n, 4), np.float32)
+        self._check(self._lib.shs_legacy_shade_samples(self._h, ctypes.byref(u), n, _fptr(ns), _fptr(wp), _fptr(cz),
+                                                       rgba.ctypes.data_as(ctypes.c_void_p),
+                                                       pq.ctypes.data_as(ctypes.c_void_p)))
+        return rgba, pq
 
     def resolve_frame(self, index: int):
         f = self._frame

@@ -20,7 +20,13 @@ SHADING_FLAT = 0
 SHADING_GOURAUD = 1
 SHADING_PHONG = 2
 SHADING_BLINN_PHONG = 3
-SHADING_NAMES = {"flat": 0, "gouraud": 1, "phong": 2, "blinn_phong": 3}
+SHADING_TOON = 4
+SHADING_GOOCH = 5
+SHADING_OREN_NAYAR = 6
+SHADING_NORMAL_VIS = 7
+SHADING_DEPTH_VIS = 8
+SHADING_NAMES = {"flat": 0, "gouraud": 1, "phong": 2, "blinn_phong": 3, "toon": 4, "gooch": 5, "oren_nayar": 6,
+                 "normal_vis": 7, "depth_vis": 8}
 
 FRAME_PREQUANT = 1
 FRAME_PRESENT = 2
@@ -267,6 +273,7 @@ SIGNATURES = [
     ("shs_render_legacy", ctypes.c_int, [_P, ctypes.POINTER(FrameDesc), ctypes.POINTER(LegacyDraw), ctypes.c_int32]),
     ("shs_render_legacy_batch", ctypes.c_int, [_P, ctypes.POINTER(FrameDesc), ctypes.POINTER(LegacyDraw), ctypes.c_int32,
                                                ctypes.c_int32]),
+    ("shs_legacy_shade_samples", ctypes.c_int, [_P, ctypes.POINTER(LegacyDraw), ctypes.c_int32, _F, _F, _F, _P, _P]),
     ("shs_resolve", ctypes.c_int, [_P, _P, _P]),
     ("shs_resolve_frame", ctypes.c_int, [_P, ctypes.c_int32, _P, _P]),
     ("shs_resolve_present", ctypes.c_int, [_P, ctypes.c_int32, _P, ctypes.c_int32]),

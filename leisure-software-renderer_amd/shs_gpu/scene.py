@@ -18,7 +18,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _abi
-from . import Draw, Frame, SHADING_BLINN_PHONG, SHADING_FLAT, SHADING_GOURAUD, SHADING_PHONG
+from . import Draw, Frame, SHADING_BLINN_PHONG, SHADING_FLAT, SHADING_GOURAUD, SHADING_PHONG, SHADING_TOON
 
 REPO = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 ASSETS = os.path.join(REPO, "assets")
@@ -132,7 +132,10 @@ def monkey_scene(width, height, shading=SHADING_BLINN_PHONG, yaw=0.0, pitch=0.0,
     mesh = monkey()
     view, proj = camera(cam_pos, yaw, pitch)
     model = model_trs((0.0, 0.0, 10.0), rotation, (4.0, 4.0, 4.0))
-    if shading in (SHADING_BLINN_PHONG, SHADING_GOURAUD):
+    if shading in (SHADING_BLINN_PHONG, SHADING_GOURAUD) or shading >= SHADING_TOON:
+        # (the Toon, Gooch, Oren-Nayar and split-screen demos keep the Blinn-Phong demo's light and colour:
+        # toon_shading.cpp:117-118, gooch_shading.cpp:181-185, oren_nayar_shading.cpp:126-127,
+        # normal_zbuffer_debug.cpp:162-168)
         light, color = LIGHT_BLINN, COLOR_BLUE
     elif shading == SHADING_PHONG:
         light, color = LIGHT_PHONG, COLOR_BLUE
