@@ -45,6 +45,11 @@ extern "C" {
 #define SHS_SHADING_OREN_NAYAR 6   /* hello_pipeline_oren_nayar_shading.cpp:57-99    */
 #define SHS_SHADING_NORMAL_VIS 7   /* hello_pipeline_normal_zbuffer_debug.cpp:57-69  */
 #define SHS_SHADING_DEPTH_VIS 8    /* hello_pipeline_normal_zbuffer_debug.cpp:105-120 (reads the clip z) */
+/* The texture-mapping pipeline: the Blinn-Phong shader with baseColor from sample_nearest, and its own
+ * draw_triangle_tile -- perspective-correct depth, world position and UV from the corners' 1 / w, pixels
+ * with invw_sum <= 0 skipped.  Reads the mesh's UVs (shs_mesh_upload_soup_uv) and the draw's texture
+ * (shs_render_legacy_batch_tex, the one render call that takes it). */
+#define SHS_SHADING_TEXTURED 9     /* hello_pipeline_texture_mapping.cpp:66-116, 205-294 */
 
 typedef struct shs_ctx shs_ctx;
 
@@ -105,6 +110,12 @@ int shs_synchronize(shs_ctx *ctx);
  *      shs_renderer.hpp:1296-1298; uploaded once, device resident) ------------------------ */
 int shs_mesh_upload_soup(shs_ctx *ctx, const float *positions, const float *normals, int32_t n_tris,
                          int32_t *mesh_id);
+/* ... with the third vertex stream, ModelGeometry::uvs: uvs[6 * n_tris], (u, v) per corner.  A mesh
+ * uploaded without UVs (uvs NULL, or shs_mesh_upload_soup) and drawn with SHS_SHADING_TEXTURED reads
+ * vec2(0) per corner, as ModelGeometry stores for a mesh without texture coordinates
+ * (shs_renderer.hpp:1285-1290).  The other shading models ignore the UVs. */
+int shs_mesh_upload_soup_uv(shs_ctx *ctx, const float *positions, const float *normals, const float *uvs, int32_t n_tris,
+                            int32_t *mesh_id);
 int shs_mesh_release(shs_ctx *ctx, int32_t mesh_id);
 /* A handle in dst to src's uploaded mesh (legacy soup or library MeshData), on the same device, without
  * a copy: frames in flight on several contexts read one device copy of each mesh.  The buffers stay
@@ -133,6 +144,23 @@ int shs_render_legacy(shs_ctx *ctx, const shs_frame_desc *frame, const shs_legac
 #define SHS_MAX_BATCH_FRAMES 1024
 int shs_render_legacy_batch(shs_ctx *ctx, const shs_frame_desc *frame, const shs_legacy_draw *draws, int32_t n_draws,
                             int32_t n_frames);
+
+/* shs_render_legacy_batch with the textured draws' albedo textures: albedo_tex[n_frames * n_draws], parallel
+ * to draws, shs_texture_upload ids -- texel (x, y) at byte 4 * (y * w + x), the layout Texture2D::texels
+ * holds after the host's loader has run (its flip included).  Read only for draws of
+ * SHS_SHADING_TEXTURED; id 0 takes the shader's else branch (Uniforms::color), an unknown id is
+ * SHS_ERR_INVALID.  albedo_tex NULL: every id 0.  This is the entry point of SHS_SHADING_TEXTURED:
+ * shs_render_legacy[_batch] take the models they have always taken, SHS_SHADING_FLAT .. SHS_SHADING_DEPTH_VIS,
+ * and answer a textured draw, like any other model they do not know, with SHS_ERR_INVALID ("bad shading
+ * model").  For every other batch the two calls are the same.  shs_texture_release of a texture a batch in
+ * flight samples finishes the batch first. */
+int shs_render_legacy_batch_tex(shs_ctx *ctx, const shs_frame_desc *frame, const shs_legacy_draw *draws, const int32_t *albedo_tex,
+                                int32_t n_draws, int32_t n_frames);
+
+/* sample_nearest alone (synchronous), through the function the rasters call: uv[2n] -> rgba[4n], the
+ * texel's r, g, b with alpha 255 (the shader does not read alpha).  The textured model's counterpart of
+ * shs_legacy_shade_samples, which rejects SHS_SHADING_TEXTURED (its inputs are not that pipeline's). */
+int shs_legacy_sample_nearest(shs_ctx *ctx, int32_t tex_id, int32_t n, const float *uv, uint8_t *rgba);
 
 /* The legacy fragment shaders alone, for n samples (synchronous): the kernel shades each sample with
  * the function the rasters shade a winning pixel with.  uniforms: light_dir, camera_pos, color and
@@ -806,6 +834,8 @@ int shs_group_context(shs_group *g, int32_t rank, shs_ctx **ctx);
 int shs_group_mesh_upload(shs_group *g, const float *positions, int32_t n_verts, const float *normals, int32_t n_normals,
                           const float *uvs, int32_t n_uvs, const uint32_t *indices, int64_t n_indices, int32_t *mesh_id);
 int shs_group_mesh_upload_soup(shs_group *g, const float *positions, const float *normals, int32_t n_tris, int32_t *mesh_id);
+int shs_group_mesh_upload_soup_uv(shs_group *g, const float *positions, const float *normals, const float *uvs, int32_t n_tris,
+                                  int32_t *mesh_id);
 int shs_group_texture_upload(shs_group *g, const uint8_t *rgba, int32_t w, int32_t h, int32_t *tex_id);
 int shs_group_lights_upload(shs_group *g, const shs_culling_light *lights, int32_t n_lights);
 int shs_group_lights_upload_typed(shs_group *g, const shs_culling_light *cull, const shs_light_props *props, int32_t n_lights);
@@ -821,6 +851,10 @@ int shs_group_render_shadow_map(shs_group *g, int32_t w, int32_t h, const float 
                                 int32_t n_casters, float light_viewproj_out[16]);
 int shs_group_render_pbr_forward(shs_group *g, const shs_lib_frame *frame, const shs_lib_draw *draws, int32_t n_draws);
 int shs_group_render_legacy(shs_group *g, const shs_frame_desc *frame, const shs_legacy_draw *draws, int32_t n_draws);
+/* ... with albedo_tex[n_draws] (shs_group_texture_upload ids, or NULL) as shs_render_legacy_batch_tex: the
+ * group call that takes SHS_SHADING_TEXTURED. */
+int shs_group_render_legacy_tex(shs_group *g, const shs_frame_desc *frame, const shs_legacy_draw *draws, const int32_t *albedo_tex,
+                                int32_t n_draws);
 /* Compose the last frame's target (SHS_TARGET_*) on rank 0's context, asynchronously. */
 int shs_group_gather(shs_group *g, int target);
 int shs_group_synchronize(shs_group *g);

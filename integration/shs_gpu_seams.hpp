@@ -8,6 +8,7 @@
 //
 //   Seam 1  LegacyRendererSystemGPU<SceneT, ObjectT, SHADING>: replaces RendererSystem of
 //           hello-3d-primitives/hello_pipeline_{blinn_phong,phong,gouraud,flat,toon,gooch,oren_nayar}_shading.cpp
+//           and hello_pipeline_texture_mapping.cpp
 //           (the 80x80 tile-job loop of process(), :244-313 in the Blinn-Phong demo), and with three
 //           draws per object the split-screen hello_pipeline_normal_zbuffer_debug.cpp.
 //   Seam 3  PassShadowMapGPU / PassPBRForwardGPU: IRenderPass implementations with the ids,
@@ -56,7 +57,9 @@ struct Device {
 //                                                                      SHS_SHADING_BLINN_PHONG>(scene);
 // (SHS_SHADING_PHONG / _GOURAUD / _FLAT in the other three demos; SHS_SHADING_TOON / _GOOCH /
 // _OREN_NAYAR in hello_pipeline_{toon,gooch,oren_nayar}_shading.cpp, whose Uniforms and vertex shader
-// are the Blinn-Phong demo's, as are SHS_SHADING_NORMAL_VIS / _DEPTH_VIS's).  Everything else -- the scene,
+// are the Blinn-Phong demo's, as are SHS_SHADING_NORMAL_VIS / _DEPTH_VIS's; SHS_SHADING_TEXTURED in
+// hello_pipeline_texture_mapping.cpp with ObjectT = SubaruObject, whose geometry->uvs and albedo are passed
+// through -- process() sets use_texture whenever the object has a valid albedo, :336).  Everything else -- the scene,
 // the LogicSystem / Viewer camera update, Canvas::fill_pixel, copy_to_SDLSurface and the SDL loop --
 // is unchanged.  The job system is no longer used for rendering.
 //
@@ -68,7 +71,7 @@ struct Device {
 template <class SceneT, class ObjectT, int SHADING>
 class LegacyRendererSystemGPU : public shs::AbstractSystem {
 public:
-    static_assert(SHADING >= SHS_SHADING_FLAT && SHADING <= SHS_SHADING_DEPTH_VIS, "a legacy shading model");
+    static_assert(SHADING >= SHS_SHADING_FLAT && SHADING <= SHS_SHADING_TEXTURED, "a legacy shading model");
     static constexpr int kTileX = 80, kTileY = 80;   // TILE_SIZE_X / _Y (blinn_phong_shading.cpp:29-30)
 
     explicit LegacyRendererSystemGPU(SceneT *scene, int device_index = 0)
@@ -87,6 +90,7 @@ public:
         const glm::vec3 light_dir_view = glm::normalize(glm::vec3(view * glm::vec4(scene_->light_direction, 0.0f)));
 
         draws_.clear();
+        albedo_.clear();
         for (shs::AbstractObject3D *object : scene_->scene_objects) {
             auto *obj = dynamic_cast<ObjectT *>(object);   // the demo's `if (!monkey) continue;`
             if (!obj) continue;
@@ -112,6 +116,8 @@ public:
             }
             d.color[0] = obj->color.r; d.color[1] = obj->color.g; d.color[2] = obj->color.b; d.color[3] = obj->color.a;
             draws_.push_back(d);
+            // Uniforms::albedo / use_texture (texture_mapping.cpp:56-57): the object's texture, 0 without one
+            if constexpr (SHADING == SHS_SHADING_TEXTURED) albedo_.push_back(texture_id(obj->albedo));
         }
 
         shs_frame_desc f{};
@@ -124,7 +130,8 @@ public:
         // main() clears the canvas black before render (:441, Canvas::fill_pixel); the GPU frame
         // writes every pixel, clear included
         f.clear_color[0] = 0; f.clear_color[1] = 0; f.clear_color[2] = 0; f.clear_color[3] = 255;
-        check(dev_.ctx, shs_render_legacy(dev_.ctx, &f, draws_.data(), static_cast<int32_t>(draws_.size())));
+        check(dev_.ctx, shs_render_legacy_batch_tex(dev_.ctx, &f, draws_.data(), albedo_.empty() ? nullptr : albedo_.data(),
+                                                    static_cast<int32_t>(draws_.size()), 1));
         // Canvas::buffer() (Buffer<Color>, canvas rows bottom-up, RGBA8 -- shs_renderer.hpp:308-342, 753-796)
         // and ZBuffer::buffer() (screen rows as the legacy pipelines index it, :652-702)
         check(dev_.ctx, shs_resolve(dev_.ctx, reinterpret_cast<uint8_t *>(canvas.buffer().raw()), z_buffer_.buffer().raw()));
@@ -143,9 +150,31 @@ private:
         const auto &nrm = obj->geometry->normals;
         static_assert(sizeof(glm::vec3) == 12, "ModelGeometry vectors are packed float triples");
         int32_t id = -1;
-        check(dev_.ctx, shs_mesh_upload_soup(dev_.ctx, glm::value_ptr(tri[0]), glm::value_ptr(nrm[0]),
-                                             static_cast<int32_t>(tri.size() / 3), &id));
+        if constexpr (SHADING == SHS_SHADING_TEXTURED) {
+            // the third stream, ModelGeometry::uvs (one vec2 per corner; vec2(0) where the file has none)
+            const auto &uvs = obj->geometry->uvs;
+            static_assert(sizeof(glm::vec2) == 8, "ModelGeometry::uvs are packed float pairs");
+            check(dev_.ctx, shs_mesh_upload_soup_uv(dev_.ctx, glm::value_ptr(tri[0]), glm::value_ptr(nrm[0]),
+                                                    uvs.size() == tri.size() ? glm::value_ptr(uvs[0]) : nullptr,
+                                                    static_cast<int32_t>(tri.size() / 3), &id));
+        } else {
+            check(dev_.ctx, shs_mesh_upload_soup(dev_.ctx, glm::value_ptr(tri[0]), glm::value_ptr(nrm[0]),
+                                                 static_cast<int32_t>(tri.size() / 3), &id));
+        }
         mesh_ids_.emplace(obj->geometry, id);
+        return id;
+    }
+
+    // A Texture2D (shs_renderer.hpp:351-364) as it stands after the host's loader: texels.raw() is w * h
+    // Colors, texel (x, y) at y * w + x.  Uploaded once per texture; 0 (Uniforms::color) when there is none.
+    int32_t texture_id(const shs::Texture2D *tex) {
+        if (!tex || !tex->valid()) return 0;
+        auto it = tex_ids_.find(tex);
+        if (it != tex_ids_.end()) return it->second;
+        static_assert(sizeof(shs::Color) == 4, "Texture2D::texels are RGBA8");
+        int32_t id = 0;
+        check(dev_.ctx, shs_texture_upload(dev_.ctx, reinterpret_cast<const uint8_t *>(tex->texels.raw()), tex->w, tex->h, &id));
+        tex_ids_.emplace(tex, id);
         return id;
     }
 
@@ -153,7 +182,9 @@ private:
     Device dev_;
     shs::ZBuffer z_buffer_;
     std::vector<shs_legacy_draw> draws_;
+    std::vector<int32_t> albedo_;   // SHS_SHADING_TEXTURED: parallel to draws_
     std::unordered_map<const void *, int32_t> mesh_ids_;
+    std::unordered_map<const void *, int32_t> tex_ids_;
 };
 
 // =====================================================================================================

@@ -139,6 +139,33 @@ int shs_mesh_upload_soup(shs_ctx *ctx, const float *positions, const float *norm
     return SHS_OK;
 }
 
+int shs_mesh_upload_soup_uv(shs_ctx *ctx, const float *positions, const float *normals, const float *uvs, int32_t n_tris,
+                            int32_t *mesh_id) {
+    if (!uvs) return shs_mesh_upload_soup(ctx, positions, normals, n_tris, mesh_id);
+    if (!ctx || !positions || !normals || n_tris <= 0 || !mesh_id) return SHS_ERR_INVALID;
+    if (set_dev(ctx)) return SHS_ERR_HIP;
+    // the UVs share the normals' allocation (DrawGPU has no third pointer): 9 * n_tris floats, then 6 * n_tris
+    Mesh m;
+    const size_t bytes = (size_t)n_tris * 9 * sizeof(float), uv_bytes = (size_t)n_tris * 6 * sizeof(float);
+    HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&m.pos), bytes));
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(&m.nrm), bytes + uv_bytes);
+    if (e == hipSuccess) e = hipMemcpy(m.pos, positions, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(m.nrm, normals, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(m.nrm + (size_t)n_tris * 9, uvs, uv_bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(m.pos);
+        if (m.nrm) (void)hipFree(m.nrm);
+        ctx->err = hipGetErrorString(e);
+        return SHS_ERR_HIP;
+    }
+    m.n_tris = n_tris;
+    m.soup_uv = true;
+    m.live = true;
+    ctx->meshes.push_back(m);
+    *mesh_id = (int32_t)ctx->meshes.size() - 1;
+    return SHS_OK;
+}
+
 int shs_mesh_release(shs_ctx *ctx, int32_t id) {
     if (!ctx || id < 0 || id >= (int32_t)ctx->meshes.size() || !ctx->meshes[id].live) return SHS_ERR_INVALID;
     if (set_dev(ctx)) return SHS_ERR_HIP;
@@ -205,6 +232,25 @@ static void build_draw(const shs_legacy_draw &in, const Mesh &m, int32_t base, D
         o.ocol[i] = (float)in.color[i] / 255.0f;   // glm::vec3(r,g,b) / 255.0f
         o.colf[i] = (float)in.color[i];            // int colour promoted in u.color.r * intensity
     }
+}
+
+// A model-9 draw's texture and UV stream (shs_device.hpp: DrawGPU::pad0, colf).  tex_id 0, or a texture
+// released since the call (a batch re-issued after an overflow): Uniforms::color.
+static void bind_texture(const shs_ctx *ctx, const Mesh &m, int32_t tex_id, DrawGPU &o) {
+    o.pad0 = m.soup_uv ? 1 : 0;
+    std::memset(o.colf, 0, sizeof o.colf);
+    if (tex_id <= 0 || tex_id > (int32_t)ctx->textures.size() || !ctx->textures[(size_t)tex_id - 1].live) return;
+    const Texture &t = ctx->textures[(size_t)tex_id - 1];
+    const uint64_t p = reinterpret_cast<uint64_t>(t.texels);
+    const uint32_t w[4] = {(uint32_t)p, (uint32_t)(p >> 32), (uint32_t)t.w, (uint32_t)t.h};
+    std::memcpy(o.colf, w, sizeof w);
+}
+// The batch's draw i into o, as build_draw, with a textured draw's binding.
+static void build_batch_draw(const shs_ctx *ctx, int i, int32_t base, DrawGPU &o) {
+    const shs_legacy_draw &d = ctx->last_draws[i];
+    build_draw(d, ctx->meshes[d.mesh_id], base, o);
+    if (d.shading == SHS_SHADING_TEXTURED)
+        bind_texture(ctx, ctx->meshes[d.mesh_id], ctx->last_tex.empty() ? 0 : ctx->last_tex[i], o);
 }
 
 static int harvest_slot(shs_ctx *ctx, int k) {
@@ -292,10 +338,15 @@ static int enqueue_frame(shs_ctx *ctx) {
     // device draw table; the frame buffers the pending raster writes must not be reallocated under it
     const size_t npx0 = (size_t)f.width * f.height;
     const bool pipe = ctx->legacy_pipeline && scan && !ghost_list_env && n_draws_all > shs_dev::KARG_DRAWS && !ctx->want_timeline;
+    // A batch with a textured draw runs the kernels compiled with the texture-mapping pipeline (RF_TEX_MODEL),
+    // whose workspace has the side planes: k_pipe never runs one batch's raster with the other kind's setup.
+    bool tex_batch = false;
+    for (int i = 0; i < n_draws_all; ++i) tex_batch = tex_batch || ctx->last_draws[i].shading == SHS_SHADING_TEXTURED;
+    const bool pend_other = ctx->pend.on && ((ctx->pend.fp.flags & shs_dev::RF_TEX_MODEL) != 0u) != tex_batch;
     const bool grows = ctx->color.cap < npx0 * 4 * n_frames || ctx->depth.cap < npx0 * n_frames ||
                        ((f.flags & SHS_FRAME_PREQUANT) && ctx->prequant.cap < npx0 * n_frames) ||
                        ((f.flags & SHS_FRAME_PRESENT) && ctx->present.cap < npx0 * n_frames);
-    if ((!pipe || grows) && flush_pending(ctx)) return SHS_ERR_HIP;
+    if ((!pipe || grows || pend_other) && flush_pending(ctx)) return SHS_ERR_HIP;
 
     // This batch's workspace slot.  Its previous user (batch n - 2) is complete on the host side once
     // its k_setup is (the pinned draw table is rewritten below), and on the device side once its
@@ -309,7 +360,8 @@ static int enqueue_frame(shs_ctx *ctx) {
     if (ws.used) HIP_TRY(ctx, hipEventSynchronize(ws.setup_done));
     *ws.h_ov = 0u;   // the slot's previous setup (the only other writer) is done
 
-    if (ensure(ctx, ws.recs, nt_all) || ensure(ctx, ws.rext, nt_all) || ensure(ctx, ws.shade, nt_all) || ensure(ctx, ws.boxes, nt_all) ||
+    // (a textured batch: the float bboxes, then the three side planes of shs_device.hpp's RF_TEX_MODEL)
+    if (ensure(ctx, ws.recs, nt_all) || ensure(ctx, ws.rext, nt_all * (tex_batch ? 4 : 1)) || ensure(ctx, ws.shade, nt_all) || ensure(ctx, ws.boxes, nt_all) ||
         ensure(ctx, ws.slivers, nt_all))
         return SHS_ERR_HIP;
     const size_t n_bt_all = (size_t)n_tiles * n_frames;
@@ -380,7 +432,7 @@ static int enqueue_frame(shs_ctx *ctx) {
         for (int i = 0; i < n_draws_all; ++i) {
             if (i % std::max(n_draws, 1) == 0) base = 0;
             const shs_legacy_draw &d = ctx->last_draws[i];
-            build_draw(d, ctx->meshes[d.mesh_id], base, ka.d[i]);
+            build_batch_draw(ctx, i, base, ka.d[i]);
             base += ctx->meshes[d.mesh_id].n_tris;
         }
     } else {
@@ -403,7 +455,7 @@ static int enqueue_frame(shs_ctx *ctx) {
         for (int i = 0; i < n_draws_all; ++i) {
             if (i % std::max(n_draws, 1) == 0) base = 0;
             const shs_legacy_draw &d = ctx->last_draws[i];
-            build_draw(d, ctx->meshes[d.mesh_id], base, ws.h_draws[i]);
+            build_batch_draw(ctx, i, base, ws.h_draws[i]);
             base += ctx->meshes[d.mesh_id].n_tris;
         }
         if (same_layout) {
@@ -429,7 +481,7 @@ static int enqueue_frame(shs_ctx *ctx) {
     fp.n_tris = n_tris; fp.n_draws = n_draws;
     fp.clear_rgba = (uint32_t)f.clear_color[0] | ((uint32_t)f.clear_color[1] << 8) | ((uint32_t)f.clear_color[2] << 16) |
                     ((uint32_t)f.clear_color[3] << 24);
-    fp.flags = (f.flags & (SHS_EXPERIMENTS ? ~0u : ~shs_dev::DBG_MASK) & ~(shs_dev::RF_PER_PIXEL | shs_dev::RF_NO_RECS | shs_dev::RF_SHARED_VARY | shs_dev::RF_GHOST_INLINE | shs_dev::RF_XCD_ROWS | shs_dev::RF_FULL_CLEAR | shs_dev::RF_TILE_GROUPS | shs_dev::RF_GROUP_SPANS | shs_dev::RF_EXT_MODELS)) | (ctx->pair_loop ? 0u : shs_dev::RF_PER_PIXEL) |
+    fp.flags = (f.flags & (SHS_EXPERIMENTS ? ~0u : ~shs_dev::DBG_MASK) & ~(shs_dev::RF_PER_PIXEL | shs_dev::RF_NO_RECS | shs_dev::RF_SHARED_VARY | shs_dev::RF_GHOST_INLINE | shs_dev::RF_XCD_ROWS | shs_dev::RF_FULL_CLEAR | shs_dev::RF_TILE_GROUPS | shs_dev::RF_GROUP_SPANS | shs_dev::RF_EXT_MODELS | shs_dev::RF_TEX_MODEL)) | (ctx->pair_loop ? 0u : shs_dev::RF_PER_PIXEL) |
                (full_clear ? shs_dev::RF_FULL_CLEAR : 0u);
     fp.bin_cap = ctx->bin_cap;
     fp.spill_cap = (uint32_t)std::min<size_t>(ws.spill.cap, 0xffffffffu);
@@ -452,7 +504,7 @@ static int enqueue_frame(shs_ctx *ctx) {
     // staged candidates' draw -> matrix -> position chain costs more raster latency than the 184 B of
     // record traffic it removes).
     static const bool no_recs_env = shs_exp_env("SHS_LEGACY_NORECS") && std::atoi(shs_exp_env("SHS_LEGACY_NORECS")) != 0;
-    const bool no_recs = !fp.scan_mode && no_recs_env;
+    const bool no_recs = !fp.scan_mode && no_recs_env && !tex_batch;   // (a textured batch keeps its records)
     if (no_recs) {
         fp.flags |= shs_dev::RF_NO_RECS;
         if (ensure(ctx, ws.tdraw, nt_all)) return SHS_ERR_HIP;
@@ -480,6 +532,7 @@ static int enqueue_frame(shs_ctx *ctx) {
     // every other batch the ones without.
     for (int i = 0; i < n_draws_all; ++i)
         if (ctx->last_draws[i].shading > SHS_SHADING_BLINN_PHONG) fp.flags |= shs_dev::RF_EXT_MODELS;
+    if (tex_batch) fp.flags |= shs_dev::RF_TEX_MODEL;
     // Bin-mode row groups dealt to one XCD (RF_XCD_ROWS): SHS_LEGACY_XCD_ROWS=0 turns it off (timing
     // experiments).
     static const bool xcd_rows_env = [] { const char *e = shs_exp_env("SHS_LEGACY_XCD_ROWS"); return !e || std::atoi(e) != 0; }();
@@ -682,10 +735,10 @@ int shs_legacy_ensure_final(shs_ctx *ctx) {
     return *p.h_ov ? finish_frame(ctx) : SHS_OK;
 }
 
-extern "C" {
-
-int shs_render_legacy_batch(shs_ctx *ctx, const shs_frame_desc *frame, const shs_legacy_draw *draws, int32_t n_draws,
-                            int32_t n_frames) {
+// shs_render_legacy_batch (max_model = SHS_SHADING_DEPTH_VIS: the models it has always taken, in the order
+// it has always checked them) and shs_render_legacy_batch_tex (max_model = SHS_SHADING_TEXTURED).
+static int render_legacy_batch(shs_ctx *ctx, const shs_frame_desc *frame, const shs_legacy_draw *draws, const int32_t *albedo_tex,
+                               int32_t n_draws, int32_t n_frames, int max_model) {
     if (!ctx || !frame || n_draws < 0 || (n_draws > 0 && !draws) || n_frames < 1 || n_frames > SHS_MAX_BATCH_FRAMES)
         return SHS_ERR_INVALID;
     const shs_frame_desc &f = *frame;
@@ -700,9 +753,17 @@ int shs_render_legacy_batch(shs_ctx *ctx, const shs_frame_desc *frame, const shs
             ctx->err = "bad mesh id (not a legacy soup mesh)";
             return SHS_ERR_INVALID;
         }
-        if (draws[i].shading < SHS_SHADING_FLAT || draws[i].shading > SHS_SHADING_DEPTH_VIS) {
+        if (draws[i].shading < SHS_SHADING_FLAT || draws[i].shading > max_model) {
             ctx->err = "bad shading model";
             return SHS_ERR_INVALID;
+        }
+        // (albedo_tex is read for the textured draws alone; 0 = no texture)
+        if (draws[i].shading == SHS_SHADING_TEXTURED && albedo_tex && albedo_tex[i] != 0) {
+            const int32_t t = albedo_tex[i];
+            if (t < 0 || t > (int32_t)ctx->textures.size() || !ctx->textures[(size_t)t - 1].live) {
+                ctx->err = "bad texture id";
+                return SHS_ERR_INVALID;
+            }
         }
     }
     // every frame of a batch submits the same number of triangles (one submission-order layout)
@@ -726,9 +787,23 @@ int shs_render_legacy_batch(shs_ctx *ctx, const shs_frame_desc *frame, const shs
     }
     ctx->frame = f;
     ctx->last_draws.assign(draws, draws + n_all);
+    if (albedo_tex) ctx->last_tex.assign(albedo_tex, albedo_tex + n_all);
+    else ctx->last_tex.clear();
     ctx->last_n_frames = n_frames;
     ctx->frame_draws = n_draws;
     return enqueue_frame(ctx);
+}
+
+extern "C" {
+
+int shs_render_legacy_batch(shs_ctx *ctx, const shs_frame_desc *frame, const shs_legacy_draw *draws, int32_t n_draws,
+                            int32_t n_frames) {
+    return render_legacy_batch(ctx, frame, draws, nullptr, n_draws, n_frames, SHS_SHADING_DEPTH_VIS);
+}
+
+int shs_render_legacy_batch_tex(shs_ctx *ctx, const shs_frame_desc *frame, const shs_legacy_draw *draws, const int32_t *albedo_tex,
+                                int32_t n_draws, int32_t n_frames) {
+    return render_legacy_batch(ctx, frame, draws, albedo_tex, n_draws, n_frames, SHS_SHADING_TEXTURED);
 }
 
 int shs_render_legacy(shs_ctx *ctx, const shs_frame_desc *frame, const shs_legacy_draw *draws, int32_t n_draws) {
@@ -759,6 +834,32 @@ int shs_legacy_shade_samples(shs_ctx *ctx, const shs_legacy_draw *uniforms, int3
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e == hipSuccess && rgba) e = hipMemcpy(rgba, cw, N * 4, hipMemcpyDeviceToHost);
     if (e == hipSuccess && prequant) e = hipMemcpy(prequant, pq, 4 * N * sizeof(float), hipMemcpyDeviceToHost);
+    (void)hipFree(buf);
+    if (e != hipSuccess) {
+        ctx->err = hipGetErrorString(e);
+        return SHS_ERR_HIP;
+    }
+    return SHS_OK;
+}
+
+int shs_legacy_sample_nearest(shs_ctx *ctx, int32_t tex_id, int32_t n, const float *uv, uint8_t *rgba) {
+    if (!ctx || n < 0 || (n > 0 && (!uv || !rgba))) return SHS_ERR_INVALID;
+    if (tex_id <= 0 || tex_id > (int32_t)ctx->textures.size() || !ctx->textures[(size_t)tex_id - 1].live) {
+        ctx->err = "bad texture id";
+        return SHS_ERR_INVALID;
+    }
+    if (n == 0) return SHS_OK;
+    const Texture &t = ctx->textures[(size_t)tex_id - 1];
+    if (set_dev(ctx)) return SHS_ERR_HIP;
+    float2 *buf = nullptr;   // n (u, v), then n colour words and n texel indices
+    const size_t N = (size_t)n;
+    HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&buf), N * (sizeof(float2) + 2 * sizeof(uint32_t))));
+    uint32_t *cw = reinterpret_cast<uint32_t *>(buf + N);
+    int32_t *ix = reinterpret_cast<int32_t *>(cw + N);
+    hipError_t e = hipMemcpy(buf, uv, N * sizeof(float2), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = shs_internal::tex::launch_sample_nearest(t.texels, t.w, t.h, n, buf, cw, ix, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e == hipSuccess) e = hipMemcpy(rgba, cw, N * 4, hipMemcpyDeviceToHost);
     (void)hipFree(buf);
     if (e != hipSuccess) {
         ctx->err = hipGetErrorString(e);

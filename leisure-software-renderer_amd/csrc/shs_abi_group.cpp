@@ -247,6 +247,18 @@ int shs_group_mesh_upload_soup(shs_group *g, const float *positions, const float
     return SHS_OK;
 }
 
+int shs_group_mesh_upload_soup_uv(shs_group *g, const float *positions, const float *normals, const float *uvs, int32_t n_tris,
+                                  int32_t *mesh_id) {
+    if (!g || !mesh_id) return SHS_ERR_INVALID;
+    std::vector<int32_t> ids(g->ctx.size(), -1);
+    const int rc = for_ranks(g, [&](int r, shs_ctx *c) { return shs_mesh_upload_soup_uv(c, positions, normals, uvs, n_tris, &ids[r]); });
+    if (rc) return rc;
+    for (int32_t id : ids)
+        if (id != ids[0]) { g->err = "mesh ids differ across ranks (upload every mesh through the group)"; return SHS_ERR_INVALID; }
+    *mesh_id = ids[0];
+    return SHS_OK;
+}
+
 int shs_group_texture_upload(shs_group *g, const uint8_t *rgba, int32_t w, int32_t h, int32_t *tex_id) {
     if (!g || !tex_id) return SHS_ERR_INVALID;
     std::vector<int32_t> ids(g->ctx.size(), 0);
@@ -321,6 +333,18 @@ int shs_group_render_legacy(shs_group *g, const shs_frame_desc *frame, const shs
         f.shard_rank = r;
         f.shard_count = n;
         return shs_render_legacy(c, &f, draws, n_draws);
+    });
+}
+
+int shs_group_render_legacy_tex(shs_group *g, const shs_frame_desc *frame, const shs_legacy_draw *draws, const int32_t *albedo_tex,
+                                int32_t n_draws) {
+    if (!g || !frame) return SHS_ERR_INVALID;
+    const int n = (int)g->ctx.size();
+    return for_ranks(g, [&](int r, shs_ctx *c) {
+        shs_frame_desc f = *frame;
+        f.shard_rank = r;
+        f.shard_count = n;
+        return shs_render_legacy_batch_tex(c, &f, draws, albedo_tex, n_draws, 1);
     });
 }
 

@@ -944,6 +944,11 @@ int shs_texture_release(shs_ctx *ctx, int32_t tex_id) {
         for (int32_t id : ctx->sky_face_tex)
             if (id == tex_id) { ctx->err = "texture is a face of the current sky (shs_lib_set_sky another first)"; return SHS_ERR_INVALID; }
     if (set_dev(ctx)) return SHS_ERR_HIP;
+    {   // a legacy batch in flight may sample it (SHS_SHADING_TEXTURED): its raster is launched and, should
+        // it have overflowed a capacity, re-issued while the texture still exists -- as a mesh's release
+        const int rc = shs_legacy_ensure_final(ctx);
+        if (rc) return rc;
+    }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->setup_stream));
     Texture &t = ctx->textures[(size_t)tex_id - 1];

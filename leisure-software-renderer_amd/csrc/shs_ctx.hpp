@@ -42,6 +42,7 @@ struct Mesh {
     float4 *cbox = nullptr;          // library mesh: per 256-triangle chunk its model-space box (min, max)
     uint32_t *orig = nullptr;        // library mesh stored in spatial order: per stored triangle its MeshData index
     bool borrowed = false;           // shs_mesh_share: another context's buffers (never freed here)
+    bool soup_uv = false;            // legacy soup uploaded with UVs: 6 floats per triangle follow nrm's 9 * n_tris
 };
 
 // A Texture2DData (resources/texture.hpp:23-49) on the device: w * h Color texels, y * w + x.
@@ -146,6 +147,7 @@ struct shs_ctx {
     // last frame (re-issued if a bin capacity overflowed)
     shs_frame_desc frame{};
     std::vector<shs_legacy_draw> last_draws;
+    std::vector<int32_t> last_tex;   // the last batch's albedo_tex ids, parallel to last_draws (empty: none given)
     bool have_frame = false;
     bool need_check = false;
     int last_n_frames = 1;           // frames of the last batch (last_draws holds n_frames x frame_draws)

@@ -20,7 +20,7 @@ struct alignas(16) DrawGPU {
     int32_t tri_base;        // global index of this draw's first triangle (submission order)
     int32_t n_tris;
     int32_t shading;         // SHS_SHADING_*
-    int32_t pad0;
+    int32_t pad0;            // SHS_SHADING_TEXTURED: bit 0 = UVs follow the normals (else 0)
     float mvp[16];           // Uniforms::mvp
     float model[16];         // Uniforms::model (Flat: Uniforms::mv)
     float nmat[12];          // mat3(transpose(inverse(model))) (Flat: mat3(mv)), col-major, 9 used
@@ -172,6 +172,16 @@ constexpr uint32_t RF_GROUP_SPANS = 1u << 23;
 // (frame flags bit 24, set by the host): the launch wrappers take the compilation that has their shaders
 // (shs_legacy_ext.hip).  No kernel reads it.
 constexpr uint32_t RF_EXT_MODELS = 1u << 24;
+// A draw of the batch has SHS_SHADING_TEXTURED (frame flags bit 25, set by the host): the launch wrappers
+// take the third compilation (shs_legacy_tex.hip), whose records carry the corners' 1 / w.  No kernel
+// reads it.  Such a batch's FrameBuffers::rext holds four planes of n_frames * n_tris float4s (tex_side):
+// 0 the float bboxes; 1 per triangle (invw0, invw1, invw2, 1.0f for a model-9 triangle else 0); 2 and 3
+// a model-9 triangle's uv_i * invw_i: (u0 v0 u1 v1) and (u2 v2 0 0).
+constexpr uint32_t RF_TEX_MODEL = 1u << 25;
+constexpr int SHADING_TEXTURED = 9;   // SHS_SHADING_TEXTURED
+// A model-9 draw's DrawGPU: pad0 bit 0 = the mesh has UVs (6 floats per triangle after the normals'
+// 9 * n_tris floats, else vec2(0) per corner); colf = its texture, {texel pointer lo, hi, w, h} as bits
+// (a null pointer: Uniforms::color, the shader's else branch).
 #ifndef SHS_GROUP_X
 #define SHS_GROUP_X 2                // (-DSHS_GROUP_X=.. -DSHS_GROUP_Y=..: timing experiments)
 #endif

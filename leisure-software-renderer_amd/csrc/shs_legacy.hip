@@ -56,15 +56,68 @@ template <typename T> __device__ __forceinline__ void LEGACY_STORE(T v, T *p) { 
 // batch that draws one of them (RF_EXT_MODELS).  Without the macro none of their code is compiled, so
 // the kernels of the Flat .. Blinn-Phong batches are the same instructions and registers as before the
 // models existed.
+//
+// The texture-mapping pipeline (SHS_SHADING_TEXTURED, hello_pipeline_texture_mapping.cpp:66-116, 205-294)
+// is a third compilation (shs_legacy_tex.hip defines SHS_LEGACY_TEX as well: namespace shs_dev::tex, the
+// extended models included, for batches that mix them), launched only for a batch that draws model 9
+// (RF_TEX_MODEL).  Its draw_triangle_tile tests another depth -- perspective-correct, from the corners'
+// 1 / w -- so this compilation's TriRec carries them; everything it adds sits behind SHS_LEGACY_TEX.
+#ifdef SHS_LEGACY_TEX
+#define SHS_EXT_NS tex
+#define SHS_TEX_PARAM(decl) , decl
+#define SHS_TEX_ARG(x) , x
+#define SHS_TEX_ONLY(...) __VA_ARGS__
+#else
+#define SHS_EXT_NS ext
+#define SHS_TEX_PARAM(decl)
+#define SHS_TEX_ARG(x)
+#define SHS_TEX_ONLY(...)
+#endif
 namespace shs_dev {
 #ifdef SHS_LEGACY_EXT
-namespace ext {
+namespace SHS_EXT_NS {
 using shs_dev::mark_run;     // (shs_wave.hpp's overloads, beside the ones declared below)
 using shs_dev::pair_owner;
 constexpr bool EXT_MODELS = true;
 #else
 constexpr bool EXT_MODELS = false;
 #endif
+
+#ifdef SHS_LEGACY_TEX
+// The record with the corners' invw = 1.0f / w (texture_mapping.cpp:228-229) for a model-9 triangle
+// (tex != 0; z0..z2 then hold q_i = (clip_z_i * invw_i) * invw_i, :230 and :260-262).  Other triangles of
+// the batch: zeros.  112 B = seven float4s wherever a record is copied whole (REC4).
+struct alignas(16) TriRec : shs_dev::TriRec {
+    float iw0, iw1, iw2;
+    uint32_t tex;
+};
+static_assert(sizeof(TriRec) == 112, "the base record, then one float4");
+__device__ __forceinline__ void set_iw(TriRec &r, float4 iw) {
+    r.iw0 = iw.x; r.iw1 = iw.y; r.iw2 = iw.z;
+    r.tex = __float_as_uint(iw.w);
+}
+// Plane k of a textured batch's side array (RF_TEX_MODEL in shs_device.hpp), entry tri of the frame fb views.
+__device__ __forceinline__ float4 *tex_side(const FrameParams &fp, const FrameBuffers &fb, int k, uint32_t tri) {
+    return fb.rext + (size_t)k * (size_t)fp.n_frames * (size_t)fp.n_tris + tri;
+}
+#endif
+constexpr int REC4 = (int)(sizeof(TriRec) / sizeof(float4));   // a whole record's float4s
+
+// The depth draw_triangle_tile tests and stores at barycentrics (u, v, w).  Flat .. the depth visualiser:
+// the barycentric sum of the corners' NDC z (blinn_phong_shading.cpp:228).  SHS_SHADING_TEXTURED
+// (texture_mapping.cpp:256-263): invw_sum = (u invw0 + v invw1) + w invw2, the pixel skipped when it is
+// <= 0, else z_over_w / invw_sum with z_over_w the same sum over q_i -- a skipped pixel returns NaN, which
+// like a NaN depth passes no z test (a NaN invw_sum is not skipped there and divides to NaN).
+__device__ __forceinline__ float tri_depth(const TriRec &r, float u, float v, float w) {
+    const float z = (u * r.z0 + v * r.z1) + w * r.z2;
+#ifdef SHS_LEGACY_TEX
+    if (r.tex) {
+        const float s = (u * r.iw0 + v * r.iw1) + w * r.iw2;
+        return s <= 0.0f ? __builtin_nanf("") : z / s;
+    }
+#endif
+    return z;
+}
 
 // ---- k_setup --------------------------------------------------------------------------------
 
@@ -153,7 +206,7 @@ __device__ __forceinline__ TriRec rec_from(const float4 *s) {
     TriRec r;
     float4 *d = reinterpret_cast<float4 *>(&r);
 #pragma unroll
-    for (int j = 0; j < 6; ++j) d[j] = s[j];
+    for (int j = 0; j < REC4; ++j) d[j] = s[j];
     return r;
 }
 
@@ -178,6 +231,7 @@ __device__ __forceinline__ TriRec rec_from_hot(const FrameParams &fp, float4 h0,
     r.fminx = e.x; r.fmaxx = e.y; r.fminy = e.z; r.fmaxy = e.w;
     r.ibx = pack16(floor_clamped(e.x, 0, fp.W), floor_clamped(e.y, -1, fp.W - 1));
     r.iby = pack16(floor_clamped(e.z, 0, fp.H), floor_clamped(e.w, -1, fp.H - 1));
+    SHS_TEX_ONLY(set_iw(r, make_float4(0.f, 0.f, 0.f, 0.f));)   // (the callers with a side entry set it)
     return r;
 }
 
@@ -222,14 +276,24 @@ __device__ __forceinline__ void load9(const float *src, float (&v)[9]) {
 }
 
 // VS position of one corner (mvp * vec4(p, 1)) and Canvas::clip_to_screen (shs_renderer.hpp:823-831).
+// SHS_LEGACY_TEX, tex (a model-9 draw): iw = 1.0f / w and sz = (clip z * iw) * iw, the corner's term of
+// z_over_w (texture_mapping.cpp:228-230, :260-262: ndc = vec3(position) * invw, then ndc.z * invw); x and
+// y keep clip_to_screen's divides (:225).  Otherwise iw = 0.
 __device__ __forceinline__ void vertex_screen(const FrameParams &fp, const float *mvp, float x, float y, float z, float &sx,
-                                              float &sy, float &sz) {
+                                              float &sy, float &sz SHS_TEX_PARAM(bool tex) SHS_TEX_PARAM(float &iw)) {
     float cx, cy, cz, cw;
     m4p(mvp, x, y, z, cx, cy, cz, cw);
     const float nx = cx / cw, ny = cy / cw, nz = cz / cw;
     sx = (nx + 1.0f) * 0.5f * (float)(fp.W - 1);
     sy = (1.0f - ny) * 0.5f * (float)(fp.H - 1);
     sz = nz;
+#ifdef SHS_LEGACY_TEX
+    iw = 0.0f;
+    if (tex) {
+        iw = 1.0f / cw;
+        sz = (cz * iw) * iw;
+    }
+#endif
 }
 
 // The part of a record that is plain float arithmetic on its screen corners: the per-triangle half of
@@ -254,6 +318,7 @@ __device__ __forceinline__ TriRec rec_geometry(int draw, int local, const float 
     r.fmaxx = g_max(g_max(sx[0], sx[1]), sx[2]);
     r.fminy = g_min(g_min(sy[0], sy[1]), sy[2]);
     r.fmaxy = g_max(g_max(sy[0], sy[1]), sy[2]);
+    SHS_TEX_ONLY(set_iw(r, make_float4(0.f, 0.f, 0.f, 0.f));)   // (quad_make_rec / make_rec set a model-9 triangle's)
     return r;
 }
 
@@ -303,9 +368,19 @@ __device__ __forceinline__ TriRec rec_from_screen(const FrameParams &fp, int dra
 
 __device__ __forceinline__ TriRec make_rec(const FrameParams &fp, const DrawGPU &dr, int draw, int local, const float (&p)[9]) {
     float sx[3], sy[3], sz[3];
+#ifdef SHS_LEGACY_TEX
+    const bool tex = dr.shading == SHADING_TEXTURED;
+    float iw[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) vertex_screen(fp, dr.mvp, p[3 * k], p[3 * k + 1], p[3 * k + 2], sx[k], sy[k], sz[k], tex, iw[k]);
+    TriRec r = rec_from_screen(fp, draw, local, sx, sy, sz);
+    set_iw(r, make_float4(iw[0], iw[1], iw[2], tex ? 1.0f : 0.0f));
+    return r;
+#else
 #pragma unroll
     for (int k = 0; k < 3; ++k) vertex_screen(fp, dr.mvp, p[3 * k], p[3 * k + 1], p[3 * k + 2], sx[k], sy[k], sz[k]);
     return rec_from_screen(fp, draw, local, sx, sy, sz);
+#endif
 }
 
 // ---- quad-lane triangle setup ---------------------------------------------------------------
@@ -329,11 +404,22 @@ __device__ __forceinline__ float quad_bcast(float v, int k) {
 __device__ __forceinline__ TriRec quad_make_rec(const FrameParams &fp, const DrawGPU &dr, int draw, int local,
                                                 const float (&p3)[3]) {
     float vx, vy, vz;
-    vertex_screen(fp, dr.mvp, p3[0], p3[1], p3[2], vx, vy, vz);
     float sx[3], sy[3], sz[3];
+#ifdef SHS_LEGACY_TEX
+    const bool tex = dr.shading == SHADING_TEXTURED;
+    float viw, iw[3];
+    vertex_screen(fp, dr.mvp, p3[0], p3[1], p3[2], vx, vy, vz, tex, viw);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { sx[k] = quad_bcast(vx, k); sy[k] = quad_bcast(vy, k); sz[k] = quad_bcast(vz, k); iw[k] = quad_bcast(viw, k); }
+    TriRec r = rec_from_screen(fp, draw, local, sx, sy, sz);
+    set_iw(r, make_float4(iw[0], iw[1], iw[2], tex ? 1.0f : 0.0f));
+    return r;
+#else
+    vertex_screen(fp, dr.mvp, p3[0], p3[1], p3[2], vx, vy, vz);
 #pragma unroll
     for (int k = 0; k < 3; ++k) { sx[k] = quad_bcast(vx, k); sy[k] = quad_bcast(vy, k); sz[k] = quad_bcast(vz, k); }
     return rec_from_screen(fp, draw, local, sx, sy, sz);
+#endif
 }
 
 // Index of the draw owning triangle gid, and whether the whole wave shares it (then the draw's
@@ -507,11 +593,11 @@ __device__ __forceinline__ int edge_coord(int i, int before, int n_rt, int after
 }
 
 struct GhostScratch {           // per-wave LDS
-    float4 rec[6];
+    float4 rec[REC4];
 };
 
 struct SliverRecs {             // per-wave LDS (RF_GHOST_INLINE): the records of the wave's 16 triangles' slivers
-    float4 rec[16 * 6];
+    float4 rec[16 * REC4];
 };
 
 // The draw of triangle gid from its setup block's first draw d0 (FrameBuffers::bdraw): a block of 64
@@ -698,7 +784,7 @@ __device__ __forceinline__ void sliver_pixels(const FrameParams &fp, const Frame
                 const bool in_ibox = px >= ix0 && px <= ix1 && py >= iy0 && py <= iy1;   // k_raster's part
                 if (!in_ibox && (fp.count == 1 || owned_bin_tile(fp, px / TILE, py / TILE)) &&
                     bary_pass(t, (float)px + 0.5f, (float)py + 0.5f, u, v, w)) {
-                    z = (u * t.z0 + v * t.z1) + w * t.z2;
+                    z = tri_depth(t, u, v, w);
                     pass = z < FLT_MAX;   // NaN / FLT_MAX never pass the strict z test
                 }
             }
@@ -738,7 +824,7 @@ __device__ __forceinline__ void ghost_wave(const FrameParams &fp, const FrameBuf
         if (lane == src) {
             const float4 *q = reinterpret_cast<const float4 *>(&r);
 #pragma unroll
-            for (int j = 0; j < 6; ++j) gs.rec[j] = q[j];
+            for (int j = 0; j < REC4; ++j) gs.rec[j] = q[j];
         }
         wave_lds_sync();
         const TriRec t = rec_from(gs.rec);
@@ -839,6 +925,7 @@ __device__ __forceinline__ void quad_store_rec_at(TriRec *rec, const TriRec &r) 
         }
         dst[j] = make_float2(x, y);
     }
+    SHS_TEX_ONLY(if (q == 0) reinterpret_cast<float4 *>(rec)[6] = make_float4(r.iw0, r.iw1, r.iw2, __uint_as_float(r.tex));)
 }
 
 // The stored record (TriHot) and, for ghosts, the float bbox.
@@ -873,15 +960,37 @@ __device__ __forceinline__ uint32_t setup_quad(const FrameParams &fp, const Fram
         // winner); its varyings are, in the other frames, when frame 0's are shared (quad-uniform tests)
         const bool culled = r.flags & TRI_CULLED;
         if (!culled) quad_store_rec(fb, tri, r);
+#ifdef SHS_LEGACY_TEX
+        // every kept triangle's side entry (zeros unless model 9: the rasters stage it with each candidate)
+        if (!culled && q == 0) *tex_side(fp, fb, 1, (uint32_t)tri) = make_float4(r.iw0, r.iw1, r.iw2, __uint_as_float(r.tex));
+#endif
         if (vary && (!culled || (fp.flags & RF_SHARED_VARY))) {
             f3 a, nr;
             corner_varyings(dr, p3, n3, a, nr);
+#ifdef SHS_LEGACY_TEX
+            if (dr.shading == SHADING_TEXTURED) {
+                // world_pos_i * invw_i and uv_i * invw_i (texture_mapping.cpp:277-279, :285-287: the
+                // reference forms them per pixel from these pixel-independent operands -- the same bits);
+                // this lane's corner.  A mesh without UVs: vec2(0) per corner (shs_renderer.hpp:1289).
+                const float iwq = q == 0 ? r.iw0 : q == 1 ? r.iw1 : r.iw2;
+                a = sc3(a, iwq);
+                float cu = 0.0f, cv = 0.0f;
+                if (dr.pad0 & 1) {
+                    const float *T = dr.nrm + 9 * (size_t)dr.n_tris + 6 * (size_t)local + 2 * qv;
+                    cu = T[0]; cv = T[1];
+                }
+                if (q < 3) {
+                    float *dst = reinterpret_cast<float *>(tex_side(fp, fb, q < 2 ? 2 : 3, (uint32_t)tri)) + (q == 1 ? 2 : 0);
+                    dst[0] = cu * iwq; dst[1] = cv * iwq;
+                }
+            }
+#endif
             quad_store_shade(fb, tri, dbase + d, dr.shading, a, nr);   // the draw-table index of the batch
         }
     }
     if (q == 0) fb.boxes[tri] = make_uint2(r.gbx, r.gby);   // culled: the empty box (0, -1)
     if (sliv && (r.flags & (TRI_UNBOUNDED | TRI_CULLED)) == TRI_UNBOUNDED)   // quad-uniform
-        quad_store_rec_at(reinterpret_cast<TriRec *>(sliv + ((__lane_id() >> 2) & 15) * 6), r);
+        quad_store_rec_at(reinterpret_cast<TriRec *>(sliv + ((__lane_id() >> 2) & 15) * REC4), r);
     gbox = make_uint2(r.gbx, r.gby);
     return r.flags;
 }
@@ -1044,7 +1153,7 @@ __device__ __forceinline__ void setup_block(const FrameParams &fp, const FrameBu
             const int src = __ffsll((unsigned long long)todo) - 1;
             todo &= todo - 1;
             wave_lds_sync();   // the quads' record stores are complete
-            const TriRec t = rec_from(sliv + (src >> 2) * 6);
+            const TriRec t = rec_from(sliv + (src >> 2) * REC4);
             sliver_pixels(fp, fb, cnt, t, (uint32_t)__shfl(tri, src), (uint32_t)frame, 0, 64);
         }
     }
@@ -1118,8 +1227,9 @@ __global__ __launch_bounds__(256, BIN ? SHS_BIN_SETUP_WAVES : SHS_SCAN_SETUP_WAV
 constexpr int GHOST_LIST_BLOCKS = SHS_GHOST_BLOCKS;
 
 // A wave's items are known up front: lane j loads the sliver entry of its j-th next item in one round
-// trip.  (It shades nothing: one compilation serves every batch.)
-#ifndef SHS_LEGACY_EXT
+// trip.  (It shades nothing: one compilation serves every batch but the textured ones, whose slivers'
+// depth needs the side entries.)
+#if !defined(SHS_LEGACY_EXT) || defined(SHS_LEGACY_TEX)
 __global__ __launch_bounds__(256) void k_ghost(FrameParams fp, FrameBuffers fb_all) {
     uint32_t *cnt = fb_all.counters + fp.parity * CSET;
     const int n = (int)min(cnt[C_SLIVER], (uint32_t)fp.n_tris * (uint32_t)fp.n_frames);
@@ -1140,9 +1250,21 @@ __global__ __launch_bounds__(256) void k_ghost(FrameParams fp, FrameBuffers fb_a
         for (int k = 0; k < 16; ++k) h[k] = src[k];
 #pragma unroll
         for (int k = 0; k < 4; ++k) bb[k] = ext[k];
+#ifdef SHS_LEGACY_TEX
+        ConstF *side = (ConstF *)(fb_all.rext + ((size_t)fp.n_frames + frame) * fp.n_tris + tri);   // plane 1 (tex_side)
+        float iw[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) iw[k] = side[k];
+        TriRec r = rec_from_hot(fp, make_float4(h[0], h[1], h[2], h[3]), make_float4(h[4], h[5], h[6], h[7]),
+                                make_float4(h[8], h[9], h[10], h[11]), make_float4(h[12], h[13], h[14], h[15]),
+                                make_float4(bb[0], bb[1], bb[2], bb[3]));
+        set_iw(r, make_float4(iw[0], iw[1], iw[2], iw[3]));
+        return r;
+#else
         return rec_from_hot(fp, make_float4(h[0], h[1], h[2], h[3]), make_float4(h[4], h[5], h[6], h[7]),
                             make_float4(h[8], h[9], h[10], h[11]), make_float4(h[12], h[13], h[14], h[15]),
                             make_float4(bb[0], bb[1], bb[2], bb[3]));
+#endif
     };
     for (int base = gw; base < n_items; base += 64 * waves) {   // wave-uniform
         const int mine = base + lane * waves;
@@ -1368,6 +1490,57 @@ __device__ __forceinline__ void interp_varyings(const ShadeRec &sr, float u, flo
     interp_varyings(sr, sr.shading, u, v, w, A, N);
 }
 
+#ifdef SHS_LEGACY_TEX
+// sample_nearest (shs_renderer.hpp:367-377) of a w x h texture, texel (x, y) at y * w + x (Texture2D::texels
+// as the host's loader leaves it): one coordinate -> its texel column / row.  Math::saturate is
+// (v < 0) ? 0 : (v > 1 ? 1 : v), so a NaN stays NaN; std::lround rounds halves away from zero -- the
+// product lies in [0, n - 1], where that is trunc plus one when the (exact) fraction is >= 0.5; then the
+// integer clamp.  A NaN coordinate: glibc's lroundf on x86-64 returns LONG_MIN (the conversion's
+// "integer indefinite"), whose (int) is 0, which the clamp keeps -- texel column / row 0, spelled out here
+// as byte_x86 spells its conversion (tests/legacy_texture_ref prints what the restatement gives).
+__device__ __forceinline__ int nearest_coord(float c, int n) {
+    const float s = (c < 0.0f) ? 0.0f : (c > 1.0f ? 1.0f : c);
+    const float x = s * (float)(n - 1);
+    if (!(x == x)) return 0;
+    const float t = truncf(x);
+    const int i = (int)t + ((x - t >= 0.5f) ? 1 : 0);
+    return min(max(i, 0), n - 1);
+}
+// ... the texel's index and its Color as vec3(tc.r, tc.g, tc.b) / 255.0f (texture_mapping.cpp:101-102;
+// alpha is not read).
+__device__ __forceinline__ int nearest_index(int tw, int th, float tu, float tv) {
+    return nearest_coord(tv, th) * tw + nearest_coord(tu, tw);
+}
+__device__ __forceinline__ f3 texel_color(const uint32_t *texels, int index) {
+    const uint32_t tc = texels[index];
+    return f3{(float)(tc & 0xffu) / 255.0f, (float)((tc >> 8) & 0xffu) / 255.0f, (float)((tc >> 16) & 0xffu) / 255.0f};
+}
+
+// A model-9 winner (texture_mapping.cpp:256, :269-288, then the FS :79-116): the normal is the affine sum
+// (shade_interp normalises it), world position and UV the sums over value_i * invw_i divided by invw_sum
+// (glm's vec / scalar: each component), and the Blinn-Phong body shades with baseColor from the sampler --
+// shade_interp's model 3 with the draw's ocol replaced.  du[3] holds the draw's texture (DrawGPU::colf of
+// a model-9 draw); a null pointer leaves ocol, Uniforms::color (:103-105).
+__device__ __forceinline__ void shade_textured(const FrameParams &fp, const FrameBuffers &fb, uint32_t id, const TriRec &r,
+                                               const ShadeRec &sr, const float4 (&du)[4], float u, float v, float w, float pre[3]) {
+    float4 d4[4] = {du[0], du[1], du[2], du[3]};
+    f3 A, N;
+    interp_varyings(sr, SHADING_TEXTURED, u, v, w, A, N);
+    const float s = (u * r.iw0 + v * r.iw1) + w * r.iw2;
+    A = f3{A.x / s, A.y / s, A.z / s};
+    const uint32_t *texels = global_ptr(reinterpret_cast<const uint32_t *>((uint64_t)__float_as_uint(d4[3].x) |
+                                                                             ((uint64_t)__float_as_uint(d4[3].y) << 32)));
+    if (texels) {
+        const float4 ta = *tex_side(fp, fb, 2, id), tb = *tex_side(fp, fb, 3, id);
+        const float su = (u * ta.x + v * ta.z) + w * tb.x, sv = (u * ta.y + v * ta.w) + w * tb.y;
+        const int tw = __float_as_int(d4[3].z), th = __float_as_int(d4[3].w);
+        const f3 base = texel_color(texels, nearest_index(tw, th, su / s, sv / s));
+        d4[2] = make_float4(base.x, base.y, base.z, 0.0f);
+    }
+    shade_interp(d4, 3, A, N, pre);
+}
+#endif
+
 __device__ __forceinline__ void shade_winner(const float4 *du, const ShadeRec &sr, float u, float v, float w, float pre[3]) {
     const float4 d4[4] = {du[0], du[1], du[2], du[3]};
     f3 A, N;
@@ -1407,12 +1580,16 @@ __device__ __forceinline__ bool pixel_test(const FrameParams &fp, const TriRec &
     }
     float u, v, w;
     if (!(test && bary_pass(r, (float)px + 0.5f, (float)py + 0.5f, u, v, w))) return false;
-    z = (u * r.z0 + v * r.z1) + w * r.z2;
+    z = tri_depth(r, u, v, w);
     return z < FLT_MAX;   // NaN and FLT_MAX never beat the FLT_MAX clear
 }
 
 constexpr int RCHUNK = 64;         // candidate records staged per pass (one wave scans their areas)
+#ifdef SHS_LEGACY_TEX
+constexpr int LDS_DRAWS = 48;      // (the staged side entries take the 1 KB of sixteen draws: the same LDS in all)
+#else
 constexpr int LDS_DRAWS = 64;      // draws whose shading uniforms are kept in LDS
+#endif
 constexpr int PAIR_WORDS = RCHUNK * RTW * RTH / 64;   // pair-start bitmap words (a box is <= 256 px)
 constexpr int PAIR_CAP = PAIR_WORDS * 64;             // pairs one pass lays out (groups: the rest in further passes)
 constexpr uint32_t SLOT_NONE = 127u;                  // key slot field: winner not staged in LDS
@@ -1432,6 +1609,9 @@ __device__ __forceinline__ void key_winner(unsigned long long key, bool slot_key
 struct RasterShared {
     float4 rec[RCHUNK * 4];           // staged triangle records (TriHot, 4 KB)
     float4 ext[RCHUNK];               // ... their float bboxes (ghosts; every candidate in scan mode, 1 KB)
+#ifdef SHS_LEGACY_TEX
+    float4 iw[RCHUNK];                // ... their side entries (invw0 invw1 invw2, model 9 or 0; tex_side plane 1, 1 KB)
+#endif
     float4 srec[RCHUNK * 5];          // staged shading records (single-pass tiles, 5 KB)
     unsigned long long key[RTH * RTW];// per-pixel (z, index) keys (2 KB)
     unsigned long long bits[PAIR_WORDS]; // bit k: a staged candidate's pairs start at pair k (2 KB)
@@ -1441,7 +1621,7 @@ struct RasterShared {
     uint32_t wtot[4];                 // per wave: pairs << 11 | segments (the staging pass's block prefix)
     uint32_t id[RCHUNK];
     uint32_t cand[CAND];
-    float4 du[LDS_DRAWS * 4];         // per-draw {light, cam, ocol, colf} (4 KB)
+    float4 du[LDS_DRAWS * 4];         // per-draw {light, cam, ocol, colf} (4 KB; SHS_LEGACY_TEX: 3 KB)
     unsigned long long smask[4];      // stale clear: per wave, the tiles of a 256-tile chunk that need the clear
     uint32_t nc, item, cov, maxbin, npairs;
     uint32_t nclr;                    // tiles this workgroup's strips cleared (rstat)
@@ -1529,7 +1709,8 @@ __device__ __forceinline__ void stage_from_mesh(const FrameParams &fp, const Fra
         n3[0] = Nn[0]; n3[1] = Nn[1]; n3[2] = Nn[2];
     }
     float vx, vy, vz;
-    vertex_screen(fp, dr.mvp, p3[0], p3[1], p3[2], vx, vy, vz);
+    SHS_TEX_ONLY(float no_iw;)   // (RF_NO_RECS batches draw no model 9: the host keeps their records)
+    vertex_screen(fp, dr.mvp, p3[0], p3[1], p3[2], vx, vy, vz SHS_TEX_ARG(false) SHS_TEX_ARG(no_iw));
     float sx[3], sy[3], sz[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) { sx[k] = quad_bcast(vx, k); sy[k] = quad_bcast(vy, k); sz[k] = quad_bcast(vz, k); }
@@ -1556,11 +1737,13 @@ __device__ __forceinline__ void resolve_from_mesh(const FrameParams &fp, const F
     float u, v, w;
     {
         float sx[3], sy[3], sz[3];
+        SHS_TEX_ONLY(float no_iw;)
 #pragma unroll
-        for (int k = 0; k < 3; ++k) vertex_screen(fp, dr.mvp, P[3 * k], P[3 * k + 1], P[3 * k + 2], sx[k], sy[k], sz[k]);
+        for (int k = 0; k < 3; ++k)
+            vertex_screen(fp, dr.mvp, P[3 * k], P[3 * k + 1], P[3 * k + 2], sx[k], sy[k], sz[k] SHS_TEX_ARG(false) SHS_TEX_ARG(no_iw));
         const TriRec r = rec_from_stored(fp, d, local, sx, sy, sz, 0u, make_uint2(0u, 0u));
         bary_pass(r, (float)px + 0.5f, (float)py + 0.5f, u, v, w);   // the winner's own values
-        depth = (u * r.z0 + v * r.z1) + w * r.z2;
+        depth = tri_depth(r, u, v, w);
     }
     if (!shade) return;
     const float *Nn = dr.nrm + 9 * (size_t)local;
@@ -1594,7 +1777,7 @@ __device__ __forceinline__ void resolve_from_mesh(const FrameParams &fp, const F
 // C3 step slower.
 template <bool PIN>
 __device__ __forceinline__ void stage_stored(const FrameBuffers &fb, RasterShared &sh, uint32_t c, int m, bool single,
-                                             bool all_ext) {
+                                             bool all_ext SHS_TEX_PARAM(const FrameParams &fp)) {
     const int tid = threadIdx.x;
     constexpr int NQ = (RCHUNK * 4 + 255) / 256, NS = (RCHUNK * 5 + 255) / 256;
     float4 q[NQ], s[NS], e = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -1610,6 +1793,7 @@ __device__ __forceinline__ void stage_stored(const FrameBuffers &fb, RasterShare
     {
         const uint32_t ce = tid < m ? sh.cand[c + tid] : 0u;
         if (tid < m && (all_ext || (ce & BIN_GHOST))) e = fb.rext[ce & ~BIN_GHOST];
+        SHS_TEX_ONLY(if (tid < m) sh.iw[tid] = *tex_side(fp, fb, 1, ce & ~BIN_GHOST);)
     }
 #pragma unroll
     for (int k = 0; k < NS; ++k) {   // (single: one staging pass, c == 0)
@@ -1739,7 +1923,8 @@ __device__ __forceinline__ int pair_owner(const RasterShared &sh, int k0, int la
 // Staged candidate o at pixel (px, py): whether the pixel passes, and then its key.
 __device__ __forceinline__ bool staged_key(const FrameParams &fp, const RasterShared &sh, int o, int px, int py, bool slot_keys,
                                            bool single, unsigned long long &key) {
-    const TriRec r = rec_from_hot(fp, &sh.rec[o * 4], &sh.ext[o]);
+    TriRec r = rec_from_hot(fp, &sh.rec[o * 4], &sh.ext[o]);
+    SHS_TEX_ONLY(set_iw(r, sh.iw[o]);)
     float z;
     if (!pixel_test(fp, r, px, py, z)) return false;
     key = cand_key(z, sh.id[o], slot_keys, single ? (uint32_t)o : SLOT_NONE);
@@ -1787,7 +1972,13 @@ __device__ __forceinline__ TriRec winner_records(const FrameParams &fp, const Fr
     for (int k = 0; k < 4; ++k) h4[k] = s4[k];
 #pragma unroll
     for (int k = 0; k < 5; ++k) e4[k] = g4[k];
+#ifdef SHS_LEGACY_TEX
+    TriRec r = rec_from_hot(fp, h4[0], h4[1], h4[2], h4[3], make_float4(0.f, 0.f, 0.f, 0.f));
+    set_iw(r, staged ? sh.iw[slot] : *tex_side(fp, fb, 1, id));
+    return r;
+#else
     return rec_from_hot(fp, h4[0], h4[1], h4[2], h4[3], make_float4(0.f, 0.f, 0.f, 0.f));
+#endif
 }
 
 // The shaded floats as the pixel's colour (truncated to uint8 like the reference) and prequant value.
@@ -1817,11 +2008,17 @@ __device__ __forceinline__ void shade_stored_winner(const FrameParams &fp, const
     const TriRec r = winner_records(fp, fb, sh, id, slot, sr);
     float u, v, w;
     bary_pass(r, (float)px + 0.5f, (float)py + 0.5f, u, v, w);   // the winner's own values
-    depth = (u * r.z0 + v * r.z1) + w * r.z2;
+    depth = tri_depth(r, u, v, w);
     if (SHS_DBG(fp, DBG_SKIP_SHADE)) return;
     const int wd = dbase + r.draw;   // the frame's draw (ShadeRec::draw is frame 0's when shared)
     const float4 *du = wd < LDS_DRAWS ? &sh.du[wd * 4] : reinterpret_cast<const float4 *>(draws[wd].light);
     float pre[3];
+#ifdef SHS_LEGACY_TEX
+    if (sr.shading == SHADING_TEXTURED) {
+        const float4 d4[4] = {du[0], du[1], du[2], du[3]};
+        shade_textured(fp, fb, id, r, sr, d4, u, v, w, pre);
+    } else
+#endif
     shade_winner(du, sr, u, v, w, pre);
     pack_pixel(pre, rgba, pq);
 }
@@ -1857,7 +2054,13 @@ __device__ __forceinline__ TriRec staged_records(const FrameParams &fp, const Ra
     for (int k = 0; k < 4; ++k) { const v4f q = s4[k]; h4[k] = make_float4(q.x, q.y, q.z, q.w); }
 #pragma unroll
     for (int k = 0; k < 5; ++k) { const v4f q = g4[k]; e[4 * k] = q.x; e[4 * k + 1] = q.y; e[4 * k + 2] = q.z; e[4 * k + 3] = q.w; }
+#ifdef SHS_LEGACY_TEX
+    TriRec r = rec_from_hot(fp, h4[0], h4[1], h4[2], h4[3], make_float4(0.f, 0.f, 0.f, 0.f));
+    set_iw(r, sh.iw[slot]);
+    return r;
+#else
     return rec_from_hot(fp, h4[0], h4[1], h4[2], h4[3], make_float4(0.f, 0.f, 0.f, 0.f));
+#endif
 }
 
 // store_pixel for the tile at (X0, Y0) without 64-bit vector addresses, at any frame size: each plane's
@@ -1986,7 +2189,7 @@ __device__ __forceinline__ void raster_tile(const FrameParams &fp, const FrameBu
                     stage_from_mesh(fp, fb, draws + dbase, dbase, sh.cand[c + ci] & ~BIN_GHOST, single, &sh.rec[ci * 4], &sh.ext[ci],
                                     &sh.srec[ci * 5]);
             } else {
-                stage_stored<!SPANS>(fb, sh, c, m, single, scan);
+                stage_stored<!SPANS>(fb, sh, c, m, single, scan SHS_TEX_ARG(fp));
             }
             __syncthreads();
             tl_mark(tl, tls, 2);
@@ -2111,7 +2314,7 @@ __device__ __forceinline__ void raster_tile(const FrameParams &fp, const FrameBu
                 const TriRec r = winner_records(fp, fb, sh, id, slot, sr);
                 float u, v, w;
                 bary_pass(r, (float)px + 0.5f, (float)py + 0.5f, u, v, w);   // the winner's own values
-                depth = (u * r.z0 + v * r.z1) + w * r.z2;
+                depth = tri_depth(r, u, v, w);
                 if (shade) {
                     const int wd = dbase + r.draw;   // the frame's draw (ShadeRec::draw is frame 0's when shared)
                     if (wd < LDS_DRAWS) load_du(&sh.du[wd * 4], du);
@@ -2262,7 +2465,7 @@ __device__ __forceinline__ void raster_group(uint32_t n_frag, int frame, int rt0
             const FrameParams fp = ac->fp;
             // stage the records, float bboxes and (single-pass groups) shade records: one round trip
             if (tid < m) sh.id[tid] = sh.cand[c + tid];
-            stage_stored<true>(frame_view(fp, arg_buffers(ac), frame), sh, c, m, single, true);
+            stage_stored<true>(frame_view(fp, arg_buffers(ac), frame), sh, c, m, single, true SHS_TEX_ARG(fp));
             __syncthreads();
             tl_mark(tl, tls, 2);
             bool boxes = true;
@@ -2434,12 +2637,19 @@ __device__ __forceinline__ void raster_group(uint32_t n_frag, int frame, int rt0
                 const TriRec r = staged_records(fp, sh, slot, sr);
                 float u, v, w;
                 bary_pass(r, (float)px + 0.5f, (float)py + 0.5f, u, v, w);   // the winner's own values
-                depth = (u * r.z0 + v * r.z1) + w * r.z2;
+                depth = tri_depth(r, u, v, w);
                 if (!SHS_DBG(fp, DBG_SKIP_SHADE)) {
                     f3 A, N;
                     float pre[3];
-                    interp_varyings(sr, sshading, u, v, w, A, N);
-                    shade_interp(sdu, sshading, A, N, pre);
+#ifdef SHS_LEGACY_TEX
+                    if (sshading == SHADING_TEXTURED) {
+                        shade_textured(fp, fb, id, r, sr, sdu, u, v, w, pre);
+                    } else
+#endif
+                    {
+                        interp_varyings(sr, sshading, u, v, w, A, N);
+                        shade_interp(sdu, sshading, A, N, pre);
+                    }
                     pack_pixel(pre, rgba, pq);
                 }
             }
@@ -2739,7 +2949,7 @@ __global__ __launch_bounds__(256, SHS_LEGACY_RASTER_WAVES) void k_raster(FramePa
         // 0.0356 ms per single frame without them.)
         const uint32_t n_busy = min(cnt[C_BUSY], (uint32_t)(fp.tiles_x * fp.tiles_y * (TILE / RTH) * fp.n_frames));
         const uint32_t n_frag = min(cnt[C_FRAG], fp.frag_cap);
-        static_assert(LDS_DRAWS * 4 == 256, "one per-draw uniform float4 per thread");
+        static_assert(LDS_DRAWS * 4 <= 256, "one per-draw uniform float4 per thread");
         const int n_draws_all = fp.n_draws * fp.n_frames;
         const float4 du_first = tid < min(n_draws_all, LDS_DRAWS) * 4 ? reinterpret_cast<const float4 *>(draws[tid >> 2].light)[tid & 3]
                                                                        : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -2898,21 +3108,37 @@ __global__ __launch_bounds__(256) void k_legacy_fs_sample(float4 u0, float4 u1, 
     prequant[i] = q;
 }
 
-}  // namespace ext
+#ifdef SHS_LEGACY_TEX
+// shs_legacy_sample_nearest: the sampler alone, one (u, v) per lane through the functions shade_textured
+// samples with -> the texel's bytes with alpha 255 (the shader reads r, g, b only), and its index.
+__global__ __launch_bounds__(256) void k_legacy_sample_nearest(const uint32_t *texels, int tw, int th, int n, const float2 *uv,
+                                                               uint32_t *rgba, int32_t *index) {
+    const int i = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (i >= n) return;
+    const float2 c = uv[i];
+    const int k = nearest_index(tw, th, c.x, c.y);
+    rgba[i] = (texels[k] & 0x00ffffffu) | (255u << 24);
+    index[i] = k;
+}
+#endif
+
+}  // namespace ext / tex
 #endif
 }  // namespace shs_dev
 
 // ---- launch wrappers (called by shs_abi.cpp) -----------------------------------------------
 // A batch with an extended shading model (RF_EXT_MODELS) takes the wrappers of the second compilation
-// (shs_internal::ext: the same code over namespace shs_dev::ext's kernels).
+// (shs_internal::ext: the same code over namespace shs_dev::ext's kernels); one that draws the textured
+// model (RF_TEX_MODEL) those of the third (shs_internal::tex), whatever else it draws.
 namespace shs_internal {
 using namespace shs_dev;
 #ifdef SHS_LEGACY_EXT
-namespace ext {
-using namespace shs_dev::ext;
+namespace SHS_EXT_NS {
+using namespace shs_dev::SHS_EXT_NS;
 #define SHS_EXT_DISPATCH(flags, call)
 #else
-#define SHS_EXT_DISPATCH(flags, call) \
+#define SHS_EXT_DISPATCH(flags, call)               \
+    if ((flags) & RF_TEX_MODEL) return tex::call;   \
     if ((flags) & RF_EXT_MODELS) return ext::call
 #endif
 
@@ -2931,8 +3157,11 @@ hipError_t launch_setup(const FrameParams &fp, const FrameBuffers &fb, const KAr
     return hipGetLastError();
 }
 
-#ifndef SHS_LEGACY_EXT
+#if !defined(SHS_LEGACY_EXT) || defined(SHS_LEGACY_TEX)
 hipError_t launch_ghost(const FrameParams &fp, const FrameBuffers &fb, hipStream_t s) {
+#ifndef SHS_LEGACY_TEX
+    if (fp.flags & RF_TEX_MODEL) return tex::launch_ghost(fp, fb, s);
+#endif
     hipLaunchKernelGGL(k_ghost, dim3(GHOST_LIST_BLOCKS), dim3(256), 0, s, fp, fb);
     return hipGetLastError();
 }
@@ -2986,7 +3215,14 @@ hipError_t launch_fs_sample(const DrawGPU &d, int n, const float *in, uint32_t *
                        prequant);
     return hipGetLastError();
 }
-}  // namespace ext
+#ifdef SHS_LEGACY_TEX
+hipError_t launch_sample_nearest(const uint32_t *texels, int tw, int th, int n, const float2 *uv, uint32_t *rgba, int32_t *index,
+                                 hipStream_t s) {
+    hipLaunchKernelGGL(k_legacy_sample_nearest, dim3((n + 255) / 256), dim3(256), 0, s, texels, tw, th, n, uv, rgba, index);
+    return hipGetLastError();
+}
+#endif
+}  // namespace ext / tex
 #endif
 
 }  // namespace shs_internal

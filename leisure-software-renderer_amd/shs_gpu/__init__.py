@@ -14,13 +14,13 @@ import numpy as np
 
 from . import _abi
 from ._abi import (FRAME_PREQUANT, FRAME_PRESENT, SHADING_BLINN_PHONG, SHADING_DEPTH_VIS, SHADING_FLAT, SHADING_GOOCH,
-                   SHADING_GOURAUD, SHADING_NAMES, SHADING_NORMAL_VIS, SHADING_OREN_NAYAR, SHADING_PHONG, SHADING_TOON,
-                   FrameDesc, LegacyDraw, RasterStats)
+                   SHADING_GOURAUD, SHADING_NAMES, SHADING_NORMAL_VIS, SHADING_OREN_NAYAR, SHADING_PHONG, SHADING_TEXTURED,
+                   SHADING_TOON, FrameDesc, LegacyDraw, RasterStats)
 
 __all__ = [
     "ShsError", "Context", "Frame", "Draw", "SHADING_FLAT", "SHADING_GOURAUD", "SHADING_PHONG",
     "SHADING_BLINN_PHONG", "SHADING_TOON", "SHADING_GOOCH", "SHADING_OREN_NAYAR", "SHADING_NORMAL_VIS",
-    "SHADING_DEPTH_VIS", "SHADING_NAMES", "FRAME_PREQUANT", "lib",
+    "SHADING_DEPTH_VIS", "SHADING_TEXTURED", "SHADING_NAMES", "FRAME_PREQUANT", "lib",
 ]
 
 lib = _abi.lib
@@ -46,6 +46,10 @@ class Draw:
     light_dir: np.ndarray        # float32[3]  (Flat: light_dir_view)
     camera_pos: np.ndarray       # float32[3]
     color: tuple = (60, 100, 200, 255)
+    # SHADING_TEXTURED: an uploaded texture id (0: no texture, Uniforms::color) or an object with .rgba [h, w, 4].
+    # A frame or batch with any draw's albedo_tex set goes through shs_render_legacy_batch_tex, the call that
+    # takes the textured model; with none set it is shs_render_legacy[_batch], which takes models 0..8 as ever.
+    albedo_tex: object = None
 
 
 @dataclass
@@ -113,12 +117,24 @@ class Context:
         key = id(mesh)
         if key in self._meshes:
             return self._meshes[key][0]
-        pos = np.ascontiguousarray(mesh.positions, dtype=np.float32)
-        nrm = np.ascontiguousarray(mesh.normals, dtype=np.float32)
+        mid = self.upload_soup(mesh.positions, mesh.normals, getattr(mesh, "uvs", None))
+        self._meshes[key] = (mid, mesh)
+        return mid
+
+    def upload_soup(self, positions, normals, uvs=None) -> int:
+        """shs_mesh_upload_soup[_uv]: positions / normals float32 [n, 9] and, for SHADING_TEXTURED, uvs [n, 6]
+        (ModelGeometry::uvs; None: the model reads vec2(0) per corner) -> mesh id."""
+        pos = np.ascontiguousarray(positions, dtype=np.float32)
+        nrm = np.ascontiguousarray(normals, dtype=np.float32)
         assert pos.shape == nrm.shape and pos.shape[-1] == 9
         mid = ctypes.c_int32()
-        self._check(self._lib.shs_mesh_upload_soup(self._h, _fptr(pos), _fptr(nrm), pos.shape[0], ctypes.byref(mid)))
-        self._meshes[key] = (mid.value, mesh)
+        if uvs is None:
+            self._check(self._lib.shs_mesh_upload_soup(self._h, _fptr(pos), _fptr(nrm), pos.shape[0], ctypes.byref(mid)))
+        else:
+            uv = np.ascontiguousarray(uvs, dtype=np.float32)
+            assert uv.shape == (pos.shape[0], 6)
+            self._check(self._lib.shs_mesh_upload_soup_uv(self._h, _fptr(pos), _fptr(nrm), _fptr(uv), pos.shape[0],
+                                                          ctypes.byref(mid)))
         return mid.value
 
     # -- frames -------------------------------------------------------------------------------
@@ -136,7 +152,18 @@ class Context:
                 a.camera_pos[k] = float(d.camera_pos[k])
             for k in range(4):
                 a.color[k] = int(d.color[k])
+        arr.albedo_tex = self._tex_array(draws)   # (travels with the draws: the parallel array of ids, or None)
         return arr
+
+    def _tex_array(self, draws):
+        """The draws' albedo_tex as shs_render_legacy_batch_tex's parallel id array; None when no draw has one."""
+        texs = [getattr(d, "albedo_tex", None) for d in draws]
+        if all(t is None for t in texs):
+            return None
+        ids = (ctypes.c_int32 * max(len(draws), 1))()
+        for i, t in enumerate(texs):
+            ids[i] = 0 if t is None else (int(t) if isinstance(t, (int, np.integer)) else self.upload_texture(t))
+        return ids
 
     def prepare(self, frame: Frame, draws):
         """Build the ctypes frame/draw arrays once (re-used by render_prepared in timed loops)."""
@@ -144,7 +171,11 @@ class Context:
 
     def render_prepared(self, prepared):
         frame, desc, arr, n = prepared
-        self._check(self._lib.shs_render_legacy(self._h, ctypes.byref(desc), arr, n))
+        tex = getattr(arr, "albedo_tex", None)
+        if tex is None:
+            self._check(self._lib.shs_render_legacy(self._h, ctypes.byref(desc), arr, n))
+        else:
+            self._check(self._lib.shs_render_legacy_batch_tex(self._h, ctypes.byref(desc), arr, tex, n, 1))
         self._frame = frame
 
     def render(self, frame: Frame, draws):
@@ -159,13 +190,30 @@ class Context:
 
     def render_batch_prepared(self, prepared):
         frame, desc, arr, n, n_frames = prepared
-        self._check(self._lib.shs_render_legacy_batch(self._h, ctypes.byref(desc), arr, n, n_frames))
+        tex = getattr(arr, "albedo_tex", None)
+        if tex is None:
+            self._check(self._lib.shs_render_legacy_batch(self._h, ctypes.byref(desc), arr, n, n_frames))
+        else:
+            self._check(self._lib.shs_render_legacy_batch_tex(self._h, ctypes.byref(desc), arr, tex, n, n_frames))
         self._frame = frame
         self._n_frames = n_frames
 
     def render_batch(self, frame: Frame, frames_draws):
         """shs_render_legacy_batch: one k_setup + k_raster pair renders every frame of the batch."""
         self.render_batch_prepared(self.prepare_batch(frame, frames_draws))
+
+    def legacy_sample_nearest(self, tex, uv):
+        """shs_legacy_sample_nearest: sample_nearest of texture `tex` (an id, or an object with .rgba) at uv [n, 2]
+        through the function the rasters call -> rgba uint8 [n, 4] (alpha 255)."""
+        tid = int(tex) if isinstance(tex, (int, np.integer)) else self.upload_texture(tex)
+        c = np.ascontiguousarray(np.asarray(uv, np.float32).reshape(-1, 2))
+        rgba = np.zeros((c.shape[0], 4), np.uint8)
+        self._check(self._lib.shs_legacy_sample_nearest(self._h, tid, c.shape[0], _fptr(c), rgba.ctypes.data_as(ctypes.c_void_p)))
+        return rgba
+
+    def release_texture(self, tex_id):
+        """shs_texture_release (a legacy batch in flight that samples it is finished first)."""
+        self._check(self._lib.shs_texture_release(self._h, int(tex_id)))
 
     def legacy_shade_samples(self, shading, light_dir, camera_pos, color, normal_sum, world_pos, clip_z):
         """shs_legacy_shade_samples: the legacy fragment shader `shading` (any model but Flat and Gouraud) for n

@@ -25,6 +25,8 @@ SHADING_GOOCH = 5
 SHADING_OREN_NAYAR = 6
 SHADING_NORMAL_VIS = 7
 SHADING_DEPTH_VIS = 8
+SHADING_TEXTURED = 9
+# (the models a scene of meshes and Uniforms alone can draw; SHADING_TEXTURED also needs UVs and a texture)
 SHADING_NAMES = {"flat": 0, "gouraud": 1, "phong": 2, "blinn_phong": 3, "toon": 4, "gooch": 5, "oren_nayar": 6,
                  "normal_vis": 7, "depth_vis": 8}
 
@@ -268,11 +270,15 @@ SIGNATURES = [
     ("shs_get_stream", _P, [_P]),
     ("shs_synchronize", ctypes.c_int, [_P]),
     ("shs_mesh_upload_soup", ctypes.c_int, [_P, _F, _F, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)]),
+    ("shs_mesh_upload_soup_uv", ctypes.c_int, [_P, _F, _F, _F, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)]),
     ("shs_mesh_share", ctypes.c_int, [_P, _P, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)]),
     ("shs_mesh_release", ctypes.c_int, [_P, ctypes.c_int32]),
     ("shs_render_legacy", ctypes.c_int, [_P, ctypes.POINTER(FrameDesc), ctypes.POINTER(LegacyDraw), ctypes.c_int32]),
     ("shs_render_legacy_batch", ctypes.c_int, [_P, ctypes.POINTER(FrameDesc), ctypes.POINTER(LegacyDraw), ctypes.c_int32,
                                                ctypes.c_int32]),
+    ("shs_render_legacy_batch_tex", ctypes.c_int, [_P, ctypes.POINTER(FrameDesc), ctypes.POINTER(LegacyDraw),
+                                                    ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_int32]),
+    ("shs_legacy_sample_nearest", ctypes.c_int, [_P, ctypes.c_int32, ctypes.c_int32, _F, _P]),
     ("shs_legacy_shade_samples", ctypes.c_int, [_P, ctypes.POINTER(LegacyDraw), ctypes.c_int32, _F, _F, _F, _P, _P]),
     ("shs_resolve", ctypes.c_int, [_P, _P, _P]),
     ("shs_resolve_frame", ctypes.c_int, [_P, ctypes.c_int32, _P, _P]),
@@ -361,6 +367,9 @@ SIGNATURES = [
     ("shs_group_mesh_upload", ctypes.c_int, [_P, _F, ctypes.c_int32, _F, ctypes.c_int32, _F, ctypes.c_int32,
                                              ctypes.POINTER(ctypes.c_uint32), ctypes.c_int64, ctypes.POINTER(ctypes.c_int32)]),
     ("shs_group_mesh_upload_soup", ctypes.c_int, [_P, _F, _F, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)]),
+    ("shs_group_mesh_upload_soup_uv", ctypes.c_int, [_P, _F, _F, _F, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)]),
+    ("shs_group_render_legacy_tex", ctypes.c_int, [_P, ctypes.POINTER(FrameDesc), ctypes.POINTER(LegacyDraw),
+                                                    ctypes.POINTER(ctypes.c_int32), ctypes.c_int32]),
     ("shs_group_texture_upload", ctypes.c_int, [_P, _P, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)]),
     ("shs_group_lights_upload", ctypes.c_int, [_P, ctypes.POINTER(CullingLightC), ctypes.c_int32]),
     ("shs_group_lights_upload_typed", ctypes.c_int, [_P, ctypes.POINTER(CullingLightC), ctypes.POINTER(LightPropsC),

@@ -98,8 +98,15 @@ class Group:
             return self._ids[key][0]
         pos = np.ascontiguousarray(mesh.positions, dtype=np.float32)
         nrm = np.ascontiguousarray(mesh.normals, dtype=np.float32)
+        uvs = getattr(mesh, "uvs", None)
         mid = ctypes.c_int32()
-        self._check(self._lib.shs_group_mesh_upload_soup(self._h, _fptr(pos), _fptr(nrm), pos.shape[0], ctypes.byref(mid)))
+        if uvs is None:
+            self._check(self._lib.shs_group_mesh_upload_soup(self._h, _fptr(pos), _fptr(nrm), pos.shape[0], ctypes.byref(mid)))
+        else:   # (SHADING_TEXTURED reads them)
+            uv = np.ascontiguousarray(uvs, dtype=np.float32)
+            assert uv.shape == (pos.shape[0], 6)
+            self._check(self._lib.shs_group_mesh_upload_soup_uv(self._h, _fptr(pos), _fptr(nrm), _fptr(uv), pos.shape[0],
+                                                                ctypes.byref(mid)))
         self._ids[key] = (mid.value, mesh)
         return mid.value
 
@@ -210,7 +217,14 @@ class Group:
             for k in range(4):
                 a.color[k] = int(d.color[k])
         desc = frame.desc()
-        self._check(self._lib.shs_group_render_legacy(self._h, ctypes.byref(desc), arr, len(draws)))
+        texs = [getattr(d, "albedo_tex", None) for d in draws]
+        if all(t is None for t in texs):
+            self._check(self._lib.shs_group_render_legacy(self._h, ctypes.byref(desc), arr, len(draws)))
+        else:   # the textured draws' ids, uploaded through the group (shs_group_render_legacy_tex)
+            ids = (ctypes.c_int32 * max(len(draws), 1))()
+            for i, t in enumerate(texs):
+                ids[i] = 0 if t is None else (int(t) if isinstance(t, (int, np.integer)) else self.upload_texture(t))
+            self._check(self._lib.shs_group_render_legacy_tex(self._h, ctypes.byref(desc), arr, ids, len(draws)))
         for r in self.ranks:
             r._frame = frame
 

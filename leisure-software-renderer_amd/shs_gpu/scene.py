@@ -30,6 +30,7 @@ f32 = np.float32
 class Mesh:
     positions: np.ndarray   # float32 [n, 9]
     normals: np.ndarray     # float32 [n, 9]
+    uvs: np.ndarray = None  # float32 [n, 6] (ModelGeometry::uvs; None: a mesh without texture coordinates)
 
     @property
     def n_tris(self):
@@ -47,7 +48,9 @@ def load_soup(path):
         n, _ = struct.unpack("<II", fh.read(8))
         pos = np.frombuffer(fh.read(36 * n), dtype="<f4").reshape(n, 9).astype(np.float32)
         nrm = np.frombuffer(fh.read(36 * n), dtype="<f4").reshape(n, 9).astype(np.float32)
-    return Mesh(pos, nrm)
+        rest = fh.read(24 * n)   # (tools/convert_obj.py writes uvs[6 * n_tris] last)
+        uvs = np.frombuffer(rest, dtype="<f4").reshape(n, 6).astype(np.float32) if len(rest) == 24 * n else None
+    return Mesh(pos, nrm, uvs)
 
 
 def monkey() -> Mesh:
