@@ -1,7 +1,9 @@
 """ctypes wrapper of oracle/_build/libshs_oracle.so -- the CPU restatement of the reference path.
 
 TEST INFRASTRUCTURE ONLY: imported by tests/, __graft_entry__.smoke() and bench.py's cpu_baseline
-leg.  The product (libshs_gpu.so / shs_gpu) never imports this.  PARITY UNPINNED (see shs_oracle.h).
+leg.  The product (libshs_gpu.so / shs_gpu) never imports this.  The library path's entry points are pinned
+word for word against the compiled reference (reference_lib(), tests/test_lib_reference.py); the
+legacy path stays unpinned (see shs_oracle.h).
 """
 import ctypes
 import os
@@ -246,6 +248,11 @@ def _lib_draws(draws, keep):
 
 
 def pbr_forward(frame, draws, shadow_map=None):
+    """The oracle's PassPBRForward::execute (arguments and results: _pbr_forward)."""
+    return _pbr_forward(_lib_lib().ora_pbr_forward, "ora_pbr_forward", frame, draws, shadow_map)
+
+
+def _pbr_forward(entry, name, frame, draws, shadow_map):
     """PassPBRForward::execute (one rasterize_mesh per draw) -> (hdr [H,W,4], depth [H,W] | None,
     motion [H,W,2] | None, stats {tri_input, tri_after_clip, tri_raster}).  frame: shs_gpu.lib.LibFrame;
     draws: shs_gpu.lib.LibDraw with host meshes; shadow_map: float32 [h, w] sampled by draws with shadow."""
@@ -276,9 +283,9 @@ def pbr_forward(frame, draws, shadow_map=None):
         t.tile_counts, t.tile_indices = counts.ctypes.data, idx.ctypes.data
         t.cull = ctypes.addressof(cdesc)
     st = np.zeros(3, np.uint64)
-    rc = _lib_lib().ora_pbr_forward(ctypes.byref(t), arr, len(draws), st.ctypes.data)
+    rc = entry(ctypes.byref(t), arr, len(draws), st.ctypes.data)
     if rc != 0:
-        raise RuntimeError(f"ora_pbr_forward failed: {rc}")
+        raise RuntimeError(f"{name} failed: {rc}")
     return hdr, depth, motion, {"tri_input": int(st[0]), "tri_after_clip": int(st[1]), "tri_raster": int(st[2])}
 
 
@@ -399,6 +406,10 @@ def sample_texture(rgba, u, v):
 def tonemap(hdr, exposure=1.0, gamma=2.2):
     """PassTonemap + upload_ldr_to_rgba8 over hdr float32 [H, W, 4] (rows y up) ->
     (ldr uint8 [H, W, 4] rows y up, present uint8 [H, W, 4] rows top-down)."""
+    return _tonemap(_post_lib().ora_tonemap, hdr, exposure, gamma)
+
+
+def _post_lib():
     L = _lib_lib()
     if not getattr(L, "_post_ready", False):
         P = ctypes.c_void_p
@@ -407,11 +418,15 @@ def tonemap(hdr, exposure=1.0, gamma=2.2):
         L.ora_tonemap_channel.restype = ctypes.c_uint8
         L.ora_tonemap_channel.argtypes = [ctypes.c_float, ctypes.c_float, ctypes.c_float]
         L._post_ready = True
+    return L
+
+
+def _tonemap(entry, hdr, exposure, gamma):
     hdr = np.ascontiguousarray(hdr, dtype=np.float32)
     H, W = hdr.shape[:2]
     ldr = np.empty((H, W, 4), np.uint8)
     present = np.empty((H, W, 4), np.uint8)
-    L.ora_tonemap(hdr.ctypes.data, W, H, float(exposure), float(gamma), ldr.ctypes.data, present.ctypes.data)
+    entry(hdr.ctypes.data, W, H, float(exposure), float(gamma), ldr.ctypes.data, present.ctypes.data)
     return ldr, present
 
 
@@ -425,21 +440,32 @@ def motion_blur(src_ldr, depth, motion, enable=True, samples=10, strength=1.0, m
                 min_velocity_px=0.25, depth_reject=0.08, dt=1.0 / 60.0):
     """PassMotionBlur over an RT_ColorLDR (uint8 [H, W, 4], rows y up) with the depth [H, W] and motion
     [H, W, 2] planes -> uint8 [H, W, 4] (defaults: MotionBlurPassParams, frame_params.hpp:49-57)."""
+    return _motion_blur(_mb_lib().ora_motion_blur, src_ldr, depth, motion, enable, samples, strength, max_velocity_px,
+                        min_velocity_px, depth_reject, dt)
+
+
+_MB_ARGS = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 4 + [ctypes.c_float] * 5 + [ctypes.c_void_p]
+
+
+def _mb_lib():
     L = _lib_lib()
     if not getattr(L, "_mb_ready", False):
-        P = ctypes.c_void_p
         L.ora_motion_blur.restype = None
-        L.ora_motion_blur.argtypes = [P, P, P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int] + \
-            [ctypes.c_float] * 5 + [P]
+        L.ora_motion_blur.argtypes = _MB_ARGS
         L._mb_ready = True
+    return L
+
+
+def _motion_blur(entry, src_ldr, depth, motion, enable, samples, strength, max_velocity_px, min_velocity_px,
+                 depth_reject, dt):
     src = np.ascontiguousarray(src_ldr, dtype=np.uint8)
     H, W = src.shape[:2]
     dep = np.ascontiguousarray(depth, dtype=np.float32)
     mot = np.ascontiguousarray(motion, dtype=np.float32)
     out = np.empty_like(src)
-    L.ora_motion_blur(src.ctypes.data, dep.ctypes.data, mot.ctypes.data, W, H, 1 if enable else 0, int(samples),
-                      float(strength), float(max_velocity_px), float(min_velocity_px), float(depth_reject), float(dt),
-                      out.ctypes.data)
+    entry(src.ctypes.data, dep.ctypes.data, mot.ctypes.data, W, H, 1 if enable else 0, int(samples),
+          float(strength), float(max_velocity_px), float(min_velocity_px), float(depth_reject), float(dt),
+          out.ctypes.data)
     return out
 
 
@@ -718,3 +744,60 @@ def set_lib_threads(n):
     L.ora_set_lib_threads.restype = None
     L.ora_set_lib_threads.argtypes = [ctypes.c_int]
     L.ora_set_lib_threads(int(n))
+
+
+# ===== the compiled reference rasteriser (oracle/ref_lib.cpp -> _ref/libshs_ref_lib.so) ==============
+REF_LIB = os.path.join(HERE, "_ref", "libshs_ref_lib.so")
+REFERENCE = os.environ.get("SHS_REFERENCE", "/root/reference")
+_ref = None
+
+
+def reference_tree():
+    """The reference library's include directory, or None where the reference tree is absent."""
+    inc = os.path.join(REFERENCE, "cpp-folders", "src", "shs-renderer-lib", "include")
+    return inc if os.path.isdir(inc) else None
+
+
+def build_reference():
+    """`make ref` (oracle/Makefile) where the reference tree exists; an existing _ref/ is left alone otherwise."""
+    if reference_tree() is not None:
+        subprocess.run(["make", "-s", "-C", HERE, "ref", f"REFERENCE={REFERENCE}"], check=True)
+
+
+def reference_lib():
+    """The reference library's own rasterize_mesh / builtin programs / PassTonemap / PassMotionBlur, compiled
+    over the GLM stand-in behind the oracle's C ABI; None when it was never built (no reference tree)."""
+    global _ref
+    if _ref is None:
+        if not os.path.exists(REF_LIB):
+            build_reference()
+        if not os.path.exists(REF_LIB):
+            return None
+        L = ctypes.CDLL(REF_LIB)
+        P = ctypes.c_void_p
+        L.ref_pbr_forward.restype = ctypes.c_int
+        L.ref_pbr_forward.argtypes = [ctypes.POINTER(OraLibTarget), ctypes.POINTER(OraLibDraw), ctypes.c_int, P]
+        L.ref_tonemap.restype = None
+        L.ref_tonemap.argtypes = [P, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float, P, P]
+        L.ref_motion_blur.restype = None
+        L.ref_motion_blur.argtypes = _MB_ARGS
+        _ref = L
+    return _ref
+
+
+def ref_pbr_forward(frame, draws, shadow_map=None):
+    """pbr_forward's twin on the compiled reference (programs 0-4 only)."""
+    return _pbr_forward(reference_lib().ref_pbr_forward, "ref_pbr_forward", frame, draws, shadow_map)
+
+
+def ref_tonemap(hdr, exposure=1.0, gamma=2.2):
+    """PassTonemap::execute on the compiled reference -> ldr uint8 [H, W, 4] (rows y up); the present plane is
+    a demo helper's, not the library's."""
+    return _tonemap(reference_lib().ref_tonemap, hdr, exposure, gamma)[0]
+
+
+def ref_motion_blur(src_ldr, depth, motion, enable=True, samples=10, strength=1.0, max_velocity_px=20.0,
+                    min_velocity_px=0.25, depth_reject=0.08, dt=1.0 / 60.0):
+    """PassMotionBlur::execute on the compiled reference."""
+    return _motion_blur(reference_lib().ref_motion_blur, src_ldr, depth, motion, enable, samples, strength,
+                        max_velocity_px, min_velocity_px, depth_reject, dt)

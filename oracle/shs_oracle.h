@@ -10,6 +10,9 @@
  * (glm, SDL2, assimp absent), so this restatement is pinned only by its own analytic known-answer
  * tests (tests/test_oracle.py).  GLM operation order (mat*vec, dot, normalize, inverse, pow) is
  * restated from GLM's published headers (vcpkg classic mode, unversioned) -- see DESIGN.md.
+ * The library path's ora_pbr_forward (programs 0-4), ora_tonemap and ora_motion_blur ARE pinned: the
+ * reference library's headers compile over a GLM stand-in (ref_lib.cpp, glm_standin/, `make ref`) and
+ * tests/test_lib_reference.py compares every word.
  *
  * Layout conventions follow the reference exactly:
  *   color  : RGBA8, W*H*4 bytes, CANVAS rows (y up: row = H-1-y_screen) -- Canvas::draw_pixel_screen_space

@@ -3,8 +3,10 @@
  * rasterize_mesh, the builtin PBR / Blinn-Phong / debug programs, the shadow-map pass and the
  * directional shadow sampling.
  *
- * TEST INFRASTRUCTURE ONLY (see shs_oracle.h).  PARITY UNPINNED (no reference golden vectors; glm
- * operation order restated from GLM's published headers, unversioned in the reference build).
+ * TEST INFRASTRUCTURE ONLY (see shs_oracle.h).  ora_pbr_forward (rasterize_mesh, programs 0-4, texture
+ * sampling, PCF) is PINNED word for word against the reference headers compiled over a GLM stand-in
+ * (ref_lib.cpp, tests/test_lib_reference.py).  UNPINNED: GLM itself (operation order restated from its
+ * published headers, unversioned in the reference build), the shadow pass, the Forward+ program.
  * Build: oracle/Makefile (gcc -O3 -ffp-contract=off, no -ffast-math).
  *
  * Paths below are relative to /root/reference/cpp-folders/src/shs-renderer-lib/include/shs/.
