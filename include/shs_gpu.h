@@ -811,6 +811,73 @@ typedef struct shs_canvas_dof_desc {
 int shs_canvas_dof(shs_ctx *ctx, const shs_canvas_dof_desc *desc, uint8_t *color, const float *depth, uint8_t *blur_out,
                    float *focus_depth, uint32_t flags);
 
+/* ---- Canvas render-target raster: shadow pass and shadowed camera pass ------------------------------
+ * The raster the hello-render-target/ demos share, for its simplest complete host
+ * hello_shadow_mapping.cpp (paths relative to cpp-folders/src/hello-render-target/):
+ *   shs_rt_render_shadow  PASS0: draw_triangle_tile_shadow (:791-834) over the ShadowMap's tile jobs
+ *                         (:1320-1411): depth only, ndc z in [0, 1], strict '<', FLT_MAX = empty;
+ *   shs_rt_render         PASS1: draw_triangle_tile_color_depth_motion_shadow (:854-1022) with
+ *                         vertex_shader_full (:602-620) and fragment_shader_full (:699-750): near-plane
+ *                         clipping in clip space, both windings, view-z depth, perspective-correct
+ *                         world position and UV, per-pixel velocity, Blinn-Phong with the shadow lookup.
+ * The reference clamps a triangle's bbox to the tile job that runs it, so the pixels it visits depend on
+ * the job size (ref_tile_w x ref_tile_h; the demo: 80 x 80 for both passes): the same set is visited here.
+ * The planes -- colour (Canvas pixels), depth (ZBuffer: view z, FLT_MAX = empty) and velocity
+ * (Buffer<glm::vec2>) -- are in canvas rows at y * W + x, what shs_canvas_motion_blur reads; the shadow
+ * map is ShadowMap::depth_ (y down) at y * w + x.  Both calls enqueue on the context stream and return;
+ * the resolves and shs_rt_device_targets order themselves after them.  One frame at a time: a render
+ * replaces the context's previous render-target frame. */
+typedef struct shs_rt_draw {
+    int32_t mesh_id;            /* shs_mesh_upload_soup[_uv] soup (without UVs: vec2(0) per corner) */
+    int32_t albedo_tex;         /* shs_texture_upload id (use_texture), 0: base_color */
+    float model[16];            /* column-major */
+    float mvp[16];
+    float prev_mvp[16];
+    uint8_t base_color[4];
+} shs_rt_draw;
+#define SHS_RT_USE_SHADOW 1u    /* u.shadow: the map of the last shs_rt_render_shadow (else lit) */
+#define SHS_RT_PCF 2u           /* SHADOW_USE_PCF: shadow_factor_pcf_2x2, else shadow_compare */
+#define SHS_RT_PREQUANT 4u      /* keep (r, g, b) * 255 before the byte truncation and the shadow factor */
+typedef struct shs_rt_frame {
+    int32_t width, height;
+    int32_t ref_tile_w, ref_tile_h;   /* the reference's tile job size (TILE_SIZE_X, TILE_SIZE_Y) */
+    uint8_t clear_color[4];
+    float view[16];
+    float light_vp[16];
+    float light_dir_world[3];
+    float camera_pos[3];
+    float bias_base, bias_slope;      /* SHADOW_BIAS_BASE (0.0025), SHADOW_BIAS_SLOPE (0.01) */
+    float max_velocity_px;            /* MB_MAX_PIXELS (22) */
+    uint32_t flags;                   /* SHS_RT_* */
+    int32_t shading;                  /* 0: fragment_shader_full (the only value) */
+} shs_rt_frame;
+typedef struct shs_rt_stats {
+    int64_t input_tris;         /* triangles submitted */
+    int64_t polys3, polys4;     /* clipped polygons of 3 and of 4 vertices */
+    int64_t sub_tris;           /* sub-triangles that reach the raster (w and area tests passed) */
+} shs_rt_stats;
+/* Only mesh_id and model of a caster are read.  SHS_ERR_INVALID: an unknown mesh id, a non-positive size. */
+int shs_rt_render_shadow(shs_ctx *ctx, int32_t w, int32_t h, int32_t ref_tile_w, int32_t ref_tile_h, const float light_vp[16],
+                         const shs_rt_draw *casters, int32_t n_casters);
+/* SHS_ERR_INVALID: an unknown mesh or texture id, a non-positive size, unknown flags or shading, or
+ * SHS_RT_USE_SHADOW without a shadow map rendered before. */
+int shs_rt_render(shs_ctx *ctx, const shs_rt_frame *frame, const shs_rt_draw *draws, int32_t n_draws);
+/* Host copies of the last camera pass (any pointer may be NULL): color W*H*4 bytes, depth W*H floats,
+ * velocity W*H*2 floats.  Synchronous. */
+int shs_rt_resolve(shs_ctx *ctx, uint8_t *color, float *depth, float *velocity);
+int shs_rt_resolve_shadow(shs_ctx *ctx, float *shadow_map);
+/* W*H*4 floats (r, g, b, shadow factor) of a SHS_RT_PREQUANT frame, zeros where nothing was shaded. */
+int shs_rt_resolve_prequant(shs_ctx *ctx, float *prequant);
+/* Per pixel the sub-triangle whose fragment it shows (2 * triangle + fan index over the whole submission,
+ * -1 none): W*H int32.  For the parity tests. */
+int shs_rt_resolve_ids(shs_ctx *ctx, int32_t *tri_id);
+int shs_rt_get_stats(shs_ctx *ctx, shs_rt_stats *stats);
+/* The last camera pass's device planes, final in the context stream's order (as shs_device_framebuffers):
+ * valid until the next shs_rt_render of another size or shs_destroy. */
+int shs_rt_device_targets(shs_ctx *ctx, void **color_dev, void **depth_dev, void **velocity_dev);
+/* ortho_lh_zo (hello_shadow_mapping.cpp:128-140): LH, z in [0, 1]. */
+int shs_ortho_lh_zo(float left, float right, float bottom, float top, float znear, float zfar, float out16[16]);
+
 /* ---- multi-GPU from one host process (SURVEY.md 5 "Distributed communication backend", 8e) ---------
  * The reference host is one C++ process driving one render loop (hello_pipeline_blinn_phong_shading.cpp
  * :369-455; PluggablePipeline::execute, pipeline/pluggable_pipeline.hpp:980).  A group is n contexts

@@ -11,6 +11,9 @@
 //           and hello_pipeline_texture_mapping.cpp
 //           (the 80x80 tile-job loop of process(), :244-313 in the Blinn-Phong demo), and with three
 //           draws per object the split-screen hello_pipeline_normal_zbuffer_debug.cpp.
+//   Seam 1b RenderTargetSystemGPU<SceneT>: the Canvas render-target raster of
+//           hello-render-target/hello_shadow_mapping.cpp (PASS0 shadow map, PASS1 colour + depth + velocity
+//           with the shadow lookup; shs_rt_*), its planes handed on the device to shs_canvas_motion_blur.
 //   Seam 3  PassShadowMapGPU / PassPBRForwardGPU: IRenderPass implementations with the ids,
 //           contracts and resource I/O of PassShadowMapAdapter / PassPBRForwardAdapter
 //           (shs-renderer-lib/include/shs/pipeline/pass_adapters.hpp:356-394, 1005-1062), registered
@@ -185,6 +188,76 @@ private:
     std::vector<int32_t> albedo_;   // SHS_SHADING_TEXTURED: parallel to draws_
     std::unordered_map<const void *, int32_t> mesh_ids_;
     std::unordered_map<const void *, int32_t> tex_ids_;
+};
+
+// -----------------------------------------------------------------------------------------------------
+// Seam 1b -- the Canvas render-target raster (hello-render-target/hello_shadow_mapping.cpp).
+//
+// Replaces RendererSystem::process there (:1320-1600): PASS0 (shadow map), PASS1 (colour + view-z depth +
+// velocity with the shadow lookup) and PASS2 (combined_motion_blur_pass) run on the device; only the final
+// colours come back.  SceneT is that file's DemoScene (floor, car, monkey, viewer, canvas).  Uncompiled, like
+// the other seams.
+// -----------------------------------------------------------------------------------------------------
+template <class SceneT>
+class RenderTargetSystemGPU : public shs::AbstractSystem {
+public:
+    struct Object {
+        int32_t mesh_id;             // shs_mesh_upload_soup_uv of the ModelGeometry / FloorPlane soup
+        int32_t albedo_tex;          // shs_texture_upload id, 0: base_color
+        shs::Color base_color;
+        glm::mat4 model, prev_model;
+    };
+
+    RenderTargetSystemGPU(SceneT *scene, Device *dev, int shadow_size, int tile) : scene_(scene), dev_(dev), sm_(shadow_size), tile_(tile) {}
+
+    std::vector<Object> objects;     // filled once by the host after its uploads; model / prev_model per frame
+
+    void process(float) override {
+        shs::Canvas &canvas = *scene_->canvas;
+        const int W = canvas.get_width(), H = canvas.get_height();
+        const glm::mat4 view = scene_->viewer->camera->view_matrix, proj = scene_->viewer->camera->projection_matrix;
+        std::vector<shs_rt_draw> draws(objects.size());
+        for (size_t i = 0; i < objects.size(); ++i) {
+            const Object &o = objects[i];
+            shs_rt_draw &d = draws[i];
+            d.mesh_id = o.mesh_id;
+            d.albedo_tex = o.albedo_tex;
+            const glm::mat4 mvp = proj * view * o.model, prev_mvp = prev_vp_ * o.prev_model;
+            std::memcpy(d.model, glm::value_ptr(o.model), 64);
+            std::memcpy(d.mvp, glm::value_ptr(mvp), 64);
+            std::memcpy(d.prev_mvp, glm::value_ptr(prev_mvp), 64);
+            d.base_color[0] = o.base_color.r; d.base_color[1] = o.base_color.g; d.base_color[2] = o.base_color.b; d.base_color[3] = 255;
+        }
+        ok(shs_rt_render_shadow(dev_->ctx, sm_, sm_, tile_, tile_, glm::value_ptr(light_vp), draws.data(), (int32_t)draws.size()));
+        shs_rt_frame f{};
+        f.width = W; f.height = H; f.ref_tile_w = tile_; f.ref_tile_h = tile_;
+        f.clear_color[0] = 20; f.clear_color[1] = 20; f.clear_color[2] = 25; f.clear_color[3] = 255;
+        std::memcpy(f.view, glm::value_ptr(view), 64);
+        std::memcpy(f.light_vp, glm::value_ptr(light_vp), 64);
+        std::memcpy(f.light_dir_world, glm::value_ptr(light_dir_world), 12);
+        std::memcpy(f.camera_pos, glm::value_ptr(scene_->viewer->position), 12);
+        f.bias_base = 0.0025f; f.bias_slope = 0.01f; f.max_velocity_px = 22.0f;      // SHADOW_BIAS_*, MB_MAX_PIXELS
+        f.flags = SHS_RT_USE_SHADOW | SHS_RT_PCF;
+        ok(shs_rt_render(dev_->ctx, &f, draws.data(), (int32_t)draws.size()));
+        void *color = nullptr, *depth = nullptr, *velocity = nullptr;
+        ok(shs_rt_device_targets(dev_->ctx, &color, &depth, &velocity));
+        // PASS2 on the device (shs_canvas_motion_blur with SHS_CANVAS_DEVICE into a device buffer of the
+        // host's), or shs_rt_resolve into rt->color / rt->depth / rt->velocity for a CPU PASS2.
+        prev_vp_ = proj * view;
+    }
+
+    void ok(int rc) const {
+        if (rc != SHS_OK) throw std::runtime_error(shs_last_error(dev_->ctx));
+    }
+
+    glm::mat4 light_vp{1.0f};        // light_proj * light_view (:1305-1317; shs_ortho_lh_zo, shs_look_at_lh)
+    glm::vec3 light_dir_world{0.0f, -1.0f, 0.0f};
+
+private:
+    SceneT *scene_;
+    Device *dev_;
+    int sm_, tile_;
+    glm::mat4 prev_vp_{1.0f};
 };
 
 // =====================================================================================================

@@ -1,0 +1,251 @@
+// shs_abi_canvas_rt.cpp -- C ABI of the Canvas render-target raster (include/shs_gpu.h), paths relative to
+// the reference's cpp-folders/src/hello-render-target/:
+//   shs_rt_render_shadow  PASS0 of hello_shadow_mapping.cpp (:1320-1411 over draw_triangle_tile_shadow);
+//   shs_rt_render         PASS1 (draw_triangle_tile_color_depth_motion_shadow :854-1022);
+//   shs_ortho_lh_zo       ortho_lh_zo (:128-140).
+// The host forms the matrix products the shaders form first -- u.view * u.model (vertex_shader_full :616),
+// u.light_vp * u.model (shadow_vertex_shader :764) -- and the normal matrix with the GLM restatement in
+// shs_glm.hpp.  Both passes are enqueued on the context stream; the shadow map, the planes and the records
+// live in the context, so a camera pass reads the map of the shadow pass before it in stream order.
+#include <cmath>
+#include <cstring>
+
+#include "shs_canvas_rt_internal.hpp"
+#include "shs_ctx.hpp"
+#include "shs_glm.hpp"
+
+namespace {
+
+bool size_ok(shs_ctx *ctx, int W, int H, int tw, int th) {
+    if (W > 0 && H > 0 && W <= 32767 && H <= 32767 && tw > 0 && th > 0) return true;
+    ctx->err = "render target: 1 .. 32767 per side, reference tile size >= 1";
+    return false;
+}
+
+// The draw table of either pass (zm: view for the camera pass, light_vp for the shadow pass).  Returns the
+// triangle count, or -1 with ctx->err set.
+int64_t build_draws(shs_ctx *ctx, const shs_rt_draw *draws, int32_t n, const float *zmat, bool camera) {
+    ctx->rt_h_draws.clear();
+    int64_t total = 0;
+    for (int32_t i = 0; i < n; ++i) {
+        const shs_rt_draw &in = draws[i];
+        if (in.mesh_id < 0 || in.mesh_id >= (int32_t)ctx->meshes.size() || !ctx->meshes[in.mesh_id].live ||
+            ctx->meshes[in.mesh_id].lib) {
+            ctx->err = "render-target draw: unknown soup mesh id";
+            return -1;
+        }
+        const Mesh &m = ctx->meshes[in.mesh_id];
+        shs_dev::RtDrawGPU o{};
+        o.pos = m.pos;
+        o.nrm = m.nrm;
+        o.uv = m.soup_uv ? m.nrm + (size_t)m.n_tris * 9 : nullptr;
+        if (camera && in.albedo_tex != 0) {
+            if (in.albedo_tex < 0 || in.albedo_tex > (int32_t)ctx->textures.size() || !ctx->textures[(size_t)in.albedo_tex - 1].live) {
+                ctx->err = "render-target draw: unknown texture id";
+                return -1;
+            }
+            const Texture &t = ctx->textures[(size_t)in.albedo_tex - 1];
+            o.texels = t.texels;
+            o.tw = t.w;
+            o.th = t.h;
+        }
+        o.n_tris = m.n_tris;
+        o.base = (int32_t)total;
+        std::memcpy(o.mvp, in.mvp, sizeof o.mvp);
+        std::memcpy(o.prev_mvp, in.prev_mvp, sizeof o.prev_mvp);
+        std::memcpy(o.model, in.model, sizeof o.model);
+        shs_host::mul(zmat, in.model, o.zm);
+        shs_host::normal_matrix(in.model, o.n3);
+        for (int k = 0; k < 3; ++k) o.colf[k] = (float)in.base_color[k];
+        ctx->rt_h_draws.push_back(o);
+        total += m.n_tris;
+        if (total > (1 << 29)) {
+            ctx->err = "render-target pass: more than 2^29 triangles";
+            return -1;
+        }
+    }
+    return total;
+}
+
+int upload_and_launch(shs_ctx *ctx, shs_dev::RtParams &p, bool shadow_pass) {
+    const size_t nd = ctx->rt_h_draws.size();
+    if (ensure(ctx, ctx->rt_draws, std::max<size_t>(nd, 1)) || ensure(ctx, ctx->rt_recs, std::max<size_t>((size_t)p.n_recs, 1)) ||
+        ensure(ctx, ctx->rt_stats, 4))
+        return SHS_ERR_HIP;
+    if (!shadow_pass && ensure(ctx, ctx->rt_vary, std::max<size_t>((size_t)p.n_recs, 1))) return SHS_ERR_HIP;
+    if (nd) {
+        const int k = (int)(ctx->rt_pin_next++ & 1u);
+        if (!ctx->rt_pin_ev[k]) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->rt_pin_ev[k], hipEventDisableTiming));
+        else HIP_TRY(ctx, hipEventSynchronize(ctx->rt_pin_ev[k]));
+        if (ctx->rt_pin_cap[k] < nd) {
+            if (ctx->rt_pin[k]) HIP_TRY(ctx, hipHostFree(ctx->rt_pin[k]));
+            ctx->rt_pin[k] = nullptr;
+            ctx->rt_pin_cap[k] = 0;
+            HIP_TRY(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->rt_pin[k]), nd * sizeof(shs_dev::RtDrawGPU), hipHostMallocDefault));
+            ctx->rt_pin_cap[k] = nd;
+        }
+        std::memcpy(ctx->rt_pin[k], ctx->rt_h_draws.data(), nd * sizeof(shs_dev::RtDrawGPU));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->rt_draws.p, ctx->rt_pin[k], nd * sizeof(shs_dev::RtDrawGPU), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipEventRecord(ctx->rt_pin_ev[k], ctx->stream));
+    }
+    if (!shadow_pass) HIP_TRY(ctx, hipMemsetAsync(ctx->rt_stats.p, 0, 4 * sizeof(unsigned long long), ctx->stream));
+    p.draws = ctx->rt_draws.p;
+    p.recs = ctx->rt_recs.p;
+    p.vary = ctx->rt_vary.p;
+    p.stats = ctx->rt_stats.p;
+    HIP_TRY(ctx, shs_internal::launch_canvas_rt(p, shadow_pass, ctx->stream));
+    return SHS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int shs_rt_render_shadow(shs_ctx *ctx, int32_t w, int32_t h, int32_t ref_tile_w, int32_t ref_tile_h, const float light_vp[16],
+                         const shs_rt_draw *casters, int32_t n_casters) {
+    if (!ctx || !light_vp || n_casters < 0 || (n_casters > 0 && !casters)) return SHS_ERR_INVALID;
+    if (!size_ok(ctx, w, h, ref_tile_w, ref_tile_h)) return SHS_ERR_INVALID;
+    if (set_dev(ctx)) return SHS_ERR_HIP;
+    const int64_t n_tris = build_draws(ctx, casters, n_casters, light_vp, false);
+    if (n_tris < 0) return SHS_ERR_INVALID;
+    if (ensure(ctx, ctx->rt_shadow, (size_t)w * h)) return SHS_ERR_HIP;
+    shs_dev::RtParams p{};
+    p.W = w; p.H = h;
+    p.tile_w = std::min(ref_tile_w, w);   // (a job larger than the target is the whole target)
+    p.tile_h = std::min(ref_tile_h, h);
+    p.n_draws = n_casters;
+    p.n_tris = (int32_t)n_tris;
+    p.n_recs = (int32_t)n_tris;
+    p.depth = ctx->rt_shadow.p;
+    // the shadow pass shares the stats words with the camera pass: its own count is not reported
+    const int rc = upload_and_launch(ctx, p, true);
+    if (rc) return rc;
+    ctx->rt_sw = w;
+    ctx->rt_sh = h;
+    ctx->rt_have_shadow = true;
+    return SHS_OK;
+}
+
+int shs_rt_render(shs_ctx *ctx, const shs_rt_frame *f, const shs_rt_draw *draws, int32_t n_draws) {
+    if (!ctx || !f || n_draws < 0 || (n_draws > 0 && !draws)) return SHS_ERR_INVALID;
+    if (!size_ok(ctx, f->width, f->height, f->ref_tile_w, f->ref_tile_h)) return SHS_ERR_INVALID;
+    if ((f->flags & ~(SHS_RT_USE_SHADOW | SHS_RT_PCF | SHS_RT_PREQUANT)) || f->shading != 0) {
+        ctx->err = "render-target frame: unknown flags or shading";
+        return SHS_ERR_INVALID;
+    }
+    if ((f->flags & SHS_RT_USE_SHADOW) && !ctx->rt_have_shadow) {
+        ctx->err = "render-target frame: SHS_RT_USE_SHADOW without a shs_rt_render_shadow before it";
+        return SHS_ERR_INVALID;
+    }
+    if (set_dev(ctx)) return SHS_ERR_HIP;
+    const int64_t n_tris = build_draws(ctx, draws, n_draws, f->view, true);
+    if (n_tris < 0) return SHS_ERR_INVALID;
+    const size_t npx = (size_t)f->width * f->height;
+    const bool pq = (f->flags & SHS_RT_PREQUANT) != 0;
+    if (ensure(ctx, ctx->rt_color, npx) || ensure(ctx, ctx->rt_depth, npx) || ensure(ctx, ctx->rt_vel, 2 * npx) ||
+        ensure(ctx, ctx->rt_ids, npx) || (pq && ensure(ctx, ctx->rt_pq, npx)))
+        return SHS_ERR_HIP;
+    shs_dev::RtParams p{};
+    p.W = f->width; p.H = f->height;
+    p.tile_w = std::min(f->ref_tile_w, f->width);   // (a job larger than the target is the whole target)
+    p.tile_h = std::min(f->ref_tile_h, f->height);
+    p.n_draws = n_draws;
+    p.n_tris = (int32_t)n_tris;
+    p.n_recs = 2 * (int32_t)n_tris;
+    std::memcpy(&p.clear_rgba, f->clear_color, 4);
+    p.flags = f->flags;
+    std::memcpy(p.light_vp, f->light_vp, sizeof p.light_vp);
+    // glm::normalize(-u.light_dir_world) (:702), the same for every fragment
+    const shs_host::vec3 L = shs_host::gnormalize(shs_host::gneg({f->light_dir_world[0], f->light_dir_world[1], f->light_dir_world[2]}));
+    p.L[0] = L.x; p.L[1] = L.y; p.L[2] = L.z;
+    std::memcpy(p.cam, f->camera_pos, sizeof p.cam);
+    p.bias_base = f->bias_base;
+    p.bias_slope = f->bias_slope;
+    p.max_velocity = f->max_velocity_px;
+    if (f->flags & SHS_RT_USE_SHADOW) {
+        p.shadow = ctx->rt_shadow.p;
+        p.sw = ctx->rt_sw;
+        p.sh = ctx->rt_sh;
+    }
+    p.color = ctx->rt_color.p;
+    p.depth = ctx->rt_depth.p;
+    p.velocity = reinterpret_cast<float2 *>(ctx->rt_vel.p);
+    p.prequant = pq ? ctx->rt_pq.p : nullptr;
+    p.ids = ctx->rt_ids.p;
+    const int rc = upload_and_launch(ctx, p, false);
+    if (rc) {
+        ctx->rt_have_frame = false;
+        return rc;
+    }
+    ctx->rt_w = f->width;
+    ctx->rt_h = f->height;
+    ctx->rt_n_tris = n_tris;
+    ctx->rt_have_frame = true;
+    ctx->rt_have_pq = pq;
+    return SHS_OK;
+}
+
+int shs_rt_resolve(shs_ctx *ctx, uint8_t *color, float *depth, float *velocity) {
+    if (!ctx || !ctx->rt_have_frame) return SHS_ERR_INVALID;
+    if (set_dev(ctx)) return SHS_ERR_HIP;
+    const size_t npx = (size_t)ctx->rt_w * ctx->rt_h;
+    if (color) HIP_TRY(ctx, hipMemcpyAsync(color, ctx->rt_color.p, npx * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (depth) HIP_TRY(ctx, hipMemcpyAsync(depth, ctx->rt_depth.p, npx * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (velocity) HIP_TRY(ctx, hipMemcpyAsync(velocity, ctx->rt_vel.p, npx * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return SHS_OK;
+}
+
+int shs_rt_resolve_shadow(shs_ctx *ctx, float *shadow_map) {
+    if (!ctx || !shadow_map || !ctx->rt_have_shadow) return SHS_ERR_INVALID;
+    if (set_dev(ctx)) return SHS_ERR_HIP;
+    HIP_TRY(ctx, hipMemcpyAsync(shadow_map, ctx->rt_shadow.p, (size_t)ctx->rt_sw * ctx->rt_sh * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return SHS_OK;
+}
+
+int shs_rt_resolve_prequant(shs_ctx *ctx, float *prequant) {
+    if (!ctx || !prequant || !ctx->rt_have_frame || !ctx->rt_have_pq) return SHS_ERR_INVALID;
+    if (set_dev(ctx)) return SHS_ERR_HIP;
+    HIP_TRY(ctx, hipMemcpyAsync(prequant, ctx->rt_pq.p, (size_t)ctx->rt_w * ctx->rt_h * 16, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return SHS_OK;
+}
+
+int shs_rt_resolve_ids(shs_ctx *ctx, int32_t *tri_id) {
+    if (!ctx || !tri_id || !ctx->rt_have_frame) return SHS_ERR_INVALID;
+    if (set_dev(ctx)) return SHS_ERR_HIP;
+    HIP_TRY(ctx, hipMemcpyAsync(tri_id, ctx->rt_ids.p, (size_t)ctx->rt_w * ctx->rt_h * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return SHS_OK;
+}
+
+int shs_rt_get_stats(shs_ctx *ctx, shs_rt_stats *st) {
+    if (!ctx || !st || !ctx->rt_have_frame) return SHS_ERR_INVALID;
+    if (set_dev(ctx)) return SHS_ERR_HIP;
+    unsigned long long h[4] = {0, 0, 0, 0};
+    HIP_TRY(ctx, hipMemcpyAsync(h, ctx->rt_stats.p, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    st->input_tris = ctx->rt_n_tris;
+    st->polys3 = (int64_t)h[1];
+    st->polys4 = (int64_t)h[2];
+    st->sub_tris = (int64_t)h[3];
+    return SHS_OK;
+}
+
+int shs_rt_device_targets(shs_ctx *ctx, void **color_dev, void **depth_dev, void **velocity_dev) {
+    if (!ctx || !ctx->rt_have_frame) return SHS_ERR_INVALID;
+    // the passes are enqueued whole on the context stream: the planes are final in its order
+    if (color_dev) *color_dev = ctx->rt_color.p;
+    if (depth_dev) *depth_dev = ctx->rt_depth.p;
+    if (velocity_dev) *velocity_dev = ctx->rt_vel.p;
+    return SHS_OK;
+}
+
+int shs_ortho_lh_zo(float left, float right, float bottom, float top, float znear, float zfar, float out16[16]) {
+    if (!out16) return SHS_ERR_INVALID;
+    shs_host::ortho_lh_zo(left, right, bottom, top, znear, zfar, out16);
+    return SHS_OK;
+}
+
+}  // extern "C"

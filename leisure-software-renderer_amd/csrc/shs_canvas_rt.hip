@@ -1,0 +1,565 @@
+// shs_canvas_rt.hip -- the Canvas render-target raster of the hello-render-target/ demos, for
+// hello_shadow_mapping.cpp (paths relative to the reference's cpp-folders/src/hello-render-target/):
+//   PASS0  draw_triangle_tile_shadow (:791-834): depth only from the light, ndc z in [0, 1];
+//   PASS1  draw_triangle_tile_color_depth_motion_shadow (:854-1022) with vertex_shader_full (:602-620) and
+//          fragment_shader_full (:699-750): near-plane clipping in clip space, no facing cull, view-z depth
+//          in canvas rows, perspective-correct world position and UV, velocity, the shadow lookup.
+//
+// Two kernels per pass, the same two for both (template <bool SHADOW>):
+//   k_rt_setup   one lane per input triangle: the vertex shader once per corner (the reference re-runs it
+//                per tile job; it is pure), the Sutherland-Hodgman clip against z >= 0 in the reference's
+//                push order (an unclipped triangle leaves it as {v1, v2, v0}), the fan (0, i, i + 1), and per
+//                sub-triangle a raster record (RtRec, id 2 t + k) plus the corners' varyings (RtVary).
+//   k_rt_raster  one workgroup per 32x8 tile, one pixel per lane.  Rounds of RT_CHUNK records in
+//                submission order: every lane tests one record against the tile, the passing ones are
+//                compacted into LDS in order, then each lane walks them in order and keeps (best depth,
+//                shading id, u, v, w) in registers -- the strict '<' of ZBuffer::test_and_set_depth with the
+//                first of equal depths winning, and the rule that a fragment with invw_sum <= 1e-8 keeps its
+//                depth but not its colour, both without atomics.  Then the lane shades its pixel and stores
+//                colour, depth and velocity once; the clear is the value of a pixel nothing covered.
+//
+// Tile-clamp semantics.  The reference clamps a sub-triangle's bbox to the tile job
+// that runs it, so it also tests pixels outside the bbox: the clamped edge columns, rows and corners of
+// every job.  Here a pixel evaluates the reference's own visit test for the job it lies in -- (int) of the
+// clamped float bbox, per axis -- before the barycentric, so whatever a tile stages is tested exactly.  A
+// record is staged for a tile when that visited set meets the tile and the tile meets the record's cull
+// box: the legacy raster's error bound (danger_margin) proves every pixel outside it rejected.  Without the
+// cull box a tile holding a job's corner pixel would stage every record (each is visited there).  A sliver
+// with no usable bound has the whole target as its cull box: exact, not fast.
+//
+// Arithmetic: no contraction, correctly rounded '/' and sqrt (Makefile), GLM's operation order; the
+// x86-64 float -> int conversions of the reference build are spelled out where a value can leave int's
+// range; pow(x, 64.0f) by six squarings in double (as the legacy shaders' pow2k).
+#include <float.h>
+#include <limits.h>
+
+#include "shs_canvas_rt_internal.hpp"
+#include "shs_device.hpp"
+#include "../../include/shs_gpu.h"
+
+namespace shs_dev {
+namespace {
+
+struct Vy {            // VaryingsFull :588-596
+    float p[4], q[4];  // position, prev_position
+    float wp[3], n[3];
+    float uv[2];
+    float vz;
+};
+
+__device__ __forceinline__ float lerp1(float a, float b, float t) { return a + (b - a) * t; }
+
+// lerp_vary :866-875
+__device__ void lerp_vary(const Vy &a, const Vy &b, float t, Vy &o) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { o.p[k] = lerp1(a.p[k], b.p[k], t); o.q[k] = lerp1(a.q[k], b.q[k], t); }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { o.wp[k] = lerp1(a.wp[k], b.wp[k], t); o.n[k] = lerp1(a.n[k], b.n[k], t); }
+    o.uv[0] = lerp1(a.uv[0], b.uv[0], t);
+    o.uv[1] = lerp1(a.uv[1], b.uv[1], t);
+    o.vz = lerp1(a.vz, b.vz, t);
+}
+
+// intersect :885-893
+__device__ void intersect(const Vy &a, const Vy &b, Vy &o) {
+    const float az = a.p[2], bz = b.p[2];
+    const float denom = bz - az;
+    float t = (fabsf(denom) < 1e-8f) ? 0.0f : ((0.0f - az) / denom);
+    t = (t < 0.0f) ? 0.0f : (t > 1.0f ? 1.0f : t);   // clampf :86-91
+    lerp_vary(a, b, t, o);
+}
+
+__device__ __forceinline__ bool inside(const Vy &v) { return (v.p[3] > 1e-6f) && (v.p[2] >= 0.0f); }
+
+__device__ __forceinline__ bool finitef(float x) { return fabsf(x) <= FLT_MAX; }
+// floor of a float, clamped into [lo, hi] before the conversion (a NaN gives lo)
+__device__ __forceinline__ int floor_clamped(float x, int lo, int hi) {
+    return (int)fminf(fmaxf(floorf(x), (float)lo), (float)hi);
+}
+
+// The legacy raster's error bound (shs_legacy.hip danger_margin) over this record: the
+// barycentric arithmetic is the same, and the bound is orientation-independent.  A pixel whose centre lies
+// rx / ry px outside the float bbox has a minimal exact barycentric <= -max(rx / 2Wx, ry / 2Wy); the float
+// evaluation's error is at most E = e0 + ex rx + ey ry (u = 2^-24; dot products 2u, the two-product
+// differences 6u, the divide and 1 - v - w a few u more; 25 % slack), so the pixel is provably rejected
+// outside the bbox grown by (dgx, dgy) = 2 W m0, m0 = e0 / (1 - 2 (ex Wx + ey Wy)).  (-1, -1): no bound.
+__device__ double2 danger_margin(const RtRec &r) {
+    const double2 none = make_double2(-1.0, -1.0);
+    const double u = 5.9604644775390625e-08;  // 2^-24
+    const double a = fabs((double)r.v0x), b = fabs((double)r.v0y);
+    const double c = fabs((double)r.v1x), d = fabs((double)r.v1y);
+    const double Wx = (double)r.maxx - (double)r.minx, Wy = (double)r.maxy - (double)r.miny;
+    if (!(Wx > 0.0) || !(Wy > 0.0)) return none;
+    const double A00 = a * a + b * b, A11 = c * c + d * d, A01 = a * c + b * d;
+    const double Dabs = fabs((double)r.denom);
+    const double ED = 6.1 * u * (A00 * A11 + A01 * A01);
+    const double Dlow = Dabs - ED;
+    if (!(Dlow > 0.0) || !(Dabs < 1e300)) return none;
+    const double iDlow = 1.0 / Dlow, iDabs = 1.0 / Dabs;
+    const double K1 = 7.2 * u + ED * iDlow;
+    const double p0 = Wx + 0.01, q0 = Wy + 0.01;
+    const double A20 = p0 * a + q0 * b, A21 = p0 * c + q0 * d;
+    const double Nv0 = A11 * A20 + A01 * A21, Nvx = A11 * a + A01 * c, Nvy = A11 * b + A01 * d;
+    const double Nw0 = A00 * A21 + A01 * A20, Nwx = A00 * c + A01 * a, Nwy = A00 * d + A01 * b;
+    const double s = K1 * iDabs * (2.0 + 2.0 * u);
+    const double e0 = 1.25 * ((Nv0 + Nw0) * s + u * (2.0 + (2.0 * Nv0 + Nw0) * iDlow));
+    const double ex = 1.25 * ((Nvx + Nwx) * s + u * (2.0 * Nvx + Nwx) * iDlow);
+    const double ey = 1.25 * ((Nvy + Nwy) * s + u * (2.0 * Nvy + Nwy) * iDlow);
+    const double S = ex * Wx + ey * Wy;
+    if (!(S < 0.5)) return none;
+    const double m0 = e0 / (1.0 - 2.0 * S);
+    const double dgx = 2.0 * Wx * m0, dgy = 2.0 * Wy * m0;
+    return (dgx < 1e6 && dgy < 1e6) ? make_double2(dgx, dgy) : none;
+}
+
+// The pixel-independent part of barycentric_coordinate (shs_renderer.hpp:802-815), the area test and the
+// bbox over the corners that are not NaN.  false: the sub-triangle draws nothing.
+__device__ bool rec_geometry(RtRec &r, const float (&sx)[3], const float (&sy)[3], int W, int H) {
+    r.ax = sx[0]; r.ay = sy[0];
+    r.v0x = sx[1] - sx[0]; r.v0y = sy[1] - sy[0];
+    r.v1x = sx[2] - sx[0]; r.v1y = sy[2] - sy[0];
+    r.d00 = r.v0x * r.v0x + r.v0y * r.v0y;
+    r.d01 = r.v0x * r.v1x + r.v0y * r.v1y;
+    r.d11 = r.v1x * r.v1x + r.v1y * r.v1y;
+    r.denom = r.d00 * r.d11 - r.d01 * r.d01;
+    const float area = r.v0x * r.v1y - r.v0y * r.v1x;
+    float mnx = INFINITY, mxx = -INFINITY, mny = INFINITY, mxy = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        mnx = g_min(mnx, sx[i]); mxx = g_max(mxx, sx[i]);
+        mny = g_min(mny, sy[i]); mxy = g_max(mxy, sy[i]);
+    }
+    r.minx = mnx; r.maxx = mxx; r.miny = mny; r.maxy = mxy;
+    // the cull box: the integer bbox, for a sliver grown by its danger margin + 1 px; the whole target where
+    // there is no bound (or a large one): every pixel the reference visits is then tested
+    const bool dfin = finitef(r.d00) && finitef(r.d01) && finitef(r.d11) && finitef(r.denom);
+    const double2 dg = dfin ? danger_margin(r) : make_double2(-1.0, -1.0);
+    const bool unbounded = !(dg.x >= 0.0) || dg.x > GHOST_MAX_EXPAND || dg.y > GHOST_MAX_EXPAND;
+    const bool ghost = dg.x >= 0.49 || dg.y >= 0.49;
+    const double exx = ghost ? dg.x + 1.0 : 0.0, exy = ghost ? dg.y + 1.0 : 0.0;
+    const int cx0 = unbounded ? 0 : floor_clamped((float)((double)mnx - exx), 0, W);
+    const int cx1 = unbounded ? W - 1 : floor_clamped((float)((double)mxx + exx), -1, W - 1);
+    const int cy0 = unbounded ? 0 : floor_clamped((float)((double)mny - exy), 0, H);
+    const int cy1 = unbounded ? H - 1 : floor_clamped((float)((double)mxy + exy), -1, H - 1);
+    r.gbx = pack16(cx0, cx1);
+    r.gby = pack16(cy0, cy1);
+    if (fabsf(area) < 1e-8f) return false;
+    r.flags = RT_VALID | (area < 0.0f ? RT_NEG_AREA : 0u);
+    // |denom| < 1e-5 (a double comparison): every barycentric is -1, nothing passes -- not staged
+    if ((double)fabsf(r.denom) < 1e-5) r.flags = 0u;
+    return true;
+}
+
+__device__ __forceinline__ void store_rec(RtRec *dst, const RtRec &r) {
+    const float4 *s = reinterpret_cast<const float4 *>(&r);
+    float4 *d = reinterpret_cast<float4 *>(dst);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) d[k] = s[k];
+}
+
+// One camera-pass sub-triangle {a, b, c} (:931-959 up to the pixel loops): its record and varyings.  Returns
+// whether it reaches the raster (the w and area tests passed).
+__device__ bool emit_camera(const RtParams &p, int32_t id, int32_t draw, const Vy &a, const Vy &b, const Vy &c) {
+    RtRec r{};
+    r.draw = draw;
+    const Vy *tv[3] = {&a, &b, &c};
+    bool ok = true;
+    float sx[3], sy[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const float w = tv[i]->p[3];
+        if (w <= 1e-6f) ok = false;
+        // Canvas::clip_to_screen (shs_renderer.hpp:823-831)
+        const float nx = tv[i]->p[0] / w, ny = tv[i]->p[1] / w;
+        sx[i] = (nx + 1.0f) * 0.5f * (float)(p.W - 1);
+        sy[i] = (1.0f - ny) * 0.5f * (float)(p.H - 1);
+    }
+    if (ok) ok = rec_geometry(r, sx, sy, p.W, p.H);
+    if (!ok) {
+        r.flags = 0u;
+    } else {
+        r.z0 = a.vz; r.z1 = b.vz; r.z2 = c.vz;
+        r.iw0 = (fabsf(a.p[3]) < 1e-6f) ? 0.0f : 1.0f / a.p[3];
+        r.iw1 = (fabsf(b.p[3]) < 1e-6f) ? 0.0f : 1.0f / b.p[3];
+        r.iw2 = (fabsf(c.p[3]) < 1e-6f) ? 0.0f : 1.0f / c.p[3];
+        RtVary &v = p.vary[id];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { v.pos[4 * i + k] = tv[i]->p[k]; v.prev[4 * i + k] = tv[i]->q[k]; }
+#pragma unroll
+            for (int k = 0; k < 3; ++k) { v.world[3 * i + k] = tv[i]->wp[k]; v.nrm[3 * i + k] = tv[i]->n[k]; }
+            v.uv[2 * i] = tv[i]->uv[0];
+            v.uv[2 * i + 1] = tv[i]->uv[1];
+        }
+    }
+    store_rec(&p.recs[id], r);
+    return ok;
+}
+
+// One atomic per wave and counter: the wave's lanes that are here, counted by ballot.
+__device__ __forceinline__ void wave_count(unsigned long long *counter, bool mine) {
+    const unsigned long long here = __ballot(1), m = __ballot(mine);
+    const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    if (m && lane == __ffsll((long long)here) - 1) atomicAdd(counter, (unsigned long long)__popcll(m));
+}
+
+// The draw of triangle t (draws are few: the demo has three).
+__device__ __forceinline__ int find_draw(const RtParams &p, int t) {
+    int d = 0;
+    while (d + 1 < p.n_draws && t >= p.draws[d + 1].base) ++d;
+    return d;
+}
+
+template <bool SHADOW>
+__global__ __launch_bounds__(256) void k_rt_setup(const RtParams p) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= p.n_tris) return;
+    const int d = find_draw(p, t);
+    const RtDrawGPU &dr = p.draws[d];
+    const int local = t - dr.base;
+    const float *pos = dr.pos + 9 * (size_t)local;
+    if (SHADOW) {
+        // shadow_vertex_shader :761-766, clip_to_shadow_screen :774-783, :797-820
+        RtRec r{};
+        r.draw = d;
+        bool ok = true;
+        float sx[3], sy[3], sz[3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            float cx, cy, cz, cw;
+            m4p(dr.zm, pos[3 * i], pos[3 * i + 1], pos[3 * i + 2], cx, cy, cz, cw);
+            if (fabsf(cw) < 1e-6f) ok = false;
+            const float nx = cx / cw, ny = cy / cw;
+            sx[i] = (nx * 0.5f + 0.5f) * (float)(p.W - 1);
+            sy[i] = (1.0f - (ny * 0.5f + 0.5f)) * (float)(p.H - 1);
+            sz[i] = cz / cw;
+        }
+        if (ok) ok = rec_geometry(r, sx, sy, p.W, p.H);
+        if (!ok) r.flags = 0u;
+        r.z0 = sz[0]; r.z1 = sz[1]; r.z2 = sz[2];
+        store_rec(&p.recs[t], r);
+        return;
+    }
+    const float *nrm = dr.nrm + 9 * (size_t)local;
+    const float *uv = dr.uv ? dr.uv + 6 * (size_t)local : nullptr;
+    Vy in[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {   // vertex_shader_full :602-620
+        const float x = pos[3 * i], y = pos[3 * i + 1], z = pos[3 * i + 2];
+        m4p(dr.mvp, x, y, z, in[i].p[0], in[i].p[1], in[i].p[2], in[i].p[3]);
+        m4p(dr.prev_mvp, x, y, z, in[i].q[0], in[i].q[1], in[i].q[2], in[i].q[3]);
+        float ww, vx, vy, vw;
+        m4p(dr.model, x, y, z, in[i].wp[0], in[i].wp[1], in[i].wp[2], ww);
+        const f3 n = normalize3(m3v(dr.n3, f3{nrm[3 * i], nrm[3 * i + 1], nrm[3 * i + 2]}));
+        in[i].n[0] = n.x; in[i].n[1] = n.y; in[i].n[2] = n.z;
+        in[i].uv[0] = uv ? uv[2 * i] : 0.0f;
+        in[i].uv[1] = uv ? uv[2 * i + 1] : 0.0f;
+        m4p(dr.zm, x, y, z, vx, vy, in[i].vz, vw);
+    }
+    // clip_poly_near_z :877-913: at most four vertices leave a triangle
+    Vy poly[4];
+    int n = 0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const Vy &A = in[i];
+        const Vy &B = in[(i + 1) % 3];
+        const bool a_in = inside(A), b_in = inside(B);
+        if (a_in && b_in) {
+            if (n < 4) poly[n] = B;
+            ++n;
+        } else if (a_in && !b_in) {
+            if (n < 4) intersect(A, B, poly[n]);
+            ++n;
+        } else if (!a_in && b_in) {
+            if (n < 4) intersect(A, B, poly[n]);
+            ++n;
+            if (n < 4) poly[n] = B;
+            ++n;
+        }
+    }
+    RtRec none{};
+    bool r0 = false, r1 = false;
+    if (n >= 3) r0 = emit_camera(p, 2 * t, d, poly[0], poly[1], poly[2]);
+    else store_rec(&p.recs[2 * t], none);
+    if (n >= 4) r1 = emit_camera(p, 2 * t + 1, d, poly[0], poly[2], poly[3]);
+    else store_rec(&p.recs[2 * t + 1], none);
+    wave_count(&p.stats[1], n == 3);
+    wave_count(&p.stats[2], n == 4);
+    wave_count(&p.stats[3], r0);
+    wave_count(&p.stats[3], r1);
+}
+
+// ---- k_rt_raster -----------------------------------------------------------------------------------
+
+// (int)f as the reference's x86-64 build converts it (cvttss2si: NaN and out-of-range give INT_MIN)
+__device__ __forceinline__ int int_x86(float f) {
+    return (f >= -2147483648.0f && f < 2147483648.0f) ? (int)f : INT_MIN;
+}
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+// (int)std::lround(x) of a product that is NaN or lies in [0, n - 1] (as the legacy
+// texture path's nearest_coord): halves away from zero; glibc's lroundf(NaN) is LONG_MIN, whose (int) is 0
+__device__ __forceinline__ int lround_x86(float x) {
+    if (!(x == x)) return 0;
+    const float t = truncf(x);
+    return (int)t + ((x - t >= 0.5f) ? 1 : 0);
+}
+__device__ __forceinline__ float pow64(float x) {
+    double d = (double)x;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) d = d * d;
+    return (float)d;
+}
+__device__ __forceinline__ uint32_t byte_x86(float x) { return x == x ? (uint32_t)(int32_t)x & 0xffu : 0u; }
+
+// The reference's visited interval of one axis inside the job [tmin, tmax] (:806-815, :822): the float bbox
+// clamped to the job, empty when min > max, then (int) of both ends.
+__device__ __forceinline__ bool visit_axis(float mn, float mx, float tmin, float tmax, int &lo, int &hi) {
+    const float bmin = g_max(tmin, g_min(tmax, mn));
+    const float bmax = g_min(tmax, g_max(tmin, mx));
+    lo = (int)bmin;
+    hi = (int)bmax;
+    return !(bmin > bmax);
+}
+
+// Does the reference visit any pixel of [g0, g1] on this axis?  The jobs j0 .. j1 that overlap the range (the
+// same for every record: the caller divides once), each with its own clamp (n: the axis' size, tile: the job size).
+__device__ __forceinline__ bool axis_meets(float mn, float mx, int g0, int g1, int j0, int j1, int tile, int n) {
+    for (int j = j0; j <= j1; ++j) {
+        const int tmin = j * tile, tmax = min((j + 1) * tile, n) - 1;
+        int lo, hi;
+        if (!visit_axis(mn, mx, (float)tmin, (float)tmax, lo, hi)) continue;
+        if (lo <= min(g1, tmax) && hi >= max(g0, tmin)) return true;
+    }
+    return false;
+}
+
+__device__ __forceinline__ float sm_sample(const RtParams &p, int x, int y) {   // ShadowMap::sample :637-640
+    if (x < 0 || x >= p.sw || y < 0 || y >= p.sh) return FLT_MAX;
+    return p.shadow[(size_t)y * p.sw + x];
+}
+
+// shadow_uvz_from_world, shadow_compare / shadow_factor_pcf_2x2 (:628-693) as fragment_shader_full calls them
+__device__ float shadow_factor(const RtParams &p, f3 wp, float ndotl) {
+    float cx, cy, cz, cw;
+    m4p(p.light_vp, wp.x, wp.y, wp.z, cx, cy, cz, cw);
+    if (fabsf(cw) < 1e-6f) return 1.0f;
+    const float nx = cx / cw, ny = cy / cw, z = cz / cw;
+    if (z < 0.0f || z > 1.0f) return 1.0f;
+    const float u = nx * 0.5f + 0.5f;
+    const float v = 1.0f - (ny * 0.5f + 0.5f);
+    const float slope = 1.0f - g_clamp01(ndotl);
+    const float bias = p.bias_base + p.bias_slope * slope;
+    if (!(p.flags & SHS_RT_PCF)) {
+        if (u < 0.0f || u > 1.0f || v < 0.0f || v > 1.0f) return 1.0f;
+        const int x = lround_x86(u * (float)(p.sw - 1));
+        const int y = lround_x86(v * (float)(p.sh - 1));
+        const float d = sm_sample(p, x, y);
+        if (d == FLT_MAX) return 1.0f;
+        return (z <= d + bias) ? 1.0f : 0.0f;
+    }
+    const float fx = u * (float)(p.sw - 1);
+    const float fy = v * (float)(p.sh - 1);
+    const int x0 = clampi(int_x86(floorf(fx)), 0, p.sw - 1);
+    const int y0 = clampi(int_x86(floorf(fy)), 0, p.sh - 1);
+    const int x1 = clampi(x0 + 1, 0, p.sw - 1);
+    const int y1 = clampi(y0 + 1, 0, p.sh - 1);
+    const float s00 = (z <= sm_sample(p, x0, y0) + bias) ? 1.0f : 0.0f;
+    const float s10 = (z <= sm_sample(p, x1, y0) + bias) ? 1.0f : 0.0f;
+    const float s01 = (z <= sm_sample(p, x0, y1) + bias) ? 1.0f : 0.0f;
+    const float s11 = (z <= sm_sample(p, x1, y1) + bias) ? 1.0f : 0.0f;
+    return 0.25f * (((s00 + s10) + s01) + s11);
+}
+
+// Canvas::clip_to_screen's x and y of an interpolated clip position
+__device__ __forceinline__ void to_screen(const RtParams &p, float x, float y, float w, float &sx, float &sy) {
+    const float nx = x / w, ny = y / w;
+    sx = (nx + 1.0f) * 0.5f * (float)(p.W - 1);
+    sy = (1.0f - ny) * 0.5f * (float)(p.H - 1);
+}
+
+// The shown fragment of a camera-pass pixel (:971-1013) at the shading sub-triangle's barycentrics.
+__device__ void shade_pixel(const RtParams &p, int32_t id, float u, float v, float w, uint32_t &rgba, float2 &vel, float4 &pq) {
+    const RtRec &r = p.recs[id];
+    const RtVary &y = p.vary[id];
+    const RtDrawGPU &dr = p.draws[r.draw];
+    const float iw0 = r.iw0, iw1 = r.iw1, iw2 = r.iw2;
+    const float invw_sum = (u * iw0 + v * iw1) + w * iw2;
+    float pos[4], prev[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        pos[k] = (u * y.pos[k] + v * y.pos[4 + k]) + w * y.pos[8 + k];
+        prev[k] = (u * y.prev[k] + v * y.prev[4 + k]) + w * y.prev[8 + k];
+    }
+    const f3 nsum = {(u * y.nrm[0] + v * y.nrm[3]) + w * y.nrm[6], (u * y.nrm[1] + v * y.nrm[4]) + w * y.nrm[7],
+                     (u * y.nrm[2] + v * y.nrm[5]) + w * y.nrm[8]};
+    const f3 in_normal = normalize3(nsum);
+    f3 wp;
+    wp.x = ((u * (y.world[0] * iw0) + v * (y.world[3] * iw1)) + w * (y.world[6] * iw2)) / invw_sum;
+    wp.y = ((u * (y.world[1] * iw0) + v * (y.world[4] * iw1)) + w * (y.world[7] * iw2)) / invw_sum;
+    wp.z = ((u * (y.world[2] * iw0) + v * (y.world[5] * iw1)) + w * (y.world[8] * iw2)) / invw_sum;
+    const float tu = ((u * (y.uv[0] * iw0) + v * (y.uv[2] * iw1)) + w * (y.uv[4] * iw2)) / invw_sum;
+    const float tv = ((u * (y.uv[1] * iw0) + v * (y.uv[3] * iw1)) + w * (y.uv[5] * iw2)) / invw_sum;
+    // velocity :1002-1011
+    float csx, csy, psx, psy;
+    to_screen(p, pos[0], pos[1], pos[3], csx, csy);
+    to_screen(p, prev[0], prev[1], prev[3], psx, psy);
+    float vx = csx - psx, vy = -(csy - psy);
+    const float len = sqrtf(vx * vx + vy * vy);
+    if (len > p.max_velocity && len > 1e-6f) {
+        const float s = p.max_velocity / len;
+        vx *= s;
+        vy *= s;
+    }
+    vel = make_float2(vx, vy);
+    // fragment_shader_full :699-750
+    const f3 N = normalize3(in_normal);
+    const f3 L = {p.L[0], p.L[1], p.L[2]};
+    const f3 V = normalize3(sub3(f3{p.cam[0], p.cam[1], p.cam[2]}, wp));
+    const float ambient = 0.18f * 1.0f;
+    const float ndotl = dot3(N, L);
+    const float diffuse = g_max(ndotl, 0.0f) * 1.0f;
+    const f3 H = normalize3(add3(L, V));
+    const float spec = pow64(g_max(dot3(N, H), 0.0f));
+    const float specular = (0.45f * spec) * 1.0f;
+    f3 base = {dr.colf[0] / 255.0f, dr.colf[1] / 255.0f, dr.colf[2] / 255.0f};
+    if (dr.texels) {
+        // sample_nearest (shs_renderer.hpp:367-377)
+        const float su = (tu < 0.0f) ? 0.0f : (tu > 1.0f ? 1.0f : tu);
+        const float sv = (tv < 0.0f) ? 0.0f : (tv > 1.0f ? 1.0f : tv);
+        const int x = clampi(lround_x86(su * (float)(dr.tw - 1)), 0, dr.tw - 1);
+        const int yy = clampi(lround_x86(sv * (float)(dr.th - 1)), 0, dr.th - 1);
+        const uint32_t tc = dr.texels[(size_t)yy * dr.tw + x];
+        base = f3{(float)(tc & 0xffu) / 255.0f, (float)((tc >> 8) & 0xffu) / 255.0f, (float)((tc >> 16) & 0xffu) / 255.0f};
+    }
+    float shadow = 1.0f;
+    if (p.shadow) shadow = shadow_factor(p, wp, ndotl);
+    const float lit = ambient + shadow * (diffuse + specular);
+    const float pr = g_clamp01(lit * base.x) * 255, pg = g_clamp01(lit * base.y) * 255, pb = g_clamp01(lit * base.z) * 255;
+    rgba = byte_x86(pr) | (byte_x86(pg) << 8) | (byte_x86(pb) << 16) | 0xff000000u;
+    pq = make_float4(pr, pg, pb, shadow);
+}
+
+template <bool SHADOW>
+__global__ __launch_bounds__(256) void k_rt_raster(const RtParams p) {
+    __shared__ float4 s_rec[RT_CHUNK * 6];
+    __shared__ int32_t s_id[RT_CHUNK];
+    __shared__ int s_wave[4];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int tiles_x = (p.W + RT_TW - 1) / RT_TW;
+    const int gx0 = (int)(blockIdx.x % tiles_x) * RT_TW, gy0 = (int)(blockIdx.x / tiles_x) * RT_TH;   // screen space, y down
+    const int gx1 = min(gx0 + RT_TW, p.W) - 1, gy1 = min(gy0 + RT_TH, p.H) - 1;
+    const int px = gx0 + (tid & (RT_TW - 1)), py = gy0 + tid / RT_TW;
+    const bool live = px < p.W && py < p.H;
+    // the reference tile job this pixel lies in
+    const int jx = px / p.tile_w, jy = py / p.tile_h;
+    const float tminx = (float)(jx * p.tile_w), tmaxx = (float)(min((jx + 1) * p.tile_w, p.W) - 1);
+    const float tminy = (float)(jy * p.tile_h), tmaxy = (float)(min((jy + 1) * p.tile_h, p.H) - 1);
+    const float Px = (float)px + 0.5f, Py = (float)py + 0.5f;
+    // the jobs this tile overlaps
+    const int j0x = gx0 / p.tile_w, j1x = gx1 / p.tile_w, j0y = gy0 / p.tile_h, j1y = gy1 / p.tile_h;
+
+    float best = FLT_MAX;
+    int32_t sid = -1;
+    float su = 0.0f, sv = 0.0f, sw = 0.0f;
+
+    for (int base = 0; base < p.n_recs; base += RT_CHUNK) {
+        // one record per lane: is any pixel of this tile visited?
+        const int ri = base + tid;
+        bool cand = false;
+        if (ri < p.n_recs) {
+            const float4 *g = reinterpret_cast<const float4 *>(&p.recs[ri]);
+            const float4 q3 = g[3], q4 = g[4];   // (z2, flags, minx, maxx) (miny, maxy, gbx, gby)
+            const uint32_t gbx = __float_as_uint(q4.z), gby = __float_as_uint(q4.w);
+            cand = (__float_as_uint(q3.y) & RT_VALID) && lo16(gbx) <= gx1 && hi16(gbx) >= gx0 && lo16(gby) <= gy1 &&
+                   hi16(gby) >= gy0 && axis_meets(q3.z, q3.w, gx0, gx1, j0x, j1x, p.tile_w, p.W) &&
+                   axis_meets(q4.x, q4.y, gy0, gy1, j0y, j1y, p.tile_h, p.H);
+        }
+        const unsigned long long m = __ballot(cand);
+        if (lane == 0) s_wave[wave] = __popcll(m);
+        __syncthreads();
+        int slot = __popcll(m & ((1ull << lane) - 1ull));
+        int n_c = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (k < wave) slot += s_wave[k];
+            n_c += s_wave[k];
+        }
+        if (cand) {
+            const float4 *g = reinterpret_cast<const float4 *>(&p.recs[ri]);
+#pragma unroll
+            for (int k = 0; k < 6; ++k) s_rec[slot * 6 + k] = g[k];
+            s_id[slot] = ri;
+        }
+        __syncthreads();
+        if (live) {
+            for (int c = 0; c < n_c; ++c) {
+                const float4 a3 = s_rec[c * 6 + 3], a4 = s_rec[c * 6 + 4];
+                int lo, hi;
+                if (!visit_axis(a3.z, a3.w, tminx, tmaxx, lo, hi) || px < lo || px > hi) continue;
+                if (!visit_axis(a4.x, a4.y, tminy, tmaxy, lo, hi) || py < lo || py > hi) continue;
+                const float4 a0 = s_rec[c * 6 + 0], a1 = s_rec[c * 6 + 1], a2 = s_rec[c * 6 + 2];
+                // barycentric_coordinate (shs_renderer.hpp:809-820)
+                const float vpx = Px - a0.x, vpy = Py - a0.y;
+                const float d20 = vpx * a0.z + vpy * a0.w;
+                const float d21 = vpx * a1.x + vpy * a1.y;
+                const float v = (a2.x * d20 - a1.w * d21) / a2.y;
+                const float w = (a1.z * d21 - a1.w * d20) / a2.y;
+                const float u = 1.0f - v - w;
+                if (u < 0 || v < 0 || w < 0) continue;
+                const float z = (u * a2.z + v * a2.w) + w * a3.x;
+                if (SHADOW) {
+                    if (z < 0.0f || z > 1.0f) continue;
+                    if (z < best) best = z;
+                } else {
+                    if (!(z < best)) continue;
+                    best = z;
+                    const float4 a5 = s_rec[c * 6 + 5];   // (iw0, iw1, iw2, draw)
+                    const float invw_sum = (u * a5.x + v * a5.y) + w * a5.z;
+                    if (invw_sum <= 1e-8f) continue;
+                    sid = s_id[c];
+                    su = u; sv = v; sw = w;
+                }
+            }
+        }
+        __syncthreads();
+    }
+    if (!live) return;
+    if (SHADOW) {
+        p.depth[(size_t)py * p.W + px] = best;
+        return;
+    }
+    uint32_t rgba = p.clear_rgba;
+    float2 vel = make_float2(0.0f, 0.0f);
+    float4 pq = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (sid >= 0) shade_pixel(p, sid, su, sv, sw, rgba, vel, pq);
+    const size_t o = (size_t)(p.H - 1 - py) * p.W + px;   // canvas rows
+    p.color[o] = rgba;
+    p.depth[o] = best;
+    p.velocity[o] = vel;
+    p.ids[o] = sid;
+    if (p.prequant) p.prequant[o] = pq;
+}
+
+}  // namespace
+}  // namespace shs_dev
+
+namespace shs_internal {
+
+hipError_t launch_canvas_rt(const shs_dev::RtParams &p, bool shadow_pass, hipStream_t s) {
+    using namespace shs_dev;
+    if (p.n_tris > 0) {
+        const int grid = (p.n_tris + 255) / 256;
+        if (shadow_pass) hipLaunchKernelGGL(k_rt_setup<true>, dim3(grid), dim3(256), 0, s, p);
+        else hipLaunchKernelGGL(k_rt_setup<false>, dim3(grid), dim3(256), 0, s, p);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    const int tiles = ((p.W + RT_TW - 1) / RT_TW) * ((p.H + RT_TH - 1) / RT_TH);
+    if (shadow_pass) hipLaunchKernelGGL(k_rt_raster<true>, dim3(tiles), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(k_rt_raster<false>, dim3(tiles), dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+
+}  // namespace shs_internal

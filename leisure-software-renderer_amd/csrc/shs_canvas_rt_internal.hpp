@@ -1,0 +1,81 @@
+// shs_canvas_rt_internal.hpp -- launch interface of shs_canvas_rt.hip: the Canvas render-target raster of
+// hello-render-target/hello_shadow_mapping.cpp (shadow pass and shadowed camera pass; include/shs_gpu.h).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+namespace shs_dev {
+
+// One sub-triangle as the raster walks it, 96 B (six float4s): the pixel-independent terms of
+// Canvas::barycentric_coordinate over its screen corners {A, B, C}, the depth the pass tests at the corners
+// (camera pass: view z; shadow pass: ndc z), the float bbox of the corners (NaN corners left out, as the
+// reference's glm::min / glm::max fold leaves them out), the cull box and the corners' invw of the camera pass.
+struct alignas(16) RtRec {
+    float ax, ay, v0x, v0y;          // A, v0 = B - A
+    float v1x, v1y, d00, d01;        // v1 = C - A
+    float d11, denom, z0, z1;
+    float z2;
+    uint32_t flags;                  // RT_VALID | RT_NEG_AREA
+    float minx, maxx;
+    float miny, maxy;
+    uint32_t gbx, gby;               // cull box, packed int16 (lo | hi << 16): outside it no pixel can pass
+    float iw0, iw1, iw2;
+    int32_t draw;
+};
+static_assert(sizeof(RtRec) == 96, "RtRec is staged as six float4s");
+constexpr uint32_t RT_VALID = 1u, RT_NEG_AREA = 2u;
+
+// The corners' varyings (VaryingsFull) of a camera-pass sub-triangle, read by the pixels it shades.
+struct alignas(16) RtVary {
+    float pos[12];                   // position (clip), corner-major
+    float prev[12];                  // prev_position
+    float world[9];
+    float nrm[9];
+    float uv[6];
+};
+static_assert(sizeof(RtVary) == 192, "RtVary: 48 floats");
+
+struct RtDrawGPU {
+    const float *pos;                // soup: 9 floats per triangle
+    const float *nrm;
+    const float *uv;                 // 6 floats per triangle, or null
+    const uint32_t *texels;          // or null: base colour
+    int32_t tw, th;
+    int32_t n_tris, base;            // the draw's first triangle in the submission
+    float mvp[16], prev_mvp[16], model[16];
+    float zm[16];                    // camera pass: view * model; shadow pass: light_vp * model
+    float n3[12];                    // mat3(transpose(inverse(model))), column-major 3x3
+    float colf[4];                   // (float)base_color.rgb
+};
+
+constexpr int RT_TW = 32, RT_TH = 8;     // raster tile: one 256-thread workgroup, one pixel per lane
+constexpr int RT_CHUNK = 256;            // records examined (and at most staged in LDS) per round
+
+struct RtParams {
+    int32_t W, H, tile_w, tile_h;    // the target and the reference's tile job size
+    int32_t n_draws, n_tris, n_recs;
+    uint32_t clear_rgba, flags;      // SHS_RT_*
+    float light_vp[16];
+    float L[3];                      // normalize(-light_dir_world)
+    float cam[3];
+    float bias_base, bias_slope, max_velocity;
+    const float *shadow;             // or null
+    int32_t sw, sh;
+    const RtDrawGPU *draws;
+    RtRec *recs;
+    RtVary *vary;
+    unsigned long long *stats;       // 4 counters (shs_rt_stats), zeroed before the setup
+    uint32_t *color;
+    float *depth;                    // camera pass: view z in canvas rows; shadow pass: the map
+    float2 *velocity;
+    float4 *prequant;                // or null
+    int32_t *ids;
+};
+
+}  // namespace shs_dev
+
+namespace shs_internal {
+// setup (one lane per input triangle) then raster (one workgroup per 32x8 tile) of either pass
+hipError_t launch_canvas_rt(const shs_dev::RtParams &p, bool shadow_pass, hipStream_t s);
+}  // namespace shs_internal

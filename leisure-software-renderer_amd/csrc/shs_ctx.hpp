@@ -11,6 +11,7 @@
 #include "shs_device.hpp"
 #include "shs_lib_device.hpp"
 #include "shs_canvas_post_internal.hpp"
+#include "shs_canvas_rt_internal.hpp"
 #include "shs_debugdraw_internal.hpp"
 #include "shs_lightbin_internal.hpp"
 #include "shs_occlusion_internal.hpp"
@@ -338,6 +339,27 @@ struct shs_ctx {
     // Canvas-API multi-pass extras (shs_abi_canvas_post.cpp)
     DevBuf<uint32_t> cp_a, cp_b, cp_src;
     DevBuf<float> cp_depth, cp_vel, cp_focus;
+
+    // Canvas render-target raster (shs_abi_canvas_rt.cpp): the last camera pass's planes and the last
+    // shadow pass's map; the records and draw table are shared by the two passes (stream order)
+    DevBuf<shs_dev::RtDrawGPU> rt_draws;
+    DevBuf<shs_dev::RtRec> rt_recs;
+    DevBuf<shs_dev::RtVary> rt_vary;
+    DevBuf<unsigned long long> rt_stats;
+    DevBuf<uint32_t> rt_color;
+    DevBuf<float> rt_depth, rt_vel, rt_shadow;
+    DevBuf<float4> rt_pq;
+    DevBuf<int32_t> rt_ids;
+    std::vector<shs_dev::RtDrawGPU> rt_h_draws;
+    // pinned staging of the draw table, two slots used in turn: a slot is rewritten only after the copy
+    // that last read it (rt_pin_ev) is done
+    shs_dev::RtDrawGPU *rt_pin[2] = {nullptr, nullptr};
+    size_t rt_pin_cap[2] = {0, 0};
+    hipEvent_t rt_pin_ev[2] = {nullptr, nullptr};
+    uint32_t rt_pin_next = 0;
+    int rt_w = 0, rt_h = 0, rt_sw = 0, rt_sh = 0;
+    int64_t rt_n_tris = 0;
+    bool rt_have_frame = false, rt_have_shadow = false, rt_have_pq = false;
 };
 
 // Re-enqueues the tonemap after lib_finish re-issued the camera pass (shs_abi_post.cpp).

@@ -241,6 +241,17 @@ inline void ortho_lh_no(float l, float r, float b, float t, float zn, float zf, 
     m[14] = -(zf + zn) / (zf - zn);
 }
 
+// ortho_lh_zo (hello-render-target/hello_shadow_mapping.cpp:128-140): LH, NDC z in [0, 1], the demo's own
+inline void ortho_lh_zo(float l, float r, float b, float t, float zn, float zf, float *m) {
+    identity(m);
+    m[0] = 2.0f / (r - l);
+    m[5] = 2.0f / (t - b);
+    m[10] = 1.0f / (zf - zn);
+    m[12] = -(r + l) / (r - l);
+    m[13] = -(t + b) / (t - b);
+    m[14] = -zn / (zf - zn);
+}
+
 // RenderItem model matrix (pass_pbr_forward.hpp:136-141, pass_shadow_map.hpp:56-64):
 // translate * rotate(x) * rotate(y) * rotate(z) * scale, each applied to the running matrix
 inline void model_euler(vec3 pos, vec3 rot, vec3 scl, float *out) {

@@ -18,7 +18,7 @@ from ._abi import (FRAME_PREQUANT, FRAME_PRESENT, SHADING_BLINN_PHONG, SHADING_D
                    SHADING_TOON, FrameDesc, LegacyDraw, RasterStats)
 
 __all__ = [
-    "ShsError", "Context", "Frame", "Draw", "SHADING_FLAT", "SHADING_GOURAUD", "SHADING_PHONG",
+    "ShsError", "Context", "Frame", "Draw", "RtFrame", "RtDraw", "SHADING_FLAT", "SHADING_GOURAUD", "SHADING_PHONG",
     "SHADING_BLINN_PHONG", "SHADING_TOON", "SHADING_GOOCH", "SHADING_OREN_NAYAR", "SHADING_NORMAL_VIS",
     "SHADING_DEPTH_VIS", "SHADING_TEXTURED", "SHADING_NAMES", "FRAME_PREQUANT", "lib",
 ]
@@ -76,6 +76,37 @@ class Frame:
         return d
 
 
+@dataclass
+class RtDraw:
+    """One object of the Canvas render-target passes (shs_rt_draw): the per-object part of
+    hello_shadow_mapping.cpp's Uniforms.  The shadow pass reads mesh and model only."""
+    mesh: object                 # Mesh (positions / normals [n, 9], optional uvs [n, 6]) or an uploaded soup id
+    model: np.ndarray            # float32[16], column-major
+    mvp: np.ndarray = None
+    prev_mvp: np.ndarray = None
+    base_color: tuple = (200, 200, 200, 255)
+    albedo_tex: object = None    # an uploaded texture id, an object with .rgba [h, w, 4], or None (base_color)
+
+
+@dataclass
+class RtFrame:
+    """The camera pass's frame (shs_rt_frame); the defaults are the demo's constants."""
+    width: int
+    height: int
+    view: np.ndarray
+    light_vp: np.ndarray
+    light_dir_world: tuple
+    camera_pos: tuple
+    ref_tile: tuple = (80, 80)
+    clear_color: tuple = (20, 20, 25, 255)
+    bias_base: float = 0.0025
+    bias_slope: float = 0.01
+    max_velocity_px: float = 22.0
+    use_shadow: bool = True
+    pcf: bool = True
+    prequant: bool = False
+
+
 class Context:
     """A libshs_gpu context bound to one HIP device (one host thread at a time)."""
 
@@ -90,6 +121,8 @@ class Context:
         self._frame = None
         self._lib_frame = None
         self._shadow_size = None
+        self._rt_size = None
+        self._rt_shadow_size = None
 
     def _check(self, rc):
         if rc != 0:
@@ -589,6 +622,91 @@ class Context:
         self._check(self._lib.shs_canvas_dof(self._h, ctypes.byref(d), _ptr(color), _ptr(depth),
                                              _ptr(blur), ctypes.byref(f), self.CANVAS_DEVICE if dev else 0))
         return color, blur, f.value
+
+    # -- Canvas render-target raster (hello_shadow_mapping.cpp PASS0 / PASS1) ---------------------
+    def _rt_draw_array(self, draws):
+        arr = (_abi.RtDrawC * max(len(draws), 1))()
+        for i, d in enumerate(draws):
+            arr[i].mesh_id = d.mesh if isinstance(d.mesh, int) else self.upload_mesh(d.mesh)
+            tex = d.albedo_tex
+            arr[i].albedo_tex = 0 if tex is None else (int(tex) if isinstance(tex, (int, np.integer)) else self.upload_texture(tex))
+            for name in ("model", "mvp", "prev_mvp"):
+                m = getattr(d, name)
+                if m is not None:
+                    getattr(arr[i], name)[:] = [float(v) for v in np.asarray(m, dtype=np.float32).reshape(16)]
+            for k in range(4):
+                arr[i].base_color[k] = int(d.base_color[k])
+        return arr
+
+    def rt_render_shadow(self, size, light_vp, casters, ref_tile=(80, 80)):
+        """shs_rt_render_shadow: PASS0 over a size = (w, h) map (an int: square), asynchronous."""
+        w, h = (size, size) if isinstance(size, int) else size
+        lvp = np.ascontiguousarray(light_vp, dtype=np.float32).reshape(16)
+        arr = self._rt_draw_array(casters)
+        self._check(self._lib.shs_rt_render_shadow(self._h, w, h, ref_tile[0], ref_tile[1], _fptr(lvp), arr, len(casters)))
+        self._rt_shadow_size = (w, h)
+
+    def rt_render(self, frame, draws):
+        """shs_rt_render: PASS1 (colour, view-z depth, velocity; the shadow lookup), asynchronous."""
+        f = _abi.RtFrameC()
+        f.width, f.height = frame.width, frame.height
+        f.ref_tile_w, f.ref_tile_h = frame.ref_tile
+        for k in range(4):
+            f.clear_color[k] = int(frame.clear_color[k])
+        f.view[:] = [float(v) for v in np.asarray(frame.view, dtype=np.float32).reshape(16)]
+        f.light_vp[:] = [float(v) for v in np.asarray(frame.light_vp, dtype=np.float32).reshape(16)]
+        f.light_dir_world[:] = [float(v) for v in frame.light_dir_world]
+        f.camera_pos[:] = [float(v) for v in frame.camera_pos]
+        f.bias_base, f.bias_slope, f.max_velocity_px = frame.bias_base, frame.bias_slope, frame.max_velocity_px
+        f.flags = (_abi.RT_USE_SHADOW if frame.use_shadow else 0) | (_abi.RT_PCF if frame.pcf else 0) | \
+                  (_abi.RT_PREQUANT if frame.prequant else 0)
+        arr = self._rt_draw_array(draws)
+        self._check(self._lib.shs_rt_render(self._h, ctypes.byref(f), arr, len(draws)))
+        self._rt_size = (frame.width, frame.height)
+
+    def _rt_dims(self, shadow=False):
+        size = self._rt_shadow_size if shadow else self._rt_size
+        if size is None:
+            raise ShsError(-1, "no render-target shadow map rendered" if shadow else "no render-target frame rendered")
+        return size
+
+    def rt_resolve(self):
+        """-> (color uint8 [H, W, 4], depth float32 [H, W], velocity float32 [H, W, 2]), canvas rows."""
+        W, H = self._rt_dims()
+        color = np.empty((H, W, 4), np.uint8)
+        depth = np.empty((H, W), np.float32)
+        vel = np.empty((H, W, 2), np.float32)
+        self._check(self._lib.shs_rt_resolve(self._h, _ptr(color), _ptr(depth), _ptr(vel)))
+        return color, depth, vel
+
+    def rt_resolve_shadow(self):
+        w, h = self._rt_dims(shadow=True)
+        sm = np.empty((h, w), np.float32)
+        self._check(self._lib.shs_rt_resolve_shadow(self._h, _ptr(sm)))
+        return sm
+
+    def rt_resolve_prequant(self):
+        W, H = self._rt_dims()
+        pq = np.empty((H, W, 4), np.float32)
+        self._check(self._lib.shs_rt_resolve_prequant(self._h, _ptr(pq)))
+        return pq
+
+    def rt_resolve_ids(self):
+        W, H = self._rt_dims()
+        ids = np.empty((H, W), np.int32)
+        self._check(self._lib.shs_rt_resolve_ids(self._h, _ptr(ids)))
+        return ids
+
+    def rt_stats(self) -> dict:
+        st = _abi.RtStatsC()
+        self._check(self._lib.shs_rt_get_stats(self._h, ctypes.byref(st)))
+        return {k: getattr(st, k) for k, _ in st._fields_}
+
+    def rt_device_targets(self):
+        """Device pointers of the last camera pass: (colour W*H*4 bytes, depth W*H, velocity float2 W*H)."""
+        a, b, c = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+        self._check(self._lib.shs_rt_device_targets(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
+        return a.value, b.value, c.value
 
     def lib_device_targets(self):
         """Device pointers of the library targets: (hdr float4 W*H, depth W*H, motion float2 W*H)."""

@@ -211,6 +211,29 @@ class CanvasDofDescC(ctypes.Structure):
                 ("range", ctypes.c_float), ("max_blur", ctypes.c_float)]
 
 
+RT_USE_SHADOW, RT_PCF, RT_PREQUANT = 1, 2, 4
+
+
+class RtDrawC(ctypes.Structure):
+    """shs_rt_draw: one object of the Canvas render-target passes."""
+    _fields_ = [("mesh_id", ctypes.c_int32), ("albedo_tex", ctypes.c_int32), ("model", _F16), ("mvp", _F16),
+                ("prev_mvp", _F16), ("base_color", ctypes.c_uint8 * 4)]
+
+
+class RtFrameC(ctypes.Structure):
+    """shs_rt_frame: the camera pass's frame-wide uniforms and constants."""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("ref_tile_w", ctypes.c_int32),
+                ("ref_tile_h", ctypes.c_int32), ("clear_color", ctypes.c_uint8 * 4), ("view", _F16), ("light_vp", _F16),
+                ("light_dir_world", _F3), ("camera_pos", _F3), ("bias_base", ctypes.c_float),
+                ("bias_slope", ctypes.c_float), ("max_velocity_px", ctypes.c_float), ("flags", ctypes.c_uint32),
+                ("shading", ctypes.c_int32)]
+
+
+class RtStatsC(ctypes.Structure):
+    _fields_ = [("input_tris", ctypes.c_int64), ("polys3", ctypes.c_int64), ("polys4", ctypes.c_int64),
+                ("sub_tris", ctypes.c_int64)]
+
+
 class TonemapDescC(ctypes.Structure):
     _fields_ = [("exposure", ctypes.c_float), ("gamma", ctypes.c_float), ("flags", ctypes.c_uint32)]
 LIGHT_CULL_NONE, LIGHT_CULL_TILED, LIGHT_CULL_TILED_DEPTH, LIGHT_CULL_CLUSTERED = 0, 1, 2, 3
@@ -316,6 +339,17 @@ SIGNATURES = [
     ("shs_canvas_motion_blur", ctypes.c_int, [_P, ctypes.POINTER(CanvasMotionBlurDescC), _P, _P, _P, _P, ctypes.c_uint32]),
     ("shs_canvas_gaussian_blur", ctypes.c_int, [_P, ctypes.c_int32, ctypes.c_int32, _P, _P, ctypes.c_int32, ctypes.c_uint32]),
     ("shs_canvas_dof", ctypes.c_int, [_P, ctypes.POINTER(CanvasDofDescC), _P, _P, _P, _F, ctypes.c_uint32]),
+    ("shs_rt_render_shadow", ctypes.c_int, [_P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _F,
+                                            ctypes.POINTER(RtDrawC), ctypes.c_int32]),
+    ("shs_rt_render", ctypes.c_int, [_P, ctypes.POINTER(RtFrameC), ctypes.POINTER(RtDrawC), ctypes.c_int32]),
+    ("shs_rt_resolve", ctypes.c_int, [_P, _P, _P, _P]),
+    ("shs_rt_resolve_shadow", ctypes.c_int, [_P, _P]),
+    ("shs_rt_resolve_prequant", ctypes.c_int, [_P, _P]),
+    ("shs_rt_resolve_ids", ctypes.c_int, [_P, _P]),
+    ("shs_rt_get_stats", ctypes.c_int, [_P, ctypes.POINTER(RtStatsC)]),
+    ("shs_rt_device_targets", ctypes.c_int, [_P, ctypes.POINTER(_P), ctypes.POINTER(_P), ctypes.POINTER(_P)]),
+    ("shs_ortho_lh_zo", ctypes.c_int, [ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                                       ctypes.c_float, _F]),
     ("shs_motion_blur", ctypes.c_int, [_P, ctypes.POINTER(MotionBlurDescC)]),
     ("shs_resolve_motion_blur", ctypes.c_int, [_P, _P, _P]),
     ("shs_light_shafts", ctypes.c_int, [_P, ctypes.POINTER(LightShaftsDescC)]),
