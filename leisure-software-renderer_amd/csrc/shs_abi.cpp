@@ -1170,4 +1170,30 @@ int shs_mat4_inverse(const float m[16], float out[16]) {
     return SHS_OK;
 }
 
+int shs_look_at_lh(const float eye[3], const float center[3], const float up[3], float out16[16]) {
+    if (!eye || !center || !up || !out16) return SHS_ERR_INVALID;
+    shs_host::look_at_lh({eye[0], eye[1], eye[2]}, {center[0], center[1], center[2]}, {up[0], up[1], up[2]}, out16);
+    return SHS_OK;
+}
+
+int shs_perspective_lh_no(float fovy, float aspect, float zn, float zf, float out16[16]) {
+    if (!out16) return SHS_ERR_INVALID;
+    shs_host::perspective_lh_no(fovy, aspect, zn, zf, out16);
+    return SHS_OK;
+}
+
+int shs_model_euler(const float pos[3], const float rot[3], const float scl[3], float out16[16]) {
+    if (!pos || !rot || !scl || !out16) return SHS_ERR_INVALID;
+    shs_host::model_euler({pos[0], pos[1], pos[2]}, {rot[0], rot[1], rot[2]}, {scl[0], scl[1], scl[2]}, out16);
+    return SHS_OK;
+}
+
+int shs_dir_light_camera_aabb(const float sun_dir[3], const float mn[3], const float mx[3], float margin, uint32_t res,
+                              float view16[16], float proj16[16], float viewproj16[16]) {
+    if (!sun_dir || !mn || !mx || !view16 || !proj16 || !viewproj16) return SHS_ERR_INVALID;
+    shs_host::dir_light_camera_aabb({sun_dir[0], sun_dir[1], sun_dir[2]}, {mn[0], mn[1], mn[2]}, {mx[0], mx[1], mx[2]}, margin,
+                                    res, view16, proj16, viewproj16);
+    return SHS_OK;
+}
+
 }  // extern "C"

@@ -1,5 +1,5 @@
 // shs_ctx.hpp -- the libshs_gpu context (struct shs_ctx) shared by the ABI translation units
-// (shs_abi.cpp: legacy path; shs_abi_lib.cpp: library path).
+// (shs_abi.cpp: legacy path; shs_abi_lib.cpp, shs_abi_shadow.cpp, shs_abi_mesh.cpp, shs_abi_sky.cpp, shs_abi_light_cull.cpp: library path).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,6 +10,7 @@
 #include "../../include/shs_gpu.h"
 #include "shs_device.hpp"
 #include "shs_lib_device.hpp"
+#include "shs_lib_plan.hpp"
 #include "shs_canvas_post_internal.hpp"
 #include "shs_canvas_rt_internal.hpp"
 #include "shs_debugdraw_internal.hpp"
@@ -275,8 +276,7 @@ struct shs_ctx {
     const uint32_t *blkcov_zero_at = nullptr;
     size_t blkcov_zero_cap = 0;
     uint64_t blkcov_zero_key = 0;
-    int lib_resolve_resident[16] = {};  // resident k_lib_resolve workgroups ((Forward+, PBR, mixed, typed) x
-                                        // (sharded rank's build, whole frame's build)), then the sky builds'
+    int lib_resolve_resident[shs_plan::RESOLVE_VARIANTS] = {};  // resident k_lib_resolve workgroups, by shs_plan::resolve_variant
     // shs_lib_set_sky: the sky model later camera passes paint behind the meshes (model SKY_NONE: none; each
     // pass's LibFrameParams keeps its own copy), and the texture ids of a cubemap's faces (shs_texture_release)
     shs_dev::SkyParams sky{};
@@ -429,5 +429,5 @@ inline int set_dev(shs_ctx *ctx) {
     return SHS_OK;
 }
 
-// Frees the library-path workspaces (shs_abi_lib.cpp); called by shs_destroy.
+// Frees the library-path workspaces, meshes' textures and tables (shs_abi_lib.cpp); called by shs_destroy.
 void shs_lib_release(shs_ctx *ctx);

@@ -1,7 +1,7 @@
 """Library passes under a known, inconsistent history.
 
 A camera or shadow pass chooses how it rasters from what an earlier pass of the same context measured
-(shs_abi_lib.cpp, enqueue_pass / check_pass), not from the pass in front of it:
+(shs_lib_plan.hpp plan_lib_pass, shs_abi_lib.cpp check_pass), not from the pass in front of it:
 
   * shallow raster (256-candidate rounds) when the last checked pass's fullest bin list was <= 256 (scan
     mode: its primitive count), else the deep one (1024); a context's first pass runs deep;
@@ -201,7 +201,7 @@ def _ref(oracle_mod, sc):
 
 # ---- the host's rule, restated (the expected variant of a pass from the last checked one) -----------
 class HostRule:
-    """What enqueue_pass decides from the statistics check_pass left (camera pass)."""
+    """What plan_lib_pass decides from the statistics check_pass left (camera pass)."""
 
     def __init__(self):
         self.checked, self.maxbin, self.extra, self.bin_cap, self.part = False, 0, 0, 256, 0

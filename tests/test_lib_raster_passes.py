@@ -24,7 +24,7 @@ from test_sorted_lists import _render_check
 W, H = 64, 32
 SIZES = [1, 127, 128, 129, 255, 256, 257, 1023, 1024, 1025]
 COVER_Z = -0.95
-SCAN_MAX, PAD = 512, 600   # shs_abi_lib.cpp SCAN_MAX_PRIMS; PAD > SCAN_MAX: bins at every size
+SCAN_MAX, PAD = 512, 600   # shs_lib_plan.hpp SCAN_MAX_PRIMS; PAD > SCAN_MAX: bins at every size
 # the light camera's margins are in world units: the casters are the NDC-sized soup scaled up, lit almost
 # along z -- the cover nearest the light (it hides the rest), then farthest (the small triangles show)
 SUNS = [(0.02, -0.03, 1.0), (0.02, -0.03, -1.0)]

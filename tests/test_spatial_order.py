@@ -17,7 +17,7 @@ from helpers import assert_depth_bitexact, assert_float_close
 
 
 def stored_order(pos, idx=None):
-    """csrc/shs_abi_lib.cpp spatial_order: MeshData indices by (30-bit Morton code of the float32
+    """csrc/shs_abi_mesh.cpp spatial_order: MeshData indices by (30-bit Morton code of the float32
     centroid sum in the mesh's centroid bounds, index)."""
     p = np.asarray(pos, np.float32).reshape(-1, 3)
     tri = (np.asarray(idx, np.int64).reshape(-1, 3) if idx is not None else np.arange(p.shape[0]).reshape(-1, 3))
