@@ -826,7 +826,20 @@ int shs_canvas_dof(shs_ctx *ctx, const shs_canvas_dof_desc *desc, uint8_t *color
  * (Buffer<glm::vec2>) -- are in canvas rows at y * W + x, what shs_canvas_motion_blur reads; the shadow
  * map is ShadowMap::depth_ (y down) at y * w + x.  Both calls enqueue on the context stream and return;
  * the resolves and shs_rt_device_targets order themselves after them.  One frame at a time: a render
- * replaces the context's previous render-target frame. */
+ * replaces the context's previous render-target frame.
+ *
+ * shs_rt_frame::shading chooses the camera pass's fragment shader over the same raster:
+ *   0  fragment_shader_full of hello_shadow_mapping.cpp, as above;
+ *   1  fragment_shader_softshadow of hello_shadow_mapping_soft.cpp (:991-1040; its PASS1 is
+ *      draw_triangle_tile_color_depth_softshadow :845-986, tile jobs of 160): Blinn-Phong whose ambient
+ *      and diffuse terms take the base colour and whose specular term does not, under
+ *      pcss_shadow_factor (:333-445) -- a centre lookup, a blocker search and a variable-radius PCF over
+ *      POISSON_32 rotated per screen pixel, with the constants of shs_rt_set_pcss.  That demo has no
+ *      motion buffer: the velocity plane is all zeros and prev_mvp is not used.  SHS_RT_PCF has no
+ *      effect; SHS_RT_USE_SHADOW and SHS_RT_PREQUANT keep their meaning (the prequant plane's fourth
+ *      float is the PCSS factor).  The per-pixel rotations' cos / sin are the host libm's, as the
+ *      reference's: the first soft frame of a size builds a width * height table of them (16 B per
+ *      pixel, at most 2^26 pixels) and keeps it until the size changes. */
 typedef struct shs_rt_draw {
     int32_t mesh_id;            /* shs_mesh_upload_soup[_uv] soup (without UVs: vec2(0) per corner) */
     int32_t albedo_tex;         /* shs_texture_upload id (use_texture), 0: base_color */
@@ -849,8 +862,26 @@ typedef struct shs_rt_frame {
     float bias_base, bias_slope;      /* SHADOW_BIAS_BASE (0.0025), SHADOW_BIAS_SLOPE (0.01) */
     float max_velocity_px;            /* MB_MAX_PIXELS (22) */
     uint32_t flags;                   /* SHS_RT_* */
-    int32_t shading;                  /* 0: fragment_shader_full (the only value) */
+    int32_t shading;                  /* 0: fragment_shader_full, 1: fragment_shader_softshadow */
 } shs_rt_frame;
+/* The PCSS constants of shading 1 (hello_shadow_mapping_soft.cpp:101-116), kept in the context. */
+typedef struct shs_rt_pcss {
+    float light_uv_radius;        /* LIGHT_UV_RADIUS_BASE (0.0035) */
+    float search_radius_texels;   /* PCSS_BLOCKER_SEARCH_RADIUS_TEXELS (18) */
+    float min_filter_texels;      /* PCSS_MIN_FILTER_RADIUS_TEXELS (1) */
+    float max_filter_texels;      /* PCSS_MAX_FILTER_RADIUS_TEXELS (28) */
+    float epsilon;                /* PCSS_EPSILON (1e-5) */
+    int32_t blocker_samples;      /* PCSS_BLOCKER_SAMPLES (12), 0..64 */
+    int32_t pcf_samples;          /* PCSS_PCF_SAMPLES (24), 0..64 */
+} shs_rt_pcss;
+/* NULL: the demo's constants, also the default.  SHS_ERR_INVALID: a non-finite float or a count outside
+ * 0..64 (the context keeps what it had).  Counts above 32 wrap through POISSON_32[i & 31], as the reference. */
+int shs_rt_set_pcss(shs_ctx *ctx, const shs_rt_pcss *pcss);
+/* pcss_shadow_factor for n samples with the context's PCSS constants, through the device function the
+ * raster calls: map is a host w x h ShadowMap (y down, FLT_MAX = empty), uv 2n, z and bias n each, pxpy
+ * 2n screen pixels (the rotation's seed), out n factors.  Synchronous; for tests of the edge cases. */
+int shs_rt_pcss_samples(shs_ctx *ctx, const float *map, int32_t w, int32_t h, int32_t n, const float *uv, const float *z,
+                        const float *bias, const int32_t *pxpy, float *out);
 typedef struct shs_rt_stats {
     int64_t input_tris;         /* triangles submitted */
     int64_t polys3, polys4;     /* clipped polygons of 3 and of 4 vertices */
@@ -859,8 +890,8 @@ typedef struct shs_rt_stats {
 /* Only mesh_id and model of a caster are read.  SHS_ERR_INVALID: an unknown mesh id, a non-positive size. */
 int shs_rt_render_shadow(shs_ctx *ctx, int32_t w, int32_t h, int32_t ref_tile_w, int32_t ref_tile_h, const float light_vp[16],
                          const shs_rt_draw *casters, int32_t n_casters);
-/* SHS_ERR_INVALID: an unknown mesh or texture id, a non-positive size, unknown flags or shading, or
- * SHS_RT_USE_SHADOW without a shadow map rendered before. */
+/* SHS_ERR_INVALID: an unknown mesh or texture id, a non-positive size, unknown flags, a shading other than
+ * 0 or 1, or SHS_RT_USE_SHADOW without a shadow map rendered before. */
 int shs_rt_render(shs_ctx *ctx, const shs_rt_frame *frame, const shs_rt_draw *draws, int32_t n_draws);
 /* Host copies of the last camera pass (any pointer may be NULL): color W*H*4 bytes, depth W*H floats,
  * velocity W*H*2 floats.  Synchronous. */

@@ -260,6 +260,71 @@ private:
     glm::mat4 prev_vp_{1.0f};
 };
 
+// -----------------------------------------------------------------------------------------------------
+// Seam 1b, soft -- hello-render-target/hello_shadow_mapping_soft.cpp.
+//
+// Replaces RendererSystem::process there (:1082-1400): the same two calls as the hard demo, with that file's tile
+// jobs of 160 (TILE_SIZE_X / TILE_SIZE_Y :82-83) and shading = 1 (fragment_shader_softshadow :991-1040 over
+// pcss_shadow_factor :333-445).  That demo has no motion buffer and no blur stage: prev_mvp is left zero, the
+// velocity plane comes out zero and the colours are the frame.  The PCSS constants (:101-116) are the context's
+// defaults; a host that changes them calls shs_rt_set_pcss once.  Uncompiled, like the other seams.
+// -----------------------------------------------------------------------------------------------------
+template <class SceneT>
+class SoftShadowSystemGPU : public shs::AbstractSystem {
+public:
+    using Object = typename RenderTargetSystemGPU<SceneT>::Object;   // prev_model is not used
+
+    SoftShadowSystemGPU(SceneT *scene, Device *dev, int shadow_size = 2048, int tile = 160)
+        : scene_(scene), dev_(dev), sm_(shadow_size), tile_(tile) {}
+
+    std::vector<Object> objects;
+
+    void set_pcss(const shs_rt_pcss *pcss) { ok(shs_rt_set_pcss(dev_->ctx, pcss)); }   // nullptr: the demo's constants
+
+    void process(float) override {
+        shs::Canvas &canvas = *scene_->canvas;
+        const int W = canvas.get_width(), H = canvas.get_height();
+        const glm::mat4 view = scene_->viewer->camera->view_matrix, proj = scene_->viewer->camera->projection_matrix;
+        std::vector<shs_rt_draw> draws(objects.size());
+        for (size_t i = 0; i < objects.size(); ++i) {
+            const Object &o = objects[i];
+            shs_rt_draw &d = draws[i];
+            d = shs_rt_draw{};
+            d.mesh_id = o.mesh_id;
+            d.albedo_tex = o.albedo_tex;
+            const glm::mat4 mvp = proj * view * o.model;
+            std::memcpy(d.model, glm::value_ptr(o.model), 64);
+            std::memcpy(d.mvp, glm::value_ptr(mvp), 64);
+            d.base_color[0] = o.base_color.r; d.base_color[1] = o.base_color.g; d.base_color[2] = o.base_color.b; d.base_color[3] = 255;
+        }
+        ok(shs_rt_render_shadow(dev_->ctx, sm_, sm_, tile_, tile_, glm::value_ptr(light_vp), draws.data(), (int32_t)draws.size()));
+        shs_rt_frame f{};
+        f.width = W; f.height = H; f.ref_tile_w = tile_; f.ref_tile_h = tile_;
+        f.clear_color[0] = 20; f.clear_color[1] = 20; f.clear_color[2] = 25; f.clear_color[3] = 255;
+        std::memcpy(f.view, glm::value_ptr(view), 64);
+        std::memcpy(f.light_vp, glm::value_ptr(light_vp), 64);
+        std::memcpy(f.light_dir_world, glm::value_ptr(light_dir_world), 12);
+        std::memcpy(f.camera_pos, glm::value_ptr(scene_->viewer->position), 12);
+        f.bias_base = 0.0025f; f.bias_slope = 0.01f;                                 // SHADOW_BIAS_BASE, SHADOW_BIAS_SLOPE
+        f.flags = SHS_RT_USE_SHADOW;                                                 // (SHS_RT_PCF has no effect here)
+        f.shading = 1;
+        ok(shs_rt_render(dev_->ctx, &f, draws.data(), (int32_t)draws.size()));
+        // shs_rt_resolve(ctx, colours, nullptr, nullptr) into the canvas, or shs_rt_device_targets for a device consumer
+    }
+
+    void ok(int rc) const {
+        if (rc != SHS_OK) throw std::runtime_error(shs_last_error(dev_->ctx));
+    }
+
+    glm::mat4 light_vp{1.0f};
+    glm::vec3 light_dir_world{0.4668f, -0.3487f, 0.8127f};   // LIGHT_DIR_WORLD :90 (the shader normalises it)
+
+private:
+    SceneT *scene_;
+    Device *dev_;
+    int sm_, tile_;
+};
+
 // =====================================================================================================
 // Seam 3 -- the library's plugin pipeline (shs-renderer-lib/include/shs/pipeline/).
 // =====================================================================================================

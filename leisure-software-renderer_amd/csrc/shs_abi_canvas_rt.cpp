@@ -2,7 +2,9 @@
 // the reference's cpp-folders/src/hello-render-target/:
 //   shs_rt_render_shadow  PASS0 of hello_shadow_mapping.cpp (:1320-1411 over draw_triangle_tile_shadow);
 //   shs_rt_render         PASS1 (draw_triangle_tile_color_depth_motion_shadow :854-1022);
-//   shs_ortho_lh_zo       ortho_lh_zo (:128-140).
+//   shs_ortho_lh_zo       ortho_lh_zo (:128-140);
+// and of hello_shadow_mapping_soft.cpp: shs_rt_render with shading 1 (its PASS1, :845-1040), shs_rt_set_pcss (the
+// constants :101-116), shs_rt_pcss_samples (pcss_shadow_factor :333-445 alone) and the per-pixel rotation table.
 // The host forms the matrix products the shaders form first -- u.view * u.model (vertex_shader_full :616),
 // u.light_vp * u.model (shadow_vertex_shader :764) -- and the normal matrix with the GLM restatement in
 // shs_glm.hpp.  Both passes are enqueued on the context stream; the shadow map, the planes and the records
@@ -67,7 +69,56 @@ int64_t build_draws(shs_ctx *ctx, const shs_rt_draw *draws, int32_t n, const flo
     return total;
 }
 
-int upload_and_launch(shs_ctx *ctx, shs_dev::RtParams &p, bool shadow_pass) {
+// hash_u32 / hash01 (hello_shadow_mapping_soft.cpp:306-319) and the two rotations pcss_shadow_factor forms from
+// the screen pixel (:359-360, :422): {cos(ang), sin(ang), cos(ang2), sin(ang2)} with the host libm, as rotate2
+// (:320-325) takes them.  The kernels consume these; they never call a device sin / cos.
+uint32_t hash_u32(uint32_t x) {
+    x ^= x >> 16;
+    x *= 0x7feb352dU;
+    x ^= x >> 15;
+    x *= 0x846ca68bU;
+    x ^= x >> 16;
+    return x;
+}
+float hash01(uint32_t x) { return float(hash_u32(x) & 0x00FFFFFFu) / float(0x01000000u); }
+void pixel_rotation(int px, int py, float out[4]) {
+    const uint32_t seed = (uint32_t)px * 1973u ^ (uint32_t)py * 9277u ^ 0x9e3779b9u;
+    const float ang = hash01(seed) * 6.2831853f;
+    const float ang2 = hash01(seed ^ 0xB5297A4Du) * 6.2831853f;
+    out[0] = std::cos(ang);
+    out[1] = std::sin(ang);
+    out[2] = std::cos(ang2);
+    out[3] = std::sin(ang2);
+}
+
+// The rotation table of a W x H soft frame, entry py * W + px (screen rows): built and uploaded on the first
+// soft frame of a size, kept until the size changes.  The upload is finished before the host copy goes.
+int ensure_rotations(shs_ctx *ctx, int W, int H) {
+    if (ctx->rt_rot.p && ctx->rt_rot_w == W && ctx->rt_rot_h == H) return SHS_OK;
+    const size_t npx = (size_t)W * H;
+    if (npx > ((size_t)1 << 26)) {
+        ctx->err = "render-target frame: shading 1 keeps 16 B per pixel, at most 2^26 pixels";
+        return SHS_ERR_INVALID;
+    }
+    ctx->rt_rot_w = ctx->rt_rot_h = 0;
+    if (ensure(ctx, ctx->rt_rot, npx)) return SHS_ERR_HIP;
+    std::vector<float> host(4 * npx);
+    for (int py = 0; py < H; ++py)
+        for (int px = 0; px < W; ++px) pixel_rotation(px, py, &host[4 * ((size_t)py * W + px)]);
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->rt_rot.p, host.data(), npx * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->rt_rot_w = W;
+    ctx->rt_rot_h = H;
+    return SHS_OK;
+}
+
+bool pcss_ok(const shs_rt_pcss &c) {
+    return std::isfinite(c.light_uv_radius) && std::isfinite(c.search_radius_texels) && std::isfinite(c.min_filter_texels) &&
+           std::isfinite(c.max_filter_texels) && std::isfinite(c.epsilon) && c.blocker_samples >= 0 && c.blocker_samples <= 64 &&
+           c.pcf_samples >= 0 && c.pcf_samples <= 64;
+}
+
+int upload_and_launch(shs_ctx *ctx, shs_dev::RtParams &p, bool shadow_pass, int shading = 0) {
     const size_t nd = ctx->rt_h_draws.size();
     if (ensure(ctx, ctx->rt_draws, std::max<size_t>(nd, 1)) || ensure(ctx, ctx->rt_recs, std::max<size_t>((size_t)p.n_recs, 1)) ||
         ensure(ctx, ctx->rt_stats, 4))
@@ -93,7 +144,7 @@ int upload_and_launch(shs_ctx *ctx, shs_dev::RtParams &p, bool shadow_pass) {
     p.recs = ctx->rt_recs.p;
     p.vary = ctx->rt_vary.p;
     p.stats = ctx->rt_stats.p;
-    HIP_TRY(ctx, shs_internal::launch_canvas_rt(p, shadow_pass, ctx->stream));
+    HIP_TRY(ctx, shs_internal::launch_canvas_rt(p, shadow_pass, shading, ctx->stream));
     return SHS_OK;
 }
 
@@ -129,8 +180,13 @@ int shs_rt_render_shadow(shs_ctx *ctx, int32_t w, int32_t h, int32_t ref_tile_w,
 int shs_rt_render(shs_ctx *ctx, const shs_rt_frame *f, const shs_rt_draw *draws, int32_t n_draws) {
     if (!ctx || !f || n_draws < 0 || (n_draws > 0 && !draws)) return SHS_ERR_INVALID;
     if (!size_ok(ctx, f->width, f->height, f->ref_tile_w, f->ref_tile_h)) return SHS_ERR_INVALID;
-    if ((f->flags & ~(SHS_RT_USE_SHADOW | SHS_RT_PCF | SHS_RT_PREQUANT)) || f->shading != 0) {
-        ctx->err = "render-target frame: unknown flags or shading";
+    if (f->flags & ~(SHS_RT_USE_SHADOW | SHS_RT_PCF | SHS_RT_PREQUANT)) {
+        ctx->err = "render-target frame: unknown flags";
+        return SHS_ERR_INVALID;
+    }
+    if (f->shading != 0 && f->shading != 1) {
+        ctx->err = "render-target frame: shading " + std::to_string(f->shading) +
+                   " (0: fragment_shader_full, 1: fragment_shader_softshadow)";
         return SHS_ERR_INVALID;
     }
     if ((f->flags & SHS_RT_USE_SHADOW) && !ctx->rt_have_shadow) {
@@ -172,7 +228,20 @@ int shs_rt_render(shs_ctx *ctx, const shs_rt_frame *f, const shs_rt_draw *draws,
     p.velocity = reinterpret_cast<float2 *>(ctx->rt_vel.p);
     p.prequant = pq ? ctx->rt_pq.p : nullptr;
     p.ids = ctx->rt_ids.p;
-    const int rc = upload_and_launch(ctx, p, false);
+    if (f->shading == 1) {
+        const int rr = ensure_rotations(ctx, f->width, f->height);
+        if (rr) return rr;
+        p.rot = ctx->rt_rot.p;
+        const shs_rt_pcss &c = ctx->rt_pcss;
+        p.pcss_light = c.light_uv_radius;
+        p.pcss_search = c.search_radius_texels;
+        p.pcss_min = c.min_filter_texels;
+        p.pcss_max = c.max_filter_texels;
+        p.pcss_eps = c.epsilon;
+        p.pcss_blockers = c.blocker_samples;
+        p.pcss_taps = c.pcf_samples;
+    }
+    const int rc = upload_and_launch(ctx, p, false, f->shading);
     if (rc) {
         ctx->rt_have_frame = false;
         return rc;
@@ -239,6 +308,56 @@ int shs_rt_device_targets(shs_ctx *ctx, void **color_dev, void **depth_dev, void
     if (color_dev) *color_dev = ctx->rt_color.p;
     if (depth_dev) *depth_dev = ctx->rt_depth.p;
     if (velocity_dev) *velocity_dev = ctx->rt_vel.p;
+    return SHS_OK;
+}
+
+int shs_rt_set_pcss(shs_ctx *ctx, const shs_rt_pcss *pcss) {
+    if (!ctx) return SHS_ERR_INVALID;
+    const shs_rt_pcss demo = {0.0035f, 18.0f, 1.0f, 28.0f, 1e-5f, 12, 24};
+    if (pcss && !pcss_ok(*pcss)) {
+        ctx->err = "shs_rt_set_pcss: a non-finite constant or a sample count outside 0..64";
+        return SHS_ERR_INVALID;
+    }
+    ctx->rt_pcss = pcss ? *pcss : demo;
+    return SHS_OK;
+}
+
+int shs_rt_pcss_samples(shs_ctx *ctx, const float *map, int32_t w, int32_t h, int32_t n, const float *uv, const float *z,
+                        const float *bias, const int32_t *pxpy, float *out) {
+    if (!ctx || !map || w <= 0 || h <= 0 || w > 32767 || h > 32767 || n < 0 || (n > 0 && (!uv || !z || !bias || !pxpy || !out)))
+        return SHS_ERR_INVALID;
+    if (n == 0) return SHS_OK;
+    if (set_dev(ctx)) return SHS_ERR_HIP;
+    const size_t nm = (size_t)w * h, ns = (size_t)n;
+    // the workspace: uv (2 n), z (n), bias (n), out (n)
+    if (ensure(ctx, ctx->rt_ps_map, nm) || ensure(ctx, ctx->rt_ps_io, 5 * ns) || ensure(ctx, ctx->rt_ps_rot, ns)) return SHS_ERR_HIP;
+    std::vector<float> rot(4 * ns);
+    for (size_t i = 0; i < ns; ++i) pixel_rotation(pxpy[2 * i], pxpy[2 * i + 1], &rot[4 * i]);
+    float *io = ctx->rt_ps_io.p;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->rt_ps_map.p, map, nm * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(io, uv, 2 * ns * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(io + 2 * ns, z, ns * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(io + 3 * ns, bias, ns * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->rt_ps_rot.p, rot.data(), ns * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
+    shs_dev::RtPcssSamples q{};
+    q.map = ctx->rt_ps_map.p;
+    q.w = w; q.h = h; q.n = n;
+    q.uv = io;
+    q.z = io + 2 * ns;
+    q.bias = io + 3 * ns;
+    q.rot = ctx->rt_ps_rot.p;
+    q.out = io + 4 * ns;
+    const shs_rt_pcss &c = ctx->rt_pcss;
+    q.pcss_light = c.light_uv_radius;
+    q.pcss_search = c.search_radius_texels;
+    q.pcss_min = c.min_filter_texels;
+    q.pcss_max = c.max_filter_texels;
+    q.pcss_eps = c.epsilon;
+    q.pcss_blockers = c.blocker_samples;
+    q.pcss_taps = c.pcf_samples;
+    HIP_TRY(ctx, shs_internal::launch_pcss_samples(q, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(out, q.out, ns * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // (the pageable staging above is consumed by now)
     return SHS_OK;
 }
 

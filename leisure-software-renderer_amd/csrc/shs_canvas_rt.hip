@@ -4,6 +4,13 @@
 //   PASS1  draw_triangle_tile_color_depth_motion_shadow (:854-1022) with vertex_shader_full (:602-620) and
 //          fragment_shader_full (:699-750): near-plane clipping in clip space, no facing cull, view-z depth
 //          in canvas rows, perspective-correct world position and UV, velocity, the shadow lookup.
+// and for hello_shadow_mapping_soft.cpp ("soft :line"), whose PASS0 is the same depth raster and whose PASS1
+// (draw_triangle_tile_color_depth_softshadow, soft :845-986) is the same clipped raster without the velocity:
+//   shading 1  fragment_shader_softshadow (soft :991-1040) over pcss_shadow_factor (soft :333-445): a centre
+//          lookup, a blocker search and a variable-radius PCF over a Poisson disc rotated per screen pixel.
+//          The rotations' cos / sin come from a host table (RtParams::rot): the reference takes them from its
+//          libm, which is not correctly rounded, and one ulp can move a tap to another texel.
+//          k_rt_raster<false, 1> differs from k_rt_raster<false, 0> in the shade alone.
 //
 // Two kernels per pass, the same two for both (template <bool SHADOW>):
 //   k_rt_setup   one lane per input triangle: the vertex shader once per corner (the reference re-runs it
@@ -371,6 +378,76 @@ __device__ float shadow_factor(const RtParams &p, f3 wp, float ndotl) {
     return 0.25f * (((s00 + s10) + s01) + s11);
 }
 
+// ---- hello_shadow_mapping_soft.cpp: the PCSS shadow factor ------------------------------------------
+
+// POISSON_32 (soft :267-301); a tap's index is wave-uniform, so these are scalar loads
+__constant__ float2 c_poisson32[32] = {
+    {-0.613392f, 0.617481f},  {0.170019f, -0.040254f},  {-0.299417f, 0.791925f},  {0.645680f, 0.493210f},
+    {-0.651784f, 0.717887f},  {0.421003f, 0.027070f},   {-0.817194f, -0.271096f}, {-0.705374f, -0.668203f},
+    {0.977050f, -0.108615f},  {0.063326f, 0.142369f},   {0.203528f, 0.214331f},   {-0.667531f, 0.326090f},
+    {-0.098422f, -0.295755f}, {-0.885922f, 0.215369f},  {0.566637f, 0.605213f},   {0.039766f, -0.396100f},
+    {0.751946f, 0.453352f},   {0.078707f, -0.715323f},  {-0.075838f, -0.529344f}, {0.724479f, -0.580798f},
+    {0.222999f, -0.215125f},  {-0.467574f, -0.405438f}, {-0.248268f, -0.814753f}, {0.354411f, -0.887570f},
+    {0.175817f, 0.382366f},   {0.487472f, -0.063082f},  {-0.084078f, 0.898312f},  {0.488876f, -0.783441f},
+    {0.470016f, 0.217933f},   {-0.696890f, -0.549791f}, {-0.149693f, 0.605762f},  {0.034211f, 0.979980f}};
+
+struct PcssMap {   // the soft demo's file-local ShadowMap (:191-225) and the constants of shs_rt_pcss
+    const float *depth;
+    int w, h;
+    float light, search, fmin, fmax, eps;
+    int blockers, taps;
+};
+
+// shadow_sample_depth_uv (soft :252-261) over ShadowMap::sample (:219-224), which clamps: a uv outside [0, 1]
+// is FLT_MAX (empty) without a read; a NaN passes the range test and reads texel 0 of its axis.  The load is
+// unconditional at a clamped address, so the taps of a loop are independent gathers the compiler may batch.
+__device__ __forceinline__ float pcss_tap(const PcssMap &m, float u, float v) {
+    const bool off = u < 0.0f || u > 1.0f || v < 0.0f || v > 1.0f;
+    const int x = clampi(lround_x86(u * (float)(m.w - 1)), 0, m.w - 1);
+    const int y = clampi(lround_x86(v * (float)(m.h - 1)), 0, m.h - 1);
+    const float d = m.depth[(size_t)y * m.w + x];
+    return off ? FLT_MAX : d;
+}
+
+// pcss_shadow_factor (soft :333-445).  rot: {cos(ang), sin(ang), cos(ang2), sin(ang2)} of the screen pixel, the
+// host libm's values; rotate2's multiplies and add / subtract run here.
+__device__ float pcss_shadow_factor(const PcssMap &m, float u, float v, float z, float bias, float4 rot) {
+    if (u < 0.0f || u > 1.0f || v < 0.0f || v > 1.0f) return 1.0f;
+    if (pcss_tap(m, u, v) == FLT_MAX) return 1.0f;
+    const float tsu = 1.0f / (float)m.w, tsv = 1.0f / (float)m.h;
+    const float sru = m.search * tsu, srv = m.search * tsv;
+    const float ztest = z - bias;
+    float bsum = 0.0f;
+    int bcnt = 0;
+#pragma unroll 4
+    for (int i = 0; i < m.blockers; ++i) {
+        const float2 o = c_poisson32[i & 31];
+        const float ox = rot.x * o.x - rot.y * o.y, oy = rot.y * o.x + rot.x * o.y;
+        const float d = pcss_tap(m, u + ox * sru, v + oy * srv);
+        const bool blocks = d != FLT_MAX && d < ztest;
+        bsum = blocks ? bsum + d : bsum;
+        bcnt += blocks ? 1 : 0;
+    }
+    if (bcnt <= 0) return 1.0f;
+    const float avg = bsum / (float)bcnt;
+    const float zb = g_max(m.eps, avg), zr = g_max(m.eps, z);   // std::max(a, b): (a < b) ? b : a
+    const float ratio = g_max(0.0f, (zr - zb) / zb);
+    const float fuu = m.light * ratio, fuv = m.light * ratio;
+    float ft = 0.5f * (fuu / tsu + fuv / tsv);
+    ft = (ft < m.fmin) ? m.fmin : (ft > m.fmax ? m.fmax : ft);  // clampf :127-132
+    const float fru = ft * tsu, frv = ft * tsv;
+    if (m.taps <= 0) return 1.0f;
+    float lit = 0.0f;
+#pragma unroll 4
+    for (int i = 0; i < m.taps; ++i) {
+        const float2 o = c_poisson32[i & 31];
+        const float ox = rot.z * o.x - rot.w * o.y, oy = rot.w * o.x + rot.z * o.y;
+        const float d = pcss_tap(m, u + ox * fru, v + oy * frv);
+        lit += (d == FLT_MAX || z <= d + bias) ? 1.0f : 0.0f;   // empty and off-map taps count as lit
+    }
+    return lit / (float)m.taps;
+}
+
 // Canvas::clip_to_screen's x and y of an interpolated clip position
 __device__ __forceinline__ void to_screen(const RtParams &p, float x, float y, float w, float &sx, float &sy) {
     const float nx = x / w, ny = y / w;
@@ -440,7 +517,71 @@ __device__ void shade_pixel(const RtParams &p, int32_t id, float u, float v, flo
     pq = make_float4(pr, pg, pb, shadow);
 }
 
-template <bool SHADOW>
+// The shown fragment of hello_shadow_mapping_soft.cpp's camera pass (soft :961-979) at screen pixel (px, py):
+// the same interpolation without position / prev_position (that demo has no motion buffer), then
+// fragment_shader_softshadow (soft :991-1040) -- not the hard shader with other constants: the ambient and the
+// diffuse term are multiplied by the base colour, the specular term is not.
+__device__ void shade_pixel_soft(const RtParams &p, int32_t id, float u, float v, float w, int px, int py, uint32_t &rgba, float4 &pq) {
+    const RtRec &r = p.recs[id];
+    const RtVary &y = p.vary[id];
+    const RtDrawGPU &dr = p.draws[r.draw];
+    const float iw0 = r.iw0, iw1 = r.iw1, iw2 = r.iw2;
+    const float invw_sum = (u * iw0 + v * iw1) + w * iw2;
+    const f3 nsum = {(u * y.nrm[0] + v * y.nrm[3]) + w * y.nrm[6], (u * y.nrm[1] + v * y.nrm[4]) + w * y.nrm[7],
+                     (u * y.nrm[2] + v * y.nrm[5]) + w * y.nrm[8]};
+    const f3 in_normal = normalize3(nsum);
+    f3 wp;
+    wp.x = ((u * (y.world[0] * iw0) + v * (y.world[3] * iw1)) + w * (y.world[6] * iw2)) / invw_sum;
+    wp.y = ((u * (y.world[1] * iw0) + v * (y.world[4] * iw1)) + w * (y.world[7] * iw2)) / invw_sum;
+    wp.z = ((u * (y.world[2] * iw0) + v * (y.world[5] * iw1)) + w * (y.world[8] * iw2)) / invw_sum;
+    const float tu = ((u * (y.uv[0] * iw0) + v * (y.uv[2] * iw1)) + w * (y.uv[4] * iw2)) / invw_sum;
+    const float tv = ((u * (y.uv[1] * iw0) + v * (y.uv[3] * iw1)) + w * (y.uv[5] * iw2)) / invw_sum;
+    const f3 N = normalize3(in_normal);
+    const f3 L = {p.L[0], p.L[1], p.L[2]};
+    const f3 V = normalize3(sub3(f3{p.cam[0], p.cam[1], p.cam[2]}, wp));
+    f3 base = {dr.colf[0] / 255.0f, dr.colf[1] / 255.0f, dr.colf[2] / 255.0f};
+    if (dr.texels) {
+        // sample_nearest (soft :167-186)
+        const float su = (tu < 0.0f) ? 0.0f : (tu > 1.0f ? 1.0f : tu);
+        const float sv = (tv < 0.0f) ? 0.0f : (tv > 1.0f ? 1.0f : tv);
+        const int x = clampi(lround_x86(su * (float)(dr.tw - 1)), 0, dr.tw - 1);
+        const int yy = clampi(lround_x86(sv * (float)(dr.th - 1)), 0, dr.th - 1);
+        const uint32_t tc = dr.texels[(size_t)yy * dr.tw + x];
+        base = f3{(float)(tc & 0xffu) / 255.0f, (float)((tc >> 8) & 0xffu) / 255.0f, (float)((tc >> 16) & 0xffu) / 255.0f};
+    }
+    const float ndotl = dot3(N, L);
+    const float diffuse = g_max(ndotl, 0.0f) * 1.0f;
+    const f3 H = normalize3(add3(L, V));
+    const float spec = pow64(g_max(dot3(N, H), 0.0f));
+    const float specular = (0.45f * spec) * 1.0f;
+    float shadow = 1.0f;
+    if (p.shadow) {
+        // shadow_uvz_from_world (soft :231-250)
+        float cx, cy, cz, cw;
+        m4p(p.light_vp, wp.x, wp.y, wp.z, cx, cy, cz, cw);
+        if (!(fabsf(cw) < 1e-6f)) {
+            const float nx = cx / cw, ny = cy / cw, z = cz / cw;
+            if (!(z < 0.0f || z > 1.0f)) {
+                const float su = nx * 0.5f + 0.5f;
+                const float sv = 1.0f - (ny * 0.5f + 0.5f);
+                const float slope = 1.0f - g_clamp01(ndotl);
+                const float bias = p.bias_base + p.bias_slope * slope;
+                const PcssMap m = {p.shadow, p.sw, p.sh, p.pcss_light, p.pcss_search, p.pcss_min, p.pcss_max, p.pcss_eps,
+                                   p.pcss_blockers, p.pcss_taps};
+                shadow = pcss_shadow_factor(m, su, sv, z, bias, p.rot[(size_t)py * p.W + px]);
+            }
+        }
+    }
+    // amb = 0.22 * baseColor; direct = shadow * (diffuse * baseColor + specular); clamp(amb + direct)
+    const float pr = g_clamp01(0.22f * base.x + shadow * (diffuse * base.x + specular)) * 255;
+    const float pg = g_clamp01(0.22f * base.y + shadow * (diffuse * base.y + specular)) * 255;
+    const float pb = g_clamp01(0.22f * base.z + shadow * (diffuse * base.z + specular)) * 255;
+    rgba = byte_x86(pr) | (byte_x86(pg) << 8) | (byte_x86(pb) << 16) | 0xff000000u;
+    pq = make_float4(pr, pg, pb, shadow);
+}
+
+// SHADING: shs_rt_frame::shading of the camera pass, a compile-time choice (the shadow pass ignores it)
+template <bool SHADOW, int SHADING = 0>
 __global__ __launch_bounds__(256) void k_rt_raster(const RtParams p) {
     __shared__ float4 s_rec[RT_CHUNK * 6];
     __shared__ int32_t s_id[RT_CHUNK];
@@ -533,7 +674,11 @@ __global__ __launch_bounds__(256) void k_rt_raster(const RtParams p) {
     uint32_t rgba = p.clear_rgba;
     float2 vel = make_float2(0.0f, 0.0f);
     float4 pq = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (sid >= 0) shade_pixel(p, sid, su, sv, sw, rgba, vel, pq);
+    if constexpr (SHADING == 1) {
+        if (sid >= 0) shade_pixel_soft(p, sid, su, sv, sw, px, py, rgba, pq);   // the velocity plane stays zero
+    } else {
+        if (sid >= 0) shade_pixel(p, sid, su, sv, sw, rgba, vel, pq);
+    }
     const size_t o = (size_t)(p.H - 1 - py) * p.W + px;   // canvas rows
     p.color[o] = rgba;
     p.depth[o] = best;
@@ -542,12 +687,26 @@ __global__ __launch_bounds__(256) void k_rt_raster(const RtParams p) {
     if (p.prequant) p.prequant[o] = pq;
 }
 
+// shs_rt_pcss_samples: one lane per sample through the device function the raster calls
+__global__ __launch_bounds__(256) void k_rt_pcss_samples(const RtPcssSamples q) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= q.n) return;
+    const PcssMap m = {q.map, q.w, q.h, q.pcss_light, q.pcss_search, q.pcss_min, q.pcss_max, q.pcss_eps, q.pcss_blockers, q.pcss_taps};
+    q.out[i] = pcss_shadow_factor(m, q.uv[2 * i], q.uv[2 * i + 1], q.z[i], q.bias[i], q.rot[i]);
+}
+
 }  // namespace
 }  // namespace shs_dev
 
 namespace shs_internal {
 
-hipError_t launch_canvas_rt(const shs_dev::RtParams &p, bool shadow_pass, hipStream_t s) {
+hipError_t launch_pcss_samples(const shs_dev::RtPcssSamples &q, hipStream_t s) {
+    if (q.n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(shs_dev::k_rt_pcss_samples, dim3((q.n + 255) / 256), dim3(256), 0, s, q);
+    return hipGetLastError();
+}
+
+hipError_t launch_canvas_rt(const shs_dev::RtParams &p, bool shadow_pass, int shading, hipStream_t s) {
     using namespace shs_dev;
     if (p.n_tris > 0) {
         const int grid = (p.n_tris + 255) / 256;
@@ -558,6 +717,7 @@ hipError_t launch_canvas_rt(const shs_dev::RtParams &p, bool shadow_pass, hipStr
     }
     const int tiles = ((p.W + RT_TW - 1) / RT_TW) * ((p.H + RT_TH - 1) / RT_TH);
     if (shadow_pass) hipLaunchKernelGGL(k_rt_raster<true>, dim3(tiles), dim3(256), 0, s, p);
+    else if (shading == 1) hipLaunchKernelGGL((k_rt_raster<false, 1>), dim3(tiles), dim3(256), 0, s, p);
     else hipLaunchKernelGGL(k_rt_raster<false>, dim3(tiles), dim3(256), 0, s, p);
     return hipGetLastError();
 }

@@ -1,5 +1,6 @@
 // shs_canvas_rt_internal.hpp -- launch interface of shs_canvas_rt.hip: the Canvas render-target raster of
-// hello-render-target/hello_shadow_mapping.cpp (shadow pass and shadowed camera pass; include/shs_gpu.h).
+// hello-render-target/hello_shadow_mapping.cpp (shadow pass and shadowed camera pass; include/shs_gpu.h) and
+// of hello_shadow_mapping_soft.cpp (the same passes with the PCSS fragment shader, shs_rt_frame::shading 1).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -71,11 +72,29 @@ struct RtParams {
     float2 *velocity;
     float4 *prequant;                // or null
     int32_t *ids;
+    // shading 1 only (appended: the hard instantiations' argument offsets stay as they were)
+    const float4 *rot;               // per screen pixel py * W + px: {cos(ang), sin(ang), cos(ang2), sin(ang2)}
+    float pcss_light, pcss_search, pcss_min, pcss_max, pcss_eps;   // shs_rt_pcss
+    int32_t pcss_blockers, pcss_taps;
+};
+
+// pcss_shadow_factor for a list of samples (shs_rt_pcss_samples): everything on the device
+struct RtPcssSamples {
+    const float *map;                // w x h, y down
+    int32_t w, h, n;
+    const float *uv;                 // 2 n
+    const float *z, *bias;           // n each
+    const float4 *rot;               // n: the rotations of each sample's screen pixel, formed by the host
+    float *out;                      // n
+    float pcss_light, pcss_search, pcss_min, pcss_max, pcss_eps;
+    int32_t pcss_blockers, pcss_taps;
 };
 
 }  // namespace shs_dev
 
 namespace shs_internal {
 // setup (one lane per input triangle) then raster (one workgroup per 32x8 tile) of either pass
-hipError_t launch_canvas_rt(const shs_dev::RtParams &p, bool shadow_pass, hipStream_t s);
+// shading: shs_rt_frame::shading of the camera pass (0: fragment_shader_full, 1: fragment_shader_softshadow)
+hipError_t launch_canvas_rt(const shs_dev::RtParams &p, bool shadow_pass, int shading, hipStream_t s);
+hipError_t launch_pcss_samples(const shs_dev::RtPcssSamples &q, hipStream_t s);
 }  // namespace shs_internal

@@ -360,6 +360,12 @@ struct shs_ctx {
     int rt_w = 0, rt_h = 0, rt_sw = 0, rt_sh = 0;
     int64_t rt_n_tris = 0;
     bool rt_have_frame = false, rt_have_shadow = false, rt_have_pq = false;
+    // shading 1 (hello_shadow_mapping_soft.cpp): the PCSS constants (shs_rt_set_pcss; the demo's by default),
+    // the per-pixel rotation table of the last soft frame's size, and the workspace of shs_rt_pcss_samples
+    shs_rt_pcss rt_pcss = {0.0035f, 18.0f, 1.0f, 28.0f, 1e-5f, 12, 24};
+    DevBuf<float4> rt_rot, rt_ps_rot;
+    DevBuf<float> rt_ps_map, rt_ps_io;
+    int rt_rot_w = 0, rt_rot_h = 0;
 };
 
 // Re-enqueues the tonemap after lib_finish re-issued the camera pass (shs_abi_post.cpp).

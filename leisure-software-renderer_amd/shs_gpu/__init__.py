@@ -18,7 +18,7 @@ from ._abi import (FRAME_PREQUANT, FRAME_PRESENT, SHADING_BLINN_PHONG, SHADING_D
                    SHADING_TOON, FrameDesc, LegacyDraw, RasterStats)
 
 __all__ = [
-    "ShsError", "Context", "Frame", "Draw", "RtFrame", "RtDraw", "SHADING_FLAT", "SHADING_GOURAUD", "SHADING_PHONG",
+    "ShsError", "Context", "Frame", "Draw", "RtFrame", "RtDraw", "RtPcss", "SHADING_FLAT", "SHADING_GOURAUD", "SHADING_PHONG",
     "SHADING_BLINN_PHONG", "SHADING_TOON", "SHADING_GOOCH", "SHADING_OREN_NAYAR", "SHADING_NORMAL_VIS",
     "SHADING_DEPTH_VIS", "SHADING_TEXTURED", "SHADING_NAMES", "FRAME_PREQUANT", "lib",
 ]
@@ -105,6 +105,19 @@ class RtFrame:
     use_shadow: bool = True
     pcf: bool = True
     prequant: bool = False
+    shading: int = 0             # 0: fragment_shader_full, 1: fragment_shader_softshadow (PCSS; Context.rt_set_pcss)
+
+
+@dataclass
+class RtPcss:
+    """The PCSS constants of RtFrame.shading 1 (shs_rt_pcss); the defaults are hello_shadow_mapping_soft.cpp's."""
+    light_uv_radius: float = 0.0035
+    search_radius_texels: float = 18.0
+    min_filter_texels: float = 1.0
+    max_filter_texels: float = 28.0
+    epsilon: float = 1e-5
+    blocker_samples: int = 12
+    pcf_samples: int = 24
 
 
 class Context:
@@ -660,9 +673,32 @@ class Context:
         f.bias_base, f.bias_slope, f.max_velocity_px = frame.bias_base, frame.bias_slope, frame.max_velocity_px
         f.flags = (_abi.RT_USE_SHADOW if frame.use_shadow else 0) | (_abi.RT_PCF if frame.pcf else 0) | \
                   (_abi.RT_PREQUANT if frame.prequant else 0)
+        f.shading = int(frame.shading)
         arr = self._rt_draw_array(draws)
         self._check(self._lib.shs_rt_render(self._h, ctypes.byref(f), arr, len(draws)))
         self._rt_size = (frame.width, frame.height)
+
+    def rt_set_pcss(self, pcss=None):
+        """shs_rt_set_pcss: the PCSS constants of shading 1 (an RtPcss; None: the demo's)."""
+        if pcss is None:
+            self._check(self._lib.shs_rt_set_pcss(self._h, None))
+            return
+        c = _abi.RtPcssC(pcss.light_uv_radius, pcss.search_radius_texels, pcss.min_filter_texels, pcss.max_filter_texels,
+                         pcss.epsilon, int(pcss.blocker_samples), int(pcss.pcf_samples))
+        self._check(self._lib.shs_rt_set_pcss(self._h, ctypes.byref(c)))
+
+    def rt_pcss_samples(self, shadow_map, uv, z, bias, pxpy):
+        """shs_rt_pcss_samples: pcss_shadow_factor of n samples over a host map [h, w] -> float32 [n], synchronous."""
+        sm = np.ascontiguousarray(shadow_map, np.float32)
+        uv = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+        n = uv.shape[0]
+        z = np.ascontiguousarray(z, np.float32).reshape(n)
+        bias = np.ascontiguousarray(bias, np.float32).reshape(n)
+        pxpy = np.ascontiguousarray(pxpy, np.int32).reshape(n, 2)
+        out = np.empty(n, np.float32)
+        self._check(self._lib.shs_rt_pcss_samples(self._h, _ptr(sm), sm.shape[1], sm.shape[0], n, _ptr(uv), _ptr(z), _ptr(bias),
+                                                  _ptr(pxpy), _ptr(out)))
+        return out
 
     def _rt_dims(self, shadow=False):
         size = self._rt_shadow_size if shadow else self._rt_size

@@ -229,6 +229,13 @@ class RtFrameC(ctypes.Structure):
                 ("shading", ctypes.c_int32)]
 
 
+class RtPcssC(ctypes.Structure):
+    """shs_rt_pcss: the PCSS constants of shs_rt_frame::shading 1."""
+    _fields_ = [("light_uv_radius", ctypes.c_float), ("search_radius_texels", ctypes.c_float),
+                ("min_filter_texels", ctypes.c_float), ("max_filter_texels", ctypes.c_float), ("epsilon", ctypes.c_float),
+                ("blocker_samples", ctypes.c_int32), ("pcf_samples", ctypes.c_int32)]
+
+
 class RtStatsC(ctypes.Structure):
     _fields_ = [("input_tris", ctypes.c_int64), ("polys3", ctypes.c_int64), ("polys4", ctypes.c_int64),
                 ("sub_tris", ctypes.c_int64)]
@@ -342,6 +349,8 @@ SIGNATURES = [
     ("shs_rt_render_shadow", ctypes.c_int, [_P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _F,
                                             ctypes.POINTER(RtDrawC), ctypes.c_int32]),
     ("shs_rt_render", ctypes.c_int, [_P, ctypes.POINTER(RtFrameC), ctypes.POINTER(RtDrawC), ctypes.c_int32]),
+    ("shs_rt_set_pcss", ctypes.c_int, [_P, ctypes.POINTER(RtPcssC)]),
+    ("shs_rt_pcss_samples", ctypes.c_int, [_P, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P, _P]),
     ("shs_rt_resolve", ctypes.c_int, [_P, _P, _P, _P]),
     ("shs_rt_resolve_shadow", ctypes.c_int, [_P, _P]),
     ("shs_rt_resolve_prequant", ctypes.c_int, [_P, _P]),
