@@ -839,7 +839,16 @@ int shs_canvas_dof(shs_ctx *ctx, const shs_canvas_dof_desc *desc, uint8_t *color
  *      effect; SHS_RT_USE_SHADOW and SHS_RT_PREQUANT keep their meaning (the prequant plane's fourth
  *      float is the PCSS factor).  The per-pixel rotations' cos / sin are the host libm's, as the
  *      reference's: the first soft frame of a size builds a width * height table of them (16 B per
- *      pixel, at most 2^26 pixels) and keeps it until the size changes. */
+ *      pixel, at most 2^26 pixels) and keeps it until the size changes.
+ *   2  fragment_shader_pbr of hello_pbr.cpp (:627-727), through shs_rt_render_pbr only (shs_rt_render rejects
+ *      it: the shader needs the per-draw uniforms of shs_rt_pbr_draw).  That demo's PASS0 and PASS1 rasters
+ *      (:827-870, :883-1045) are hello_shadow_mapping.cpp's, so shs_rt_render_shadow serves it unchanged and
+ *      its PASS2 is shs_canvas_motion_blur over shs_rt_device_targets.  Cook-Torrance GGX under the shadow
+ *      lookup of shading 0 (SHS_RT_USE_SHADOW, SHS_RT_PCF, bias_base, bias_slope), plus image-based lighting
+ *      from the EnvIBL of shs_rt_set_ibl; Reinhard tonemap and gamma 2.2 to bytes.  The velocity plane is
+ *      written as for shading 0.  Not built: skybox_background_pass (:733-799) -- uncovered pixels keep
+ *      clear_color -- and the IBL precompute, which stays on the host (its results come in through
+ *      shs_rt_set_ibl). */
 typedef struct shs_rt_draw {
     int32_t mesh_id;            /* shs_mesh_upload_soup[_uv] soup (without UVs: vec2(0) per corner) */
     int32_t albedo_tex;         /* shs_texture_upload id (use_texture), 0: base_color */
@@ -862,7 +871,8 @@ typedef struct shs_rt_frame {
     float bias_base, bias_slope;      /* SHADOW_BIAS_BASE (0.0025), SHADOW_BIAS_SLOPE (0.01) */
     float max_velocity_px;            /* MB_MAX_PIXELS (22) */
     uint32_t flags;                   /* SHS_RT_* */
-    int32_t shading;                  /* 0: fragment_shader_full, 1: fragment_shader_softshadow */
+    int32_t shading;                  /* 0: fragment_shader_full, 1: fragment_shader_softshadow,
+                                         2: fragment_shader_pbr (shs_rt_render_pbr) */
 } shs_rt_frame;
 /* The PCSS constants of shading 1 (hello_shadow_mapping_soft.cpp:101-116), kept in the context. */
 typedef struct shs_rt_pcss {
@@ -891,7 +901,7 @@ typedef struct shs_rt_stats {
 int shs_rt_render_shadow(shs_ctx *ctx, int32_t w, int32_t h, int32_t ref_tile_w, int32_t ref_tile_h, const float light_vp[16],
                          const shs_rt_draw *casters, int32_t n_casters);
 /* SHS_ERR_INVALID: an unknown mesh or texture id, a non-positive size, unknown flags, a shading other than
- * 0 or 1, or SHS_RT_USE_SHADOW without a shadow map rendered before. */
+ * 0 or 1 (2 goes through shs_rt_render_pbr), or SHS_RT_USE_SHADOW without a shadow map rendered before. */
 int shs_rt_render(shs_ctx *ctx, const shs_rt_frame *frame, const shs_rt_draw *draws, int32_t n_draws);
 /* Host copies of the last camera pass (any pointer may be NULL): color W*H*4 bytes, depth W*H floats,
  * velocity W*H*2 floats.  Synchronous. */
@@ -906,6 +916,37 @@ int shs_rt_get_stats(shs_ctx *ctx, shs_rt_stats *stats);
 /* The last camera pass's device planes, final in the context stream's order (as shs_device_framebuffers):
  * valid until the next shs_rt_render of another size or shs_destroy. */
 int shs_rt_device_targets(shs_ctx *ctx, void **color_dev, void **depth_dev, void **velocity_dev);
+/* hello_pbr.cpp's per-object uniforms that fragment_shader_pbr and vertex_shader_full read beside shs_rt_draw
+ * (whose base_color is MaterialPBR::baseColor_srgb): element i goes with shs_rt_draw[i]. */
+typedef struct shs_rt_pbr_draw {
+    float normal_mat[9];              /* u.normal_mat, column-major mat3, supplied by the caller as the demo does
+                                         (:1482 mat3(1) for the floor, :1557 transpose(inverse(mat3(model)))) */
+    float metallic, roughness, ao;    /* MaterialPBR :474-482 */
+    float ibl_diffuse_intensity, ibl_specular_intensity, ibl_reflection_strength;   /* :516-518 */
+} shs_rt_pbr_draw;
+/* The shader's constants (hello_pbr.cpp:150-155), kept in the context. */
+typedef struct shs_rt_pbr {
+    float exposure;                   /* PBR_EXPOSURE 1.75 */
+    float min_roughness;              /* PBR_MIN_ROUGHNESS 0.04 */
+    float direct_intensity;           /* DIRECT_LIGHT_INTENSITY 3.0 */
+} shs_rt_pbr;
+/* NULL: the demo's constants, also the default.  SHS_ERR_INVALID: a non-finite constant (the context keeps
+ * what it had). */
+int shs_rt_set_pbr(shs_ctx *ctx, const shs_rt_pbr *pbr);
+/* EnvIBL (shs/resources/ibl.hpp:21-59) from host floats: irr = 6 faces of irr_size^2 rgb; spec = mip
+ * 0..mip_count-1 concatenated, mip m = 6 faces of max(1, spec_base >> m)^2 rgb (ibl.hpp:168); texel (x, y) of a
+ * face at y * size + x.  irr == NULL: no IBL (u.ibl == nullptr), also the default.  Kept in the context until
+ * the next call.  Synchronous.  SHS_ERR_INVALID: a size <= 0 (or above 8192), mip_count outside 1..16, spec
+ * NULL (the context keeps what it had). */
+int shs_rt_set_ibl(shs_ctx *ctx, int32_t irr_size, const float *irr, int32_t spec_base, int32_t mip_count, const float *spec);
+/* PASS1 of hello_pbr.cpp: the raster of shs_rt_render with fragment_shader_pbr.  frame->shading must be 2.
+ * SHS_ERR_INVALID as shs_rt_render, and for any other shading. */
+int shs_rt_render_pbr(shs_ctx *ctx, const shs_rt_frame *frame, const shs_rt_draw *draws, const shs_rt_pbr_draw *pbr_draws,
+                      int32_t n_draws);
+/* sample_cubemap_linear_vec(env_irradiance, dir) and sample_prefiltered_spec_trilinear(spec, dir, lod)
+ * (ibl.hpp:236-286) of the context's IBL for n directions through the device functions the raster calls: dirs3
+ * 3n, lod n, both outputs 3n.  Synchronous; for tests of the edge cases.  SHS_ERR_INVALID without an IBL. */
+int shs_rt_ibl_samples(shs_ctx *ctx, int32_t n, const float *dirs3, const float *lod, float *irr_rgb3, float *spec_rgb3);
 /* ortho_lh_zo (hello_shadow_mapping.cpp:128-140): LH, z in [0, 1]. */
 int shs_ortho_lh_zo(float left, float right, float bottom, float top, float znear, float zfar, float out16[16]);
 

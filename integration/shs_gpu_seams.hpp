@@ -325,6 +325,96 @@ private:
     int sm_, tile_;
 };
 
+// -----------------------------------------------------------------------------------------------------
+// Seam 1b, PBR -- hello-render-target/hello_pbr.cpp.
+//
+// Replaces RendererSystem::process there: PASS0 is the hard demo's (draw_triangle_tile_shadow :827-870), PASS1 the
+// hard demo's raster (draw_triangle_tile_color_depth_motion :883-1045) with fragment_shader_pbr (:627-727) through
+// shs_rt_render_pbr and shading = 2, PASS2 combined_motion_blur_pass (:1051-1252) through shs_canvas_motion_blur over
+// shs_rt_device_targets.  The IBL precompute (:1855-1875) stays on the host at start-up; set_ibl hands its results
+// over once.  skybox_background_pass (:733-799) is not built: uncovered pixels keep the clear colour.  Uncompiled,
+// like the other seams.
+// -----------------------------------------------------------------------------------------------------
+template <class SceneT>
+class PbrSystemGPU : public shs::AbstractSystem {
+public:
+    struct Object {
+        typename RenderTargetSystemGPU<SceneT>::Object geom;   // base_color is MaterialPBR::baseColor_srgb
+        shs_rt_pbr_draw pbr;                                    // u.normal_mat, u.mat, the three IBL knobs (:474-518)
+    };
+
+    PbrSystemGPU(SceneT *scene, Device *dev, int shadow_size = 2048, int tile = 160)
+        : scene_(scene), dev_(dev), sm_(shadow_size), tile_(tile) {}
+
+    std::vector<Object> objects;     // geom.model / prev_model and pbr.normal_mat per frame
+
+    void set_pbr(const shs_rt_pbr *k) { ok(shs_rt_set_pbr(dev_->ctx, k)); }   // nullptr: the demo's constants
+
+    // EnvIBL (shs/resources/ibl.hpp:21-59) flattened to floats: the six faces of the irradiance map, then of each mip
+    template <class EnvIblT>
+    void set_ibl(const EnvIblT &ibl) {
+        std::vector<float> irr, spec;
+        auto put = [](std::vector<float> &out, const auto &cube) {
+            for (int f = 0; f < 6; ++f)
+                for (const glm::vec3 &c : cube.face[f]) { out.push_back(c.x); out.push_back(c.y); out.push_back(c.z); }
+        };
+        put(irr, ibl.env_irradiance);
+        for (const auto &m : ibl.env_prefiltered_spec.mip) put(spec, m);
+        ok(shs_rt_set_ibl(dev_->ctx, ibl.env_irradiance.size, irr.data(), ibl.env_prefiltered_spec.mip[0].size,
+                          ibl.env_prefiltered_spec.mip_count(), spec.data()));
+    }
+
+    void process(float) override {
+        shs::Canvas &canvas = *scene_->canvas;
+        const int W = canvas.get_width(), H = canvas.get_height();
+        const glm::mat4 view = scene_->viewer->camera->view_matrix, proj = scene_->viewer->camera->projection_matrix;
+        std::vector<shs_rt_draw> draws(objects.size());
+        std::vector<shs_rt_pbr_draw> mats(objects.size());
+        for (size_t i = 0; i < objects.size(); ++i) {
+            const auto &o = objects[i].geom;
+            shs_rt_draw &d = draws[i];
+            d.mesh_id = o.mesh_id;
+            d.albedo_tex = o.albedo_tex;
+            const glm::mat4 mvp = proj * view * o.model, prev_mvp = prev_vp_ * o.prev_model;
+            std::memcpy(d.model, glm::value_ptr(o.model), 64);
+            std::memcpy(d.mvp, glm::value_ptr(mvp), 64);
+            std::memcpy(d.prev_mvp, glm::value_ptr(prev_mvp), 64);
+            d.base_color[0] = o.base_color.r; d.base_color[1] = o.base_color.g; d.base_color[2] = o.base_color.b; d.base_color[3] = 255;
+            mats[i] = objects[i].pbr;
+        }
+        ok(shs_rt_render_shadow(dev_->ctx, sm_, sm_, tile_, tile_, glm::value_ptr(light_vp), draws.data(), (int32_t)draws.size()));
+        shs_rt_frame f{};
+        f.width = W; f.height = H; f.ref_tile_w = tile_; f.ref_tile_h = tile_;
+        f.clear_color[0] = 20; f.clear_color[1] = 20; f.clear_color[2] = 25; f.clear_color[3] = 255;
+        std::memcpy(f.view, glm::value_ptr(view), 64);
+        std::memcpy(f.light_vp, glm::value_ptr(light_vp), 64);
+        std::memcpy(f.light_dir_world, glm::value_ptr(light_dir_world), 12);
+        std::memcpy(f.camera_pos, glm::value_ptr(scene_->viewer->position), 12);
+        f.bias_base = 0.0025f; f.bias_slope = 0.01f; f.max_velocity_px = 22.0f;      // SHADOW_BIAS_* :113-114, MB_MAX_PIXELS
+        f.flags = SHS_RT_USE_SHADOW | SHS_RT_PCF;                                    // SHADOW_USE_PCF :117
+        f.shading = 2;
+        ok(shs_rt_render_pbr(dev_->ctx, &f, draws.data(), mats.data(), (int32_t)draws.size()));
+        void *color = nullptr, *depth = nullptr, *velocity = nullptr;
+        ok(shs_rt_device_targets(dev_->ctx, &color, &depth, &velocity));
+        // PASS2 on the device (shs_canvas_motion_blur with SHS_CANVAS_DEVICE into a device buffer of the host's), or
+        // shs_rt_resolve into rt->color / rt->depth / rt->velocity for a CPU PASS2.
+        prev_vp_ = proj * view;
+    }
+
+    void ok(int rc) const {
+        if (rc != SHS_OK) throw std::runtime_error(shs_last_error(dev_->ctx));
+    }
+
+    glm::mat4 light_vp{1.0f};
+    glm::vec3 light_dir_world{0.4668f, -0.3487f, 0.8127f};   // LIGHT_DIR_WORLD (the shader normalises it)
+
+private:
+    SceneT *scene_;
+    Device *dev_;
+    int sm_, tile_;
+    glm::mat4 prev_vp_{1.0f};
+};
+
 // =====================================================================================================
 // Seam 3 -- the library's plugin pipeline (shs-renderer-lib/include/shs/pipeline/).
 // =====================================================================================================

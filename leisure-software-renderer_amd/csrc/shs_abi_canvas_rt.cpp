@@ -5,6 +5,9 @@
 //   shs_ortho_lh_zo       ortho_lh_zo (:128-140);
 // and of hello_shadow_mapping_soft.cpp: shs_rt_render with shading 1 (its PASS1, :845-1040), shs_rt_set_pcss (the
 // constants :101-116), shs_rt_pcss_samples (pcss_shadow_factor :333-445 alone) and the per-pixel rotation table.
+// and of hello_pbr.cpp ("pbr :line"): shs_rt_render_pbr (its PASS1, pbr :883-1045 with fragment_shader_pbr :627-727),
+// shs_rt_set_pbr (the constants pbr :150-155), shs_rt_set_ibl (EnvIBL, shs/resources/ibl.hpp:21-59) and
+// shs_rt_ibl_samples (the two IBL samplers alone, ibl.hpp:215-286).
 // The host forms the matrix products the shaders form first -- u.view * u.model (vertex_shader_full :616),
 // u.light_vp * u.model (shadow_vertex_shader :764) -- and the normal matrix with the GLM restatement in
 // shs_glm.hpp.  Both passes are enqueued on the context stream; the shadow map, the planes and the records
@@ -24,10 +27,30 @@ bool size_ok(shs_ctx *ctx, int W, int H, int tw, int th) {
     return false;
 }
 
+// srgb_to_linear of a byte (shs_renderer.hpp:273-276 over color_to_rgb01 :291-293): pow(c / 255, 2.2) with the host's
+// libm, as the reference evaluates it.  Both base-colour branches of fragment_shader_pbr start from bytes.
+const float *srgb_table() {
+    struct Lut {
+        float v[256];
+        Lut() {
+            const volatile float gamma = 2.2f;   // (a run-time exponent: the libm call is not folded at compile time)
+            for (int c = 0; c < 256; ++c) v[c] = std::pow(float(c) / 255.0f, gamma);
+        }
+    };
+    static const Lut lut;
+    return lut.v;
+}
+
+float saturate(float v) { return (v < 0.0f) ? 0.0f : (v > 1.0f ? 1.0f : v); }
+float clampf(float v, float lo, float hi) { return (v < lo) ? lo : (v > hi ? hi : v); }
+
 // The draw table of either pass (zm: view for the camera pass, light_vp for the shadow pass).  Returns the
-// triangle count, or -1 with ctx->err set.
-int64_t build_draws(shs_ctx *ctx, const shs_rt_draw *draws, int32_t n, const float *zmat, bool camera) {
+// triangle count, or -1 with ctx->err set.  pbr: the PBR pass's per-draw uniforms (element i with draws[i]), or
+// null for the other passes.
+int64_t build_draws(shs_ctx *ctx, const shs_rt_draw *draws, int32_t n, const float *zmat, bool camera,
+                    const shs_rt_pbr_draw *pbr = nullptr) {
     ctx->rt_h_draws.clear();
+    ctx->rt_h_pbr.clear();
     int64_t total = 0;
     for (int32_t i = 0; i < n; ++i) {
         const shs_rt_draw &in = draws[i];
@@ -59,6 +82,20 @@ int64_t build_draws(shs_ctx *ctx, const shs_rt_draw *draws, int32_t n, const flo
         shs_host::mul(zmat, in.model, o.zm);
         shs_host::normal_matrix(in.model, o.n3);
         for (int k = 0; k < 3; ++k) o.colf[k] = (float)in.base_color[k];
+        if (pbr) {
+            // u.normal_mat is the caller's (pbr :1482, :1557); the per-draw steps of fragment_shader_pbr (pbr :646-652,
+            // :697, :706) are done here once
+            const shs_rt_pbr_draw &m = pbr[i];
+            std::memcpy(o.n3, m.normal_mat, 9 * sizeof(float));
+            shs_dev::RtPbrDrawGPU g{};
+            for (int k = 0; k < 3; ++k) g.base[k] = srgb_table()[in.base_color[k]];
+            g.metallic = saturate(m.metallic);
+            g.roughness = clampf(m.roughness, ctx->rt_pbr.min_roughness, 1.0f);
+            g.ao = saturate(m.ao);
+            g.ibl_diffuse = saturate(m.ibl_diffuse_intensity);
+            g.ibl_specular = saturate(m.ibl_specular_intensity) * saturate(m.ibl_reflection_strength);
+            ctx->rt_h_pbr.push_back(g);
+        }
         ctx->rt_h_draws.push_back(o);
         total += m.n_tris;
         if (total > (1 << 29)) {
@@ -120,7 +157,12 @@ bool pcss_ok(const shs_rt_pcss &c) {
 
 int upload_and_launch(shs_ctx *ctx, shs_dev::RtParams &p, bool shadow_pass, int shading = 0) {
     const size_t nd = ctx->rt_h_draws.size();
-    if (ensure(ctx, ctx->rt_draws, std::max<size_t>(nd, 1)) || ensure(ctx, ctx->rt_recs, std::max<size_t>((size_t)p.n_recs, 1)) ||
+    // the PBR pass's material table rides behind the draw table (sizeof(RtDrawGPU) is a multiple of 16): one copy
+    static_assert(sizeof(shs_dev::RtDrawGPU) % 16 == 0, "the material table behind the draws is read as float4s");
+    const size_t npbr = ctx->rt_h_pbr.size();
+    const size_t extra = (npbr * sizeof(shs_dev::RtPbrDrawGPU) + sizeof(shs_dev::RtDrawGPU) - 1) / sizeof(shs_dev::RtDrawGPU);
+    const size_t nslot = nd + extra;
+    if (ensure(ctx, ctx->rt_draws, std::max<size_t>(nslot, 1)) || ensure(ctx, ctx->rt_recs, std::max<size_t>((size_t)p.n_recs, 1)) ||
         ensure(ctx, ctx->rt_stats, 4))
         return SHS_ERR_HIP;
     if (!shadow_pass && ensure(ctx, ctx->rt_vary, std::max<size_t>((size_t)p.n_recs, 1))) return SHS_ERR_HIP;
@@ -128,19 +170,22 @@ int upload_and_launch(shs_ctx *ctx, shs_dev::RtParams &p, bool shadow_pass, int 
         const int k = (int)(ctx->rt_pin_next++ & 1u);
         if (!ctx->rt_pin_ev[k]) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->rt_pin_ev[k], hipEventDisableTiming));
         else HIP_TRY(ctx, hipEventSynchronize(ctx->rt_pin_ev[k]));
-        if (ctx->rt_pin_cap[k] < nd) {
+        if (ctx->rt_pin_cap[k] < nslot) {
             if (ctx->rt_pin[k]) HIP_TRY(ctx, hipHostFree(ctx->rt_pin[k]));
             ctx->rt_pin[k] = nullptr;
             ctx->rt_pin_cap[k] = 0;
-            HIP_TRY(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->rt_pin[k]), nd * sizeof(shs_dev::RtDrawGPU), hipHostMallocDefault));
-            ctx->rt_pin_cap[k] = nd;
+            HIP_TRY(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->rt_pin[k]), nslot * sizeof(shs_dev::RtDrawGPU), hipHostMallocDefault));
+            ctx->rt_pin_cap[k] = nslot;
         }
         std::memcpy(ctx->rt_pin[k], ctx->rt_h_draws.data(), nd * sizeof(shs_dev::RtDrawGPU));
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->rt_draws.p, ctx->rt_pin[k], nd * sizeof(shs_dev::RtDrawGPU), hipMemcpyHostToDevice, ctx->stream));
+        if (npbr) std::memcpy(ctx->rt_pin[k] + nd, ctx->rt_h_pbr.data(), npbr * sizeof(shs_dev::RtPbrDrawGPU));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->rt_draws.p, ctx->rt_pin[k], nd * sizeof(shs_dev::RtDrawGPU) + npbr * sizeof(shs_dev::RtPbrDrawGPU),
+                                    hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(ctx, hipEventRecord(ctx->rt_pin_ev[k], ctx->stream));
     }
     if (!shadow_pass) HIP_TRY(ctx, hipMemsetAsync(ctx->rt_stats.p, 0, 4 * sizeof(unsigned long long), ctx->stream));
     p.draws = ctx->rt_draws.p;
+    p.pbr_draws = npbr ? reinterpret_cast<const shs_dev::RtPbrDrawGPU *>(ctx->rt_draws.p + nd) : nullptr;
     p.recs = ctx->rt_recs.p;
     p.vary = ctx->rt_vary.p;
     p.stats = ctx->rt_stats.p;
@@ -148,45 +193,12 @@ int upload_and_launch(shs_ctx *ctx, shs_dev::RtParams &p, bool shadow_pass, int 
     return SHS_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int shs_rt_render_shadow(shs_ctx *ctx, int32_t w, int32_t h, int32_t ref_tile_w, int32_t ref_tile_h, const float light_vp[16],
-                         const shs_rt_draw *casters, int32_t n_casters) {
-    if (!ctx || !light_vp || n_casters < 0 || (n_casters > 0 && !casters)) return SHS_ERR_INVALID;
-    if (!size_ok(ctx, w, h, ref_tile_w, ref_tile_h)) return SHS_ERR_INVALID;
-    if (set_dev(ctx)) return SHS_ERR_HIP;
-    const int64_t n_tris = build_draws(ctx, casters, n_casters, light_vp, false);
-    if (n_tris < 0) return SHS_ERR_INVALID;
-    if (ensure(ctx, ctx->rt_shadow, (size_t)w * h)) return SHS_ERR_HIP;
-    shs_dev::RtParams p{};
-    p.W = w; p.H = h;
-    p.tile_w = std::min(ref_tile_w, w);   // (a job larger than the target is the whole target)
-    p.tile_h = std::min(ref_tile_h, h);
-    p.n_draws = n_casters;
-    p.n_tris = (int32_t)n_tris;
-    p.n_recs = (int32_t)n_tris;
-    p.depth = ctx->rt_shadow.p;
-    // the shadow pass shares the stats words with the camera pass: its own count is not reported
-    const int rc = upload_and_launch(ctx, p, true);
-    if (rc) return rc;
-    ctx->rt_sw = w;
-    ctx->rt_sh = h;
-    ctx->rt_have_shadow = true;
-    return SHS_OK;
-}
-
-int shs_rt_render(shs_ctx *ctx, const shs_rt_frame *f, const shs_rt_draw *draws, int32_t n_draws) {
-    if (!ctx || !f || n_draws < 0 || (n_draws > 0 && !draws)) return SHS_ERR_INVALID;
+// PASS1 of the three demos: pbr null for shading 0 / 1 (shs_rt_render), the per-draw PBR uniforms for shading 2
+// (shs_rt_render_pbr).  Nothing of the context changes before the last rejection.
+int render_camera(shs_ctx *ctx, const shs_rt_frame *f, const shs_rt_draw *draws, const shs_rt_pbr_draw *pbr, int32_t n_draws) {
     if (!size_ok(ctx, f->width, f->height, f->ref_tile_w, f->ref_tile_h)) return SHS_ERR_INVALID;
     if (f->flags & ~(SHS_RT_USE_SHADOW | SHS_RT_PCF | SHS_RT_PREQUANT)) {
         ctx->err = "render-target frame: unknown flags";
-        return SHS_ERR_INVALID;
-    }
-    if (f->shading != 0 && f->shading != 1) {
-        ctx->err = "render-target frame: shading " + std::to_string(f->shading) +
-                   " (0: fragment_shader_full, 1: fragment_shader_softshadow)";
         return SHS_ERR_INVALID;
     }
     if ((f->flags & SHS_RT_USE_SHADOW) && !ctx->rt_have_shadow) {
@@ -194,7 +206,7 @@ int shs_rt_render(shs_ctx *ctx, const shs_rt_frame *f, const shs_rt_draw *draws,
         return SHS_ERR_INVALID;
     }
     if (set_dev(ctx)) return SHS_ERR_HIP;
-    const int64_t n_tris = build_draws(ctx, draws, n_draws, f->view, true);
+    const int64_t n_tris = build_draws(ctx, draws, n_draws, f->view, true, pbr);
     if (n_tris < 0) return SHS_ERR_INVALID;
     const size_t npx = (size_t)f->width * f->height;
     const bool pq = (f->flags & SHS_RT_PREQUANT) != 0;
@@ -241,6 +253,19 @@ int shs_rt_render(shs_ctx *ctx, const shs_rt_frame *f, const shs_rt_draw *draws,
         p.pcss_blockers = c.blocker_samples;
         p.pcss_taps = c.pcf_samples;
     }
+    if (f->shading == 2) {
+        if (!ctx->rt_have_lut) {
+            if (ensure(ctx, ctx->rt_srgb_lut, 256)) return SHS_ERR_HIP;
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->rt_srgb_lut.p, srgb_table(), 256 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            ctx->rt_have_lut = true;
+        }
+        p.srgb_lut = ctx->rt_srgb_lut.p;
+        p.ibl = ctx->rt_ibl_mips > 0 ? ctx->rt_ibl.p : nullptr;
+        p.ibl_mips = ctx->rt_ibl_mips;
+        p.pbr_exposure = ctx->rt_pbr.exposure;
+        p.pbr_intensity = ctx->rt_pbr.direct_intensity;
+    }
     const int rc = upload_and_launch(ctx, p, false, f->shading);
     if (rc) {
         ctx->rt_have_frame = false;
@@ -252,6 +277,55 @@ int shs_rt_render(shs_ctx *ctx, const shs_rt_frame *f, const shs_rt_draw *draws,
     ctx->rt_have_frame = true;
     ctx->rt_have_pq = pq;
     return SHS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int shs_rt_render_shadow(shs_ctx *ctx, int32_t w, int32_t h, int32_t ref_tile_w, int32_t ref_tile_h, const float light_vp[16],
+                         const shs_rt_draw *casters, int32_t n_casters) {
+    if (!ctx || !light_vp || n_casters < 0 || (n_casters > 0 && !casters)) return SHS_ERR_INVALID;
+    if (!size_ok(ctx, w, h, ref_tile_w, ref_tile_h)) return SHS_ERR_INVALID;
+    if (set_dev(ctx)) return SHS_ERR_HIP;
+    const int64_t n_tris = build_draws(ctx, casters, n_casters, light_vp, false);
+    if (n_tris < 0) return SHS_ERR_INVALID;
+    if (ensure(ctx, ctx->rt_shadow, (size_t)w * h)) return SHS_ERR_HIP;
+    shs_dev::RtParams p{};
+    p.W = w; p.H = h;
+    p.tile_w = std::min(ref_tile_w, w);   // (a job larger than the target is the whole target)
+    p.tile_h = std::min(ref_tile_h, h);
+    p.n_draws = n_casters;
+    p.n_tris = (int32_t)n_tris;
+    p.n_recs = (int32_t)n_tris;
+    p.depth = ctx->rt_shadow.p;
+    // the shadow pass shares the stats words with the camera pass: its own count is not reported
+    const int rc = upload_and_launch(ctx, p, true);
+    if (rc) return rc;
+    ctx->rt_sw = w;
+    ctx->rt_sh = h;
+    ctx->rt_have_shadow = true;
+    return SHS_OK;
+}
+
+int shs_rt_render(shs_ctx *ctx, const shs_rt_frame *f, const shs_rt_draw *draws, int32_t n_draws) {
+    if (!ctx || !f || n_draws < 0 || (n_draws > 0 && !draws)) return SHS_ERR_INVALID;
+    if (f->shading != 0 && f->shading != 1) {
+        ctx->err = "render-target frame: shading " + std::to_string(f->shading) +
+                   " (0: fragment_shader_full, 1: fragment_shader_softshadow; 2, fragment_shader_pbr, goes through shs_rt_render_pbr)";
+        return SHS_ERR_INVALID;
+    }
+    return render_camera(ctx, f, draws, nullptr, n_draws);
+}
+
+int shs_rt_render_pbr(shs_ctx *ctx, const shs_rt_frame *f, const shs_rt_draw *draws, const shs_rt_pbr_draw *pbr_draws, int32_t n_draws) {
+    if (!ctx || !f || n_draws < 0 || (n_draws > 0 && (!draws || !pbr_draws))) return SHS_ERR_INVALID;
+    if (f->shading != 2) {
+        ctx->err = "shs_rt_render_pbr: shading " + std::to_string(f->shading) + " (2: fragment_shader_pbr)";
+        return SHS_ERR_INVALID;
+    }
+    static const shs_rt_pbr_draw none{};
+    return render_camera(ctx, f, draws, n_draws > 0 ? pbr_draws : &none, n_draws);
 }
 
 int shs_rt_resolve(shs_ctx *ctx, uint8_t *color, float *depth, float *velocity) {
@@ -357,6 +431,91 @@ int shs_rt_pcss_samples(shs_ctx *ctx, const float *map, int32_t w, int32_t h, in
     q.pcss_taps = c.pcf_samples;
     HIP_TRY(ctx, shs_internal::launch_pcss_samples(q, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(out, q.out, ns * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // (the pageable staging above is consumed by now)
+    return SHS_OK;
+}
+
+int shs_rt_set_pbr(shs_ctx *ctx, const shs_rt_pbr *pbr) {
+    if (!ctx) return SHS_ERR_INVALID;
+    const shs_rt_pbr demo = {1.75f, 0.04f, 3.0f};
+    if (pbr && !(std::isfinite(pbr->exposure) && std::isfinite(pbr->min_roughness) && std::isfinite(pbr->direct_intensity))) {
+        ctx->err = "shs_rt_set_pbr: a non-finite constant";
+        return SHS_ERR_INVALID;
+    }
+    ctx->rt_pbr = pbr ? *pbr : demo;
+    return SHS_OK;
+}
+
+int shs_rt_set_ibl(shs_ctx *ctx, int32_t irr_size, const float *irr, int32_t spec_base, int32_t mip_count, const float *spec) {
+    if (!ctx) return SHS_ERR_INVALID;
+    if (!irr) {   // u.ibl == nullptr; a frame in flight keeps reading the old levels, which stay allocated
+        ctx->rt_ibl_mips = 0;
+        return SHS_OK;
+    }
+    if (irr_size <= 0 || spec_base <= 0 || mip_count < 1 || mip_count > 16 || !spec || irr_size > 8192 || spec_base > 8192) {
+        ctx->err = "shs_rt_set_ibl: sizes 1 .. 8192, 1 .. 16 mips, both maps given";
+        return SHS_ERR_INVALID;
+    }
+    // the level table, then the texels padded to float4 (shs_canvas_rt_internal.hpp)
+    int32_t size[shs_dev::RT_IBL_LEVELS] = {irr_size};
+    size_t total = shs_dev::RT_IBL_LEVELS;
+    std::vector<float4> host(total);
+    for (int l = 0; l <= mip_count; ++l) {
+        if (l > 0) size[l] = std::max(1, spec_base >> (l - 1));   // ibl.hpp:168
+        const int32_t hd[4] = {(int32_t)total, size[l], 0, 0};
+        std::memcpy(&host[l], hd, sizeof hd);
+        total += (size_t)6 * size[l] * size[l];
+    }
+    if (total > ((size_t)1 << 27)) {
+        ctx->err = "shs_rt_set_ibl: more than 2^27 texels";
+        return SHS_ERR_INVALID;
+    }
+    host.resize(total);
+    size_t o = shs_dev::RT_IBL_LEVELS;
+    const float *src = irr;
+    for (int l = 0; l <= mip_count; ++l) {
+        if (l == 1) src = spec;
+        const size_t n = (size_t)6 * size[l] * size[l];
+        for (size_t i = 0; i < n; ++i) host[o + i] = make_float4(src[3 * i], src[3 * i + 1], src[3 * i + 2], 0.0f);
+        o += n;
+        src += 3 * n;
+    }
+    if (set_dev(ctx)) return SHS_ERR_HIP;
+    // a camera pass in flight may still read the levels: finish it before they are overwritten
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->rt_ibl_mips = 0;
+    if (ensure(ctx, ctx->rt_ibl, total)) return SHS_ERR_HIP;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->rt_ibl.p, host.data(), total * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // (the pageable staging is consumed by now)
+    ctx->rt_ibl_mips = mip_count;
+    return SHS_OK;
+}
+
+int shs_rt_ibl_samples(shs_ctx *ctx, int32_t n, const float *dirs3, const float *lod, float *irr_rgb3, float *spec_rgb3) {
+    if (!ctx || n < 0 || (n > 0 && (!dirs3 || !lod || !irr_rgb3 || !spec_rgb3))) return SHS_ERR_INVALID;
+    if (ctx->rt_ibl_mips <= 0) {
+        ctx->err = "shs_rt_ibl_samples: no IBL set (shs_rt_set_ibl)";
+        return SHS_ERR_INVALID;
+    }
+    if (n == 0) return SHS_OK;
+    if (set_dev(ctx)) return SHS_ERR_HIP;
+    const size_t ns = (size_t)n;
+    // the workspace: dirs (3 n), lod (n), irradiance (3 n), specular (3 n)
+    if (ensure(ctx, ctx->rt_is_io, 10 * ns)) return SHS_ERR_HIP;
+    float *io = ctx->rt_is_io.p;
+    HIP_TRY(ctx, hipMemcpyAsync(io, dirs3, 3 * ns * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(io + 3 * ns, lod, ns * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    shs_dev::RtIblSamples q{};
+    q.ibl = ctx->rt_ibl.p;
+    q.ibl_mips = ctx->rt_ibl_mips;
+    q.n = n;
+    q.dirs = io;
+    q.lod = io + 3 * ns;
+    q.irr = io + 4 * ns;
+    q.spec = io + 7 * ns;
+    HIP_TRY(ctx, shs_internal::launch_ibl_samples(q, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(irr_rgb3, q.irr, 3 * ns * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(spec_rgb3, q.spec, 3 * ns * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // (the pageable staging above is consumed by now)
     return SHS_OK;
 }

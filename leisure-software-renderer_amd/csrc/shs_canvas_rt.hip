@@ -11,6 +11,10 @@
 //          The rotations' cos / sin come from a host table (RtParams::rot): the reference takes them from its
 //          libm, which is not correctly rounded, and one ulp can move a tap to another texel.
 //          k_rt_raster<false, 1> differs from k_rt_raster<false, 0> in the shade alone.
+// and for hello_pbr.cpp ("pbr :line"), whose PASS0 / PASS1 rasters (pbr :827-870, :883-1045) are the hard demo's:
+//   shading 2  fragment_shader_pbr (pbr :627-727): Cook-Torrance GGX under the 2x2-PCF shadow, plus image-based
+//          lighting from an irradiance cubemap and a prefiltered-specular mip chain (shs/resources/ibl.hpp:215-286;
+//          RtParams::ibl).  k_rt_raster<false, 2>, launched by shs_rt_render_pbr, again differs in the shade alone.
 //
 // Two kernels per pass, the same two for both (template <bool SHADOW>):
 //   k_rt_setup   one lane per input triangle: the vertex shader once per corner (the reference re-runs it
@@ -580,6 +584,183 @@ __device__ void shade_pixel_soft(const RtParams &p, int32_t id, float u, float v
     pq = make_float4(pr, pg, pb, shadow);
 }
 
+// ---- hello_pbr.cpp: image-based lighting and the GGX fragment shader ("pbr :line") ------------------
+
+// sample_face_bilinear_linear_vec (shs/resources/ibl.hpp:215-234) over a level of the IBL allocation (RtParams::ibl).
+// std::clamp keeps a NaN; (int)std::floor is the x86-64 conversion, so a NaN coordinate reads texel 0 and 1.
+__device__ f3 ibl_sample_face(const float4 *ibl, int first, int size, int face, float u, float v) {
+    u = (u < 0.0f) ? 0.0f : (1.0f < u ? 1.0f : u);
+    v = (v < 0.0f) ? 0.0f : (1.0f < v ? 1.0f : v);
+    const float fx = u * (float)(size - 1);
+    const float fy = v * (float)(size - 1);
+    const int x0 = clampi(int_x86(floorf(fx)), 0, size - 1);
+    const int y0 = clampi(int_x86(floorf(fy)), 0, size - 1);
+    const int x1 = clampi(x0 + 1, 0, size - 1);
+    const int y1 = clampi(y0 + 1, 0, size - 1);
+    const float tx = fx - (float)x0;
+    const float ty = fy - (float)y0;
+    const float4 *f = ibl + first + (size_t)face * size * size;
+    const float4 c00 = f[y0 * size + x0], c10 = f[y0 * size + x1], c01 = f[y1 * size + x0], c11 = f[y1 * size + x1];
+    // glm::mix(x, y, a): x * (1 - a) + y * a
+    const float ux = 1.0f - tx, uy = 1.0f - ty;
+    const f3 cx0 = {c00.x * ux + c10.x * tx, c00.y * ux + c10.y * tx, c00.z * ux + c10.z * tx};
+    const f3 cx1 = {c01.x * ux + c11.x * tx, c01.y * ux + c11.y * tx, c01.z * ux + c11.z * tx};
+    return {cx0.x * uy + cx1.x * ty, cx0.y * uy + cx1.y * ty, cx0.z * uy + cx1.z * ty};
+}
+
+// sample_cubemap_linear_vec (ibl.hpp:236-270) of level `level` (0: irradiance, 1 + m: specular mip m)
+__device__ f3 ibl_sample_cube(const float4 *ibl, int level, f3 d) {
+    const int4 hd = reinterpret_cast<const int4 *>(ibl)[level];   // {first texel, size}
+    const float len = sqrtf(dot3(d, d));
+    if (len < 1e-8f) return {0.0f, 0.0f, 0.0f};
+    d = {d.x / len, d.y / len, d.z / len};
+    const float ax = fabsf(d.x), ay = fabsf(d.y), az = fabsf(d.z);
+    int face;
+    float u, v;
+    if (ax >= ay && ax >= az) {
+        if (d.x > 0.0f) { face = 0; u = -d.z / ax; v = d.y / ax; }
+        else            { face = 1; u = d.z / ax; v = d.y / ax; }
+    } else if (ay >= ax && ay >= az) {
+        if (d.y > 0.0f) { face = 2; u = d.x / ay; v = -d.z / ay; }
+        else            { face = 3; u = d.x / ay; v = d.z / ay; }
+    } else {
+        if (d.z > 0.0f) { face = 4; u = d.x / az; v = d.y / az; }
+        else            { face = 5; u = -d.x / az; v = d.y / az; }
+    }
+    u = 0.5f * (u + 1.0f);
+    v = 0.5f * (v + 1.0f);
+    return ibl_sample_face(ibl, hd.x, hd.y, face, u, v);
+}
+
+// sample_prefiltered_spec_trilinear (ibl.hpp:272-286); a NaN lod passes std::clamp and converts to INT_MIN, whose
+// mip index is clamped here (the reference would index out of its vector)
+__device__ f3 ibl_sample_trilinear(const float4 *ibl, int mips, f3 d, float lod) {
+    const float mmax = (float)(mips - 1);
+    lod = (lod < 0.0f) ? 0.0f : (mmax < lod ? mmax : lod);
+    const int m0 = clampi(int_x86(floorf(lod)), 0, mips - 1);
+    const int m1 = min(m0 + 1, mips - 1);
+    const float t = lod - (float)m0;
+    const f3 c0 = ibl_sample_cube(ibl, 1 + m0, d);
+    const f3 c1 = ibl_sample_cube(ibl, 1 + m1, d);
+    const float s = 1.0f - t;
+    return {c0.x * s + c1.x * t, c0.y * s + c1.y * t, c0.z * s + c1.z * t};
+}
+
+__device__ __forceinline__ float saturate(float v) { return (v < 0.0f) ? 0.0f : (v > 1.0f ? 1.0f : v); }
+
+// The shown fragment of hello_pbr.cpp's camera pass (pbr :986-1035, the hard demo's interpolation and velocity)
+// through fragment_shader_pbr (pbr :627-727): Cook-Torrance GGX under the hard demo's shadow lookup, plus the
+// irradiance and prefiltered-specular IBL.  The direct term is finished before the IBL gathers start.
+__device__ void shade_pixel_pbr(const RtParams &p, int32_t id, float u, float v, float w, uint32_t &rgba, float2 &vel, float4 &pq) {
+    const RtRec &r = p.recs[id];
+    const RtVary &y = p.vary[id];
+    const RtDrawGPU &dr = p.draws[r.draw];
+    const float iw0 = r.iw0, iw1 = r.iw1, iw2 = r.iw2;
+    const float invw_sum = (u * iw0 + v * iw1) + w * iw2;
+    {   // velocity (pbr :1017-1026)
+        float pos[4], prev[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            pos[k] = (u * y.pos[k] + v * y.pos[4 + k]) + w * y.pos[8 + k];
+            prev[k] = (u * y.prev[k] + v * y.prev[4 + k]) + w * y.prev[8 + k];
+        }
+        float csx, csy, psx, psy;
+        to_screen(p, pos[0], pos[1], pos[3], csx, csy);
+        to_screen(p, prev[0], prev[1], prev[3], psx, psy);
+        float vx = csx - psx, vy = -(csy - psy);
+        const float len = sqrtf(vx * vx + vy * vy);
+        if (len > p.max_velocity && len > 1e-6f) {
+            const float s = p.max_velocity / len;
+            vx *= s;
+            vy *= s;
+        }
+        vel = make_float2(vx, vy);
+    }
+    const f3 nsum = {(u * y.nrm[0] + v * y.nrm[3]) + w * y.nrm[6], (u * y.nrm[1] + v * y.nrm[4]) + w * y.nrm[7],
+                     (u * y.nrm[2] + v * y.nrm[5]) + w * y.nrm[8]};
+    const f3 in_normal = normalize3(nsum);
+    f3 wp;
+    wp.x = ((u * (y.world[0] * iw0) + v * (y.world[3] * iw1)) + w * (y.world[6] * iw2)) / invw_sum;
+    wp.y = ((u * (y.world[1] * iw0) + v * (y.world[4] * iw1)) + w * (y.world[7] * iw2)) / invw_sum;
+    wp.z = ((u * (y.world[2] * iw0) + v * (y.world[5] * iw1)) + w * (y.world[8] * iw2)) / invw_sum;
+    const f3 N = normalize3(in_normal);
+    const f3 V = normalize3(sub3(f3{p.cam[0], p.cam[1], p.cam[2]}, wp));
+    const f3 L = {p.L[0], p.L[1], p.L[2]};
+    const f3 H = normalize3(add3(V, L));
+    const float ndotl = dot3(N, L);
+    const float NoV = g_max(0.0f, dot3(N, V)), NoL = g_max(0.0f, ndotl), NoH = g_max(0.0f, dot3(N, H));
+    const float4 m0 = reinterpret_cast<const float4 *>(&p.pbr_draws[r.draw])[0];   // base rgb, metallic
+    const float4 m1 = reinterpret_cast<const float4 *>(&p.pbr_draws[r.draw])[1];   // roughness, ao, ibl diffuse, ibl specular
+    f3 base = {m0.x, m0.y, m0.z};
+    if (dr.texels) {
+        // sample_nearest_srgb = sample_nearest (shs_renderer.hpp:367-381), then srgb_to_linear of the bytes
+        const float tu = ((u * (y.uv[0] * iw0) + v * (y.uv[2] * iw1)) + w * (y.uv[4] * iw2)) / invw_sum;
+        const float tv = ((u * (y.uv[1] * iw0) + v * (y.uv[3] * iw1)) + w * (y.uv[5] * iw2)) / invw_sum;
+        const float su = saturate(tu), sv = saturate(tv);
+        const int x = clampi(lround_x86(su * (float)(dr.tw - 1)), 0, dr.tw - 1);
+        const int yy = clampi(lround_x86(sv * (float)(dr.th - 1)), 0, dr.th - 1);
+        const uint32_t tc = dr.texels[(size_t)yy * dr.tw + x];
+        base = f3{p.srgb_lut[tc & 0xffu], p.srgb_lut[(tc >> 8) & 0xffu], p.srgb_lut[(tc >> 16) & 0xffu]};
+    }
+    const float metallic = m0.w, roughness = m1.x, ao = m1.y;
+    const float om = 1.0f - metallic;
+    const f3 F0 = {0.04f * om + base.x * metallic, 0.04f * om + base.y * metallic, 0.04f * om + base.z * metallic};
+    // fresnel_schlick (pbr :242-249), then the blue attenuation
+    const float fx = 1.0f - saturate(NoV);
+    const float fx2 = fx * fx;
+    const float fx5 = fx2 * fx2 * fx;
+    const f3 Fr = {(F0.x + (1.0f - F0.x) * fx5) * 1.0f, (F0.y + (1.0f - F0.y) * fx5) * 0.96f, (F0.z + (1.0f - F0.z) * fx5) * 0.90f};
+    const f3 kd = {(1.0f - Fr.x) * om, (1.0f - Fr.y) * om, (1.0f - Fr.z) * om};
+    // ndf_ggx (:251-257), g_smith over g_schlick_ggx (:259-277; its second clamp of the roughness changes nothing)
+    const float PI = 3.14159265358979323846f;
+    const float alpha = roughness * roughness;
+    const float sh = saturate(NoH);
+    const float a2 = alpha * alpha;
+    const float dd = (sh * sh) * (a2 - 1.0f) + 1.0f;
+    const float D = a2 / (PI * dd * dd);
+    const float r1 = roughness + 1.0f;
+    const float k = (r1 * r1) / 8.0f;
+    const float sv_ = saturate(NoV), sl_ = saturate(NoL);
+    const float G = (sv_ / (sv_ * (1.0f - k) + k)) * (sl_ / (sl_ * (1.0f - k) + k));
+    const float DG = D * G;
+    const float den = g_max(1e-6f, 4.0f * NoV * NoL);
+    float shadow = 1.0f;
+    if (p.shadow) shadow = shadow_factor(p, wp, ndotl);
+    f3 c;
+    {
+        const float ipi = 1.0f / PI;
+        const float I = p.pbr_intensity;
+        c.x = ((((kd.x * base.x) * ipi + (DG * Fr.x) / den) * I) * NoL) * shadow;
+        c.y = ((((kd.y * base.y) * ipi + (DG * Fr.y) / den) * I) * NoL) * shadow;
+        c.z = ((((kd.z * base.z) * ipi + (DG * Fr.z) / den) * I) * NoL) * shadow;
+    }
+    f3 ibl = {0.0f, 0.0f, 0.0f};
+    if (p.ibl) {
+        const f3 irr = ibl_sample_cube(p.ibl, 0, N);
+        // glm::reflect(-V, N): I - N * dot(N, I) * 2
+        const f3 I = {-V.x, -V.y, -V.z};
+        const float ni = dot3(N, I);
+        const f3 R = {I.x - N.x * ni * 2.0f, I.y - N.y * ni * 2.0f, I.z - N.z * ni * 2.0f};
+        const float lod = roughness * (float)(p.ibl_mips - 1);
+        const f3 pre = ibl_sample_trilinear(p.ibl, p.ibl_mips, R, lod);
+        ibl.x = ((irr.x * base.x) * kd.x) * m1.z + (pre.x * Fr.x) * m1.w;
+        ibl.y = ((irr.y * base.y) * kd.y) * m1.z + (pre.y * Fr.y) * m1.w;
+        ibl.z = ((irr.z * base.z) * kd.z) * m1.z + (pre.z * Fr.z) * m1.w;
+    }
+    float out[3] = {c.x + ibl.x * ao, c.y + ibl.y * ao, c.z + ibl.z * ao};
+    const float bs[3] = {base.x, base.y, base.z};
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        float x = out[i] + (bs[i] * 0.03f) * ao;   // the minimum ambient
+        x = x * p.pbr_exposure;
+        x = x / (1.0f + x);                        // tonemap_reinhard
+        x = powf(g_clamp01(x), 1.0f / 2.2f);       // linear_to_srgb
+        out[i] = g_clamp01(x) * 255.0f;            // rgb01_to_color
+    }
+    rgba = byte_x86(out[0]) | (byte_x86(out[1]) << 8) | (byte_x86(out[2]) << 16) | 0xff000000u;
+    pq = make_float4(out[0], out[1], out[2], shadow);
+}
+
 // SHADING: shs_rt_frame::shading of the camera pass, a compile-time choice (the shadow pass ignores it)
 template <bool SHADOW, int SHADING = 0>
 __global__ __launch_bounds__(256) void k_rt_raster(const RtParams p) {
@@ -676,6 +857,8 @@ __global__ __launch_bounds__(256) void k_rt_raster(const RtParams p) {
     float4 pq = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     if constexpr (SHADING == 1) {
         if (sid >= 0) shade_pixel_soft(p, sid, su, sv, sw, px, py, rgba, pq);   // the velocity plane stays zero
+    } else if constexpr (SHADING == 2) {
+        if (sid >= 0) shade_pixel_pbr(p, sid, su, sv, sw, rgba, vel, pq);
     } else {
         if (sid >= 0) shade_pixel(p, sid, su, sv, sw, rgba, vel, pq);
     }
@@ -695,6 +878,17 @@ __global__ __launch_bounds__(256) void k_rt_pcss_samples(const RtPcssSamples q) 
     q.out[i] = pcss_shadow_factor(m, q.uv[2 * i], q.uv[2 * i + 1], q.z[i], q.bias[i], q.rot[i]);
 }
 
+// shs_rt_ibl_samples: one lane per direction through the device functions the raster calls
+__global__ __launch_bounds__(256) void k_rt_ibl_samples(const RtIblSamples q) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= q.n) return;
+    const f3 d = {q.dirs[3 * i], q.dirs[3 * i + 1], q.dirs[3 * i + 2]};
+    const f3 a = ibl_sample_cube(q.ibl, 0, d);
+    const f3 b = ibl_sample_trilinear(q.ibl, q.ibl_mips, d, q.lod[i]);
+    q.irr[3 * i] = a.x; q.irr[3 * i + 1] = a.y; q.irr[3 * i + 2] = a.z;
+    q.spec[3 * i] = b.x; q.spec[3 * i + 1] = b.y; q.spec[3 * i + 2] = b.z;
+}
+
 }  // namespace
 }  // namespace shs_dev
 
@@ -703,6 +897,12 @@ namespace shs_internal {
 hipError_t launch_pcss_samples(const shs_dev::RtPcssSamples &q, hipStream_t s) {
     if (q.n <= 0) return hipSuccess;
     hipLaunchKernelGGL(shs_dev::k_rt_pcss_samples, dim3((q.n + 255) / 256), dim3(256), 0, s, q);
+    return hipGetLastError();
+}
+
+hipError_t launch_ibl_samples(const shs_dev::RtIblSamples &q, hipStream_t s) {
+    if (q.n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(shs_dev::k_rt_ibl_samples, dim3((q.n + 255) / 256), dim3(256), 0, s, q);
     return hipGetLastError();
 }
 
@@ -718,6 +918,7 @@ hipError_t launch_canvas_rt(const shs_dev::RtParams &p, bool shadow_pass, int sh
     const int tiles = ((p.W + RT_TW - 1) / RT_TW) * ((p.H + RT_TH - 1) / RT_TH);
     if (shadow_pass) hipLaunchKernelGGL(k_rt_raster<true>, dim3(tiles), dim3(256), 0, s, p);
     else if (shading == 1) hipLaunchKernelGGL((k_rt_raster<false, 1>), dim3(tiles), dim3(256), 0, s, p);
+    else if (shading == 2) hipLaunchKernelGGL((k_rt_raster<false, 2>), dim3(tiles), dim3(256), 0, s, p);
     else hipLaunchKernelGGL(k_rt_raster<false>, dim3(tiles), dim3(256), 0, s, p);
     return hipGetLastError();
 }

@@ -1,6 +1,7 @@
 // shs_canvas_rt_internal.hpp -- launch interface of shs_canvas_rt.hip: the Canvas render-target raster of
 // hello-render-target/hello_shadow_mapping.cpp (shadow pass and shadowed camera pass; include/shs_gpu.h) and
-// of hello_shadow_mapping_soft.cpp (the same passes with the PCSS fragment shader, shs_rt_frame::shading 1).
+// of hello_shadow_mapping_soft.cpp (the same passes with the PCSS fragment shader, shs_rt_frame::shading 1) and
+// hello_pbr.cpp (the same passes with the GGX + IBL fragment shader, shading 2 through shs_rt_render_pbr).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -50,6 +51,24 @@ struct RtDrawGPU {
     float colf[4];                   // (float)base_color.rgb
 };
 
+// The per-draw part of hello_pbr.cpp's Uniforms that fragment_shader_pbr reads (:474-482, :516-518), after the
+// per-draw operations the host has done: 32 B, two dwordx4 loads of a shaded pixel.
+struct alignas(16) RtPbrDrawGPU {
+    float base[3];                   // srgb_to_linear(color_to_rgb01(baseColor_srgb)): three table entries
+    float metallic;                  // saturate(mat.metallic)
+    float roughness;                 // clampf(mat.roughness, min_roughness, 1)
+    float ao;                        // saturate(mat.ao)
+    float ibl_diffuse;               // saturate(ibl_diffuse_intensity)
+    float ibl_specular;              // saturate(ibl_specular_intensity) * saturate(ibl_reflection_strength)
+};
+static_assert(sizeof(RtPbrDrawGPU) == 32, "RtPbrDrawGPU: two float4s");
+
+// The EnvIBL levels (shs/resources/ibl.hpp:21-59) in one allocation of float4s: RT_IBL_LEVELS headers, then the
+// texels, rgb padded to 16 B so that a bilinear corner is one dwordx4 load.  Header l holds, as int bits,
+// {first texel, size}: level 0 is env_irradiance, level 1 + m is env_prefiltered_spec.mip[m].  Face f of a level
+// starts size * size * f texels after its first; texel (x, y) of a face is at y * size + x.
+constexpr int RT_IBL_LEVELS = 17;
+
 constexpr int RT_TW = 32, RT_TH = 8;     // raster tile: one 256-thread workgroup, one pixel per lane
 constexpr int RT_CHUNK = 256;            // records examined (and at most staged in LDS) per round
 
@@ -76,6 +95,22 @@ struct RtParams {
     const float4 *rot;               // per screen pixel py * W + px: {cos(ang), sin(ang), cos(ang2), sin(ang2)}
     float pcss_light, pcss_search, pcss_min, pcss_max, pcss_eps;   // shs_rt_pcss
     int32_t pcss_blockers, pcss_taps;
+    // shading 2 only (appended likewise)
+    const RtPbrDrawGPU *pbr_draws;   // element i goes with draws[i]
+    const float *srgb_lut;           // 256 floats: pow(c / 255, 2.2) with the host's libm
+    const float4 *ibl;               // the levels above, or null: u.ibl == nullptr
+    int32_t ibl_mips;                // env_prefiltered_spec.mip_count()
+    float pbr_exposure, pbr_intensity;   // shs_rt_pbr (min_roughness is folded into RtPbrDrawGPU::roughness)
+};
+
+// sample_cubemap_linear_vec(env_irradiance, dir) and sample_prefiltered_spec_trilinear(spec, dir, lod) for a list
+// of directions (shs_rt_ibl_samples): everything on the device
+struct RtIblSamples {
+    const float4 *ibl;
+    int32_t ibl_mips, n;
+    const float *dirs;               // 3 n
+    const float *lod;                // n
+    float *irr, *spec;               // 3 n each
 };
 
 // pcss_shadow_factor for a list of samples (shs_rt_pcss_samples): everything on the device
@@ -94,7 +129,9 @@ struct RtPcssSamples {
 
 namespace shs_internal {
 // setup (one lane per input triangle) then raster (one workgroup per 32x8 tile) of either pass
-// shading: shs_rt_frame::shading of the camera pass (0: fragment_shader_full, 1: fragment_shader_softshadow)
+// shading: shs_rt_frame::shading of the camera pass (0: fragment_shader_full, 1: fragment_shader_softshadow,
+// 2: fragment_shader_pbr)
 hipError_t launch_canvas_rt(const shs_dev::RtParams &p, bool shadow_pass, int shading, hipStream_t s);
 hipError_t launch_pcss_samples(const shs_dev::RtPcssSamples &q, hipStream_t s);
+hipError_t launch_ibl_samples(const shs_dev::RtIblSamples &q, hipStream_t s);
 }  // namespace shs_internal

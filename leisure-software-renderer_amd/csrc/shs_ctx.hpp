@@ -366,6 +366,14 @@ struct shs_ctx {
     DevBuf<float4> rt_rot, rt_ps_rot;
     DevBuf<float> rt_ps_map, rt_ps_io;
     int rt_rot_w = 0, rt_rot_h = 0;
+    // shading 2 (hello_pbr.cpp): the shader's constants (shs_rt_set_pbr; the demo's by default), the IBL levels of
+    // shs_rt_set_ibl (rt_ibl_mips 0: none), the sRGB -> linear table and the workspace of shs_rt_ibl_samples
+    shs_rt_pbr rt_pbr = {1.75f, 0.04f, 3.0f};
+    DevBuf<float4> rt_ibl;
+    int rt_ibl_mips = 0;
+    DevBuf<float> rt_srgb_lut, rt_is_io;
+    bool rt_have_lut = false;
+    std::vector<shs_dev::RtPbrDrawGPU> rt_h_pbr;
 };
 
 // Re-enqueues the tonemap after lib_finish re-issued the camera pass (shs_abi_post.cpp).

@@ -18,7 +18,7 @@ from ._abi import (FRAME_PREQUANT, FRAME_PRESENT, SHADING_BLINN_PHONG, SHADING_D
                    SHADING_TOON, FrameDesc, LegacyDraw, RasterStats)
 
 __all__ = [
-    "ShsError", "Context", "Frame", "Draw", "RtFrame", "RtDraw", "RtPcss", "SHADING_FLAT", "SHADING_GOURAUD", "SHADING_PHONG",
+    "ShsError", "Context", "Frame", "Draw", "RtFrame", "RtDraw", "RtPcss", "RtPbrDraw", "RtPbr", "SHADING_FLAT", "SHADING_GOURAUD", "SHADING_PHONG",
     "SHADING_BLINN_PHONG", "SHADING_TOON", "SHADING_GOOCH", "SHADING_OREN_NAYAR", "SHADING_NORMAL_VIS",
     "SHADING_DEPTH_VIS", "SHADING_TEXTURED", "SHADING_NAMES", "FRAME_PREQUANT", "lib",
 ]
@@ -105,7 +105,8 @@ class RtFrame:
     use_shadow: bool = True
     pcf: bool = True
     prequant: bool = False
-    shading: int = 0             # 0: fragment_shader_full, 1: fragment_shader_softshadow (PCSS; Context.rt_set_pcss)
+    shading: int = 0             # 0: fragment_shader_full, 1: fragment_shader_softshadow (PCSS; Context.rt_set_pcss),
+                                 # 2: fragment_shader_pbr (Context.rt_render_pbr only)
 
 
 @dataclass
@@ -118,6 +119,27 @@ class RtPcss:
     epsilon: float = 1e-5
     blocker_samples: int = 12
     pcf_samples: int = 24
+
+
+@dataclass
+class RtPbrDraw:
+    """hello_pbr.cpp's per-object uniforms beside an RtDraw (shs_rt_pbr_draw); the defaults are MaterialPBR's and
+    Uniforms'.  normal_mat: float32[9], column-major mat3, as the demo supplies it (None: mat3(1))."""
+    normal_mat: np.ndarray = None
+    metallic: float = 0.0
+    roughness: float = 0.5
+    ao: float = 1.0
+    ibl_diffuse_intensity: float = 0.30
+    ibl_specular_intensity: float = 0.35
+    ibl_reflection_strength: float = 1.00
+
+
+@dataclass
+class RtPbr:
+    """The constants of fragment_shader_pbr (shs_rt_pbr); the defaults are hello_pbr.cpp's."""
+    exposure: float = 1.75
+    min_roughness: float = 0.04
+    direct_intensity: float = 3.0
 
 
 class Context:
@@ -661,6 +683,11 @@ class Context:
 
     def rt_render(self, frame, draws):
         """shs_rt_render: PASS1 (colour, view-z depth, velocity; the shadow lookup), asynchronous."""
+        arr = self._rt_draw_array(draws)
+        self._check(self._lib.shs_rt_render(self._h, ctypes.byref(self._rt_frame_c(frame)), arr, len(draws)))
+        self._rt_size = (frame.width, frame.height)
+
+    def _rt_frame_c(self, frame):
         f = _abi.RtFrameC()
         f.width, f.height = frame.width, frame.height
         f.ref_tile_w, f.ref_tile_h = frame.ref_tile
@@ -674,9 +701,56 @@ class Context:
         f.flags = (_abi.RT_USE_SHADOW if frame.use_shadow else 0) | (_abi.RT_PCF if frame.pcf else 0) | \
                   (_abi.RT_PREQUANT if frame.prequant else 0)
         f.shading = int(frame.shading)
+        return f
+
+    def rt_render_pbr(self, frame, draws, pbr_draws):
+        """shs_rt_render_pbr: PASS1 of hello_pbr.cpp (frame.shading 2; pbr_draws: one RtPbrDraw per draw), asynchronous."""
+        if len(pbr_draws) != len(draws):
+            raise ShsError(-1, "rt_render_pbr: one RtPbrDraw per draw")
         arr = self._rt_draw_array(draws)
-        self._check(self._lib.shs_rt_render(self._h, ctypes.byref(f), arr, len(draws)))
+        mat = (_abi.RtPbrDrawC * max(len(draws), 1))()
+        for i, m in enumerate(pbr_draws):
+            n3 = np.eye(3, dtype=np.float32).reshape(9) if m.normal_mat is None else np.asarray(m.normal_mat, np.float32).reshape(9)
+            mat[i].normal_mat[:] = [float(v) for v in n3]
+            for name in ("metallic", "roughness", "ao", "ibl_diffuse_intensity", "ibl_specular_intensity", "ibl_reflection_strength"):
+                setattr(mat[i], name, float(getattr(m, name)))
+        self._check(self._lib.shs_rt_render_pbr(self._h, ctypes.byref(self._rt_frame_c(frame)), arr, mat, len(draws)))
         self._rt_size = (frame.width, frame.height)
+
+    def rt_set_pbr(self, pbr=None):
+        """shs_rt_set_pbr: the constants of shading 2 (an RtPbr; None: the demo's)."""
+        if pbr is None:
+            self._check(self._lib.shs_rt_set_pbr(self._h, None))
+            return
+        c = _abi.RtPbrC(pbr.exposure, pbr.min_roughness, pbr.direct_intensity)
+        self._check(self._lib.shs_rt_set_pbr(self._h, ctypes.byref(c)))
+
+    def rt_set_ibl(self, irr=None, spec_mips=None):
+        """shs_rt_set_ibl: irr float32 [6, n, n, 3] and spec_mips a list of [6, s_m, s_m, 3] with
+        s_m = max(1, s_0 >> m); irr None: no IBL.  Synchronous."""
+        if irr is None:
+            self._check(self._lib.shs_rt_set_ibl(self._h, 0, None, 0, 0, None))
+            return
+        irr = np.ascontiguousarray(irr, np.float32)
+        mips = [np.ascontiguousarray(m, np.float32) for m in spec_mips]
+        base = mips[0].shape[1] if mips else 0
+        for m, a in enumerate([irr] + mips):
+            want = irr.shape[1] if m == 0 else max(1, base >> (m - 1))
+            if a.ndim != 4 or a.shape != (6, want, want, 3):
+                raise ShsError(-1, f"rt_set_ibl: level {m} has shape {a.shape}")
+        spec = np.concatenate([m.reshape(-1) for m in mips]) if mips else np.zeros(0, np.float32)
+        one = np.zeros(1, np.float32)       # (an empty level still goes down as a pointer: the library rejects the size)
+        self._check(self._lib.shs_rt_set_ibl(self._h, irr.shape[1], _ptr(irr if irr.size else one), base, len(mips),
+                                             _ptr(spec if spec.size else one)))
+
+    def rt_ibl_samples(self, dirs, lod):
+        """shs_rt_ibl_samples: (irradiance at dir, trilinear prefiltered specular at (dir, lod)) -> two float32 [n, 3]."""
+        dirs = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        n = dirs.shape[0]
+        lod = np.ascontiguousarray(lod, np.float32).reshape(n)
+        a, b = np.empty((n, 3), np.float32), np.empty((n, 3), np.float32)
+        self._check(self._lib.shs_rt_ibl_samples(self._h, n, _ptr(dirs), _ptr(lod), _ptr(a), _ptr(b)))
+        return a, b
 
     def rt_set_pcss(self, pcss=None):
         """shs_rt_set_pcss: the PCSS constants of shading 1 (an RtPcss; None: the demo's)."""

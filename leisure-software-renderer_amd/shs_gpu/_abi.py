@@ -236,6 +236,18 @@ class RtPcssC(ctypes.Structure):
                 ("blocker_samples", ctypes.c_int32), ("pcf_samples", ctypes.c_int32)]
 
 
+class RtPbrDrawC(ctypes.Structure):
+    """shs_rt_pbr_draw: hello_pbr.cpp's per-object uniforms beside shs_rt_draw."""
+    _fields_ = [("normal_mat", ctypes.c_float * 9), ("metallic", ctypes.c_float), ("roughness", ctypes.c_float),
+                ("ao", ctypes.c_float), ("ibl_diffuse_intensity", ctypes.c_float), ("ibl_specular_intensity", ctypes.c_float),
+                ("ibl_reflection_strength", ctypes.c_float)]
+
+
+class RtPbrC(ctypes.Structure):
+    """shs_rt_pbr: the constants of fragment_shader_pbr."""
+    _fields_ = [("exposure", ctypes.c_float), ("min_roughness", ctypes.c_float), ("direct_intensity", ctypes.c_float)]
+
+
 class RtStatsC(ctypes.Structure):
     _fields_ = [("input_tris", ctypes.c_int64), ("polys3", ctypes.c_int64), ("polys4", ctypes.c_int64),
                 ("sub_tris", ctypes.c_int64)]
@@ -351,6 +363,11 @@ SIGNATURES = [
     ("shs_rt_render", ctypes.c_int, [_P, ctypes.POINTER(RtFrameC), ctypes.POINTER(RtDrawC), ctypes.c_int32]),
     ("shs_rt_set_pcss", ctypes.c_int, [_P, ctypes.POINTER(RtPcssC)]),
     ("shs_rt_pcss_samples", ctypes.c_int, [_P, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P, _P]),
+    ("shs_rt_set_pbr", ctypes.c_int, [_P, ctypes.POINTER(RtPbrC)]),
+    ("shs_rt_set_ibl", ctypes.c_int, [_P, ctypes.c_int32, _P, ctypes.c_int32, ctypes.c_int32, _P]),
+    ("shs_rt_render_pbr", ctypes.c_int, [_P, ctypes.POINTER(RtFrameC), ctypes.POINTER(RtDrawC), ctypes.POINTER(RtPbrDrawC),
+                                         ctypes.c_int32]),
+    ("shs_rt_ibl_samples", ctypes.c_int, [_P, ctypes.c_int32, _P, _P, _P, _P]),
     ("shs_rt_resolve", ctypes.c_int, [_P, _P, _P, _P]),
     ("shs_rt_resolve_shadow", ctypes.c_int, [_P, _P]),
     ("shs_rt_resolve_prequant", ctypes.c_int, [_P, _P]),
