@@ -846,9 +846,8 @@ int shs_canvas_dof(shs_ctx *ctx, const shs_canvas_dof_desc *desc, uint8_t *color
  *      its PASS2 is shs_canvas_motion_blur over shs_rt_device_targets.  Cook-Torrance GGX under the shadow
  *      lookup of shading 0 (SHS_RT_USE_SHADOW, SHS_RT_PCF, bias_base, bias_slope), plus image-based lighting
  *      from the EnvIBL of shs_rt_set_ibl; Reinhard tonemap and gamma 2.2 to bytes.  The velocity plane is
- *      written as for shading 0.  Not built: skybox_background_pass (:733-799) -- uncovered pixels keep
- *      clear_color -- and the IBL precompute, which stays on the host (its results come in through
- *      shs_rt_set_ibl). */
+ *      written as for shading 0.  Its skybox_background_pass (:733-799) is shs_rt_set_sky below.  Not built: the
+ *      IBL precompute, which stays on the host (its results come in through shs_rt_set_ibl). */
 typedef struct shs_rt_draw {
     int32_t mesh_id;            /* shs_mesh_upload_soup[_uv] soup (without UVs: vec2(0) per corner) */
     int32_t albedo_tex;         /* shs_texture_upload id (use_texture), 0: base_color */
@@ -947,6 +946,40 @@ int shs_rt_render_pbr(shs_ctx *ctx, const shs_rt_frame *frame, const shs_rt_draw
  * (ibl.hpp:236-286) of the context's IBL for n directions through the device functions the raster calls: dirs3
  * 3n, lod n, both outputs 3n.  Synchronous; for tests of the edge cases.  SHS_ERR_INVALID without an IBL. */
 int shs_rt_ibl_samples(shs_ctx *ctx, int32_t n, const float *dirs3, const float *lod, float *irr_rgb3, float *spec_rgb3);
+/* skybox_background_pass (hello_pbr.cpp:733-799; the same routine in hello_pbr_light_shafts.cpp:856-921 and
+ * hello_ibl_skybox.cpp:532-611) over the legacy AbstractSky models of hello-shs-renderer/shs_renderer.hpp: AnalyticSky
+ * (:552-611) and CubeMapSky with sample_face_bilinear (:432-517).  (These are not the library path's ProceduralSky /
+ * CubemapSky of shs_lib_set_sky; the legacy ProceduralSky :520-549 is not built: no render-target demo constructs it.)
+ * The reference draws the sky first and the triangles over it.  Here, with a sky bound, every camera pass
+ * (shs_rt_render, shs_rt_render_pbr, whatever the shading) is followed on the context stream by a background pass
+ * that colours each pixel that shows no fragment (shs_rt_resolve_ids: -1) -- also one whose fragment kept its depth
+ * but not its colour -- from the direction through the pixel's centre (:769-780; canvas x, y with y up).  Such a
+ * pixel's prequant floats are (r, g, b) * 255 before the truncation and 1; depth and velocity stay as the raster
+ * left them. */
+#define SHS_RT_SKY_NONE 0
+#define SHS_RT_SKY_ANALYTIC 1
+#define SHS_RT_SKY_CUBEMAP 2
+#define SHS_RT_SKY_ENCODE_REINHARD 0   /* * exposure, x / (1 + x), linear_to_srgb, rgb01_to_color (hello_pbr.cpp:785-789) */
+#define SHS_RT_SKY_ENCODE_CLAMP 1      /* clamp(c, 0, 1), linear_to_srgb, rgb01_to_color (hello_ibl_skybox.cpp:598-601) */
+typedef struct shs_rt_sky {
+    int32_t model, encode;       /* SHS_RT_SKY_*, SHS_RT_SKY_ENCODE_* */
+    float sun_dir[3];            /* AnalyticSky::sun_direction */
+    float intensity;             /* CubeMapSky::intensity_ */
+    int32_t face_tex[6];         /* +X -X +Y -Y +Z -Z, shs_texture_upload ids (any sizes, not necessarily square) */
+    float cam_forward[3], cam_right[3], cam_up[3];   /* Camera3D vectors, normalised by the host as the pass does */
+    float fov_degrees;           /* cam.field_of_view */
+    float exposure;              /* SKY_EXPOSURE 1.85 */
+} shs_rt_sky;
+/* NULL or SHS_RT_SKY_NONE: no sky, also the default: uncovered pixels keep clear_color.  Kept in the context for every
+ * later camera pass; no device work, cheap enough to call per frame as the camera moves.  SHS_ERR_INVALID (the
+ * context keeps what it had): an unknown model or encode, a non-finite float, a camera vector (or, for the analytic
+ * model, sun direction) that cannot be normalised, an unknown face id.  shs_texture_release of a face of the bound
+ * sky fails with SHS_ERR_INVALID: set another sky first. */
+int shs_rt_set_sky(shs_ctx *ctx, const shs_rt_sky *sky);
+/* sky.sample(dir), the linear radiance, of the bound sky for n directions through the device function the
+ * background pass calls: dirs3 and rgb3 3n.  Synchronous; for tests of the edge cases.  SHS_ERR_INVALID without a
+ * sky. */
+int shs_rt_sky_samples(shs_ctx *ctx, int32_t n, const float *dirs3, float *rgb3);
 /* ortho_lh_zo (hello_shadow_mapping.cpp:128-140): LH, z in [0, 1]. */
 int shs_ortho_lh_zo(float left, float right, float bottom, float top, float znear, float zfar, float out16[16]);
 

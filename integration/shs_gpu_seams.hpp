@@ -332,8 +332,9 @@ private:
 // hard demo's raster (draw_triangle_tile_color_depth_motion :883-1045) with fragment_shader_pbr (:627-727) through
 // shs_rt_render_pbr and shading = 2, PASS2 combined_motion_blur_pass (:1051-1252) through shs_canvas_motion_blur over
 // shs_rt_device_targets.  The IBL precompute (:1855-1875) stays on the host at start-up; set_ibl hands its results
-// over once.  skybox_background_pass (:733-799) is not built: uncovered pixels keep the clear colour.  Uncompiled,
-// like the other seams.
+// over once.  skybox_background_pass (:733-799) is set_sky: the legacy AnalyticSky / CubeMapSky behind the triangles,
+// bound per frame with the camera's vectors (shs_rt_set_sky does no device work); without it uncovered pixels keep the
+// clear colour.  Uncompiled, like the other seams.
 // -----------------------------------------------------------------------------------------------------
 template <class SceneT>
 class PbrSystemGPU : public shs::AbstractSystem {
@@ -363,6 +364,24 @@ public:
         ok(shs_rt_set_ibl(dev_->ctx, ibl.env_irradiance.size, irr.data(), ibl.env_prefiltered_spec.mip[0].size,
                           ibl.env_prefiltered_spec.mip_count(), spec.data()));
     }
+
+    // skybox_background_pass (:733-799) of the demo's AnalyticSky through this frame's camera; call it before process().
+    // A CubeMapSky host (hello_ibl_skybox.cpp:532-611) fills model = SHS_RT_SKY_CUBEMAP, encode = SHS_RT_SKY_ENCODE_CLAMP,
+    // intensity and the six faces' shs_texture_upload ids instead.
+    void set_sky(const glm::vec3 &sun_direction, float sky_exposure = 1.85f) {
+        const shs::Camera3D &cam = *scene_->viewer->camera;
+        shs_rt_sky s{};
+        s.model = SHS_RT_SKY_ANALYTIC;
+        s.encode = SHS_RT_SKY_ENCODE_REINHARD;
+        std::memcpy(s.sun_dir, glm::value_ptr(sun_direction), 12);
+        std::memcpy(s.cam_forward, glm::value_ptr(cam.direction_vector), 12);
+        std::memcpy(s.cam_right, glm::value_ptr(cam.right_vector), 12);
+        std::memcpy(s.cam_up, glm::value_ptr(cam.up_vector), 12);
+        s.fov_degrees = cam.field_of_view;
+        s.exposure = sky_exposure;
+        ok(shs_rt_set_sky(dev_->ctx, &s));
+    }
+    void clear_sky() { ok(shs_rt_set_sky(dev_->ctx, nullptr)); }
 
     void process(float) override {
         shs::Canvas &canvas = *scene_->canvas;

@@ -101,7 +101,7 @@ int shs_destroy(shs_ctx *ctx) {
     release(ctx->rt_draws); release(ctx->rt_recs); release(ctx->rt_vary); release(ctx->rt_stats); release(ctx->rt_color);
     release(ctx->rt_depth); release(ctx->rt_vel); release(ctx->rt_shadow); release(ctx->rt_pq); release(ctx->rt_ids);
     release(ctx->rt_rot); release(ctx->rt_ps_rot); release(ctx->rt_ps_map); release(ctx->rt_ps_io);
-    release(ctx->rt_ibl); release(ctx->rt_srgb_lut); release(ctx->rt_is_io);
+    release(ctx->rt_ibl); release(ctx->rt_srgb_lut); release(ctx->rt_is_io); release(ctx->rt_sky_io);
     for (int k = 0; k < 2; ++k) {
         if (ctx->rt_pin[k]) (void)hipHostFree(ctx->rt_pin[k]);
         if (ctx->rt_pin_ev[k]) (void)hipEventDestroy(ctx->rt_pin_ev[k]);

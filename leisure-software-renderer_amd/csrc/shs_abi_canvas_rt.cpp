@@ -7,7 +7,10 @@
 // constants :101-116), shs_rt_pcss_samples (pcss_shadow_factor :333-445 alone) and the per-pixel rotation table.
 // and of hello_pbr.cpp ("pbr :line"): shs_rt_render_pbr (its PASS1, pbr :883-1045 with fragment_shader_pbr :627-727),
 // shs_rt_set_pbr (the constants pbr :150-155), shs_rt_set_ibl (EnvIBL, shs/resources/ibl.hpp:21-59) and
-// shs_rt_ibl_samples (the two IBL samplers alone, ibl.hpp:215-286).
+// shs_rt_ibl_samples (the two IBL samplers alone, ibl.hpp:215-286);
+// and the background of hello_pbr.cpp, hello_pbr_light_shafts.cpp and hello_ibl_skybox.cpp: shs_rt_set_sky
+// (skybox_background_pass pbr :733-799 over AnalyticSky / CubeMapSky, hello-shs-renderer/shs_renderer.hpp:432-611; the
+// host does what depends on the sun direction and the camera alone) and shs_rt_sky_samples (sky.sample alone).
 // The host forms the matrix products the shaders form first -- u.view * u.model (vertex_shader_full :616),
 // u.light_vp * u.model (shadow_vertex_shader :764) -- and the normal matrix with the GLM restatement in
 // shs_glm.hpp.  Both passes are enqueued on the context stream; the shadow map, the planes and the records
@@ -39,6 +42,16 @@ const float *srgb_table() {
     };
     static const Lut lut;
     return lut.v;
+}
+
+// The table on the device (shading 2's base colours, the cubemap sky's texels): uploaded once per context.
+int ensure_srgb_table(shs_ctx *ctx) {
+    if (ctx->rt_have_lut) return SHS_OK;
+    if (ensure(ctx, ctx->rt_srgb_lut, 256)) return SHS_ERR_HIP;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->rt_srgb_lut.p, srgb_table(), 256 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->rt_have_lut = true;
+    return SHS_OK;
 }
 
 float saturate(float v) { return (v < 0.0f) ? 0.0f : (v > 1.0f ? 1.0f : v); }
@@ -254,19 +267,34 @@ int render_camera(shs_ctx *ctx, const shs_rt_frame *f, const shs_rt_draw *draws,
         p.pcss_taps = c.pcf_samples;
     }
     if (f->shading == 2) {
-        if (!ctx->rt_have_lut) {
-            if (ensure(ctx, ctx->rt_srgb_lut, 256)) return SHS_ERR_HIP;
-            HIP_TRY(ctx, hipMemcpyAsync(ctx->rt_srgb_lut.p, srgb_table(), 256 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            ctx->rt_have_lut = true;
-        }
+        if (ensure_srgb_table(ctx)) return SHS_ERR_HIP;
         p.srgb_lut = ctx->rt_srgb_lut.p;
         p.ibl = ctx->rt_ibl_mips > 0 ? ctx->rt_ibl.p : nullptr;
         p.ibl_mips = ctx->rt_ibl_mips;
         p.pbr_exposure = ctx->rt_pbr.exposure;
         p.pbr_intensity = ctx->rt_pbr.direct_intensity;
     }
-    const int rc = upload_and_launch(ctx, p, false, f->shading);
+    int rc = upload_and_launch(ctx, p, false, f->shading);
+    if (!rc && ctx->rt_sky.model != SHS_RT_SKY_NONE) {
+        // skybox_background_pass (pbr :733-799) behind the triangles: the pixels the raster left without a fragment
+        shs_dev::RtSkyParams q{};
+        q.W = f->width; q.H = f->height;
+        q.aspect = float(f->width) / float(f->height);
+        q.tan_half_fov = ctx->rt_sky_tan;
+        std::memcpy(q.forward, ctx->rt_sky_cam, sizeof q.forward);
+        std::memcpy(q.right, ctx->rt_sky_cam + 3, sizeof q.right);
+        std::memcpy(q.up, ctx->rt_sky_cam + 6, sizeof q.up);
+        q.exposure = ctx->rt_sky.exposure;
+        q.ids = p.ids;
+        q.color = p.color;
+        q.prequant = p.prequant;
+        q.sky = ctx->rt_sky_model;
+        const hipError_t e = shs_internal::launch_canvas_rt_sky(q, ctx->rt_sky.model, ctx->rt_sky.encode, ctx->stream);
+        if (e != hipSuccess) {
+            ctx->err = hipGetErrorString(e);
+            rc = SHS_ERR_HIP;
+        }
+    }
     if (rc) {
         ctx->rt_have_frame = false;
         return rc;
@@ -516,6 +544,114 @@ int shs_rt_ibl_samples(shs_ctx *ctx, int32_t n, const float *dirs3, const float 
     HIP_TRY(ctx, shs_internal::launch_ibl_samples(q, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(irr_rgb3, q.irr, 3 * ns * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(spec_rgb3, q.spec, 3 * ns * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // (the pageable staging above is consumed by now)
+    return SHS_OK;
+}
+
+int shs_rt_set_sky(shs_ctx *ctx, const shs_rt_sky *sky) {
+    if (!ctx) return SHS_ERR_INVALID;
+    if (!sky || sky->model == SHS_RT_SKY_NONE) {
+        ctx->rt_sky = shs_rt_sky{};
+        return SHS_OK;
+    }
+    const bool cube = sky->model == SHS_RT_SKY_CUBEMAP;
+    if ((sky->model != SHS_RT_SKY_ANALYTIC && !cube) || (sky->encode != SHS_RT_SKY_ENCODE_REINHARD && sky->encode != SHS_RT_SKY_ENCODE_CLAMP)) {
+        ctx->err = "shs_rt_set_sky: unknown model or encode";
+        return SHS_ERR_INVALID;
+    }
+    bool fin = std::isfinite(sky->intensity) && std::isfinite(sky->fov_degrees) && std::isfinite(sky->exposure);
+    for (int k = 0; k < 3; ++k)
+        fin = fin && std::isfinite(sky->sun_dir[k]) && std::isfinite(sky->cam_forward[k]) && std::isfinite(sky->cam_right[k]) &&
+              std::isfinite(sky->cam_up[k]);
+    if (!fin) {
+        ctx->err = "shs_rt_set_sky: a non-finite float";
+        return SHS_ERR_INVALID;
+    }
+    using shs_host::vec3;
+    auto finite3 = [](vec3 v) { return std::isfinite(v.x) && std::isfinite(v.y) && std::isfinite(v.z); };
+    // glm::normalize of the three camera vectors (pbr :746-748) and the pass's tangent (:744), once per call
+    const vec3 cam[3] = {shs_host::gnormalize({sky->cam_forward[0], sky->cam_forward[1], sky->cam_forward[2]}),
+                         shs_host::gnormalize({sky->cam_right[0], sky->cam_right[1], sky->cam_right[2]}),
+                         shs_host::gnormalize({sky->cam_up[0], sky->cam_up[1], sky->cam_up[2]})};
+    const float tan_half_fov = std::tan(shs_host::gradians(sky->fov_degrees) * 0.5f);
+    if (!finite3(cam[0]) || !finite3(cam[1]) || !finite3(cam[2]) || !std::isfinite(tan_half_fov)) {
+        ctx->err = "shs_rt_set_sky: a camera vector that cannot be normalised";
+        return SHS_ERR_INVALID;
+    }
+    shs_dev::RtSkyModel m{};
+    if (cube) {
+        for (int k = 0; k < 6; ++k) {
+            const int32_t id = sky->face_tex[k];
+            if (id <= 0 || id > (int32_t)ctx->textures.size() || !ctx->textures[(size_t)id - 1].live) {
+                ctx->err = "shs_rt_set_sky: unknown face texture id";
+                return SHS_ERR_INVALID;
+            }
+            const Texture &t = ctx->textures[(size_t)id - 1];
+            m.face[k] = t.texels;
+            m.fw[k] = t.w;
+            m.fh[k] = t.h;
+        }
+        m.intensity = sky->intensity;
+        if (set_dev(ctx)) return SHS_ERR_HIP;
+        if (ensure_srgb_table(ctx)) return SHS_ERR_HIP;   // (the first cubemap sky of a context uploads the table)
+        m.srgb_lut = ctx->rt_srgb_lut.p;
+    } else {
+        // AnalyticSky::sample's terms of the sun direction alone (shs_renderer.hpp:561, :568-579, :589, :596), each a
+        // single float operation in the reference's order; glm::mix(x, y, a) is x * (1 - a) + y * a
+        const vec3 s = shs_host::gneg(shs_host::gnormalize({sky->sun_dir[0], sky->sun_dir[1], sky->sun_dir[2]}));
+        if (!finite3(s)) {
+            ctx->err = "shs_rt_set_sky: a sun direction that cannot be normalised";
+            return SHS_ERR_INVALID;
+        }
+        const float lo = (s.y < 0.0f) ? 0.0f : s.y;             // glm::clamp(s.y, 0, 1): min(max(x, 0), 1)
+        const float sun_height = (1.0f < lo) ? 1.0f : lo;
+        const float a = sun_height, b = 1.0f - sun_height;
+        const float zenith_night[3] = {0.02f, 0.02f, 0.05f}, zenith_day[3] = {0.30f, 0.70f, 1.70f};
+        const float horizon_night[3] = {0.4f, 0.15f, 0.05f}, horizon_day[3] = {1.30f, 1.64f, 2.00f};
+        const float ground_base[3] = {0.30f, 0.26f, 0.22f}, glow_base[3] = {1.0f, 0.8f, 0.4f};
+        m.s[0] = s.x; m.s[1] = s.y; m.s[2] = s.z;
+        for (int k = 0; k < 3; ++k) {
+            m.zenith[k] = zenith_night[k] * b + zenith_day[k] * a;
+            m.horizon[k] = horizon_night[k] * b + horizon_day[k] * a;
+            const float half_ground = ground_base[k] * 0.5f;
+            const float ground = half_ground * b + ground_base[k] * a;
+            const float reflected = m.horizon[k] * 0.05f;
+            m.ground[k] = ground + reflected;
+            m.half_horizon[k] = m.horizon[k] * 0.5f;
+            const float glow4 = glow_base[k] * 4.0f;
+            m.glow[k] = glow4 * sun_height;
+        }
+    }
+    ctx->rt_sky = *sky;
+    ctx->rt_sky_model = m;
+    for (int k = 0; k < 3; ++k) {
+        ctx->rt_sky_cam[3 * k] = cam[k].x;
+        ctx->rt_sky_cam[3 * k + 1] = cam[k].y;
+        ctx->rt_sky_cam[3 * k + 2] = cam[k].z;
+    }
+    ctx->rt_sky_tan = tan_half_fov;
+    return SHS_OK;
+}
+
+int shs_rt_sky_samples(shs_ctx *ctx, int32_t n, const float *dirs3, float *rgb3) {
+    if (!ctx || n < 0 || (n > 0 && (!dirs3 || !rgb3))) return SHS_ERR_INVALID;
+    if (ctx->rt_sky.model == SHS_RT_SKY_NONE) {
+        ctx->err = "shs_rt_sky_samples: no sky bound (shs_rt_set_sky)";
+        return SHS_ERR_INVALID;
+    }
+    if (n == 0) return SHS_OK;
+    if (set_dev(ctx)) return SHS_ERR_HIP;
+    const size_t ns = (size_t)n;
+    if (ensure(ctx, ctx->rt_sky_io, 6 * ns)) return SHS_ERR_HIP;   // the workspace: dirs (3 n), radiance (3 n)
+    float *io = ctx->rt_sky_io.p;
+    HIP_TRY(ctx, hipMemcpyAsync(io, dirs3, 3 * ns * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    shs_dev::RtSkySamples q{};
+    q.n = n;
+    q.dirs = io;
+    q.out = io + 3 * ns;
+    q.sky = ctx->rt_sky_model;
+    HIP_TRY(ctx, shs_internal::launch_sky_samples(q, ctx->rt_sky.model, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(rgb3, q.out, 3 * ns * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // (the pageable staging above is consumed by now)
     return SHS_OK;
 }

@@ -229,6 +229,9 @@ int shs_texture_release(shs_ctx *ctx, int32_t tex_id) {
     if (ctx->sky.model == shs_dev::SKY_CUBEMAP)
         for (int32_t id : ctx->sky_face_tex)
             if (id == tex_id) { ctx->err = "texture is a face of the current sky (shs_lib_set_sky another first)"; return SHS_ERR_INVALID; }
+    if (ctx->rt_sky.model == SHS_RT_SKY_CUBEMAP)
+        for (int32_t id : ctx->rt_sky.face_tex)
+            if (id == tex_id) { ctx->err = "texture is a face of the render-target sky (shs_rt_set_sky another first)"; return SHS_ERR_INVALID; }
     if (set_dev(ctx)) return SHS_ERR_HIP;
     {   // a legacy batch in flight may sample it (SHS_SHADING_TEXTURED): its raster is launched and, should
         // it have overflowed a capacity, re-issued while the texture still exists -- as a mesh's release

@@ -15,6 +15,10 @@
 //   shading 2  fragment_shader_pbr (pbr :627-727): Cook-Torrance GGX under the 2x2-PCF shadow, plus image-based
 //          lighting from an irradiance cubemap and a prefiltered-specular mip chain (shs/resources/ibl.hpp:215-286;
 //          RtParams::ibl).  k_rt_raster<false, 2>, launched by shs_rt_render_pbr, again differs in the shade alone.
+//   the background  skybox_background_pass (pbr :733-799; the same routine in hello_pbr_light_shafts.cpp and
+//          hello_ibl_skybox.cpp) over the legacy AnalyticSky / CubeMapSky of hello-shs-renderer/shs_renderer.hpp:
+//          k_rt_sky<MODEL, ENCODE>, a pass of its own after k_rt_raster when a sky is bound (shs_rt_set_sky), which
+//          colours the pixels whose id is -1.  The reference draws the sky first and the triangles over it.
 //
 // Two kernels per pass, the same two for both (template <bool SHADOW>):
 //   k_rt_setup   one lane per input triangle: the vertex shader once per corner (the reference re-runs it
@@ -648,6 +652,15 @@ __device__ f3 ibl_sample_trilinear(const float4 *ibl, int mips, f3 d, float lod)
 
 __device__ __forceinline__ float saturate(float v) { return (v < 0.0f) ? 0.0f : (v > 1.0f ? 1.0f : v); }
 
+// One channel's way to the screen in hello_pbr.cpp (fragment_shader_pbr :722-726, skybox_background_pass :785-789):
+// the exposure, tonemap_reinhard, linear_to_srgb, and rgb01_to_color up to the truncation: the channel * 255.
+__device__ __forceinline__ float encode_reinhard(float x, float exposure) {
+    x = x * exposure;
+    x = x / (1.0f + x);                        // tonemap_reinhard
+    x = powf(g_clamp01(x), 1.0f / 2.2f);       // linear_to_srgb
+    return g_clamp01(x) * 255.0f;              // rgb01_to_color
+}
+
 // The shown fragment of hello_pbr.cpp's camera pass (pbr :986-1035, the hard demo's interpolation and velocity)
 // through fragment_shader_pbr (pbr :627-727): Cook-Torrance GGX under the hard demo's shadow lookup, plus the
 // irradiance and prefiltered-specular IBL.  The direct term is finished before the IBL gathers start.
@@ -751,11 +764,8 @@ __device__ void shade_pixel_pbr(const RtParams &p, int32_t id, float u, float v,
     const float bs[3] = {base.x, base.y, base.z};
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
-        float x = out[i] + (bs[i] * 0.03f) * ao;   // the minimum ambient
-        x = x * p.pbr_exposure;
-        x = x / (1.0f + x);                        // tonemap_reinhard
-        x = powf(g_clamp01(x), 1.0f / 2.2f);       // linear_to_srgb
-        out[i] = g_clamp01(x) * 255.0f;            // rgb01_to_color
+        const float x = out[i] + (bs[i] * 0.03f) * ao;   // the minimum ambient
+        out[i] = encode_reinhard(x, p.pbr_exposure);
     }
     rgba = byte_x86(out[0]) | (byte_x86(out[1]) << 8) | (byte_x86(out[2]) << 16) | 0xff000000u;
     pq = make_float4(out[0], out[1], out[2], shadow);
@@ -889,6 +899,146 @@ __global__ __launch_bounds__(256) void k_rt_ibl_samples(const RtIblSamples q) {
     q.spec[3 * i] = b.x; q.spec[3 * i + 1] = b.y; q.spec[3 * i + 2] = b.z;
 }
 
+// ---- skybox_background_pass (pbr :733-799) over the legacy sky models ("sky :line": hello-shs-renderer/shs_renderer.hpp)
+
+__device__ __forceinline__ f3 mix3(f3 x, f3 y, float a) {   // glm::mix(x, y, a): x * (1 - a) + y * a
+    const float b = 1.0f - a;
+    return {x.x * b + y.x * a, x.y * b + y.y * a, x.z * b + y.z * a};
+}
+__device__ __forceinline__ f3 ld3(const float *p) { return {p[0], p[1], p[2]}; }
+
+// AnalyticSky::sample (sky :558-608) after the host's part (RtSkyModel).  Its three std::pow(x, 3.0f / 4.0f / 12.0f)
+// are products in double rounded once, as pow64; everything else is + - * / sqrt and compares, so cosGamma and with
+// it the disc / edge branch are the reference's.
+__device__ f3 sky_analytic(const RtSkyModel &m, f3 dir) {
+    const f3 d = normalize3(dir);
+    const f3 s = ld3(m.s);
+    const float cosTheta = g_min(g_max(d.y, -1.0f), 1.0f);
+    const float cosGamma = dot3(d, s);
+    // glm::smoothstep(-0.15f, 0.15f, cosTheta)
+    const float t = g_clamp01((cosTheta - -0.15f) / (0.15f - -0.15f));
+    const float sky_ground = t * t * (3.0f - 2.0f * t);
+    const double up = (double)(1.0f - g_max(0.0f, cosTheta));
+    const f3 upper = mix3(ld3(m.zenith), ld3(m.horizon), (float)(up * up * up));
+    const double hz = (double)(1.0f + g_min(0.0f, cosTheta)), hz2 = hz * hz;
+    const f3 lower = mix3(ld3(m.ground), ld3(m.half_horizon), (float)(hz2 * hz2));
+    f3 c = mix3(lower, upper, sky_ground);
+    const double g = (double)g_clamp01(cosGamma), g2 = g * g, g4 = g2 * g2;
+    const float glow = (float)((g4 * g4) * g4);
+    c = add3(c, sc3(ld3(m.glow), glow));
+    if (cosGamma > 0.9998f) {
+        c = {4.0f, 3.5f, 3.0f};
+    } else if (cosGamma > 0.9992f) {
+        const float edge = (cosGamma - 0.9992f) / (0.9998f - 0.9992f);
+        c = mix3(c, f3{3.0f, 2.5f, 1.5f}, edge);
+    }
+    return c;
+}
+
+// Texture2D::get (sky :360-363) then to_lin (sky :462-465): {0, 0, 0, 0} out of bounds, which the table takes to 0 as
+// pow(0, 2.2f).  An unconditional load at a clamped address plus a select (as pcss_tap).
+__device__ __forceinline__ f3 sky_texel(const uint32_t *tex, int w, int h, const float *lut, int x, int y) {
+    const bool in = x >= 0 && x < w && y >= 0 && y < h;
+    const uint32_t raw = tex[(size_t)clampi(y, 0, h - 1) * w + clampi(x, 0, w - 1)];
+    const uint32_t tc = in ? raw : 0u;
+    return {lut[tc & 0xffu], lut[(tc >> 8) & 0xffu], lut[(tc >> 16) & 0xffu]};
+}
+
+// CubeMapSky::sample over sample_face_bilinear (sky :439-512).  A NaN coordinate passes glm::clamp and converts to
+// INT_MIN (x1 = INT_MIN + 1): all four texels are out of bounds.
+__device__ f3 sky_cubemap(const RtSkyModel &m, f3 d) {
+    const float len = sqrtf(dot3(d, d));
+    if (len < 1e-8f) return {0.0f, 0.0f, 0.0f};
+    d = {d.x / len, d.y / len, d.z / len};
+    const float ax = fabsf(d.x), ay = fabsf(d.y), az = fabsf(d.z);
+    int face;
+    float u, v;
+    if (ax >= ay && ax >= az) {
+        if (d.x > 0.0f) { face = 0; u = -d.z / ax; v = d.y / ax; }
+        else            { face = 1; u = d.z / ax; v = d.y / ax; }
+    } else if (ay >= ax && ay >= az) {
+        if (d.y > 0.0f) { face = 2; u = d.x / ay; v = -d.z / ay; }
+        else            { face = 3; u = d.x / ay; v = d.z / ay; }
+    } else {
+        if (d.z > 0.0f) { face = 4; u = d.x / az; v = d.y / az; }
+        else            { face = 5; u = -d.x / az; v = d.y / az; }
+    }
+    u = 0.5f * (u + 1.0f);
+    v = 0.5f * (v + 1.0f);
+    // the face's texture out of the kernel arguments: selects over the six, not a per-lane index into them
+    const uint32_t *tex = m.face[0];
+    int w = m.fw[0], h = m.fh[0];
+#pragma unroll
+    for (int k = 1; k < 6; ++k) {
+        const bool is = face == k;
+        tex = is ? m.face[k] : tex;
+        w = is ? m.fw[k] : w;
+        h = is ? m.fh[k] : h;
+    }
+    u = g_clamp01(u);   // glm::clamp: min(max(x, 0), 1)
+    v = g_clamp01(v);
+    const float fx = u * (float)(w - 1);
+    const float fy = v * (float)(h - 1);
+    const int x0 = int_x86(floorf(fx));
+    const int y0 = int_x86(floorf(fy));
+    const int x1 = min(x0 + 1, w - 1);
+    const int y1 = min(y0 + 1, h - 1);
+    const float tx = fx - (float)x0;
+    const float ty = fy - (float)y0;
+    const f3 v00 = sky_texel(tex, w, h, m.srgb_lut, x0, y0), v10 = sky_texel(tex, w, h, m.srgb_lut, x1, y0);
+    const f3 v01 = sky_texel(tex, w, h, m.srgb_lut, x0, y1), v11 = sky_texel(tex, w, h, m.srgb_lut, x1, y1);
+    const f3 vx0 = mix3(v00, v10, tx);
+    const f3 vx1 = mix3(v01, v11, tx);
+    return sc3(mix3(vx0, vx1, ty), m.intensity);
+}
+
+template <int MODEL>
+__device__ __forceinline__ f3 sky_sample(const RtSkyModel &m, f3 d) {
+    if constexpr (MODEL == RT_SKY_CUBEMAP) return sky_cubemap(m, d);
+    else return sky_analytic(m, d);
+}
+
+// One lane per pixel of the canvas rows: where the raster showed no fragment (id < 0), the sky through the pixel's
+// centre (pbr :769-789, canvas x and y, y up) into the colour plane and, if there is one, the prequant plane.  Depth,
+// velocity and ids are not touched.  MODEL and ENCODE are compile-time: the analytic instantiations have no gathers.
+template <int MODEL, int ENCODE>
+__global__ __launch_bounds__(256) void k_rt_sky(const RtSkyParams p) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;   // (W, H <= 32767: W * H < 2^30)
+    if (i >= (uint32_t)p.W * (uint32_t)p.H) return;
+    if (p.ids[i] >= 0) return;
+    const int x = (int)(i % (uint32_t)p.W), y = (int)(i / (uint32_t)p.W);
+    const float fx = ((float)x + 0.5f) / (float)p.W;
+    const float fy = ((float)y + 0.5f) / (float)p.H;
+    const float ndc_x = fx * 2.0f - 1.0f;
+    const float ndc_y = fy * 2.0f - 1.0f;
+    const float kr = (ndc_x * p.aspect) * p.tan_half_fov, ku = ndc_y * p.tan_half_fov;
+    const f3 dir = add3(add3(ld3(p.forward), sc3(ld3(p.right), kr)), sc3(ld3(p.up), ku));
+    const f3 c = sky_sample<MODEL>(p.sky, normalize3(dir));
+    float out[3] = {c.x, c.y, c.z};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        if constexpr (ENCODE == RT_SKY_CLAMP) {
+            // glm::clamp(c_lin, 0, 1), linear_to_srgb (whose own clamp then changes nothing), rgb01_to_color
+            // (hello_ibl_skybox.cpp:598-601)
+            const float s = powf(g_clamp01(out[k]), 1.0f / 2.2f);
+            out[k] = g_clamp01(s) * 255.0f;
+        } else {
+            out[k] = encode_reinhard(out[k], p.exposure);
+        }
+    }
+    p.color[i] = byte_x86(out[0]) | (byte_x86(out[1]) << 8) | (byte_x86(out[2]) << 16) | 0xff000000u;
+    if (p.prequant) p.prequant[i] = make_float4(out[0], out[1], out[2], 1.0f);
+}
+
+// shs_rt_sky_samples: one lane per direction through the device function the background pass calls
+template <int MODEL>
+__global__ __launch_bounds__(256) void k_rt_sky_samples(const RtSkySamples q) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= q.n) return;
+    const f3 c = sky_sample<MODEL>(q.sky, ld3(q.dirs + 3 * (size_t)i));
+    q.out[3 * (size_t)i] = c.x; q.out[3 * (size_t)i + 1] = c.y; q.out[3 * (size_t)i + 2] = c.z;
+}
+
 }  // namespace
 }  // namespace shs_dev
 
@@ -903,6 +1053,29 @@ hipError_t launch_pcss_samples(const shs_dev::RtPcssSamples &q, hipStream_t s) {
 hipError_t launch_ibl_samples(const shs_dev::RtIblSamples &q, hipStream_t s) {
     if (q.n <= 0) return hipSuccess;
     hipLaunchKernelGGL(shs_dev::k_rt_ibl_samples, dim3((q.n + 255) / 256), dim3(256), 0, s, q);
+    return hipGetLastError();
+}
+
+hipError_t launch_canvas_rt_sky(const shs_dev::RtSkyParams &p, int model, int encode, hipStream_t s) {
+    using namespace shs_dev;
+    const dim3 grid(((uint32_t)p.W * (uint32_t)p.H + 255u) / 256u), block(256);
+    const bool clamp = encode == RT_SKY_CLAMP;
+    if (model == RT_SKY_CUBEMAP) {
+        if (clamp) hipLaunchKernelGGL((k_rt_sky<RT_SKY_CUBEMAP, RT_SKY_CLAMP>), grid, block, 0, s, p);
+        else hipLaunchKernelGGL((k_rt_sky<RT_SKY_CUBEMAP, RT_SKY_REINHARD>), grid, block, 0, s, p);
+    } else {
+        if (clamp) hipLaunchKernelGGL((k_rt_sky<RT_SKY_ANALYTIC, RT_SKY_CLAMP>), grid, block, 0, s, p);
+        else hipLaunchKernelGGL((k_rt_sky<RT_SKY_ANALYTIC, RT_SKY_REINHARD>), grid, block, 0, s, p);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_sky_samples(const shs_dev::RtSkySamples &q, int model, hipStream_t s) {
+    using namespace shs_dev;
+    if (q.n <= 0) return hipSuccess;
+    const dim3 grid((q.n + 255) / 256), block(256);
+    if (model == RT_SKY_CUBEMAP) hipLaunchKernelGGL(k_rt_sky_samples<RT_SKY_CUBEMAP>, grid, block, 0, s, q);
+    else hipLaunchKernelGGL(k_rt_sky_samples<RT_SKY_ANALYTIC>, grid, block, 0, s, q);
     return hipGetLastError();
 }
 

@@ -1,7 +1,8 @@
 // shs_canvas_rt_internal.hpp -- launch interface of shs_canvas_rt.hip: the Canvas render-target raster of
 // hello-render-target/hello_shadow_mapping.cpp (shadow pass and shadowed camera pass; include/shs_gpu.h) and
 // of hello_shadow_mapping_soft.cpp (the same passes with the PCSS fragment shader, shs_rt_frame::shading 1) and
-// hello_pbr.cpp (the same passes with the GGX + IBL fragment shader, shading 2 through shs_rt_render_pbr).
+// hello_pbr.cpp (the same passes with the GGX + IBL fragment shader, shading 2 through shs_rt_render_pbr), and of the
+// background pass behind any of them (skybox_background_pass over the legacy sky models, shs_rt_set_sky).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -125,9 +126,52 @@ struct RtPcssSamples {
     int32_t pcss_blockers, pcss_taps;
 };
 
+// ---- skybox_background_pass (hello_pbr.cpp:733-799) over the legacy sky models of shs_renderer.hpp ----
+
+constexpr int RT_SKY_ANALYTIC = 1, RT_SKY_CUBEMAP = 2;   // SHS_RT_SKY_*
+constexpr int RT_SKY_REINHARD = 0, RT_SKY_CLAMP = 1;     // SHS_RT_SKY_ENCODE_*
+
+// What AbstractSky::sample reads, after the operations the host has done once per shs_rt_set_sky.
+struct RtSkyModel {
+    // AnalyticSky (:552-611): everything that depends on the sun direction alone
+    float s[3];                      // -normalize(sun_direction)
+    float zenith[3], horizon[3];     // the two mixes over sun_height :574-575
+    float ground[3];                 // ground_color :578-579
+    float half_horizon[3];           // horizon_color * 0.5f :589
+    float glow[3];                   // sun_glow_color :596
+    // CubeMapSky (:432-517): the faces +X -X +Y -Y +Z -Z, the sRGB -> linear table and intensity_
+    float intensity;
+    const uint32_t *face[6];
+    int32_t fw[6], fh[6];
+    const float *srgb_lut;           // 256 floats: pow(c / 255, 2.2) with the host's libm
+};
+
+// The background pass's own parameters (not RtParams': the raster kernels' arguments stay as they were).
+struct RtSkyParams {
+    int32_t W, H;
+    float aspect, tan_half_fov;      // float(W) / float(H); std::tan(glm::radians(fov) * 0.5f) with the host's libm
+    float forward[3], right[3], up[3];   // normalised by the host
+    float exposure;                  // SKY_EXPOSURE (the Reinhard encode only)
+    const int32_t *ids;              // the raster's id plane: id < 0 shows sky
+    uint32_t *color;
+    float4 *prequant;                // or null
+    RtSkyModel sky;
+};
+
+// sky.sample(dir) for a list of directions (shs_rt_sky_samples): everything on the device
+struct RtSkySamples {
+    int32_t n;
+    const float *dirs;               // 3 n
+    float *out;                      // 3 n
+    RtSkyModel sky;
+};
+
 }  // namespace shs_dev
 
 namespace shs_internal {
+// the background pass after a camera pass: one lane per pixel of the canvas rows (model, encode: SHS_RT_SKY_*)
+hipError_t launch_canvas_rt_sky(const shs_dev::RtSkyParams &p, int model, int encode, hipStream_t s);
+hipError_t launch_sky_samples(const shs_dev::RtSkySamples &q, int model, hipStream_t s);
 // setup (one lane per input triangle) then raster (one workgroup per 32x8 tile) of either pass
 // shading: shs_rt_frame::shading of the camera pass (0: fragment_shader_full, 1: fragment_shader_softshadow,
 // 2: fragment_shader_pbr)

@@ -374,6 +374,13 @@ struct shs_ctx {
     DevBuf<float> rt_srgb_lut, rt_is_io;
     bool rt_have_lut = false;
     std::vector<shs_dev::RtPbrDrawGPU> rt_h_pbr;
+    // the background (skybox_background_pass): the sky of shs_rt_set_sky as the caller gave it (model
+    // SHS_RT_SKY_NONE: none), what the host derives from it once per call, and the workspace of shs_rt_sky_samples
+    shs_rt_sky rt_sky = {};
+    shs_dev::RtSkyModel rt_sky_model = {};
+    float rt_sky_cam[9] = {};             // forward, right, up, normalised
+    float rt_sky_tan = 0.0f;              // std::tan(glm::radians(fov_degrees) * 0.5f)
+    DevBuf<float> rt_sky_io;
 };
 
 // Re-enqueues the tonemap after lib_finish re-issued the camera pass (shs_abi_post.cpp).

@@ -18,7 +18,7 @@ from ._abi import (FRAME_PREQUANT, FRAME_PRESENT, SHADING_BLINN_PHONG, SHADING_D
                    SHADING_TOON, FrameDesc, LegacyDraw, RasterStats)
 
 __all__ = [
-    "ShsError", "Context", "Frame", "Draw", "RtFrame", "RtDraw", "RtPcss", "RtPbrDraw", "RtPbr", "SHADING_FLAT", "SHADING_GOURAUD", "SHADING_PHONG",
+    "ShsError", "Context", "Frame", "Draw", "RtFrame", "RtDraw", "RtPcss", "RtPbrDraw", "RtPbr", "RtSky", "SHADING_FLAT", "SHADING_GOURAUD", "SHADING_PHONG",
     "SHADING_BLINN_PHONG", "SHADING_TOON", "SHADING_GOOCH", "SHADING_OREN_NAYAR", "SHADING_NORMAL_VIS",
     "SHADING_DEPTH_VIS", "SHADING_TEXTURED", "SHADING_NAMES", "FRAME_PREQUANT", "lib",
 ]
@@ -140,6 +140,22 @@ class RtPbr:
     exposure: float = 1.75
     min_roughness: float = 0.04
     direct_intensity: float = 3.0
+
+
+@dataclass
+class RtSky:
+    """The background of the camera passes (shs_rt_sky): a legacy sky model of shs_renderer.hpp and the camera of
+    skybox_background_pass; the defaults are hello_pbr.cpp's (AnalyticSky's default sun, SKY_EXPOSURE)."""
+    model: int = _abi.RT_SKY_ANALYTIC
+    encode: int = _abi.RT_SKY_ENCODE_REINHARD
+    sun_dir: tuple = (0.4668, -0.3487, 0.8127)
+    intensity: float = 1.0
+    face_tex: tuple = ()         # cubemap: +X -X +Y -Y +Z -Z, each an uploaded texture id or an object with .rgba [h, w, 4]
+    cam_forward: tuple = (0.0, 0.0, 1.0)
+    cam_right: tuple = (1.0, 0.0, 0.0)
+    cam_up: tuple = (0.0, 1.0, 0.0)
+    fov_degrees: float = 60.0
+    exposure: float = 1.85
 
 
 class Context:
@@ -751,6 +767,28 @@ class Context:
         a, b = np.empty((n, 3), np.float32), np.empty((n, 3), np.float32)
         self._check(self._lib.shs_rt_ibl_samples(self._h, n, _ptr(dirs), _ptr(lod), _ptr(a), _ptr(b)))
         return a, b
+
+    def rt_set_sky(self, sky=None):
+        """shs_rt_set_sky: the sky later camera passes draw behind the triangles (an RtSky; None: no sky, uncovered
+        pixels keep clear_color)."""
+        if sky is None:
+            self._check(self._lib.shs_rt_set_sky(self._h, None))
+            return
+        c = _abi.RtSkyC()
+        c.model, c.encode = int(sky.model), int(sky.encode)
+        c.intensity, c.fov_degrees, c.exposure = float(sky.intensity), float(sky.fov_degrees), float(sky.exposure)
+        for name in ("sun_dir", "cam_forward", "cam_right", "cam_up"):
+            getattr(c, name)[:] = [float(v) for v in getattr(sky, name)]
+        for k, tex in enumerate(tuple(sky.face_tex)[:6]):
+            c.face_tex[k] = int(tex) if isinstance(tex, (int, np.integer)) else self.upload_texture(tex)
+        self._check(self._lib.shs_rt_set_sky(self._h, ctypes.byref(c)))
+
+    def rt_sky_samples(self, dirs):
+        """shs_rt_sky_samples: the bound sky's linear radiance sky.sample(dir) -> float32 [n, 3], synchronous."""
+        dirs = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        out = np.empty_like(dirs)
+        self._check(self._lib.shs_rt_sky_samples(self._h, dirs.shape[0], _ptr(dirs), _ptr(out)))
+        return out
 
     def rt_set_pcss(self, pcss=None):
         """shs_rt_set_pcss: the PCSS constants of shading 1 (an RtPcss; None: the demo's)."""

@@ -248,6 +248,17 @@ class RtPbrC(ctypes.Structure):
     _fields_ = [("exposure", ctypes.c_float), ("min_roughness", ctypes.c_float), ("direct_intensity", ctypes.c_float)]
 
 
+RT_SKY_NONE, RT_SKY_ANALYTIC, RT_SKY_CUBEMAP = 0, 1, 2
+RT_SKY_ENCODE_REINHARD, RT_SKY_ENCODE_CLAMP = 0, 1
+
+
+class RtSkyC(ctypes.Structure):
+    """shs_rt_sky: the legacy sky model and the camera of skybox_background_pass."""
+    _fields_ = [("model", ctypes.c_int32), ("encode", ctypes.c_int32), ("sun_dir", _F3), ("intensity", ctypes.c_float),
+                ("face_tex", ctypes.c_int32 * 6), ("cam_forward", _F3), ("cam_right", _F3), ("cam_up", _F3),
+                ("fov_degrees", ctypes.c_float), ("exposure", ctypes.c_float)]
+
+
 class RtStatsC(ctypes.Structure):
     _fields_ = [("input_tris", ctypes.c_int64), ("polys3", ctypes.c_int64), ("polys4", ctypes.c_int64),
                 ("sub_tris", ctypes.c_int64)]
@@ -368,6 +379,8 @@ SIGNATURES = [
     ("shs_rt_render_pbr", ctypes.c_int, [_P, ctypes.POINTER(RtFrameC), ctypes.POINTER(RtDrawC), ctypes.POINTER(RtPbrDrawC),
                                          ctypes.c_int32]),
     ("shs_rt_ibl_samples", ctypes.c_int, [_P, ctypes.c_int32, _P, _P, _P, _P]),
+    ("shs_rt_set_sky", ctypes.c_int, [_P, ctypes.POINTER(RtSkyC)]),
+    ("shs_rt_sky_samples", ctypes.c_int, [_P, ctypes.c_int32, _P, _P]),
     ("shs_rt_resolve", ctypes.c_int, [_P, _P, _P, _P]),
     ("shs_rt_resolve_shadow", ctypes.c_int, [_P, _P]),
     ("shs_rt_resolve_prequant", ctypes.c_int, [_P, _P]),
