@@ -810,6 +810,46 @@ typedef struct shs_canvas_dof_desc {
  * (may be NULL, host) the autofocus depth. */
 int shs_canvas_dof(shs_ctx *ctx, const shs_canvas_dof_desc *desc, uint8_t *color, const float *depth, uint8_t *blur_out,
                    float *focus_depth, uint32_t flags);
+/* light_shafts_pass of hello_pbr_light_shafts.cpp (:1390-1707; PASS1.5 of its frame, :2171-2190): per pixel a
+ * volumetric ray march from the camera through height fog with a sine-noise density, the sun's visibility from
+ * the shadow map at every step, a Henyey-Greenstein phase, and a soft re-tonemap of the pixel's colour.  The
+ * fields after shadow_h are LightShaftParams (:189-218) in its order, bools as int32_t. */
+#define SHS_CANVAS_LIGHT_SHAFTS_MAX_STEPS 4096
+typedef struct shs_canvas_light_shafts_desc {
+    int32_t width, height;
+    float cam_pos[3];
+    float inv_view_proj[16];    /* glm::inverse(proj * view) (:2171), column-major: the pass inverts nothing */
+    float sun_dir_world[3];     /* sun -> scene, not normalised */
+    float light_vp[16];
+    int32_t shadow_w, shadow_h;
+    int32_t enable;             /* 1 */
+    int32_t steps;              /* 40 */
+    float max_dist;             /* 110 */
+    float min_dist;             /* 1 */
+    float base_density;         /* 0.18 */
+    float height_falloff;       /* 0.10 */
+    float noise_scale;          /* 0.65 */
+    float noise_strength;       /* 0.60 */
+    float jitter_amount;        /* 1 */
+    float ambient_strength;     /* 0.08 */
+    float sigma_s;              /* 0.030 */
+    float sigma_t;              /* 0.065 */
+    float g;                    /* 0.82 */
+    float intensity;            /* 0.35 */
+    int32_t use_shadow;         /* 1 */
+    float shadow_bias;          /* 0.0045 */
+    int32_t shadow_pcf_2x2;     /* 1 */
+} shs_canvas_light_shafts_desc;
+/* src, depth -> dst (dst == src is allowed: a pixel reads only its own).  shadow_map: shadow_w * shadow_h floats
+ * as shs_rt_resolve_shadow returns them (y down, FLT_MAX = empty); NULL: no map, every step is lit.  prequant (may
+ * be NULL): W*H*4 floats -- for a marched pixel the sRGB colour * 255 before the byte truncation and the number of
+ * steps that accumulated (those that entered the second `dens > 1e-6f` block), for a pixel the pass only copies
+ * (0, 0, 0, -1).  The sin / cos / exp / pow of the march are evaluated in double and rounded once to float; the
+ * reference takes them from the host's float libm, so a float may differ from it in its last bit.
+ * SHS_ERR_INVALID (nothing is enqueued): a non-positive size, steps above SHS_CANVAS_LIGHT_SHAFTS_MAX_STEPS, a
+ * non-finite parameter, matrix or vector, a zero-length sun_dir_world, a map without a positive size. */
+int shs_canvas_light_shafts(shs_ctx *ctx, const shs_canvas_light_shafts_desc *desc, const uint8_t *src, const float *depth,
+                            const float *shadow_map, uint8_t *dst, float *prequant, uint32_t flags);
 
 /* ---- Canvas render-target raster: shadow pass and shadowed camera pass ------------------------------
  * The raster the hello-render-target/ demos share, for its simplest complete host
@@ -915,6 +955,10 @@ int shs_rt_get_stats(shs_ctx *ctx, shs_rt_stats *stats);
 /* The last camera pass's device planes, final in the context stream's order (as shs_device_framebuffers):
  * valid until the next shs_rt_render of another size or shs_destroy. */
 int shs_rt_device_targets(shs_ctx *ctx, void **color_dev, void **depth_dev, void **velocity_dev);
+/* The device map of the last shs_rt_render_shadow (w * h floats, what shs_rt_resolve_shadow copies), final in the
+ * context stream's order: shs_canvas_light_shafts chains after the raster without a resolve.  Any pointer may be
+ * NULL.  Valid until the next shs_rt_render_shadow of another size or shs_destroy.  SHS_ERR_INVALID: no shadow map. */
+int shs_rt_device_shadow_map(shs_ctx *ctx, void **map_dev, int32_t *w, int32_t *h);
 /* hello_pbr.cpp's per-object uniforms that fragment_shader_pbr and vertex_shader_full read beside shs_rt_draw
  * (whose base_color is MaterialPBR::baseColor_srgb): element i goes with shs_rt_draw[i]. */
 typedef struct shs_rt_pbr_draw {

@@ -434,6 +434,54 @@ private:
     glm::mat4 prev_vp_{1.0f};
 };
 
+// -----------------------------------------------------------------------------------------------------
+// Seam 1c, light shafts -- hello-render-target/hello_pbr_light_shafts.cpp, PASS1.5.
+//
+// light_shafts_pass (:1525-1707) as RendererSystem::process calls it (:2171-2190), over the planes the camera pass
+// left on the device: after a PbrSystemGPU::process (or any shs_rt_render*) call apply(); the colour plane of
+// shs_rt_device_targets is rewritten in place, the shadow map is the one of shs_rt_device_shadow_map, and
+// shs_canvas_motion_blur (PASS2) follows on the same stream.  ParamsT is that file's LightShaftParams (:189-218).
+// That demo's PASS1 shader is not hello_pbr.cpp's (PCSS instead of the 2x2 PCF, no minimum ambient): its port is
+// not built yet, so a frame through PbrSystemGPU differs from the demo's in the shadows' penumbrae.  Uncompiled,
+// like the other seams.
+// -----------------------------------------------------------------------------------------------------
+template <class SceneT>
+class LightShaftsGPU {
+public:
+    LightShaftsGPU(SceneT *scene, Device *dev) : scene_(scene), dev_(dev) {}
+
+    template <class ParamsT>
+    void apply(const ParamsT &p, const glm::vec3 &sun_dir_world, const glm::mat4 &light_vp) {
+        shs::Canvas &canvas = *scene_->canvas;
+        const glm::mat4 inv_vp = glm::inverse(scene_->viewer->camera->projection_matrix * scene_->viewer->camera->view_matrix);
+        shs_canvas_light_shafts_desc d{};
+        d.width = canvas.get_width();
+        d.height = canvas.get_height();
+        std::memcpy(d.cam_pos, glm::value_ptr(scene_->viewer->position), 12);
+        std::memcpy(d.inv_view_proj, glm::value_ptr(inv_vp), 64);
+        std::memcpy(d.sun_dir_world, glm::value_ptr(sun_dir_world), 12);
+        std::memcpy(d.light_vp, glm::value_ptr(light_vp), 64);
+        d.enable = p.enable; d.steps = p.steps; d.max_dist = p.max_dist; d.min_dist = p.min_dist;
+        d.base_density = p.base_density; d.height_falloff = p.height_falloff;
+        d.noise_scale = p.noise_scale; d.noise_strength = p.noise_strength; d.jitter_amount = p.jitter_amount;
+        d.ambient_strength = p.ambient_strength; d.sigma_s = p.sigma_s; d.sigma_t = p.sigma_t; d.g = p.g;
+        d.intensity = p.intensity; d.use_shadow = p.use_shadow; d.shadow_bias = p.shadow_bias; d.shadow_pcf_2x2 = p.shadow_pcf_2x2;
+        void *color = nullptr, *depth = nullptr, *map = nullptr;
+        ok(shs_rt_device_targets(dev_->ctx, &color, &depth, nullptr));
+        if (shs_rt_device_shadow_map(dev_->ctx, &map, &d.shadow_w, &d.shadow_h) != SHS_OK) map = nullptr;   // no PASS0: all lit
+        ok(shs_canvas_light_shafts(dev_->ctx, &d, static_cast<const uint8_t *>(color), static_cast<const float *>(depth),
+                                   static_cast<const float *>(map), static_cast<uint8_t *>(color), nullptr, SHS_CANVAS_DEVICE));
+    }
+
+    void ok(int rc) const {
+        if (rc != SHS_OK) throw std::runtime_error(shs_last_error(dev_->ctx));
+    }
+
+private:
+    SceneT *scene_;
+    Device *dev_;
+};
+
 // =====================================================================================================
 // Seam 3 -- the library's plugin pipeline (shs-renderer-lib/include/shs/pipeline/).
 // =====================================================================================================

@@ -413,6 +413,14 @@ int shs_rt_device_targets(shs_ctx *ctx, void **color_dev, void **depth_dev, void
     return SHS_OK;
 }
 
+int shs_rt_device_shadow_map(shs_ctx *ctx, void **map_dev, int32_t *w, int32_t *h) {
+    if (!ctx || !ctx->rt_have_shadow) return SHS_ERR_INVALID;
+    if (map_dev) *map_dev = ctx->rt_shadow.p;
+    if (w) *w = ctx->rt_sw;
+    if (h) *h = ctx->rt_sh;
+    return SHS_OK;
+}
+
 int shs_rt_set_pcss(shs_ctx *ctx, const shs_rt_pcss *pcss) {
     if (!ctx) return SHS_ERR_INVALID;
     const shs_rt_pcss demo = {0.0035f, 18.0f, 1.0f, 28.0f, 1e-5f, 12, 24};

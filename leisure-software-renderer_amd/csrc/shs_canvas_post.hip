@@ -6,9 +6,13 @@
 //   k_canvas_gaussian      gaussian_blur_pass (hello_depth_of_field.cpp:175-251), 5 taps, one axis;
 //   k_canvas_autofocus     autofocus_depth_median_center (:257-285): the nth_element median of the
 //                          window's finite depths as a rank selection in one workgroup;
-//   k_canvas_dof_composite dof_composite_pass (:287-343).
+//   k_canvas_dof_composite dof_composite_pass (:287-343);
+//   k_canvas_light_shafts  light_shafts_pass (hello_pbr_light_shafts.cpp:1390-1707): per pixel a ray march of
+//                          up to `steps` samples through noisy height fog, each with the shadow map's
+//                          2x2 PCF through light_vp, then the pixel's soft re-tonemap.
 // One thread per pixel; every float expression keeps the reference's operation order
-// (-ffp-contract=off, correctly rounded '/' and sqrt), so the output bytes are the reference's.
+// (-ffp-contract=off, correctly rounded '/' and sqrt), so the output bytes are the reference's (the light
+// shafts' transcendentals excepted: see sin_r and its neighbours).
 #include <float.h>
 
 #include "shs_canvas_post_internal.hpp"
@@ -211,6 +215,160 @@ __global__ __launch_bounds__(256) void k_canvas_dof_composite(CanvasDofParams p)
     p.out[i] = out;
 }
 
+// ---- light_shafts_pass (hello_pbr_light_shafts.cpp:1390-1707) ----------------------------------------
+
+namespace {
+
+__device__ __forceinline__ float s_min(float a, float b) { return (b < a) ? b : a; }   // std::min, glm::min
+__device__ __forceinline__ float s_max(float a, float b) { return (a < b) ? b : a; }   // std::max, glm::max
+// (int)f as the reference's x86-64 build converts it (cvttss2si: NaN and out-of-range give INT_MIN)
+__device__ __forceinline__ int int_x86(float f) { return (f >= -2147483648.0f && f < 2147483648.0f) ? (int)f : INT_MIN; }
+// (int)std::lround(x): halves away from zero; NaN and out-of-range land on a value the caller's clamp brings to 0
+// or n - 1 as it does the reference's
+__device__ __forceinline__ int lround_x86(float x) {
+    if (!(x == x)) return 0;
+    const float t = truncf(x);
+    return int_x86(t) + ((x - t >= 0.5f) ? 1 : 0);
+}
+// The reference's sinf / cosf / expf / powf are the host libm's, close to correctly rounded: here the function in
+// double, rounded once to float (as pow64 and the analytic sky's powers in shs_canvas_rt.hip).
+__device__ __forceinline__ float sin_r(float x) { return (float)sin((double)x); }
+__device__ __forceinline__ float cos_r(float x) { return (float)cos((double)x); }
+__device__ __forceinline__ float exp_r(float x) { return (float)exp((double)x); }
+__device__ __forceinline__ float pow15_r(float x) { const double d = (double)x; return (float)(d * sqrt(d)); }
+__device__ __forceinline__ float pow_r(float x, float e) { return (float)pow((double)x, (double)e); }
+
+// volumetric_shadow_visibility (:1494-1507) over shadow_uvz_from_world (:558-576) and shadow_factor_pcf_2x2_raw /
+// shadow_compare_raw (:1450-1492).  The four loads are unconditional at clamped texels (without the PCF all four
+// are the nearest texel); every early return of the reference is a select on what they gave.
+__device__ __forceinline__ float ls_visibility(const CanvasLSParams &p, float wx, float wy, float wz) {
+    float c[4];
+    m4v(p.light_vp, wx, wy, wz, 1.0f, c);
+    const float nx = c[0] / c[3], ny = c[1] / c[3], z = c[2] / c[3];
+    bool lit = fabsf(c[3]) < 1e-6f || z < 0.0f || z > 1.0f;
+    const float u = nx * 0.5f + 0.5f;
+    const float v = 1.0f - (ny * 0.5f + 0.5f);
+    const float fx = u * (float)(p.sw - 1);
+    const float fy = v * (float)(p.sh - 1);
+    int x0, y0, x1, y1;
+    if (p.pcf) {
+        x0 = clampi(int_x86(floorf(fx)), 0, p.sw - 1);
+        y0 = clampi(int_x86(floorf(fy)), 0, p.sh - 1);
+        x1 = clampi(x0 + 1, 0, p.sw - 1);
+        y1 = clampi(y0 + 1, 0, p.sh - 1);
+    } else {
+        lit = lit || u < 0.0f || u > 1.0f || v < 0.0f || v > 1.0f;
+        x0 = x1 = clampi(lround_x86(fx), 0, p.sw - 1);
+        y0 = y1 = clampi(lround_x86(fy), 0, p.sh - 1);
+    }
+    const float d00 = p.map[y0 * p.sw + x0], d10 = p.map[y0 * p.sw + x1];
+    const float d01 = p.map[y1 * p.sw + x0], d11 = p.map[y1 * p.sw + x1];
+    const float c00 = (d00 == FLT_MAX || z <= d00 + p.bias) ? 1.0f : 0.0f;
+    const float c10 = (d10 == FLT_MAX || z <= d10 + p.bias) ? 1.0f : 0.0f;
+    const float c01 = (d01 == FLT_MAX || z <= d01 + p.bias) ? 1.0f : 0.0f;
+    const float c11 = (d11 == FLT_MAX || z <= d11 + p.bias) ? 1.0f : 0.0f;
+    const float vis = p.pcf ? 0.25f * (((c00 + c10) + c01) + c11) : c00;
+    return lit ? 1.0f : vis;
+}
+
+}  // namespace
+
+// One lane per pixel over 32 x 8 pixel tiles: a wave is two rows of 32, whose rays run side by side through the
+// shadow map.  SHADOW: p.use_shadow with a map (otherwise vis is 1 and the kernel has no map load).
+template <bool SHADOW>
+__global__ __launch_bounds__(256) void k_canvas_light_shafts(const CanvasLSParams p) {
+    const int x = (int)(blockIdx.x * 32u + (threadIdx.x & 31u));
+    const int y = (int)(blockIdx.y * 8u + (threadIdx.x >> 5));
+    if (x >= p.W || y >= p.H) return;
+    const int i = y * p.W + x;
+    const uint32_t base = p.src[i];
+    const float view_z = p.depth[i];
+    float ray_max = p.max_dist;
+    if (view_z != FLT_MAX) ray_max = s_min(ray_max, s_max(p.min_dist, view_z - 0.25f));
+    if (!p.enable || ray_max <= p.min_dist) {
+        p.dst[i] = base;
+        if (p.pq) p.pq[i] = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
+        return;
+    }
+    // reconstruct_world_dir_from_pixel (:1395-1420)
+    float vx = 0.0f, vy = 0.0f, vz = 1.0f;
+    {
+        const int py_screen = (p.H - 1) - y;
+        const float fx = ((float)x + 0.5f) / (float)p.W;
+        const float fy = ((float)py_screen + 0.5f) / (float)p.H;
+        const float ndc_x = fx * 2.0f - 1.0f;
+        const float ndc_y = 1.0f - fy * 2.0f;
+        float wf[4];
+        m4v(p.inv_vp, ndc_x, ndc_y, 1.0f, 1.0f, wf);
+        if (!(fabsf(wf[3]) < 1e-8f)) {
+            const float dx = wf[0] / wf[3] - p.cam[0], dy = wf[1] / wf[3] - p.cam[1], dz = wf[2] / wf[3] - p.cam[2];
+            const float len = sqrtf((dx * dx + dy * dy) + dz * dz);
+            if (!(len < 1e-6f)) {
+                vx = dx / len;
+                vy = dy / len;
+                vz = dz / len;
+            }
+        }
+    }
+    const float cos_theta = (vx * p.sun[0] + vy * p.sun[1]) + vz * p.sun[2];
+    // phase_hg (:1432-1440); g's clamp and its products are the host's
+    const float phase = p.one_m_gg / pow15_r(s_max(1e-4f, p.one_p_gg - p.g2 * clampf(cos_theta, -1.0f, 1.0f)));
+    const float gate = clampf((cos_theta - 0.1f) / 0.9f, 0.0f, 1.0f);
+    const float ds = ray_max / (float)p.steps;
+    const uint32_t seed = ((uint32_t)x * 1973u) ^ ((uint32_t)y * 9277u);
+    const float random_val = (float)(seed & 0xffffu) / 65536.0f;
+    float t = p.min_dist + (random_val * ds) * p.jitter;
+    float Tm = 1.0f, lr = 0.0f, lg = 0.0f, lb = 0.0f;
+    int acc = 0;
+    for (int k = 0; k < p.steps; ++k) {
+        if (t >= ray_max) break;
+        const float wx = p.cam[0] + vx * t, wy = p.cam[1] + vy * t, wz = p.cam[2] + vz * t;
+        float vis = 1.0f;
+        if (SHADOW) vis = ls_visibility(p, wx, wy, wz);   // ahead of the density tests: the gathers fly under the sin / cos / exp
+        const float h = s_max(0.0f, wy);
+        float dens = p.base_density * exp_r(-h * p.height_falloff);   // fog_density (:1423-1429)
+        if (dens > 1e-6f) {   // volumetric_cloud_noise (:1516-1522)
+            const float sx = wx * p.noise_scale, sy = wy * p.noise_scale, sz = wz * p.noise_scale;
+            const float n = (sin_r(sx) * cos_r(sy)) * sin_r(sz + sx * 0.5f);
+            const float dust = n * 0.5f + 0.5f;
+            dens *= 1.0f * (1.0f - p.noise_strength) + dust * p.noise_strength;
+        }
+        if (dens > 1e-6f) {
+            const float sigma_s = p.sigma_s * dens;
+            const float sigma_t = p.sigma_t * dens;
+            const float direct_light = (phase * vis) * gate;
+            const float light_term = direct_light * p.intensity + p.ambient;
+            float scatter = ((Tm * sigma_s) * light_term) * ds;
+            const float dist01 = t / p.dist_den;
+            const float dist_fall = 1.0f - dist01 * dist01;
+            scatter *= dist_fall;
+            const float iv = 1.0f - vis;   // glm::mix(ambient_tint, shafts_tint, vis)
+            lr += (0.60f * iv + 0.92f * vis) * scatter;
+            lg += (0.65f * iv + 0.96f * vis) * scatter;
+            lb += (0.70f * iv + 1.00f * vis) * scatter;
+            Tm *= exp_r(-sigma_t * ds);
+            ++acc;
+            if (Tm < 0.01f) break;
+        }
+        t += ds;
+    }
+    const float ls[3] = {lr, lg, lb};
+    float out[3];
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+        float o = p.srgb_lut[(base >> (8 * ch)) & 0xffu] + ls[ch];    // srgb_to_linear(color_to_srgb01(base)) + Ls
+        o = o / (1.0f + o * 0.15f);
+        o = s_min(s_max(o, 0.0f), 1.0f);                              // glm::clamp
+        o = pow_r(s_min(s_max(o, 0.0f), 1.0f), 1.0f / 2.2f);          // linear_to_srgb
+        out[ch] = s_min(s_max(o, 0.0f), 1.0f) * 255.0f;               // rgb01_to_color before the truncation
+    }
+    uint32_t rgba = 0xff000000u;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) rgba |= (out[ch] == out[ch] ? (uint32_t)(int32_t)out[ch] & 0xffu : 0u) << (8 * ch);
+    p.dst[i] = rgba;
+    if (p.pq) p.pq[i] = make_float4(out[0], out[1], out[2], (float)acc);
+}
+
 }  // namespace shs_dev
 
 namespace shs_internal {
@@ -236,6 +394,13 @@ hipError_t launch_canvas_autofocus(const CanvasDofParams &p, hipStream_t s) {
 
 hipError_t launch_canvas_dof_composite(const CanvasDofParams &p, hipStream_t s) {
     hipLaunchKernelGGL(k_canvas_dof_composite, px_grid(p.W, p.H), dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_canvas_light_shafts(const CanvasLSParams &p, hipStream_t s) {
+    const dim3 grid((unsigned)((p.W + 31) / 32), (unsigned)((p.H + 7) / 8));
+    if (p.map) hipLaunchKernelGGL(k_canvas_light_shafts<true>, grid, dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(k_canvas_light_shafts<false>, grid, dim3(256), 0, s, p);
     return hipGetLastError();
 }
 

@@ -381,6 +381,9 @@ struct shs_ctx {
     float rt_sky_cam[9] = {};             // forward, right, up, normalised
     float rt_sky_tan = 0.0f;              // std::tan(glm::radians(fov_degrees) * 0.5f)
     DevBuf<float> rt_sky_io;
+    // shs_canvas_light_shafts over host buffers (shs_abi_canvas_post.cpp): the staged shadow map and prequant plane
+    DevBuf<float> cp_map;
+    DevBuf<float4> cp_pq;
 };
 
 // Re-enqueues the tonemap after lib_finish re-issued the camera pass (shs_abi_post.cpp).

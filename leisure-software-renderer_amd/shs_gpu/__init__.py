@@ -674,6 +674,65 @@ class Context:
                                              _ptr(blur), ctypes.byref(f), self.CANVAS_DEVICE if dev else 0))
         return color, blur, f.value
 
+    # LightShaftParams (hello_pbr_light_shafts.cpp:189-218), the demo's values
+    LIGHT_SHAFTS_DEFAULTS = dict(enable=True, steps=40, max_dist=110.0, min_dist=1.0, base_density=0.18, height_falloff=0.10,
+                                 noise_scale=0.65, noise_strength=0.60, jitter_amount=1.0, ambient_strength=0.08,
+                                 sigma_s=0.030, sigma_t=0.065, g=0.82, intensity=0.35, use_shadow=True, shadow_bias=0.0045,
+                                 shadow_pcf_2x2=True)
+
+    def canvas_light_shafts(self, src, depth, cam_pos, inv_view_proj, sun_dir_world, light_vp=None, shadow_map=None,
+                            shadow_size=None, params=None, dst=None, prequant=False):
+        """light_shafts_pass (hello_pbr_light_shafts.cpp:1525-1707).  Host arrays: src uint8 [H, W, 4], depth float32
+        [H, W] (view z, FLT_MAX = empty) -> dst uint8 [H, W, 4]; torch CUDA tensors of the same shapes run on the
+        device (asynchronous on the context stream; dst may be src).  shadow_map: float32 [h, w] of the same kind as
+        src, or a device address with shadow_size = (w, h) (rt_device_shadow_map), or None (every step lit).
+        params: LightShaftParams fields over LIGHT_SHAFTS_DEFAULTS.  prequant: also return float32 [H, W, 4], the
+        colour * 255 before the byte truncation and the accumulated step count ((0, 0, 0, -1): a copied pixel)."""
+        H, W = src.shape[:2]
+        vals = dict(self.LIGHT_SHAFTS_DEFAULTS)
+        unknown = set(params or ()) - set(vals)
+        if unknown:
+            raise TypeError(f"canvas_light_shafts: unknown parameters {sorted(unknown)}")
+        vals.update(params or {})
+        d = _abi.CanvasLightShaftsDescC()
+        d.width, d.height = W, H
+        for k in range(3):
+            d.cam_pos[k], d.sun_dir_world[k] = float(cam_pos[k]), float(sun_dir_world[k])
+        lvp = np.zeros(16, np.float32) if light_vp is None else np.asarray(light_vp, np.float32).reshape(16)
+        ivp = np.asarray(inv_view_proj, np.float32).reshape(16)
+        for k in range(16):
+            d.inv_view_proj[k], d.light_vp[k] = float(ivp[k]), float(lvp[k])
+        for name, ctype in _abi.CanvasLightShaftsDescC._fields_[8:]:
+            setattr(d, name, int(vals[name]) if ctype is ctypes.c_int32 else float(vals[name]))
+        dev = _is_device(src)
+        if dev:
+            self._on_torch_stream()
+        if dst is None:
+            dst = _empty_like(src)
+        src, depth = _host_c(src, np.uint8), _host_c(depth, np.float32)
+        map_ptr = None
+        if isinstance(shadow_map, (int, np.integer)):
+            if not dev:
+                raise ValueError("canvas_light_shafts: a device shadow map goes with device buffers")
+            d.shadow_w, d.shadow_h = shadow_size
+            map_ptr = ctypes.c_void_p(int(shadow_map))
+        elif shadow_map is not None:
+            if _is_device(shadow_map) != dev:
+                raise ValueError("canvas_light_shafts: shadow_map must live where src does")
+            shadow_map = _host_c(shadow_map, np.float32)
+            d.shadow_h, d.shadow_w = shadow_map.shape
+            map_ptr = _ptr(shadow_map)
+        pq = None
+        if prequant:
+            if dev:
+                import torch
+                pq = torch.empty((H, W, 4), dtype=torch.float32, device=src.device)
+            else:
+                pq = np.empty((H, W, 4), np.float32)
+        self._check(self._lib.shs_canvas_light_shafts(self._h, ctypes.byref(d), _ptr(src), _ptr(depth), map_ptr, _ptr(dst),
+                                                      None if pq is None else _ptr(pq), self.CANVAS_DEVICE if dev else 0))
+        return (dst, pq) if prequant else dst
+
     # -- Canvas render-target raster (hello_shadow_mapping.cpp PASS0 / PASS1) ---------------------
     def _rt_draw_array(self, draws):
         arr = (_abi.RtDrawC * max(len(draws), 1))()
@@ -855,6 +914,12 @@ class Context:
         a, b, c = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
         self._check(self._lib.shs_rt_device_targets(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
         return a.value, b.value, c.value
+
+    def rt_device_shadow_map(self):
+        """-> (device address of the last rt_render_shadow's map, (w, h)): w * h float32, y down."""
+        a, w, h = ctypes.c_void_p(), ctypes.c_int32(), ctypes.c_int32()
+        self._check(self._lib.shs_rt_device_shadow_map(self._h, ctypes.byref(a), ctypes.byref(w), ctypes.byref(h)))
+        return a.value, (w.value, h.value)
 
     def lib_device_targets(self):
         """Device pointers of the library targets: (hdr float4 W*H, depth W*H, motion float2 W*H)."""

@@ -211,6 +211,20 @@ class CanvasDofDescC(ctypes.Structure):
                 ("range", ctypes.c_float), ("max_blur", ctypes.c_float)]
 
 
+class CanvasLightShaftsDescC(ctypes.Structure):
+    """shs_canvas_light_shafts_desc: the pass's inputs, then LightShaftParams in its order (bools as int32)."""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("cam_pos", ctypes.c_float * 3),
+                ("inv_view_proj", _F16), ("sun_dir_world", ctypes.c_float * 3), ("light_vp", _F16),
+                ("shadow_w", ctypes.c_int32), ("shadow_h", ctypes.c_int32),
+                ("enable", ctypes.c_int32), ("steps", ctypes.c_int32), ("max_dist", ctypes.c_float),
+                ("min_dist", ctypes.c_float), ("base_density", ctypes.c_float), ("height_falloff", ctypes.c_float),
+                ("noise_scale", ctypes.c_float), ("noise_strength", ctypes.c_float), ("jitter_amount", ctypes.c_float),
+                ("ambient_strength", ctypes.c_float), ("sigma_s", ctypes.c_float), ("sigma_t", ctypes.c_float),
+                ("g", ctypes.c_float), ("intensity", ctypes.c_float), ("use_shadow", ctypes.c_int32),
+                ("shadow_bias", ctypes.c_float), ("shadow_pcf_2x2", ctypes.c_int32)]
+
+
+CANVAS_LIGHT_SHAFTS_MAX_STEPS = 4096
 RT_USE_SHADOW, RT_PCF, RT_PREQUANT = 1, 2, 4
 
 
@@ -369,6 +383,9 @@ SIGNATURES = [
     ("shs_canvas_motion_blur", ctypes.c_int, [_P, ctypes.POINTER(CanvasMotionBlurDescC), _P, _P, _P, _P, ctypes.c_uint32]),
     ("shs_canvas_gaussian_blur", ctypes.c_int, [_P, ctypes.c_int32, ctypes.c_int32, _P, _P, ctypes.c_int32, ctypes.c_uint32]),
     ("shs_canvas_dof", ctypes.c_int, [_P, ctypes.POINTER(CanvasDofDescC), _P, _P, _P, _F, ctypes.c_uint32]),
+    ("shs_canvas_light_shafts", ctypes.c_int, [_P, ctypes.POINTER(CanvasLightShaftsDescC), _P, _P, _P, _P, _P, ctypes.c_uint32]),
+    ("shs_rt_device_shadow_map", ctypes.c_int, [_P, ctypes.POINTER(_P), ctypes.POINTER(ctypes.c_int32),
+                                                ctypes.POINTER(ctypes.c_int32)]),
     ("shs_rt_render_shadow", ctypes.c_int, [_P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _F,
                                             ctypes.POINTER(RtDrawC), ctypes.c_int32]),
     ("shs_rt_render", ctypes.c_int, [_P, ctypes.POINTER(RtFrameC), ctypes.POINTER(RtDrawC), ctypes.c_int32]),
