@@ -887,7 +887,14 @@ int shs_canvas_light_shafts(shs_ctx *ctx, const shs_canvas_light_shafts_desc *de
  *      lookup of shading 0 (SHS_RT_USE_SHADOW, SHS_RT_PCF, bias_base, bias_slope), plus image-based lighting
  *      from the EnvIBL of shs_rt_set_ibl; Reinhard tonemap and gamma 2.2 to bytes.  The velocity plane is
  *      written as for shading 0.  Its skybox_background_pass (:733-799) is shs_rt_set_sky below.  Not built: the
- *      IBL precompute, which stays on the host (its results come in through shs_rt_set_ibl). */
+ *      IBL precompute, which stays on the host (its results come in through shs_rt_set_ibl).
+ *   3  fragment_shader_pbr of hello_pbr_light_shafts.cpp (:768-850), through shs_rt_render_pbr_soft only.  That
+ *      demo's PASS1 raster (:1015-1180) is hello_pbr.cpp's with tile jobs of 160 (:117-118).  The shader is shading
+ *      2's with three differences: the shadow factor is pcss_shadow_factor (:650-762, shading 1's text; the
+ *      constants of shs_rt_set_pcss, whose defaults are this demo's :135-148 too, and shading 1's rotation table),
+ *      so SHS_RT_PCF has no effect; there is no minimum-ambient term; the direct radiance is the literal 3.0,
+ *      shs_rt_pbr::direct_intensity's default.  The velocity plane is written as for shading 2; the prequant
+ *      plane's fourth float is the PCSS factor. */
 typedef struct shs_rt_draw {
     int32_t mesh_id;            /* shs_mesh_upload_soup[_uv] soup (without UVs: vec2(0) per corner) */
     int32_t albedo_tex;         /* shs_texture_upload id (use_texture), 0: base_color */
@@ -911,7 +918,9 @@ typedef struct shs_rt_frame {
     float max_velocity_px;            /* MB_MAX_PIXELS (22) */
     uint32_t flags;                   /* SHS_RT_* */
     int32_t shading;                  /* 0: fragment_shader_full, 1: fragment_shader_softshadow,
-                                         2: fragment_shader_pbr (shs_rt_render_pbr) */
+                                         2: fragment_shader_pbr (shs_rt_render_pbr),
+                                         3: hello_pbr_light_shafts.cpp's fragment_shader_pbr :768-850 over
+                                            pcss_shadow_factor :650-762 (shs_rt_render_pbr_soft) */
 } shs_rt_frame;
 /* The PCSS constants of shading 1 (hello_shadow_mapping_soft.cpp:101-116), kept in the context. */
 typedef struct shs_rt_pcss {
@@ -940,7 +949,7 @@ typedef struct shs_rt_stats {
 int shs_rt_render_shadow(shs_ctx *ctx, int32_t w, int32_t h, int32_t ref_tile_w, int32_t ref_tile_h, const float light_vp[16],
                          const shs_rt_draw *casters, int32_t n_casters);
 /* SHS_ERR_INVALID: an unknown mesh or texture id, a non-positive size, unknown flags, a shading other than
- * 0 or 1 (2 goes through shs_rt_render_pbr), or SHS_RT_USE_SHADOW without a shadow map rendered before. */
+ * 0 or 1 (2 goes through shs_rt_render_pbr, 3 through shs_rt_render_pbr_soft), or SHS_RT_USE_SHADOW without a shadow map rendered before. */
 int shs_rt_render(shs_ctx *ctx, const shs_rt_frame *frame, const shs_rt_draw *draws, int32_t n_draws);
 /* Host copies of the last camera pass (any pointer may be NULL): color W*H*4 bytes, depth W*H floats,
  * velocity W*H*2 floats.  Synchronous. */
@@ -986,6 +995,11 @@ int shs_rt_set_ibl(shs_ctx *ctx, int32_t irr_size, const float *irr, int32_t spe
  * SHS_ERR_INVALID as shs_rt_render, and for any other shading. */
 int shs_rt_render_pbr(shs_ctx *ctx, const shs_rt_frame *frame, const shs_rt_draw *draws, const shs_rt_pbr_draw *pbr_draws,
                       int32_t n_draws);
+/* PASS1 of hello_pbr_light_shafts.cpp: the raster of shs_rt_render_pbr with that demo's fragment_shader_pbr (PBR
+ * under PCSS, no minimum ambient).  frame->shading must be 3.  SHS_ERR_INVALID as shs_rt_render_pbr, and for any other
+ * shading; a frame of more than 2^26 pixels (the rotation table of shading 1). */
+int shs_rt_render_pbr_soft(shs_ctx *ctx, const shs_rt_frame *frame, const shs_rt_draw *draws, const shs_rt_pbr_draw *pbr_draws,
+                           int32_t n_draws);
 /* sample_cubemap_linear_vec(env_irradiance, dir) and sample_prefiltered_spec_trilinear(spec, dir, lod)
  * (ibl.hpp:236-286) of the context's IBL for n directions through the device functions the raster calls: dirs3
  * 3n, lod n, both outputs 3n.  Synchronous; for tests of the edge cases.  SHS_ERR_INVALID without an IBL. */
@@ -995,7 +1009,7 @@ int shs_rt_ibl_samples(shs_ctx *ctx, int32_t n, const float *dirs3, const float 
  * (:552-611) and CubeMapSky with sample_face_bilinear (:432-517).  (These are not the library path's ProceduralSky /
  * CubemapSky of shs_lib_set_sky; the legacy ProceduralSky :520-549 is not built: no render-target demo constructs it.)
  * The reference draws the sky first and the triangles over it.  Here, with a sky bound, every camera pass
- * (shs_rt_render, shs_rt_render_pbr, whatever the shading) is followed on the context stream by a background pass
+ * (shs_rt_render, shs_rt_render_pbr, shs_rt_render_pbr_soft, whatever the shading) is followed on the context stream by a background pass
  * that colours each pixel that shows no fragment (shs_rt_resolve_ids: -1) -- also one whose fragment kept its depth
  * but not its colour -- from the direction through the pixel's centre (:769-780; canvas x, y with y up).  Such a
  * pixel's prequant floats are (r, g, b) * 255 before the truncation and 1; depth and velocity stay as the raster

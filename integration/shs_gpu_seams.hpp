@@ -410,9 +410,7 @@ public:
         std::memcpy(f.light_dir_world, glm::value_ptr(light_dir_world), 12);
         std::memcpy(f.camera_pos, glm::value_ptr(scene_->viewer->position), 12);
         f.bias_base = 0.0025f; f.bias_slope = 0.01f; f.max_velocity_px = 22.0f;      // SHADOW_BIAS_* :113-114, MB_MAX_PIXELS
-        f.flags = SHS_RT_USE_SHADOW | SHS_RT_PCF;                                    // SHADOW_USE_PCF :117
-        f.shading = 2;
-        ok(shs_rt_render_pbr(dev_->ctx, &f, draws.data(), mats.data(), (int32_t)draws.size()));
+        ok(render_pass1(f, draws.data(), mats.data(), (int32_t)draws.size()));
         void *color = nullptr, *depth = nullptr, *velocity = nullptr;
         ok(shs_rt_device_targets(dev_->ctx, &color, &depth, &velocity));
         // PASS2 on the device (shs_canvas_motion_blur with SHS_CANVAS_DEVICE into a device buffer of the host's), or
@@ -427,11 +425,46 @@ public:
     glm::mat4 light_vp{1.0f};
     glm::vec3 light_dir_world{0.4668f, -0.3487f, 0.8127f};   // LIGHT_DIR_WORLD (the shader normalises it)
 
-private:
+protected:
+    // PASS1's fragment shader: hello_pbr.cpp's under the 2x2 PCF.  PbrSoftShadowSystemGPU below replaces it.
+    virtual int render_pass1(shs_rt_frame &f, const shs_rt_draw *draws, const shs_rt_pbr_draw *mats, int32_t n) {
+        f.flags = SHS_RT_USE_SHADOW | SHS_RT_PCF;                                    // SHADOW_USE_PCF :117
+        f.shading = 2;
+        return shs_rt_render_pbr(dev_->ctx, &f, draws, mats, n);
+    }
+
     SceneT *scene_;
     Device *dev_;
+
+private:
     int sm_, tile_;
     glm::mat4 prev_vp_{1.0f};
+};
+
+// -----------------------------------------------------------------------------------------------------
+// Seam 1b, PBR under PCSS -- hello-render-target/hello_pbr_light_shafts.cpp, PASS0 and PASS1.
+//
+// That demo's RendererSystem::process is hello_pbr.cpp's up to the fragment shader: PASS1 runs its own
+// fragment_shader_pbr (:768-850) -- pcss_shadow_factor (:650-762) for the 2x2 PCF, no minimum ambient, a direct
+// radiance of 3.0 -- through shs_rt_render_pbr_soft and shading = 3, over a 1024^2 map (SHADOW_MAP_SIZE :123) and tile
+// jobs of 160.  The PCSS constants (:135-148) and the PBR constants are the context's defaults; set_pcss / set_pbr
+// change them.  set_ibl and set_sky are PbrSystemGPU's.  LightShaftsGPU::apply (PASS1.5) and shs_canvas_motion_blur
+// (PASS2) follow on the same stream.  Uncompiled, like the other seams.
+// -----------------------------------------------------------------------------------------------------
+template <class SceneT>
+class PbrSoftShadowSystemGPU : public PbrSystemGPU<SceneT> {
+public:
+    PbrSoftShadowSystemGPU(SceneT *scene, Device *dev, int shadow_size = 1024, int tile = 160)
+        : PbrSystemGPU<SceneT>(scene, dev, shadow_size, tile) {}
+
+    void set_pcss(const shs_rt_pcss *pcss) { this->ok(shs_rt_set_pcss(this->dev_->ctx, pcss)); }   // nullptr: the demo's constants
+
+protected:
+    int render_pass1(shs_rt_frame &f, const shs_rt_draw *draws, const shs_rt_pbr_draw *mats, int32_t n) override {
+        f.flags = SHS_RT_USE_SHADOW;                                                 // (SHS_RT_PCF has no effect here)
+        f.shading = 3;
+        return shs_rt_render_pbr_soft(this->dev_->ctx, &f, draws, mats, n);
+    }
 };
 
 // -----------------------------------------------------------------------------------------------------
@@ -441,9 +474,8 @@ private:
 // left on the device: after a PbrSystemGPU::process (or any shs_rt_render*) call apply(); the colour plane of
 // shs_rt_device_targets is rewritten in place, the shadow map is the one of shs_rt_device_shadow_map, and
 // shs_canvas_motion_blur (PASS2) follows on the same stream.  ParamsT is that file's LightShaftParams (:189-218).
-// That demo's PASS1 shader is not hello_pbr.cpp's (PCSS instead of the 2x2 PCF, no minimum ambient): its port is
-// not built yet, so a frame through PbrSystemGPU differs from the demo's in the shadows' penumbrae.  Uncompiled,
-// like the other seams.
+// That demo's PASS1 shader is not hello_pbr.cpp's (PCSS instead of the 2x2 PCF, no minimum ambient): it is
+// PbrSoftShadowSystemGPU above, not PbrSystemGPU.  Uncompiled, like the other seams.
 // -----------------------------------------------------------------------------------------------------
 template <class SceneT>
 class LightShaftsGPU {

@@ -8,6 +8,8 @@
 // and of hello_pbr.cpp ("pbr :line"): shs_rt_render_pbr (its PASS1, pbr :883-1045 with fragment_shader_pbr :627-727),
 // shs_rt_set_pbr (the constants pbr :150-155), shs_rt_set_ibl (EnvIBL, shs/resources/ibl.hpp:21-59) and
 // shs_rt_ibl_samples (the two IBL samplers alone, ibl.hpp:215-286);
+// and of hello_pbr_light_shafts.cpp: shs_rt_render_pbr_soft (its PASS1, :1015-1180 with fragment_shader_pbr :768-850 over
+// pcss_shadow_factor :650-762), which binds what shading 1 and shading 2 bind;
 // and the background of hello_pbr.cpp, hello_pbr_light_shafts.cpp and hello_ibl_skybox.cpp: shs_rt_set_sky
 // (skybox_background_pass pbr :733-799 over AnalyticSky / CubeMapSky, hello-shs-renderer/shs_renderer.hpp:432-611; the
 // host does what depends on the sun direction and the camera alone) and shs_rt_sky_samples (sky.sample alone).
@@ -147,7 +149,7 @@ int ensure_rotations(shs_ctx *ctx, int W, int H) {
     if (ctx->rt_rot.p && ctx->rt_rot_w == W && ctx->rt_rot_h == H) return SHS_OK;
     const size_t npx = (size_t)W * H;
     if (npx > ((size_t)1 << 26)) {
-        ctx->err = "render-target frame: shading 1 keeps 16 B per pixel, at most 2^26 pixels";
+        ctx->err = "render-target frame: shadings 1 and 3 keep 16 B per pixel, at most 2^26 pixels";
         return SHS_ERR_INVALID;
     }
     ctx->rt_rot_w = ctx->rt_rot_h = 0;
@@ -206,8 +208,8 @@ int upload_and_launch(shs_ctx *ctx, shs_dev::RtParams &p, bool shadow_pass, int 
     return SHS_OK;
 }
 
-// PASS1 of the three demos: pbr null for shading 0 / 1 (shs_rt_render), the per-draw PBR uniforms for shading 2
-// (shs_rt_render_pbr).  Nothing of the context changes before the last rejection.
+// PASS1 of the four demos: pbr null for shading 0 / 1 (shs_rt_render), the per-draw PBR uniforms for shading 2
+// (shs_rt_render_pbr) and 3 (shs_rt_render_pbr_soft).  Nothing of the context changes before the last rejection.
 int render_camera(shs_ctx *ctx, const shs_rt_frame *f, const shs_rt_draw *draws, const shs_rt_pbr_draw *pbr, int32_t n_draws) {
     if (!size_ok(ctx, f->width, f->height, f->ref_tile_w, f->ref_tile_h)) return SHS_ERR_INVALID;
     if (f->flags & ~(SHS_RT_USE_SHADOW | SHS_RT_PCF | SHS_RT_PREQUANT)) {
@@ -253,7 +255,7 @@ int render_camera(shs_ctx *ctx, const shs_rt_frame *f, const shs_rt_draw *draws,
     p.velocity = reinterpret_cast<float2 *>(ctx->rt_vel.p);
     p.prequant = pq ? ctx->rt_pq.p : nullptr;
     p.ids = ctx->rt_ids.p;
-    if (f->shading == 1) {
+    if (f->shading == 1 || f->shading == 3) {
         const int rr = ensure_rotations(ctx, f->width, f->height);
         if (rr) return rr;
         p.rot = ctx->rt_rot.p;
@@ -266,7 +268,7 @@ int render_camera(shs_ctx *ctx, const shs_rt_frame *f, const shs_rt_draw *draws,
         p.pcss_blockers = c.blocker_samples;
         p.pcss_taps = c.pcf_samples;
     }
-    if (f->shading == 2) {
+    if (f->shading == 2 || f->shading == 3) {
         if (ensure_srgb_table(ctx)) return SHS_ERR_HIP;
         p.srgb_lut = ctx->rt_srgb_lut.p;
         p.ibl = ctx->rt_ibl_mips > 0 ? ctx->rt_ibl.p : nullptr;
@@ -350,6 +352,16 @@ int shs_rt_render_pbr(shs_ctx *ctx, const shs_rt_frame *f, const shs_rt_draw *dr
     if (!ctx || !f || n_draws < 0 || (n_draws > 0 && (!draws || !pbr_draws))) return SHS_ERR_INVALID;
     if (f->shading != 2) {
         ctx->err = "shs_rt_render_pbr: shading " + std::to_string(f->shading) + " (2: fragment_shader_pbr)";
+        return SHS_ERR_INVALID;
+    }
+    static const shs_rt_pbr_draw none{};
+    return render_camera(ctx, f, draws, n_draws > 0 ? pbr_draws : &none, n_draws);
+}
+
+int shs_rt_render_pbr_soft(shs_ctx *ctx, const shs_rt_frame *f, const shs_rt_draw *draws, const shs_rt_pbr_draw *pbr_draws, int32_t n_draws) {
+    if (!ctx || !f || n_draws < 0 || (n_draws > 0 && (!draws || !pbr_draws))) return SHS_ERR_INVALID;
+    if (f->shading != 3) {
+        ctx->err = "shs_rt_render_pbr_soft: shading " + std::to_string(f->shading) + " (3: fragment_shader_pbr under PCSS)";
         return SHS_ERR_INVALID;
     }
     static const shs_rt_pbr_draw none{};

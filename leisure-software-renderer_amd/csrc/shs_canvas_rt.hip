@@ -15,6 +15,10 @@
 //   shading 2  fragment_shader_pbr (pbr :627-727): Cook-Torrance GGX under the 2x2-PCF shadow, plus image-based
 //          lighting from an irradiance cubemap and a prefiltered-specular mip chain (shs/resources/ibl.hpp:215-286;
 //          RtParams::ibl).  k_rt_raster<false, 2>, launched by shs_rt_render_pbr, again differs in the shade alone.
+// and for hello_pbr_light_shafts.cpp ("shafts :line"), whose PASS1 raster (shafts :1015-1180) is hello_pbr.cpp's:
+//   shading 3  its fragment_shader_pbr (shafts :768-850): the shader of shading 2 under pcss_shadow_factor (shafts
+//          :650-762, the soft demo's text) instead of the 2x2 PCF, without the minimum-ambient term.
+//          k_rt_raster<false, 3>, launched by shs_rt_render_pbr_soft, is shade_pixel_pbr<true>.
 //   the background  skybox_background_pass (pbr :733-799; the same routine in hello_pbr_light_shafts.cpp and
 //          hello_ibl_skybox.cpp) over the legacy AnalyticSky / CubeMapSky of hello-shs-renderer/shs_renderer.hpp:
 //          k_rt_sky<MODEL, ENCODE>, a pass of its own after k_rt_raster when a sky is bound (shs_rt_set_sky), which
@@ -664,7 +668,13 @@ __device__ __forceinline__ float encode_reinhard(float x, float exposure) {
 // The shown fragment of hello_pbr.cpp's camera pass (pbr :986-1035, the hard demo's interpolation and velocity)
 // through fragment_shader_pbr (pbr :627-727): Cook-Torrance GGX under the hard demo's shadow lookup, plus the
 // irradiance and prefiltered-specular IBL.  The direct term is finished before the IBL gathers start.
-__device__ void shade_pixel_pbr(const RtParams &p, int32_t id, float u, float v, float w, uint32_t &rgba, float2 &vel, float4 &pq) {
+// SOFT: hello_pbr_light_shafts.cpp's fragment_shader_pbr (shafts :768-850) at screen pixel (px, py) instead -- the same
+// text but for the shadow factor, which is pcss_shadow_factor over the bias of shafts :814-815 (SHS_RT_PCF is not read),
+// and the missing minimum ambient.  Its ShadowMap is the legacy one, FLT_MAX outside, where the soft demo's clamps:
+// pcss_tap never looks outside.
+template <bool SOFT>
+__device__ void shade_pixel_pbr(const RtParams &p, int32_t id, float u, float v, float w, int px, int py, uint32_t &rgba, float2 &vel,
+                                float4 &pq) {
     const RtRec &r = p.recs[id];
     const RtVary &y = p.vary[id];
     const RtDrawGPU &dr = p.draws[r.draw];
@@ -738,7 +748,27 @@ __device__ void shade_pixel_pbr(const RtParams &p, int32_t id, float u, float v,
     const float DG = D * G;
     const float den = g_max(1e-6f, 4.0f * NoV * NoL);
     float shadow = 1.0f;
-    if (p.shadow) shadow = shadow_factor(p, wp, ndotl);
+    if constexpr (SOFT) {
+        if (p.shadow) {
+            // shadow_uvz_from_world (shafts :558-576)
+            float cx, cy, cz, cw;
+            m4p(p.light_vp, wp.x, wp.y, wp.z, cx, cy, cz, cw);
+            if (!(fabsf(cw) < 1e-6f)) {
+                const float nx = cx / cw, ny = cy / cw, z = cz / cw;
+                if (!(z < 0.0f || z > 1.0f)) {
+                    const float su = nx * 0.5f + 0.5f;
+                    const float sv = 1.0f - (ny * 0.5f + 0.5f);
+                    const float slope = 1.0f - g_clamp01(ndotl);
+                    const float bias = p.bias_base + p.bias_slope * slope;
+                    const PcssMap m = {p.shadow, p.sw, p.sh, p.pcss_light, p.pcss_search, p.pcss_min, p.pcss_max, p.pcss_eps,
+                                       p.pcss_blockers, p.pcss_taps};
+                    shadow = pcss_shadow_factor(m, su, sv, z, bias, p.rot[(size_t)py * p.W + px]);
+                }
+            }
+        }
+    } else {
+        if (p.shadow) shadow = shadow_factor(p, wp, ndotl);
+    }
     f3 c;
     {
         const float ipi = 1.0f / PI;
@@ -764,7 +794,8 @@ __device__ void shade_pixel_pbr(const RtParams &p, int32_t id, float u, float v,
     const float bs[3] = {base.x, base.y, base.z};
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
-        const float x = out[i] + (bs[i] * 0.03f) * ao;   // the minimum ambient
+        float x = out[i];
+        if constexpr (!SOFT) x = x + (bs[i] * 0.03f) * ao;   // the minimum ambient (hello_pbr.cpp alone)
         out[i] = encode_reinhard(x, p.pbr_exposure);
     }
     rgba = byte_x86(out[0]) | (byte_x86(out[1]) << 8) | (byte_x86(out[2]) << 16) | 0xff000000u;
@@ -868,7 +899,9 @@ __global__ __launch_bounds__(256) void k_rt_raster(const RtParams p) {
     if constexpr (SHADING == 1) {
         if (sid >= 0) shade_pixel_soft(p, sid, su, sv, sw, px, py, rgba, pq);   // the velocity plane stays zero
     } else if constexpr (SHADING == 2) {
-        if (sid >= 0) shade_pixel_pbr(p, sid, su, sv, sw, rgba, vel, pq);
+        if (sid >= 0) shade_pixel_pbr<false>(p, sid, su, sv, sw, px, py, rgba, vel, pq);
+    } else if constexpr (SHADING == 3) {
+        if (sid >= 0) shade_pixel_pbr<true>(p, sid, su, sv, sw, px, py, rgba, vel, pq);
     } else {
         if (sid >= 0) shade_pixel(p, sid, su, sv, sw, rgba, vel, pq);
     }
@@ -1092,6 +1125,7 @@ hipError_t launch_canvas_rt(const shs_dev::RtParams &p, bool shadow_pass, int sh
     if (shadow_pass) hipLaunchKernelGGL(k_rt_raster<true>, dim3(tiles), dim3(256), 0, s, p);
     else if (shading == 1) hipLaunchKernelGGL((k_rt_raster<false, 1>), dim3(tiles), dim3(256), 0, s, p);
     else if (shading == 2) hipLaunchKernelGGL((k_rt_raster<false, 2>), dim3(tiles), dim3(256), 0, s, p);
+    else if (shading == 3) hipLaunchKernelGGL((k_rt_raster<false, 3>), dim3(tiles), dim3(256), 0, s, p);
     else hipLaunchKernelGGL(k_rt_raster<false>, dim3(tiles), dim3(256), 0, s, p);
     return hipGetLastError();
 }

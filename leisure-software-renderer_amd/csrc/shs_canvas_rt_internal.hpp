@@ -1,7 +1,8 @@
 // shs_canvas_rt_internal.hpp -- launch interface of shs_canvas_rt.hip: the Canvas render-target raster of
 // hello-render-target/hello_shadow_mapping.cpp (shadow pass and shadowed camera pass; include/shs_gpu.h) and
 // of hello_shadow_mapping_soft.cpp (the same passes with the PCSS fragment shader, shs_rt_frame::shading 1) and
-// hello_pbr.cpp (the same passes with the GGX + IBL fragment shader, shading 2 through shs_rt_render_pbr), and of the
+// hello_pbr.cpp (the same passes with the GGX + IBL fragment shader, shading 2 through shs_rt_render_pbr) and
+// hello_pbr_light_shafts.cpp (that shader under the PCSS factor, shading 3 through shs_rt_render_pbr_soft), and of the
 // background pass behind any of them (skybox_background_pass over the legacy sky models, shs_rt_set_sky).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -92,11 +93,11 @@ struct RtParams {
     float2 *velocity;
     float4 *prequant;                // or null
     int32_t *ids;
-    // shading 1 only (appended: the hard instantiations' argument offsets stay as they were)
+    // shadings 1 and 3 only (appended: the hard instantiations' argument offsets stay as they were)
     const float4 *rot;               // per screen pixel py * W + px: {cos(ang), sin(ang), cos(ang2), sin(ang2)}
     float pcss_light, pcss_search, pcss_min, pcss_max, pcss_eps;   // shs_rt_pcss
     int32_t pcss_blockers, pcss_taps;
-    // shading 2 only (appended likewise)
+    // shadings 2 and 3 only (appended likewise)
     const RtPbrDrawGPU *pbr_draws;   // element i goes with draws[i]
     const float *srgb_lut;           // 256 floats: pow(c / 255, 2.2) with the host's libm
     const float4 *ibl;               // the levels above, or null: u.ibl == nullptr
@@ -174,7 +175,7 @@ hipError_t launch_canvas_rt_sky(const shs_dev::RtSkyParams &p, int model, int en
 hipError_t launch_sky_samples(const shs_dev::RtSkySamples &q, int model, hipStream_t s);
 // setup (one lane per input triangle) then raster (one workgroup per 32x8 tile) of either pass
 // shading: shs_rt_frame::shading of the camera pass (0: fragment_shader_full, 1: fragment_shader_softshadow,
-// 2: fragment_shader_pbr)
+// 2: fragment_shader_pbr, 3: hello_pbr_light_shafts.cpp's fragment_shader_pbr)
 hipError_t launch_canvas_rt(const shs_dev::RtParams &p, bool shadow_pass, int shading, hipStream_t s);
 hipError_t launch_pcss_samples(const shs_dev::RtPcssSamples &q, hipStream_t s);
 hipError_t launch_ibl_samples(const shs_dev::RtIblSamples &q, hipStream_t s);

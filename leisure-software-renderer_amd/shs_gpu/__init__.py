@@ -106,7 +106,8 @@ class RtFrame:
     pcf: bool = True
     prequant: bool = False
     shading: int = 0             # 0: fragment_shader_full, 1: fragment_shader_softshadow (PCSS; Context.rt_set_pcss),
-                                 # 2: fragment_shader_pbr (Context.rt_render_pbr only)
+                                 # 2: fragment_shader_pbr (Context.rt_render_pbr only),
+                                 # 3: hello_pbr_light_shafts.cpp's fragment_shader_pbr, PBR under PCSS (Context.rt_render_pbr_soft only)
 
 
 @dataclass
@@ -780,8 +781,16 @@ class Context:
 
     def rt_render_pbr(self, frame, draws, pbr_draws):
         """shs_rt_render_pbr: PASS1 of hello_pbr.cpp (frame.shading 2; pbr_draws: one RtPbrDraw per draw), asynchronous."""
+        self._rt_render_pbr(self._lib.shs_rt_render_pbr, "rt_render_pbr", frame, draws, pbr_draws)
+
+    def rt_render_pbr_soft(self, frame, draws, pbr_draws):
+        """shs_rt_render_pbr_soft: PASS1 of hello_pbr_light_shafts.cpp (frame.shading 3: the PBR shader under the PCSS
+        factor of rt_set_pcss, without the minimum ambient; pbr_draws: one RtPbrDraw per draw), asynchronous."""
+        self._rt_render_pbr(self._lib.shs_rt_render_pbr_soft, "rt_render_pbr_soft", frame, draws, pbr_draws)
+
+    def _rt_render_pbr(self, entry, name, frame, draws, pbr_draws):
         if len(pbr_draws) != len(draws):
-            raise ShsError(-1, "rt_render_pbr: one RtPbrDraw per draw")
+            raise ShsError(-1, name + ": one RtPbrDraw per draw")
         arr = self._rt_draw_array(draws)
         mat = (_abi.RtPbrDrawC * max(len(draws), 1))()
         for i, m in enumerate(pbr_draws):
@@ -789,11 +798,11 @@ class Context:
             mat[i].normal_mat[:] = [float(v) for v in n3]
             for name in ("metallic", "roughness", "ao", "ibl_diffuse_intensity", "ibl_specular_intensity", "ibl_reflection_strength"):
                 setattr(mat[i], name, float(getattr(m, name)))
-        self._check(self._lib.shs_rt_render_pbr(self._h, ctypes.byref(self._rt_frame_c(frame)), arr, mat, len(draws)))
+        self._check(entry(self._h, ctypes.byref(self._rt_frame_c(frame)), arr, mat, len(draws)))
         self._rt_size = (frame.width, frame.height)
 
     def rt_set_pbr(self, pbr=None):
-        """shs_rt_set_pbr: the constants of shading 2 (an RtPbr; None: the demo's)."""
+        """shs_rt_set_pbr: the constants of shadings 2 and 3 (an RtPbr; None: the demo's)."""
         if pbr is None:
             self._check(self._lib.shs_rt_set_pbr(self._h, None))
             return
@@ -850,7 +859,7 @@ class Context:
         return out
 
     def rt_set_pcss(self, pcss=None):
-        """shs_rt_set_pcss: the PCSS constants of shading 1 (an RtPcss; None: the demo's)."""
+        """shs_rt_set_pcss: the PCSS constants of shadings 1 and 3 (an RtPcss; None: the demo's)."""
         if pcss is None:
             self._check(self._lib.shs_rt_set_pcss(self._h, None))
             return

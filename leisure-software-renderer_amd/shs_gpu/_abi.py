@@ -395,6 +395,8 @@ SIGNATURES = [
     ("shs_rt_set_ibl", ctypes.c_int, [_P, ctypes.c_int32, _P, ctypes.c_int32, ctypes.c_int32, _P]),
     ("shs_rt_render_pbr", ctypes.c_int, [_P, ctypes.POINTER(RtFrameC), ctypes.POINTER(RtDrawC), ctypes.POINTER(RtPbrDrawC),
                                          ctypes.c_int32]),
+    ("shs_rt_render_pbr_soft", ctypes.c_int, [_P, ctypes.POINTER(RtFrameC), ctypes.POINTER(RtDrawC), ctypes.POINTER(RtPbrDrawC),
+                                              ctypes.c_int32]),
     ("shs_rt_ibl_samples", ctypes.c_int, [_P, ctypes.c_int32, _P, _P, _P, _P]),
     ("shs_rt_set_sky", ctypes.c_int, [_P, ctypes.POINTER(RtSkyC)]),
     ("shs_rt_sky_samples", ctypes.c_int, [_P, ctypes.c_int32, _P, _P]),
