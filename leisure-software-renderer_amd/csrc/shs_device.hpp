@@ -380,6 +380,42 @@ __device__ __forceinline__ f3 add3(f3 a, f3 b) { return {a.x + b.x, a.y + b.y, a
 __device__ __forceinline__ f3 sub3(f3 a, f3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
 __device__ __forceinline__ f3 normalize3(f3 v) { float inv = 1.0f / sqrtf(dot3(v, v)); return sc3(v, inv); }
 
+// normalize3 of a vector that normalize3 produced (the reference normalises the interpolated normal in
+// draw_triangle_tile and again in the FS).  d = dot3(v, v) is then within a few ulps of 1 -- bit pattern
+// RENORM_ONE + k, k in -7 .. 3 over every vector tried -- and for such d the two correctly rounded
+// operations of 1.0f / sqrtf(d) are integer arithmetic on the pattern:
+//   k >= 0: d = 1 + k e (e = 2^-23), sqrt = 1 + (k/2) e - ... rounds to 1 + (k >> 1) e (an odd k sits just
+//           below the tie), and 1 / (1 + j e) = 1 - j e + ... rounds to 1 - 2 j (e/2): RENORM_ONE - (k & ~1);
+//   k <  0: d = 1 - m (e/2), m = -k, sqrt rounds to 1 - ((m + 1) >> 1) (e/2) (an odd m sits just above the
+//           tie), and 1 / (1 - j (e/2)) = 1 + (j/2) e + ... rounds to 1 + ((j + 1) >> 1) e (likewise):
+//           RENORM_ONE + ((m + 3) >> 2).
+// The second-order terms stay far from a rounding boundary for |k| <= 32 (k^2 e / 8 < 2^-16 of a step), and
+// tests/test_renorm_exact.py compares every pattern of the window with the two IEEE operations.  Outside the
+// window -- zero, negative, NaN, infinite and denormal d among it -- the general expression runs, as a branch.
+// Plain inline arithmetic: the test compiles these lines for the host (SHS_RENORM_HOST).
+// [renorm-begin]
+#ifndef SHS_RENORM_HOST
+#define SHS_RENORM_FN __device__ __forceinline__
+#define SHS_RENORM_BITS(x) __float_as_uint(x)
+#define SHS_RENORM_FLOAT(x) __uint_as_float(x)
+#endif
+constexpr uint32_t RENORM_ONE = 0x3F800000u;
+constexpr int32_t RENORM_KMIN = -32, RENORM_KMAX = 16;   // the window: patterns RENORM_ONE + KMIN .. + KMAX
+SHS_RENORM_FN bool renorm_in_window(float d) {
+    return SHS_RENORM_BITS(d) - (RENORM_ONE + (uint32_t)RENORM_KMIN) <= (uint32_t)(RENORM_KMAX - RENORM_KMIN);
+}
+SHS_RENORM_FN float renorm_inv_window(float d) {   // 1.0f / sqrtf(d) for d in the window
+    const int32_t k = (int32_t)(SHS_RENORM_BITS(d) - RENORM_ONE);
+    return SHS_RENORM_FLOAT(k >= 0 ? RENORM_ONE - (uint32_t)(k & ~1) : RENORM_ONE + (uint32_t)((3 - k) >> 2));
+}
+SHS_RENORM_FN float renorm_inv(float d) {
+    float inv = renorm_inv_window(d);
+    if (!renorm_in_window(d)) inv = 1.0f / sqrtf(d);
+    return inv;
+}
+// [renorm-end]
+__device__ __forceinline__ f3 renormalize3(f3 v) { return sc3(v, renorm_inv(dot3(v, v))); }
+
 // glm mat4*vec4 with w = 1: (m0*x + m1*y) + (m2*z + m3*1)
 __device__ __forceinline__ void m4p(const float *m, float x, float y, float z, float &ox, float &oy, float &oz, float &ow) {
     ox = (m[0] * x + m[4] * y) + (m[8] * z + m[12] * 1.0f);
@@ -413,6 +449,25 @@ __device__ __forceinline__ bool bary_pass(const TriRec &r, float Px, float Py, f
     const float thr = fabsf(r.denom) * 0x1p-100f;   // exact: |denom| >= 1e-5 keeps it normal
     const bool dneg = r.denom < 0.0f;
     if (((nv < 0.0f) != dneg && fabsf(nv) > thr) || ((nw < 0.0f) != dneg && fabsf(nw) > thr)) return false;
+    v = nv / r.denom;
+    w = nw / r.denom;
+    u = (1.0f - v) - w;
+    return !(u < 0 || v < 0 || w < 0);
+}
+
+// bary_pass without the early-out: the same operations in the same order, so (u, v, w) and the result are
+// the same bits -- a lane the early-out rejects has a nonzero negative v or w and fails the last test.
+// For callers whose waves could not skip the divides anyway: a winner's own pixel (it always passes), and
+// pixels inside conservative row spans (about two in three pass, so a wave of 64 rejected lanes is rare),
+// where the threshold, the sign and magnitude compares and the branch are pure cost.
+__device__ __forceinline__ bool bary_pass_all(const TriRec &r, float Px, float Py, float &u, float &v, float &w) {
+    const float vpx = Px - r.ax, vpy = Py - r.ay;
+    const float t0 = vpx * r.v0x, t1 = vpy * r.v0y;
+    const float d20 = t0 + t1;
+    const float t2 = vpx * r.v1x, t3 = vpy * r.v1y;
+    const float d21 = t2 + t3;
+    const float nv = r.d11 * d20 - r.d01 * d21;
+    const float nw = r.d00 * d21 - r.d01 * d20;
     v = nv / r.denom;
     w = nw / r.denom;
     u = (1.0f - v) - w;

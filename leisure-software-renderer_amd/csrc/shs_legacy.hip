@@ -1409,7 +1409,7 @@ __device__ __forceinline__ void shade_interp(const float4 (&du)[4], int shading,
         // Flat FS (flat_shading.cpp:69-98): the interpolated normal is normalised in
         // draw_triangle_tile and again in the FS; intensity = min(0.2 + max(n.l, 0), 1)
         const f3 in_n = normalize3(A);
-        const f3 nn = normalize3(in_n);
+        const f3 nn = renormalize3(in_n);
         const f3 l = {dl.x, dl.y, dl.z};
         const float diffuse = g_max(dot3(nn, l), 0.0f);
         float intensity = 0.2f + diffuse;
@@ -1441,7 +1441,7 @@ __device__ __forceinline__ void shade_interp(const float4 (&du)[4], int shading,
     const f3 in_w = A;
     const f3 L = {dl.x, dl.y, dl.z};
     const f3 cam = {dc.x, dc.y, dc.z};
-    const f3 norm = normalize3(in_n);
+    const f3 norm = renormalize3(in_n);   // (1.0f / sqrtf(d) of a d next to 1: integer arithmetic, shs_device.hpp)
     const f3 viewDir = normalize3(sub3(cam, in_w));
 #ifdef SHS_LEGACY_EXT
     if (shading >= 4) {
@@ -1562,6 +1562,8 @@ __device__ __forceinline__ void load_du(const float4 *p, float4 (&du)[4]) {
 // its barycentrics pass; returns z.  The caller's pixel lies in the triangle's bin box (every raster
 // loop walks clipped bin boxes), which is the ibox itself unless the triangle is a ghost: only
 // ghosts test the ibox.
+// EARLY: bary_pass with its early-out, or bary_pass_all (the same bits; raster_group's span pairs).
+template <bool EARLY = true>
 __device__ __forceinline__ bool pixel_test(const FrameParams &fp, const TriRec &r, int px, int py, float &z) {
     const bool in_ibox = !(r.flags & TRI_GHOST) ||
                          (px >= lo16(r.ibx) && px <= hi16(r.ibx) && py >= lo16(r.iby) && py <= hi16(r.iby));
@@ -1579,7 +1581,9 @@ __device__ __forceinline__ bool pixel_test(const FrameParams &fp, const TriRec &
                py <= (int)bmaxy;
     }
     float u, v, w;
-    if (!(test && bary_pass(r, (float)px + 0.5f, (float)py + 0.5f, u, v, w))) return false;
+    if (!(test && (EARLY ? bary_pass(r, (float)px + 0.5f, (float)py + 0.5f, u, v, w)
+                         : bary_pass_all(r, (float)px + 0.5f, (float)py + 0.5f, u, v, w))))
+        return false;
     z = tri_depth(r, u, v, w);
     return z < FLT_MAX;   // NaN and FLT_MAX never beat the FLT_MAX clear
 }
@@ -1606,14 +1610,26 @@ __device__ __forceinline__ void key_winner(unsigned long long key, bool slot_key
     slot = slot_keys ? lo & SLOT_NONE : SLOT_NONE;
 }
 
-struct RasterShared {
+// RasterSharedT<TILE_KEYS>: the tile kernels' and k_pipe's (RasterShared) holds one tile's keys; the group
+// kernels' (RasterSharedT<false>) holds none -- a group's keys are GroupShared's one array -- and is
+// otherwise the same.  The staged records, the keys and the rest are three parts in declaration order, so
+// RasterShared's layout is what it was as one struct.  The helpers below take either (class RS).
+struct RasterStaged {
     float4 rec[RCHUNK * 4];           // staged triangle records (TriHot, 4 KB)
     float4 ext[RCHUNK];               // ... their float bboxes (ghosts; every candidate in scan mode, 1 KB)
 #ifdef SHS_LEGACY_TEX
     float4 iw[RCHUNK];                // ... their side entries (invw0 invw1 invw2, model 9 or 0; tex_side plane 1, 1 KB)
 #endif
     float4 srec[RCHUNK * 5];          // staged shading records (single-pass tiles, 5 KB)
+};
+template <bool TILE_KEYS>
+struct RasterKeys {
     unsigned long long key[RTH * RTW];// per-pixel (z, index) keys (2 KB)
+};
+template <>
+struct RasterKeys<false> {};
+template <bool TILE_KEYS>
+struct RasterSharedT : RasterStaged, RasterKeys<TILE_KEYS> {
     unsigned long long bits[PAIR_WORDS]; // bit k: a staged candidate's pairs start at pair k (2 KB)
     uint32_t seg[RCHUNK * RTH];       // spans: per nonempty row span, seg_pack's word (groups: the threads' spans before the prefix)
     uint4 pinfo[RCHUNK];              // boxes: per staged candidate with pairs in the pass, its box clipped to the tile / group:
@@ -1627,12 +1643,18 @@ struct RasterShared {
     uint32_t nclr;                    // tiles this workgroup's strips cleared (rstat)
     uint16_t wown[PAIR_WORDS];        // segment (boxes: staged candidate) owning each bitmap word's first pair
 };
+using RasterShared = RasterSharedT<true>;
+static_assert(sizeof(RasterSharedT<false>) == sizeof(RasterShared) - sizeof(RasterKeys<true>), "the group kernels': no room for a tile's keys");
 
-// Tile groups (raster_group), on top of RasterShared (+6 KB, four workgroups per CU): the keys of the
-// group's tiles after the first, and the pair prefix's scalars.  Only the group kernel declares it
-// (k_pipe's and the other rasters' LDS stays what it was).
+// Tile groups (raster_group), on top of RasterSharedT<false> (+6 KB on RasterShared, four workgroups per
+// CU): the group's keys and the pair prefix's scalars.  Only the group kernel declares it (k_pipe's and
+// the other rasters' LDS stays what it was).
+// The keys are one row-major array over the group's rectangle -- GY * RTH rows of GX * RTW -- so a pixel's
+// key is at (group row) * GROUP_W + (group x): the pair loops and the ghost fragments, which know both
+// (the segment word holds them), find it without the pixel's tile.
+constexpr int GROUP_W = GX * RTW, GROUP_H = GY * RTH;
 struct GroupShared {
-    unsigned long long key[(GX * GY - 1) * RTH * RTW];
+    unsigned long long key[GROUP_H * GROUP_W];
     uint32_t npairs;                  // the pair pass's pairs
     uint32_t next;                    // the first staged candidate the pair pass left out (all fit: >= the staged count)
     uint32_t seq, pairs;              // the group's candidates and pairs so far (timeline)
@@ -1775,8 +1797,8 @@ __device__ __forceinline__ void resolve_from_mesh(const FrameParams &fp, const F
 // registers held across the whole kernel, which then spills (the group kernels; the experiments build's
 // per-pixel kernel).  Not pinned in the tile span kernels: pinned, the bin-mode one measured 0.005 ms per
 // C3 step slower.
-template <bool PIN>
-__device__ __forceinline__ void stage_stored(const FrameBuffers &fb, RasterShared &sh, uint32_t c, int m, bool single,
+template <bool PIN, class RS>
+__device__ __forceinline__ void stage_stored(const FrameBuffers &fb, RS &sh, uint32_t c, int m, bool single,
                                              bool all_ext SHS_TEX_PARAM(const FrameParams &fp)) {
     const int tid = threadIdx.x;
     constexpr int NQ = (RCHUNK * 4 + 255) / 256, NS = (RCHUNK * 5 + 255) / 256;
@@ -1816,7 +1838,8 @@ __device__ __forceinline__ void stage_stored(const FrameBuffers &fb, RasterShare
 }
 
 // mark_run / pair_owner (shs_wave.hpp) on RasterShared's bitmap and word owners for the pairs.
-__device__ __forceinline__ void mark_run(RasterShared &sh, uint32_t start, uint32_t len, uint32_t owner) {
+template <class RS>
+__device__ __forceinline__ void mark_run(RS &sh, uint32_t start, uint32_t len, uint32_t owner) {
     mark_run(sh.bits, sh.wown, start, len, owner);
 }
 
@@ -1829,7 +1852,8 @@ static_assert(RCHUNK * GX * RTW * GY * RTH < (1 << 21) && GROUP_SEGS < 2048, "th
 // block's total in ptot.  (lane, wave: the caller's -- recomputed here they cost the experiments build's
 // NO_RECS kernel eight more spilled registers.  shs_wave.hpp's block_excl_sum written out: through it, with
 // the caller's lane in the scan or not, the raster kernels' register allocation moves.)
-__device__ __forceinline__ uint32_t block_span_prefix(RasterShared &sh, uint32_t pk, int lane, int wave, uint32_t &ptot) {
+template <class RS>
+__device__ __forceinline__ uint32_t block_span_prefix(RS &sh, uint32_t pk, int lane, int wave, uint32_t &ptot) {
     const uint32_t incl = wave_incl_sum(pk);
     if (lane == 63) sh.wtot[wave] = incl;
     __syncthreads();
@@ -1847,16 +1871,16 @@ __device__ __forceinline__ uint32_t block_span_prefix(RasterShared &sh, uint32_t
 // Segment write-out: the thread's N spans (span(j)) laid end to end from its exclusive prefix ex, each as
 // word(j, first pair, x0) in seg[] with its run marked.  (write_segment: one span, sp != NO_SPAN, as
 // segment sg from pair ps; both move on.)
-template <class Word>
-__device__ __forceinline__ void write_segment(RasterShared &sh, uint32_t *seg, uint32_t &ps, uint32_t &sg, uint32_t sp, Word word) {
+template <class RS, class Word>
+__device__ __forceinline__ void write_segment(RS &sh, uint32_t *seg, uint32_t &ps, uint32_t &sg, uint32_t sp, Word word) {
     const uint32_t s0 = sp & 0xffu, wdt = (sp >> 8) - s0 + 1u;
     seg[sg] = word(ps, s0);
     mark_run(sh, ps, wdt, sg);
     ps += wdt;
     ++sg;
 }
-template <int N, class Span, class Word>
-__device__ __forceinline__ void write_segments(RasterShared &sh, uint32_t *seg, uint32_t ex, Span span, Word word) {
+template <int N, class RS, class Span, class Word>
+__device__ __forceinline__ void write_segments(RS &sh, uint32_t *seg, uint32_t ex, Span span, Word word) {
     uint32_t ps = ex >> 11, sg = ex & 2047u;
 #pragma unroll
     for (int j = 0; j < N; ++j) {
@@ -1874,8 +1898,8 @@ __device__ __forceinline__ void write_segments(RasterShared &sh, uint32_t *seg, 
 // with the lane; one always does -- and the entries are compacted by rank; the pass clears its own bitmap
 // words.  Otherwise (a tile: every staged box holds >= 1 pixel of it, so the starts are distinct, and 64
 // boxes of <= 256 px fit) entry = candidate, and the caller has cleared the bitmap.
-template <bool SPLIT>
-__device__ __forceinline__ int layout_boxes(RasterShared &sh, int c0, int m, int X0, int Y0, int X1, int Y1, int &next) {
+template <bool SPLIT, class RS>
+__device__ __forceinline__ int layout_boxes(RS &sh, int c0, int m, int X0, int Y0, int X1, int Y1, int &next) {
     const int lane = __lane_id();
     int area = 0, bx0 = 0, by0 = 0, bw = 1;
     if (lane >= c0 && lane < m) {
@@ -1918,31 +1942,34 @@ __device__ __forceinline__ int pinfo_pixel(const uint4 pi, int k, int &px, int &
     return (int)(pi.z >> 8);
 }
 
-__device__ __forceinline__ int pair_owner(const RasterShared &sh, int k0, int lane) { return pair_owner(sh.bits, sh.wown, k0, lane); }
+template <class RS>
+__device__ __forceinline__ int pair_owner(const RS &sh, int k0, int lane) { return pair_owner(sh.bits, sh.wown, k0, lane); }
 
 // Staged candidate o at pixel (px, py): whether the pixel passes, and then its key.
-__device__ __forceinline__ bool staged_key(const FrameParams &fp, const RasterShared &sh, int o, int px, int py, bool slot_keys,
+template <bool EARLY = true, class RS>
+__device__ __forceinline__ bool staged_key(const FrameParams &fp, const RS &sh, int o, int px, int py, bool slot_keys,
                                            bool single, unsigned long long &key) {
     TriRec r = rec_from_hot(fp, &sh.rec[o * 4], &sh.ext[o]);
     SHS_TEX_ONLY(set_iw(r, sh.iw[o]);)
     float z;
-    if (!pixel_test(fp, r, px, py, z)) return false;
+    if (!pixel_test<EARLY>(fp, r, px, py, z)) return false;
     key = cand_key(z, sh.id[o], slot_keys, single ? (uint32_t)o : SLOT_NONE);
     return true;
 }
 
 // One (candidate, pixel) pair task: a passing pixel's key into its key slot.
-__device__ __forceinline__ void test_pair(const FrameParams &fp, RasterShared &sh, int o, int px, int py,
+template <bool EARLY = true, class RS>
+__device__ __forceinline__ void test_pair(const FrameParams &fp, RS &sh, int o, int px, int py,
                                           unsigned long long *key_slot, bool slot_keys, bool single) {
     unsigned long long key;
-    if (staged_key(fp, sh, o, px, py, slot_keys, single, key)) atomicMin(key_slot, key);
+    if (staged_key<EARLY>(fp, sh, o, px, py, slot_keys, single, key)) atomicMin(key_slot, key);
 }
 
 // The pair loop: wave w takes the 64-pair windows w, w + 4, ... of the pass's pairs.  pair(owner, k, px,
 // py) decodes pair k to its staged candidate and pixel; key_slot(px, py) is the pixel's key, or null where
 // the pixel is not drawn.
-template <class Pair, class KeySlot>
-__device__ __forceinline__ void walk_pairs(const FrameParams &fp, RasterShared &sh, int total, bool slot_keys, bool single,
+template <bool EARLY = true, class RS, class Pair, class KeySlot>
+__device__ __forceinline__ void walk_pairs(const FrameParams &fp, RS &sh, int total, bool slot_keys, bool single,
                                            Pair pair, KeySlot key_slot) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int k0 = 64 * wave; k0 < total; k0 += 256) {
@@ -1951,7 +1978,7 @@ __device__ __forceinline__ void walk_pairs(const FrameParams &fp, RasterShared &
             int px, py;
             const int o = pair(pair_owner(sh, k0, lane), k, px, py);
             unsigned long long *slot = key_slot(px, py);
-            if (slot) test_pair(fp, sh, o, px, py, slot, slot_keys, single);
+            if (slot) test_pair<EARLY>(fp, sh, o, px, py, slot, slot_keys, single);
         }
     }
 }
@@ -1959,7 +1986,8 @@ __device__ __forceinline__ void walk_pairs(const FrameParams &fp, RasterShared &
 // The winner's records for the resolve: the staged copies when its key carries a slot (only single-pass
 // items encode one), else HBM.  Returns the raster record (its float bbox is not read here); sr: the shade
 // record.
-__device__ __forceinline__ TriRec winner_records(const FrameParams &fp, const FrameBuffers &fb, const RasterShared &sh, uint32_t id,
+template <class RS>
+__device__ __forceinline__ TriRec winner_records(const FrameParams &fp, const FrameBuffers &fb, const RS &sh, uint32_t id,
                                                  uint32_t slot, ShadeRec &sr) {
     float4 h4[4];
     float4 *e4 = reinterpret_cast<float4 *>(&sr);
@@ -2001,8 +2029,9 @@ __device__ __forceinline__ void pack_pixel(const float (&pre)[3], uint32_t &rgba
 
 // A covered pixel whose winner has stored records: (u, v, w) recomputed with the pair test's arithmetic,
 // the depth, and the winner shaded.  dbase: the frame's slice of the batch's draw table `draws`.
+template <class RS>
 __device__ __forceinline__ void shade_stored_winner(const FrameParams &fp, const FrameBuffers &fb, const DrawGPU *draws, int dbase,
-                                                    const RasterShared &sh, uint32_t id, uint32_t slot, int px, int py,
+                                                    const RS &sh, uint32_t id, uint32_t slot, int px, int py,
                                                     float &depth, uint32_t &rgba, float4 &pq) {
     ShadeRec sr;
     const TriRec r = winner_records(fp, fb, sh, id, slot, sr);
@@ -2044,7 +2073,8 @@ __device__ __forceinline__ void store_pixel(const FrameParams &fp, const FrameBu
 // winner_records for a wave whose covered lanes' keys all carry a slot: both records straight from their
 // LDS copies (ds_read with an immediate offset; no base-pointer select, no 64-bit address, and no
 // vmcnt wait that would also wait for the previous tile's stores).
-__device__ __forceinline__ TriRec staged_records(const FrameParams &fp, const RasterShared &sh, uint32_t slot, ShadeRec &sr) {
+template <class RS>
+__device__ __forceinline__ TriRec staged_records(const FrameParams &fp, const RS &sh, uint32_t slot, ShadeRec &sr) {
     // (whole 16-B vectors: copied field by field the loads are regrouped into 4-B-aligned pairs)
     typedef float v4f __attribute__((ext_vector_type(4)));
     const v4f *s4 = reinterpret_cast<const v4f *>(&sh.rec[slot * 4]), *g4 = reinterpret_cast<const v4f *>(&sh.srec[slot * 5]);
@@ -2368,7 +2398,7 @@ __device__ __forceinline__ void raster_tile(const FrameParams &fp, const FrameBu
 // TL: the timeline's marks and counters are compiled in (the instantiation launched when a timeline
 // buffer is set); first: the workgroup's first group, the one the timeline records.
 template <bool KARG, bool SPANS, bool TL, class GS>
-__device__ __forceinline__ void raster_group(uint32_t n_frag, int frame, int rt0, RasterShared &sh, GS &gs, bool first) {
+__device__ __forceinline__ void raster_group(uint32_t n_frag, int frame, int rt0, RasterSharedT<false> &sh, GS &gs, bool first) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     uint64_t *tl = nullptr;
     int tls = 0;
@@ -2412,14 +2442,17 @@ __device__ __forceinline__ void raster_group(uint32_t n_frag, int frame, int rt0
     bool single = n_items <= (uint32_t)CAND;   // one gather round and one staging pass: winners in LDS
     const uint32_t bmask = (uint32_t)__ballot(flag == epoch) & ((1u << (GX * GY)) - 1u);   // (epoch != 0)
     const int t_first = __ffs((int)bmask) - 1;
-    // A pixel of the group: its key in its tile's key array (tile 0: RasterShared's, the others GroupShared's),
-    // or null when the tile is not busy -- only the group's busy tiles are drawn (a sharded frame's group
-    // holds tiles of other shards, which setup never marks).
+    // A pixel of the group: its key in the group's row-major key array, or null when its tile is not busy
+    // -- only the group's busy tiles are drawn and reset; a key left in another tile would stay for the
+    // workgroup's later items.  A sharded frame's group holds tiles of other shards, which setup never
+    // marks, so there the pixel's tile is looked up in the busy mask.  In an unsharded frame no pair can
+    // meet an idle tile: setup marks every tile of a triangle's bin box, and a pair's pixel lies in its
+    // candidate's bin box (clipped to the group), so the lookup is skipped (a scalar branch).
+    const bool sharded = a->fp.count > 1;
     auto key_slot = [&](int px, int py) -> unsigned long long * {
-        const int tx = (px - GX0) / RTW, ty = (py - GY0) / RTH, t = ty * GX + tx;
-        if (!((bmask >> t) & 1u)) return nullptr;
-        unsigned long long *key = t ? &gs.key[(t - 1) * (RTW * RTH)] : sh.key;
-        return &key[(py - GY0 - ty * RTH) * RTW + (px - GX0 - tx * RTW)];
+        const int gx = px - GX0, gy = py - GY0;
+        if (sharded && !((bmask >> ((gy / RTH) * GX + gx / RTW)) & 1u)) return nullptr;
+        return &gs.key[gy * GROUP_W + gx];
     };
 
     for (uint32_t base = 0; base < n_items; base += CAND) {
@@ -2556,8 +2589,9 @@ __device__ __forceinline__ void raster_group(uint32_t n_frag, int frame, int rt0
                 if (!boxes) {
                     const int total = SHS_DBG(fp, DBG_SKIP_PAIRS) ? 0 : (int)(ptot >> 11);
                     if (tl && tid == 0) gs.pairs += (uint32_t)total;
-                    walk_pairs(fp, sh, total, slot_keys, single,
-                               [&](int seg, int k, int &px, int &py) { return seg_pixel(gs.seg[seg], k, GX0, GY0, px, py); }, key_slot);
+                    // (bary_pass_all: inside the spans the early-out skips nothing)
+                    walk_pairs<false>(fp, sh, total, slot_keys, single,
+                                      [&](int seg, int k, int &px, int &py) { return seg_pixel(gs.seg[seg], k, GX0, GY0, px, py); }, key_slot);
                 }
             }
             // one pair pass over the group: the staged candidates' bin boxes clipped to the group rectangle
@@ -2590,10 +2624,10 @@ __device__ __forceinline__ void raster_group(uint32_t n_frag, int frame, int rt0
         const GhostFrag g = arg_buffers(kernel_args()).frags[f];
         const int gx = (int)(g.xy & 0xffffu), gy = (int)(g.xy >> 16);
         if (g.frame == (uint32_t)frame && gx >= GX0 && gx <= GX1 && gy >= GY0 && gy <= GY1) {
-            const int tx = (gx - GX0) / RTW, ty = (gy - GY0) / RTH, t = ty * GX + tx;
-            unsigned long long *key = t ? &gs.key[(t - 1) * (RTW * RTH)] : sh.key;
-            if ((bmask >> t) & 1u)
-                atomicMin(&key[(gy - GY0 - ty * RTH) * RTW + (gx - GX0 - tx * RTW)], cand_key(g.z, g.id, slot_keys, SLOT_NONE));
+            // (the fragments are few: their tile is looked up in the busy mask in every frame)
+            const int x = gx - GX0, y = gy - GY0;
+            if ((bmask >> ((y / RTH) * GX + x / RTW)) & 1u)
+                atomicMin(&gs.key[y * GROUP_W + x], cand_key(g.z, g.id, slot_keys, SLOT_NONE));
         }
     }
     __syncthreads();
@@ -2614,7 +2648,7 @@ __device__ __forceinline__ void raster_group(uint32_t n_frag, int frame, int rt0
         const int t = __ffs((int)bm) - 1;
         const int X0 = GX0 + (t % GX) * RTW, Y0 = GY0 + (t / GX) * RTH;
         const int px = X0 + (tid & 31), py = Y0 + (tid >> 5);
-        unsigned long long *kp = t ? &gs.key[(t - 1) * (RTW * RTH) + tid] : &sh.key[tid];
+        unsigned long long *kp = &gs.key[((t / GX) * RTH + (tid >> 5)) * GROUP_W + (t % GX) * RTW + (tid & 31)];
         const unsigned long long key = *kp;
         *kp = KEY_EMPTY;   // clean for the next item (read above, by this thread only)
         uint32_t rgba = fp.clear_rgba;
@@ -2636,7 +2670,7 @@ __device__ __forceinline__ void raster_group(uint32_t n_frag, int frame, int rt0
                 ShadeRec sr;
                 const TriRec r = staged_records(fp, sh, slot, sr);
                 float u, v, w;
-                bary_pass(r, (float)px + 0.5f, (float)py + 0.5f, u, v, w);   // the winner's own values
+                bary_pass_all(r, (float)px + 0.5f, (float)py + 0.5f, u, v, w);   // the winner's own values (it passes)
                 depth = tri_depth(r, u, v, w);
                 if (!SHS_DBG(fp, DBG_SKIP_SHADE)) {
                     f3 A, N;
@@ -2744,8 +2778,9 @@ __device__ __forceinline__ void clear_strip(const FrameParams &fp, const FrameBu
 // no entry is written while another lane may still read it.  A chunk with nothing stale costs two
 // loads and two barriers.  (A busy tile's entry may be rewritten by its own workgroup meanwhile; the
 // busy flag already excludes it here.)  Returns the tiles cleared (thread 0's count).
+template <class RS>
 __device__ __forceinline__ uint32_t clear_stale_rows(const FrameParams &fp, const FrameBuffers &fb, int f, int ry0, int ry1,
-                                                     RasterShared &sh) {
+                                                     RS &sh) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const FrameBuffers fv = frame_view(fp, fb, f);
     const int rt1 = ry1 * fp.tiles_x;
@@ -2778,8 +2813,9 @@ __device__ __forceinline__ uint32_t clear_stale_rows(const FrameParams &fp, cons
 }
 
 // One clear item: raster-tile rows [sy * STRIP_RT, (sy + 1) * STRIP_RT) of frame f, in either mode.
+template <class RS>
 __device__ __forceinline__ uint32_t clear_item(const FrameParams &fp, const FrameBuffers &fb, int f, int sy, int strip_rt,
-                                               RasterShared &sh) {
+                                               RS &sh) {
     const int ry0 = sy * strip_rt, ry1 = min((sy + 1) * strip_rt, fp.rtiles_y);
     if (!(fp.flags & RF_FULL_CLEAR)) return clear_stale_rows(fp, fb, f, ry0, ry1, sh);
     // RF_FULL_CLEAR: the strips clear every owned idle tile; their stale entries are set to 0 here, a
@@ -2822,7 +2858,7 @@ constexpr int STRIP_RT = SHS_STRIP_RT;
 // the prologue, every item's fetch and every clear item read what they use through kernel_args(), and
 // raster_group does so per phase, so the loop itself carries only the item counts and the ticket.
 template <bool KARG, bool GSPANS, bool TL, class GS>
-__device__ __forceinline__ void group_items(RasterShared &sh, GS &gs) {
+__device__ __forceinline__ void group_items(RasterSharedT<false> &sh, GS &gs) {
     const int tid = threadIdx.x;
     uint64_t t_start = 0ull, c_start = 0ull;
     if constexpr (TL) {
@@ -2830,9 +2866,8 @@ __device__ __forceinline__ void group_items(RasterShared &sh, GS &gs) {
         c_start = __builtin_amdgcn_s_memtime();
     }
     if (tid == 0) { sh.cov = 0; sh.maxbin = 0; sh.nclr = 0; }
-    sh.key[tid] = KEY_EMPTY;
 #pragma unroll
-    for (int t = 0; t < GX * GY - 1; ++t) gs.key[t * (RTW * RTH) + tid] = KEY_EMPTY;
+    for (int t = 0; t < GX * GY; ++t) gs.key[t * (RTW * RTH) + tid] = KEY_EMPTY;
     uint32_t n_busy, n_frag, n_strips;
     {
         // (every independent first-touch load is issued up front: k_raster's prologue)
@@ -2929,11 +2964,12 @@ __global__ __launch_bounds__(256, SHS_LEGACY_RASTER_WAVES) void k_raster(FramePa
     static_assert(!GROUPS || (SCAN == SCAN_ALL && !NO_RECS && !SPANS && !PIX), "tile groups: the scan-mode pair kernel");
     static_assert(!GSPANS || GROUPS, "group spans: the group kernel");
     static_assert(!TL || GROUPS, "the other kernels test the timeline pointer at run time");
-    __shared__ RasterShared sh;
     if constexpr (GROUPS) {
+        __shared__ RasterSharedT<false> sh;   // (no tile's keys: the group's are gs.key)
         __shared__ typename std::conditional<GSPANS, GroupSpanShared, GroupShared>::type gs;
         group_items<KARG, GSPANS, TL>(sh, gs);
     } else {
+        __shared__ RasterShared sh;
         const int tid = threadIdx.x;
         uint32_t *cnt = fb.counters + fp.parity * CSET;
         const DrawGPU *draws = draw_table<KARG>(fb, ka);
