@@ -894,7 +894,16 @@ int shs_canvas_light_shafts(shs_ctx *ctx, const shs_canvas_light_shafts_desc *de
  *      constants of shs_rt_set_pcss, whose defaults are this demo's :135-148 too, and shading 1's rotation table),
  *      so SHS_RT_PCF has no effect; there is no minimum-ambient term; the direct radiance is the literal 3.0,
  *      shs_rt_pbr::direct_intensity's default.  The velocity plane is written as for shading 2; the prequant
- *      plane's fourth float is the PCSS factor. */
+ *      plane's fourth float is the PCSS factor.
+ *   4  fragment_shader_full of hello_ibl_skybox.cpp (:446-524), through shs_rt_render_skybox_ibl only (the shader
+ *      needs the per-draw knobs of shs_rt_skybox_ibl_draw).  That demo's PASS0 and PASS1 rasters (:646-686, :705-860)
+ *      are hello_shadow_mapping.cpp's with tile jobs of 160, its skybox_background_pass (:532-611) is shs_rt_set_sky
+ *      with SHS_RT_SKY_ENCODE_CLAMP, and its PASS2 is shs_canvas_motion_blur over shs_rt_device_targets.  Blinn-Phong
+ *      under the shadow lookup of shading 0 (SHS_RT_USE_SHADOW, SHS_RT_PCF, bias_base, bias_slope) whose ambient and
+ *      diffuse terms take the base colour and whose specular term does not, with the ambient term tinted by
+ *      sky.sample(N) and a Schlick-weighted sky.sample(reflect(-V, N)) added: u.sky is the sky bound by
+ *      shs_rt_set_sky, the one the background pass draws (no sky bound: u.sky == nullptr, tint 1, no reflection).
+ *      The velocity plane is written as for shading 0; the prequant plane's fourth float is the shadow factor. */
 typedef struct shs_rt_draw {
     int32_t mesh_id;            /* shs_mesh_upload_soup[_uv] soup (without UVs: vec2(0) per corner) */
     int32_t albedo_tex;         /* shs_texture_upload id (use_texture), 0: base_color */
@@ -920,7 +929,9 @@ typedef struct shs_rt_frame {
     int32_t shading;                  /* 0: fragment_shader_full, 1: fragment_shader_softshadow,
                                          2: fragment_shader_pbr (shs_rt_render_pbr),
                                          3: hello_pbr_light_shafts.cpp's fragment_shader_pbr :768-850 over
-                                            pcss_shadow_factor :650-762 (shs_rt_render_pbr_soft) */
+                                            pcss_shadow_factor :650-762 (shs_rt_render_pbr_soft),
+                                         4: hello_ibl_skybox.cpp's fragment_shader_full :446-524
+                                            (shs_rt_render_skybox_ibl) */
 } shs_rt_frame;
 /* The PCSS constants of shading 1 (hello_shadow_mapping_soft.cpp:101-116), kept in the context. */
 typedef struct shs_rt_pcss {
@@ -949,7 +960,7 @@ typedef struct shs_rt_stats {
 int shs_rt_render_shadow(shs_ctx *ctx, int32_t w, int32_t h, int32_t ref_tile_w, int32_t ref_tile_h, const float light_vp[16],
                          const shs_rt_draw *casters, int32_t n_casters);
 /* SHS_ERR_INVALID: an unknown mesh or texture id, a non-positive size, unknown flags, a shading other than
- * 0 or 1 (2 goes through shs_rt_render_pbr, 3 through shs_rt_render_pbr_soft), or SHS_RT_USE_SHADOW without a shadow map rendered before. */
+ * 0 or 1 (2 goes through shs_rt_render_pbr, 3 through shs_rt_render_pbr_soft, 4 through shs_rt_render_skybox_ibl), or SHS_RT_USE_SHADOW without a shadow map rendered before. */
 int shs_rt_render(shs_ctx *ctx, const shs_rt_frame *frame, const shs_rt_draw *draws, int32_t n_draws);
 /* Host copies of the last camera pass (any pointer may be NULL): color W*H*4 bytes, depth W*H floats,
  * velocity W*H*2 floats.  Synchronous. */
@@ -1009,7 +1020,7 @@ int shs_rt_ibl_samples(shs_ctx *ctx, int32_t n, const float *dirs3, const float 
  * (:552-611) and CubeMapSky with sample_face_bilinear (:432-517).  (These are not the library path's ProceduralSky /
  * CubemapSky of shs_lib_set_sky; the legacy ProceduralSky :520-549 is not built: no render-target demo constructs it.)
  * The reference draws the sky first and the triangles over it.  Here, with a sky bound, every camera pass
- * (shs_rt_render, shs_rt_render_pbr, shs_rt_render_pbr_soft, whatever the shading) is followed on the context stream by a background pass
+ * (shs_rt_render, shs_rt_render_pbr, shs_rt_render_pbr_soft, shs_rt_render_skybox_ibl, whatever the shading) is followed on the context stream by a background pass
  * that colours each pixel that shows no fragment (shs_rt_resolve_ids: -1) -- also one whose fragment kept its depth
  * but not its colour -- from the direction through the pixel's centre (:769-780; canvas x, y with y up).  Such a
  * pixel's prequant floats are (r, g, b) * 255 before the truncation and 1; depth and velocity stay as the raster
@@ -1038,6 +1049,21 @@ int shs_rt_set_sky(shs_ctx *ctx, const shs_rt_sky *sky);
  * background pass calls: dirs3 and rgb3 3n.  Synchronous; for tests of the edge cases.  SHS_ERR_INVALID without a
  * sky. */
 int shs_rt_sky_samples(shs_ctx *ctx, int32_t n, const float *dirs3, float *rgb3);
+/* hello_ibl_skybox.cpp's per-object knobs that its fragment_shader_full reads beside shs_rt_draw (Uniforms :336-339;
+ * set per object :1299-1302, :1362-1365, :1414-1417): element i goes with shs_rt_draw[i].  The shader saturates
+ * ibl_ambient, ibl_refl and ibl_refl_mix; ibl_f0 is used as given. */
+typedef struct shs_rt_skybox_ibl_draw {
+    float ibl_ambient;     /* how far the ambient term is tinted by sky.sample(N) (0.25) */
+    float ibl_refl;        /* the reflection's strength (0.35) */
+    float ibl_f0;          /* Schlick's reflectivity at normal incidence (0.04) */
+    float ibl_refl_mix;    /* per-object multiplier of the reflection (1) */
+} shs_rt_skybox_ibl_draw;
+/* PASS1 of hello_ibl_skybox.cpp: the raster of shs_rt_render with that demo's fragment_shader_full, which samples the
+ * sky bound by shs_rt_set_sky per shaded pixel; the background pass follows as after every camera pass.
+ * frame->shading must be 4.  SHS_ERR_INVALID as shs_rt_render, for any other shading, for a null ibl_draws with
+ * n_draws > 0 and for a non-finite knob (nothing is enqueued). */
+int shs_rt_render_skybox_ibl(shs_ctx *ctx, const shs_rt_frame *frame, const shs_rt_draw *draws,
+                             const shs_rt_skybox_ibl_draw *ibl_draws, int32_t n_draws);
 /* ortho_lh_zo (hello_shadow_mapping.cpp:128-140): LH, z in [0, 1]. */
 int shs_ortho_lh_zo(float left, float right, float bottom, float top, float znear, float zfar, float out16[16]);
 

@@ -468,6 +468,125 @@ protected:
 };
 
 // -----------------------------------------------------------------------------------------------------
+// Seam 1b, sky-lit -- hello-render-target/hello_ibl_skybox.cpp.
+//
+// Replaces RendererSystem::process there (:1106-1530), four calls on the context stream with no resolve in between:
+//   1. shs_rt_render_shadow with tile jobs of 160 (TILE_SIZE_X / TILE_SIZE_Y :54-55): PASS0 (:646-686) is the hard demo's;
+//   2. shs_rt_set_sky with SHS_RT_SKY_ENCODE_CLAMP and the viewer's camera: skybox_background_pass (:532-611), and the
+//      same sky is u.sky of the camera pass (:1298) -- no device work, so it is bound per frame;
+//   3. shs_rt_render_skybox_ibl, shading = 4: the hard demo's raster (:705-860) with this file's fragment_shader_full
+//      (:446-524) and the per-object knobs (:1299-1302, :1362-1365, :1414-1417);
+//   4. shs_canvas_motion_blur over shs_rt_device_targets into a device buffer of the host's: combined_motion_blur_pass
+//      (:944-1060) is hello_pbr.cpp's (:1128-1252) operation for operation -- it forms glm::inverse(curr_vp) per pixel
+//      where that one hoists it, and reads through accessors where that one reads raw pointers.
+// The sky is the scene's CubeMapSky (six uploaded face textures, which cannot be released while bound) or its
+// AnalyticSky; with neither bound the shader runs with u.sky == nullptr.  Uncompiled, like the other seams.
+// -----------------------------------------------------------------------------------------------------
+template <class SceneT>
+class IblSkyboxSystemGPU : public shs::AbstractSystem {
+public:
+    struct Object {
+        typename RenderTargetSystemGPU<SceneT>::Object geom;
+        shs_rt_skybox_ibl_draw ibl{0.25f, 0.35f, 0.04f, 1.0f};   // Uniforms :336-339
+    };
+
+    IblSkyboxSystemGPU(SceneT *scene, Device *dev, void *blurred_dev, int shadow_size = 2048, int tile = 160)
+        : scene_(scene), dev_(dev), blurred_(blurred_dev), sm_(shadow_size), tile_(tile) {}
+
+    std::vector<Object> objects;     // geom.model / prev_model per frame
+
+    // The scene's sky: a CubeMapSky's faces (+X -X +Y -Y +Z -Z, shs_texture_upload ids) and intensity_, or an
+    // AnalyticSky's sun_direction.  The camera's vectors are filled in by process().
+    void use_cubemap(const int32_t face_tex[6], float intensity) {
+        sky_ = shs_rt_sky{};
+        sky_.model = SHS_RT_SKY_CUBEMAP;
+        std::memcpy(sky_.face_tex, face_tex, sizeof sky_.face_tex);
+        sky_.intensity = intensity;
+    }
+    void use_analytic(const glm::vec3 &sun_direction) {
+        sky_ = shs_rt_sky{};
+        sky_.model = SHS_RT_SKY_ANALYTIC;
+        std::memcpy(sky_.sun_dir, glm::value_ptr(sun_direction), 12);
+    }
+    void use_no_sky() { sky_ = shs_rt_sky{}; }
+
+    void process(float) override {
+        shs::Canvas &canvas = *scene_->canvas;
+        const int W = canvas.get_width(), H = canvas.get_height();
+        const shs::Camera3D &cam = *scene_->viewer->camera;
+        const glm::mat4 view = cam.view_matrix, proj = cam.projection_matrix;
+        std::vector<shs_rt_draw> draws(objects.size());
+        std::vector<shs_rt_skybox_ibl_draw> knobs(objects.size());
+        for (size_t i = 0; i < objects.size(); ++i) {
+            const auto &o = objects[i].geom;
+            shs_rt_draw &d = draws[i];
+            d.mesh_id = o.mesh_id;
+            d.albedo_tex = o.albedo_tex;
+            const glm::mat4 mvp = proj * view * o.model, prev_mvp = prev_proj_ * prev_view_ * o.prev_model;
+            std::memcpy(d.model, glm::value_ptr(o.model), 64);
+            std::memcpy(d.mvp, glm::value_ptr(mvp), 64);
+            std::memcpy(d.prev_mvp, glm::value_ptr(prev_mvp), 64);
+            d.base_color[0] = o.base_color.r; d.base_color[1] = o.base_color.g; d.base_color[2] = o.base_color.b; d.base_color[3] = 255;
+            knobs[i] = objects[i].ibl;
+        }
+        // 1. PASS0
+        ok(shs_rt_render_shadow(dev_->ctx, sm_, sm_, tile_, tile_, glm::value_ptr(light_vp), draws.data(), (int32_t)draws.size()));
+        // 2. the sky through this frame's camera, for the camera pass's shader and the background behind it
+        if (sky_.model != SHS_RT_SKY_NONE) {
+            sky_.encode = SHS_RT_SKY_ENCODE_CLAMP;                                   // :598-601
+            std::memcpy(sky_.cam_forward, glm::value_ptr(cam.direction_vector), 12);
+            std::memcpy(sky_.cam_right, glm::value_ptr(cam.right_vector), 12);
+            std::memcpy(sky_.cam_up, glm::value_ptr(cam.up_vector), 12);
+            sky_.fov_degrees = cam.field_of_view;
+            ok(shs_rt_set_sky(dev_->ctx, &sky_));
+        } else {
+            ok(shs_rt_set_sky(dev_->ctx, nullptr));
+        }
+        // 3. PASS1
+        shs_rt_frame f{};
+        f.width = W; f.height = H; f.ref_tile_w = tile_; f.ref_tile_h = tile_;
+        f.clear_color[0] = 20; f.clear_color[1] = 20; f.clear_color[2] = 25; f.clear_color[3] = 255;
+        std::memcpy(f.view, glm::value_ptr(view), 64);
+        std::memcpy(f.light_vp, glm::value_ptr(light_vp), 64);
+        std::memcpy(f.light_dir_world, glm::value_ptr(light_dir_world), 12);
+        std::memcpy(f.camera_pos, glm::value_ptr(scene_->viewer->position), 12);
+        f.bias_base = 0.0025f; f.bias_slope = 0.01f; f.max_velocity_px = 22.0f;      // SHADOW_BIAS_*, MB_MAX_PIXELS :76
+        f.flags = SHS_RT_USE_SHADOW | SHS_RT_PCF;
+        f.shading = 4;
+        ok(shs_rt_render_skybox_ibl(dev_->ctx, &f, draws.data(), knobs.data(), (int32_t)draws.size()));
+        // 4. PASS2 over the planes the camera pass left on the device (MB_* :74-82)
+        void *color = nullptr, *depth = nullptr, *velocity = nullptr;
+        ok(shs_rt_device_targets(dev_->ctx, &color, &depth, &velocity));
+        shs_canvas_motion_blur_desc mb{};
+        mb.width = W; mb.height = H;
+        std::memcpy(mb.curr_view, glm::value_ptr(view), 64);
+        std::memcpy(mb.curr_proj, glm::value_ptr(proj), 64);
+        std::memcpy(mb.prev_view, glm::value_ptr(prev_view_), 64);
+        std::memcpy(mb.prev_proj, glm::value_ptr(prev_proj_), 64);
+        mb.samples = 12; mb.strength = 0.85f; mb.w_obj = 1.0f; mb.w_cam = 0.35f; mb.soft_knee = 1; mb.knee_px = 18.0f; mb.max_px = 22.0f;
+        ok(shs_canvas_motion_blur(dev_->ctx, &mb, static_cast<const uint8_t *>(color), static_cast<const float *>(depth),
+                                  static_cast<const float *>(velocity), static_cast<uint8_t *>(blurred_), SHS_CANVAS_DEVICE));
+        prev_view_ = view;
+        prev_proj_ = proj;
+    }
+
+    void ok(int rc) const {
+        if (rc != SHS_OK) throw std::runtime_error(shs_last_error(dev_->ctx));
+    }
+
+    glm::mat4 light_vp{1.0f};
+    glm::vec3 light_dir_world{0.4668f, -0.3487f, 0.8127f};   // (the shader normalises it)
+
+private:
+    SceneT *scene_;
+    Device *dev_;
+    void *blurred_;                  // W * H Color on the device: the frame the host presents
+    int sm_, tile_;
+    shs_rt_sky sky_{};
+    glm::mat4 prev_view_{1.0f}, prev_proj_{1.0f};
+};
+
+// -----------------------------------------------------------------------------------------------------
 // Seam 1c, light shafts -- hello-render-target/hello_pbr_light_shafts.cpp, PASS1.5.
 //
 // light_shafts_pass (:1525-1707) as RendererSystem::process calls it (:2171-2190), over the planes the camera pass

@@ -13,6 +13,8 @@
 // and the background of hello_pbr.cpp, hello_pbr_light_shafts.cpp and hello_ibl_skybox.cpp: shs_rt_set_sky
 // (skybox_background_pass pbr :733-799 over AnalyticSky / CubeMapSky, hello-shs-renderer/shs_renderer.hpp:432-611; the
 // host does what depends on the sun direction and the camera alone) and shs_rt_sky_samples (sky.sample alone).
+// and of hello_ibl_skybox.cpp ("ibl :line"): shs_rt_render_skybox_ibl (its PASS1, ibl :705-860 with fragment_shader_full
+// :446-524), which hands the sky of shs_rt_set_sky to the raster's shade as well as to the background pass.
 // The host forms the matrix products the shaders form first -- u.view * u.model (vertex_shader_full :616),
 // u.light_vp * u.model (shadow_vertex_shader :764) -- and the normal matrix with the GLM restatement in
 // shs_glm.hpp.  Both passes are enqueued on the context stream; the shadow map, the planes and the records
@@ -61,9 +63,11 @@ float clampf(float v, float lo, float hi) { return (v < lo) ? lo : (v > hi ? hi 
 
 // The draw table of either pass (zm: view for the camera pass, light_vp for the shadow pass).  Returns the
 // triangle count, or -1 with ctx->err set.  pbr: the PBR pass's per-draw uniforms (element i with draws[i]), or
-// null for the other passes.
+// null for the other passes; ibl: the sky-lit pass's per-draw knobs likewise, converted into *h_ibl (the caller's: the
+// table is a few draws long and lives for one call, so the context holds no copy).
+using IblTable = std::vector<shs_dev::RtIblDrawGPU>;
 int64_t build_draws(shs_ctx *ctx, const shs_rt_draw *draws, int32_t n, const float *zmat, bool camera,
-                    const shs_rt_pbr_draw *pbr = nullptr) {
+                    const shs_rt_pbr_draw *pbr = nullptr, const shs_rt_skybox_ibl_draw *ibl = nullptr, IblTable *h_ibl = nullptr) {
     ctx->rt_h_draws.clear();
     ctx->rt_h_pbr.clear();
     int64_t total = 0;
@@ -110,6 +114,11 @@ int64_t build_draws(shs_ctx *ctx, const shs_rt_draw *draws, int32_t n, const flo
             g.ibl_diffuse = saturate(m.ibl_diffuse_intensity);
             g.ibl_specular = saturate(m.ibl_specular_intensity) * saturate(m.ibl_reflection_strength);
             ctx->rt_h_pbr.push_back(g);
+        }
+        if (ibl) {
+            // the saturates of fragment_shader_full (ibl :502, :509), once per draw; their products stay in the shader
+            const shs_rt_skybox_ibl_draw &k = ibl[i];
+            h_ibl->push_back({saturate(k.ibl_ambient), saturate(k.ibl_refl), k.ibl_f0, saturate(k.ibl_refl_mix)});
         }
         ctx->rt_h_draws.push_back(o);
         total += m.n_tris;
@@ -170,12 +179,15 @@ bool pcss_ok(const shs_rt_pcss &c) {
            c.pcf_samples >= 0 && c.pcf_samples <= 64;
 }
 
-int upload_and_launch(shs_ctx *ctx, shs_dev::RtParams &p, bool shadow_pass, int shading = 0) {
+int upload_and_launch(shs_ctx *ctx, shs_dev::RtParams &p, bool shadow_pass, int shading = 0, int sky_model = 0,
+                      const IblTable *h_ibl = nullptr) {
     const size_t nd = ctx->rt_h_draws.size();
-    // the PBR pass's material table rides behind the draw table (sizeof(RtDrawGPU) is a multiple of 16): one copy
+    // the PBR pass's material table, or the sky-lit pass's knobs (a pass has one of the two at most), rides behind the
+    // draw table (sizeof(RtDrawGPU) is a multiple of 16): one copy
     static_assert(sizeof(shs_dev::RtDrawGPU) % 16 == 0, "the material table behind the draws is read as float4s");
-    const size_t npbr = ctx->rt_h_pbr.size();
-    const size_t extra = (npbr * sizeof(shs_dev::RtPbrDrawGPU) + sizeof(shs_dev::RtDrawGPU) - 1) / sizeof(shs_dev::RtDrawGPU);
+    const size_t npbr = ctx->rt_h_pbr.size(), nibl = h_ibl ? h_ibl->size() : 0;
+    const size_t tail = npbr * sizeof(shs_dev::RtPbrDrawGPU) + nibl * sizeof(shs_dev::RtIblDrawGPU);
+    const size_t extra = (tail + sizeof(shs_dev::RtDrawGPU) - 1) / sizeof(shs_dev::RtDrawGPU);
     const size_t nslot = nd + extra;
     if (ensure(ctx, ctx->rt_draws, std::max<size_t>(nslot, 1)) || ensure(ctx, ctx->rt_recs, std::max<size_t>((size_t)p.n_recs, 1)) ||
         ensure(ctx, ctx->rt_stats, 4))
@@ -194,23 +206,26 @@ int upload_and_launch(shs_ctx *ctx, shs_dev::RtParams &p, bool shadow_pass, int 
         }
         std::memcpy(ctx->rt_pin[k], ctx->rt_h_draws.data(), nd * sizeof(shs_dev::RtDrawGPU));
         if (npbr) std::memcpy(ctx->rt_pin[k] + nd, ctx->rt_h_pbr.data(), npbr * sizeof(shs_dev::RtPbrDrawGPU));
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->rt_draws.p, ctx->rt_pin[k], nd * sizeof(shs_dev::RtDrawGPU) + npbr * sizeof(shs_dev::RtPbrDrawGPU),
-                                    hipMemcpyHostToDevice, ctx->stream));
+        else if (nibl) std::memcpy(ctx->rt_pin[k] + nd, h_ibl->data(), nibl * sizeof(shs_dev::RtIblDrawGPU));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->rt_draws.p, ctx->rt_pin[k], nd * sizeof(shs_dev::RtDrawGPU) + tail, hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(ctx, hipEventRecord(ctx->rt_pin_ev[k], ctx->stream));
     }
     if (!shadow_pass) HIP_TRY(ctx, hipMemsetAsync(ctx->rt_stats.p, 0, 4 * sizeof(unsigned long long), ctx->stream));
     p.draws = ctx->rt_draws.p;
     p.pbr_draws = npbr ? reinterpret_cast<const shs_dev::RtPbrDrawGPU *>(ctx->rt_draws.p + nd) : nullptr;
+    p.ibl_draws = nibl ? reinterpret_cast<const shs_dev::RtIblDrawGPU *>(ctx->rt_draws.p + nd) : nullptr;
     p.recs = ctx->rt_recs.p;
     p.vary = ctx->rt_vary.p;
     p.stats = ctx->rt_stats.p;
-    HIP_TRY(ctx, shs_internal::launch_canvas_rt(p, shadow_pass, shading, ctx->stream));
+    HIP_TRY(ctx, shs_internal::launch_canvas_rt(p, shadow_pass, shading, ctx->stream, sky_model));
     return SHS_OK;
 }
 
-// PASS1 of the four demos: pbr null for shading 0 / 1 (shs_rt_render), the per-draw PBR uniforms for shading 2
-// (shs_rt_render_pbr) and 3 (shs_rt_render_pbr_soft).  Nothing of the context changes before the last rejection.
-int render_camera(shs_ctx *ctx, const shs_rt_frame *f, const shs_rt_draw *draws, const shs_rt_pbr_draw *pbr, int32_t n_draws) {
+// PASS1 of the five demos: pbr null for shading 0 / 1 (shs_rt_render), the per-draw PBR uniforms for shading 2
+// (shs_rt_render_pbr) and 3 (shs_rt_render_pbr_soft); ibl the per-draw knobs of shading 4 (shs_rt_render_skybox_ibl),
+// null for the others.  Nothing of the context changes before the last rejection.
+int render_camera(shs_ctx *ctx, const shs_rt_frame *f, const shs_rt_draw *draws, const shs_rt_pbr_draw *pbr, int32_t n_draws,
+                  const shs_rt_skybox_ibl_draw *ibl = nullptr) {
     if (!size_ok(ctx, f->width, f->height, f->ref_tile_w, f->ref_tile_h)) return SHS_ERR_INVALID;
     if (f->flags & ~(SHS_RT_USE_SHADOW | SHS_RT_PCF | SHS_RT_PREQUANT)) {
         ctx->err = "render-target frame: unknown flags";
@@ -221,7 +236,8 @@ int render_camera(shs_ctx *ctx, const shs_rt_frame *f, const shs_rt_draw *draws,
         return SHS_ERR_INVALID;
     }
     if (set_dev(ctx)) return SHS_ERR_HIP;
-    const int64_t n_tris = build_draws(ctx, draws, n_draws, f->view, true, pbr);
+    IblTable h_ibl;
+    const int64_t n_tris = build_draws(ctx, draws, n_draws, f->view, true, pbr, ibl, &h_ibl);
     if (n_tris < 0) return SHS_ERR_INVALID;
     const size_t npx = (size_t)f->width * f->height;
     const bool pq = (f->flags & SHS_RT_PREQUANT) != 0;
@@ -276,7 +292,13 @@ int render_camera(shs_ctx *ctx, const shs_rt_frame *f, const shs_rt_draw *draws,
         p.pbr_exposure = ctx->rt_pbr.exposure;
         p.pbr_intensity = ctx->rt_pbr.direct_intensity;
     }
-    int rc = upload_and_launch(ctx, p, false, f->shading);
+    int sky_model = SHS_RT_SKY_NONE;
+    if (f->shading == 4) {
+        // u.sky (ibl :1298): the sky the background pass below draws, as shs_rt_set_sky converted it
+        sky_model = ctx->rt_sky.model;
+        p.sky = ctx->rt_sky_model;
+    }
+    int rc = upload_and_launch(ctx, p, false, f->shading, sky_model, &h_ibl);
     if (!rc && ctx->rt_sky.model != SHS_RT_SKY_NONE) {
         // skybox_background_pass (pbr :733-799) behind the triangles: the pixels the raster left without a fragment
         shs_dev::RtSkyParams q{};
@@ -366,6 +388,24 @@ int shs_rt_render_pbr_soft(shs_ctx *ctx, const shs_rt_frame *f, const shs_rt_dra
     }
     static const shs_rt_pbr_draw none{};
     return render_camera(ctx, f, draws, n_draws > 0 ? pbr_draws : &none, n_draws);
+}
+
+int shs_rt_render_skybox_ibl(shs_ctx *ctx, const shs_rt_frame *f, const shs_rt_draw *draws, const shs_rt_skybox_ibl_draw *ibl_draws,
+                             int32_t n_draws) {
+    if (!ctx || !f || n_draws < 0 || (n_draws > 0 && (!draws || !ibl_draws))) return SHS_ERR_INVALID;
+    if (f->shading != 4) {
+        ctx->err = "shs_rt_render_skybox_ibl: shading " + std::to_string(f->shading) + " (4: hello_ibl_skybox.cpp's fragment_shader_full)";
+        return SHS_ERR_INVALID;
+    }
+    for (int32_t i = 0; i < n_draws; ++i) {
+        const shs_rt_skybox_ibl_draw &k = ibl_draws[i];
+        if (!(std::isfinite(k.ibl_ambient) && std::isfinite(k.ibl_refl) && std::isfinite(k.ibl_f0) && std::isfinite(k.ibl_refl_mix))) {
+            ctx->err = "shs_rt_render_skybox_ibl: a non-finite knob";
+            return SHS_ERR_INVALID;
+        }
+    }
+    static const shs_rt_skybox_ibl_draw none{};
+    return render_camera(ctx, f, draws, nullptr, n_draws, n_draws > 0 ? ibl_draws : &none);
 }
 
 int shs_rt_resolve(shs_ctx *ctx, uint8_t *color, float *depth, float *velocity) {

@@ -19,6 +19,12 @@
 //   shading 3  its fragment_shader_pbr (shafts :768-850): the shader of shading 2 under pcss_shadow_factor (shafts
 //          :650-762, the soft demo's text) instead of the 2x2 PCF, without the minimum-ambient term.
 //          k_rt_raster<false, 3>, launched by shs_rt_render_pbr_soft, is shade_pixel_pbr<true>.
+// and for hello_ibl_skybox.cpp ("ibl :line"), whose PASS0 / PASS1 rasters (ibl :646-686, :705-860) are the hard demo's:
+//   shading 4  its fragment_shader_full (ibl :446-524): the hard demo's Blinn-Phong under the 2x2 PCF -- but for the specular
+//          term, which does not take the base colour -- with the ambient term tinted by u.sky->sample(N) and a
+//          Schlick-weighted u.sky->sample(reflect(-V, N)) added; u.sky is the sky of the background pass below.
+//          k_rt_raster<false, 4 + sky model>, launched by shs_rt_render_skybox_ibl, is shade_pixel_ibl<SKY>: three
+//          instantiations (no sky, AnalyticSky, CubeMapSky), of which only the last has gathers.
 //   the background  skybox_background_pass (pbr :733-799; the same routine in hello_pbr_light_shafts.cpp and
 //          hello_ibl_skybox.cpp) over the legacy AnalyticSky / CubeMapSky of hello-shs-renderer/shs_renderer.hpp:
 //          k_rt_sky<MODEL, ENCODE>, a pass of its own after k_rt_raster when a sky is bound (shs_rt_set_sky), which
@@ -802,7 +808,109 @@ __device__ void shade_pixel_pbr(const RtParams &p, int32_t id, float u, float v,
     pq = make_float4(out[0], out[1], out[2], shadow);
 }
 
-// SHADING: shs_rt_frame::shading of the camera pass, a compile-time choice (the shadow pass ignores it)
+// ---- hello_ibl_skybox.cpp: the sky-lit Blinn-Phong fragment shader ("ibl :line") --------------------
+
+// AbstractSky::sample of the legacy sky models, defined with the background pass below
+template <int MODEL>
+__device__ __forceinline__ f3 sky_sample(const RtSkyModel &m, f3 d);
+
+__device__ __forceinline__ f3 mix3(f3 x, f3 y, float a) {   // glm::mix(x, y, a): x * (1 - a) + y * a
+    const float b = 1.0f - a;
+    return {x.x * b + y.x * a, x.y * b + y.y * a, x.z * b + y.z * a};
+}
+// glm::reflect(I, N) (detail/func_geometric.inl compute_reflect): I - N * dot(N, I) * 2, the vector scaled by the dot
+// product and then by two
+__device__ __forceinline__ f3 reflect3(f3 I, f3 N) {
+    const float ni = dot3(N, I);
+    return {I.x - N.x * ni * 2.0f, I.y - N.y * ni * 2.0f, I.z - N.z * ni * 2.0f};
+}
+
+// The shown fragment of hello_ibl_skybox.cpp's camera pass (ibl :810-852, the hard demo's interpolation and velocity)
+// through its fragment_shader_full (ibl :446-524): the hard demo's Blinn-Phong under the same shadow lookup, with the
+// ambient term tinted by u.sky->sample(N) and a Schlick-weighted u.sky->sample(reflect(-V, N)) added.  Not the hard
+// shader plus two terms: the base colour multiplies the ambient and the diffuse term, not the specular one.
+// SKY: u.sky, a compile-time choice (RT_SKY_NONE: u.sky == nullptr, envN = 1 and envR = 0; no gathers but the cubemap's).
+// Everything of the direct term is reduced to seven floats (base, shadow, diffuse, specular, F) before the sky is
+// sampled: N and V are all the two samples need.
+template <int SKY>
+__device__ void shade_pixel_ibl(const RtParams &p, int32_t id, float u, float v, float w, uint32_t &rgba, float2 &vel, float4 &pq) {
+    const RtRec &r = p.recs[id];
+    const RtVary &y = p.vary[id];
+    const RtDrawGPU &dr = p.draws[r.draw];
+    const float iw0 = r.iw0, iw1 = r.iw1, iw2 = r.iw2;
+    const float invw_sum = (u * iw0 + v * iw1) + w * iw2;
+    {   // velocity (ibl :841-850)
+        float pos[4], prev[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            pos[k] = (u * y.pos[k] + v * y.pos[4 + k]) + w * y.pos[8 + k];
+            prev[k] = (u * y.prev[k] + v * y.prev[4 + k]) + w * y.prev[8 + k];
+        }
+        float csx, csy, psx, psy;
+        to_screen(p, pos[0], pos[1], pos[3], csx, csy);
+        to_screen(p, prev[0], prev[1], prev[3], psx, psy);
+        float vx = csx - psx, vy = -(csy - psy);
+        const float len = sqrtf(vx * vx + vy * vy);
+        if (len > p.max_velocity && len > 1e-6f) {
+            const float s = p.max_velocity / len;
+            vx *= s;
+            vy *= s;
+        }
+        vel = make_float2(vx, vy);
+    }
+    const f3 nsum = {(u * y.nrm[0] + v * y.nrm[3]) + w * y.nrm[6], (u * y.nrm[1] + v * y.nrm[4]) + w * y.nrm[7],
+                     (u * y.nrm[2] + v * y.nrm[5]) + w * y.nrm[8]};
+    const f3 in_normal = normalize3(nsum);
+    f3 wp;
+    wp.x = ((u * (y.world[0] * iw0) + v * (y.world[3] * iw1)) + w * (y.world[6] * iw2)) / invw_sum;
+    wp.y = ((u * (y.world[1] * iw0) + v * (y.world[4] * iw1)) + w * (y.world[7] * iw2)) / invw_sum;
+    wp.z = ((u * (y.world[2] * iw0) + v * (y.world[5] * iw1)) + w * (y.world[8] * iw2)) / invw_sum;
+    const f3 N = normalize3(in_normal);
+    const f3 L = {p.L[0], p.L[1], p.L[2]};
+    const f3 V = normalize3(sub3(f3{p.cam[0], p.cam[1], p.cam[2]}, wp));
+    const float ndotl = dot3(N, L);
+    const float diffuse = g_max(ndotl, 0.0f) * 1.0f;
+    const f3 H = normalize3(add3(L, V));
+    const float spec = pow64(g_max(dot3(N, H), 0.0f));
+    const float specular = (0.45f * spec) * 1.0f;
+    f3 base = {dr.colf[0] / 255.0f, dr.colf[1] / 255.0f, dr.colf[2] / 255.0f};
+    if (dr.texels) {
+        // sample_nearest (shs_renderer.hpp:367-377)
+        const float tu = ((u * (y.uv[0] * iw0) + v * (y.uv[2] * iw1)) + w * (y.uv[4] * iw2)) / invw_sum;
+        const float tv = ((u * (y.uv[1] * iw0) + v * (y.uv[3] * iw1)) + w * (y.uv[5] * iw2)) / invw_sum;
+        const float su = saturate(tu), sv = saturate(tv);
+        const int x = clampi(lround_x86(su * (float)(dr.tw - 1)), 0, dr.tw - 1);
+        const int yy = clampi(lround_x86(sv * (float)(dr.th - 1)), 0, dr.th - 1);
+        const uint32_t tc = dr.texels[(size_t)yy * dr.tw + x];
+        base = f3{(float)(tc & 0xffu) / 255.0f, (float)((tc >> 8) & 0xffu) / 255.0f, (float)((tc >> 16) & 0xffu) / 255.0f};
+    }
+    float shadow = 1.0f;
+    if (p.shadow) shadow = shadow_factor(p, wp, ndotl);
+    const float4 kn = *reinterpret_cast<const float4 *>(&p.ibl_draws[r.draw]);   // ambient, refl, f0, refl_mix
+    // Math::schlick_fresnel(u.ibl_f0, max(0, N.V)) (shs_renderer.hpp:164-169)
+    const float fx = 1.0f - saturate(g_max(0.0f, dot3(N, V)));
+    const float fx2 = fx * fx;
+    const float fx5 = fx2 * fx2 * fx;
+    const float F = kn.z + (1.0f - kn.z) * fx5;
+    const float rk = (F * kn.y) * kn.w;
+    f3 envN = {1.0f, 1.0f, 1.0f}, envR = {0.0f, 0.0f, 0.0f};
+    if constexpr (SKY != RT_SKY_NONE) {
+        envN = sky_sample<SKY>(p.sky, N);
+        envR = sky_sample<SKY>(p.sky, reflect3(f3{-V.x, -V.y, -V.z}, N));
+    }
+    // ambient = 0.18 * mix(vec3(1), envN, a); amb = ambient * base; direct = shadow * (diffuse * base + specular);
+    // refl = envR * rk; clamp((amb + direct) + refl)
+    const f3 tint = mix3(f3{1.0f, 1.0f, 1.0f}, envN, kn.x);
+    const float pr = g_clamp01(((0.18f * tint.x) * base.x + shadow * (diffuse * base.x + specular)) + envR.x * rk) * 255;
+    const float pg = g_clamp01(((0.18f * tint.y) * base.y + shadow * (diffuse * base.y + specular)) + envR.y * rk) * 255;
+    const float pb = g_clamp01(((0.18f * tint.z) * base.z + shadow * (diffuse * base.z + specular)) + envR.z * rk) * 255;
+    rgba = byte_x86(pr) | (byte_x86(pg) << 8) | (byte_x86(pb) << 16) | 0xff000000u;
+    pq = make_float4(pr, pg, pb, shadow);
+}
+
+// SHADING: shs_rt_frame::shading of the camera pass, a compile-time choice (the shadow pass ignores it); shading 4 is
+// three instantiations, RT_SHADING_IBL + the sky model it samples (RT_SKY_*)
+constexpr int RT_SHADING_IBL = 4;
 template <bool SHADOW, int SHADING = 0>
 __global__ __launch_bounds__(256) void k_rt_raster(const RtParams p) {
     __shared__ float4 s_rec[RT_CHUNK * 6];
@@ -902,6 +1010,8 @@ __global__ __launch_bounds__(256) void k_rt_raster(const RtParams p) {
         if (sid >= 0) shade_pixel_pbr<false>(p, sid, su, sv, sw, px, py, rgba, vel, pq);
     } else if constexpr (SHADING == 3) {
         if (sid >= 0) shade_pixel_pbr<true>(p, sid, su, sv, sw, px, py, rgba, vel, pq);
+    } else if constexpr (SHADING >= RT_SHADING_IBL) {
+        if (sid >= 0) shade_pixel_ibl<SHADING - RT_SHADING_IBL>(p, sid, su, sv, sw, rgba, vel, pq);
     } else {
         if (sid >= 0) shade_pixel(p, sid, su, sv, sw, rgba, vel, pq);
     }
@@ -934,10 +1044,6 @@ __global__ __launch_bounds__(256) void k_rt_ibl_samples(const RtIblSamples q) {
 
 // ---- skybox_background_pass (pbr :733-799) over the legacy sky models ("sky :line": hello-shs-renderer/shs_renderer.hpp)
 
-__device__ __forceinline__ f3 mix3(f3 x, f3 y, float a) {   // glm::mix(x, y, a): x * (1 - a) + y * a
-    const float b = 1.0f - a;
-    return {x.x * b + y.x * a, x.y * b + y.y * a, x.z * b + y.z * a};
-}
 __device__ __forceinline__ f3 ld3(const float *p) { return {p[0], p[1], p[2]}; }
 
 // AnalyticSky::sample (sky :558-608) after the host's part (RtSkyModel).  Its three std::pow(x, 3.0f / 4.0f / 12.0f)
@@ -1112,7 +1218,7 @@ hipError_t launch_sky_samples(const shs_dev::RtSkySamples &q, int model, hipStre
     return hipGetLastError();
 }
 
-hipError_t launch_canvas_rt(const shs_dev::RtParams &p, bool shadow_pass, int shading, hipStream_t s) {
+hipError_t launch_canvas_rt(const shs_dev::RtParams &p, bool shadow_pass, int shading, hipStream_t s, int sky_model) {
     using namespace shs_dev;
     if (p.n_tris > 0) {
         const int grid = (p.n_tris + 255) / 256;
@@ -1126,6 +1232,11 @@ hipError_t launch_canvas_rt(const shs_dev::RtParams &p, bool shadow_pass, int sh
     else if (shading == 1) hipLaunchKernelGGL((k_rt_raster<false, 1>), dim3(tiles), dim3(256), 0, s, p);
     else if (shading == 2) hipLaunchKernelGGL((k_rt_raster<false, 2>), dim3(tiles), dim3(256), 0, s, p);
     else if (shading == 3) hipLaunchKernelGGL((k_rt_raster<false, 3>), dim3(tiles), dim3(256), 0, s, p);
+    else if (shading == 4 && sky_model == RT_SKY_CUBEMAP)
+        hipLaunchKernelGGL((k_rt_raster<false, RT_SHADING_IBL + RT_SKY_CUBEMAP>), dim3(tiles), dim3(256), 0, s, p);
+    else if (shading == 4 && sky_model == RT_SKY_ANALYTIC)
+        hipLaunchKernelGGL((k_rt_raster<false, RT_SHADING_IBL + RT_SKY_ANALYTIC>), dim3(tiles), dim3(256), 0, s, p);
+    else if (shading == 4) hipLaunchKernelGGL((k_rt_raster<false, RT_SHADING_IBL + RT_SKY_NONE>), dim3(tiles), dim3(256), 0, s, p);
     else hipLaunchKernelGGL(k_rt_raster<false>, dim3(tiles), dim3(256), 0, s, p);
     return hipGetLastError();
 }

@@ -3,7 +3,9 @@
 // of hello_shadow_mapping_soft.cpp (the same passes with the PCSS fragment shader, shs_rt_frame::shading 1) and
 // hello_pbr.cpp (the same passes with the GGX + IBL fragment shader, shading 2 through shs_rt_render_pbr) and
 // hello_pbr_light_shafts.cpp (that shader under the PCSS factor, shading 3 through shs_rt_render_pbr_soft), and of the
-// background pass behind any of them (skybox_background_pass over the legacy sky models, shs_rt_set_sky).
+// background pass behind any of them (skybox_background_pass over the legacy sky models, shs_rt_set_sky), and of
+// hello_ibl_skybox.cpp (the hard demo's passes with the sky-lit fragment shader, shading 4 through
+// shs_rt_render_skybox_ibl, which samples the bound sky per pixel).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -65,11 +67,41 @@ struct alignas(16) RtPbrDrawGPU {
 };
 static_assert(sizeof(RtPbrDrawGPU) == 32, "RtPbrDrawGPU: two float4s");
 
+// The per-draw knobs of hello_ibl_skybox.cpp's Uniforms (:336-339) after the three saturates of fragment_shader_full
+// (:502, :509), which the host does; the products stay in the shader.  16 B: one dwordx4 load of a shaded pixel.
+struct alignas(16) RtIblDrawGPU {
+    float ambient;                   // saturate(ibl_ambient)
+    float refl;                      // saturate(ibl_refl)
+    float f0;                        // ibl_f0
+    float refl_mix;                  // saturate(ibl_refl_mix)
+};
+static_assert(sizeof(RtIblDrawGPU) == 16, "RtIblDrawGPU: one float4");
+
 // The EnvIBL levels (shs/resources/ibl.hpp:21-59) in one allocation of float4s: RT_IBL_LEVELS headers, then the
 // texels, rgb padded to 16 B so that a bilinear corner is one dwordx4 load.  Header l holds, as int bits,
 // {first texel, size}: level 0 is env_irradiance, level 1 + m is env_prefiltered_spec.mip[m].  Face f of a level
 // starts size * size * f texels after its first; texel (x, y) of a face is at y * size + x.
 constexpr int RT_IBL_LEVELS = 17;
+
+// ---- skybox_background_pass (hello_pbr.cpp:733-799) over the legacy sky models of shs_renderer.hpp ----
+
+constexpr int RT_SKY_NONE = 0, RT_SKY_ANALYTIC = 1, RT_SKY_CUBEMAP = 2;   // SHS_RT_SKY_*
+constexpr int RT_SKY_REINHARD = 0, RT_SKY_CLAMP = 1;     // SHS_RT_SKY_ENCODE_*
+
+// What AbstractSky::sample reads, after the operations the host has done once per shs_rt_set_sky.
+struct RtSkyModel {
+    // AnalyticSky (:552-611): everything that depends on the sun direction alone
+    float s[3];                      // -normalize(sun_direction)
+    float zenith[3], horizon[3];     // the two mixes over sun_height :574-575
+    float ground[3];                 // ground_color :578-579
+    float half_horizon[3];           // horizon_color * 0.5f :589
+    float glow[3];                   // sun_glow_color :596
+    // CubeMapSky (:432-517): the faces +X -X +Y -Y +Z -Z, the sRGB -> linear table and intensity_
+    float intensity;
+    const uint32_t *face[6];
+    int32_t fw[6], fh[6];
+    const float *srgb_lut;           // 256 floats: pow(c / 255, 2.2) with the host's libm
+};
 
 constexpr int RT_TW = 32, RT_TH = 8;     // raster tile: one 256-thread workgroup, one pixel per lane
 constexpr int RT_CHUNK = 256;            // records examined (and at most staged in LDS) per round
@@ -103,6 +135,9 @@ struct RtParams {
     const float4 *ibl;               // the levels above, or null: u.ibl == nullptr
     int32_t ibl_mips;                // env_prefiltered_spec.mip_count()
     float pbr_exposure, pbr_intensity;   // shs_rt_pbr (min_roughness is folded into RtPbrDrawGPU::roughness)
+    // shading 4 only (appended likewise)
+    RtSkyModel sky;                  // u.sky: the sky of shs_rt_set_sky (read by the analytic / cubemap instantiations)
+    const RtIblDrawGPU *ibl_draws;   // element i goes with draws[i]
 };
 
 // sample_cubemap_linear_vec(env_irradiance, dir) and sample_prefiltered_spec_trilinear(spec, dir, lod) for a list
@@ -125,26 +160,6 @@ struct RtPcssSamples {
     float *out;                      // n
     float pcss_light, pcss_search, pcss_min, pcss_max, pcss_eps;
     int32_t pcss_blockers, pcss_taps;
-};
-
-// ---- skybox_background_pass (hello_pbr.cpp:733-799) over the legacy sky models of shs_renderer.hpp ----
-
-constexpr int RT_SKY_ANALYTIC = 1, RT_SKY_CUBEMAP = 2;   // SHS_RT_SKY_*
-constexpr int RT_SKY_REINHARD = 0, RT_SKY_CLAMP = 1;     // SHS_RT_SKY_ENCODE_*
-
-// What AbstractSky::sample reads, after the operations the host has done once per shs_rt_set_sky.
-struct RtSkyModel {
-    // AnalyticSky (:552-611): everything that depends on the sun direction alone
-    float s[3];                      // -normalize(sun_direction)
-    float zenith[3], horizon[3];     // the two mixes over sun_height :574-575
-    float ground[3];                 // ground_color :578-579
-    float half_horizon[3];           // horizon_color * 0.5f :589
-    float glow[3];                   // sun_glow_color :596
-    // CubeMapSky (:432-517): the faces +X -X +Y -Y +Z -Z, the sRGB -> linear table and intensity_
-    float intensity;
-    const uint32_t *face[6];
-    int32_t fw[6], fh[6];
-    const float *srgb_lut;           // 256 floats: pow(c / 255, 2.2) with the host's libm
 };
 
 // The background pass's own parameters (not RtParams': the raster kernels' arguments stay as they were).
@@ -175,8 +190,9 @@ hipError_t launch_canvas_rt_sky(const shs_dev::RtSkyParams &p, int model, int en
 hipError_t launch_sky_samples(const shs_dev::RtSkySamples &q, int model, hipStream_t s);
 // setup (one lane per input triangle) then raster (one workgroup per 32x8 tile) of either pass
 // shading: shs_rt_frame::shading of the camera pass (0: fragment_shader_full, 1: fragment_shader_softshadow,
-// 2: fragment_shader_pbr, 3: hello_pbr_light_shafts.cpp's fragment_shader_pbr)
-hipError_t launch_canvas_rt(const shs_dev::RtParams &p, bool shadow_pass, int shading, hipStream_t s);
+// 2: fragment_shader_pbr, 3: hello_pbr_light_shafts.cpp's fragment_shader_pbr, 4: hello_ibl_skybox.cpp's
+// fragment_shader_full); sky_model: u.sky of shading 4 (RT_SKY_*), which chooses among its three instantiations
+hipError_t launch_canvas_rt(const shs_dev::RtParams &p, bool shadow_pass, int shading, hipStream_t s, int sky_model = 0);
 hipError_t launch_pcss_samples(const shs_dev::RtPcssSamples &q, hipStream_t s);
 hipError_t launch_ibl_samples(const shs_dev::RtIblSamples &q, hipStream_t s);
 }  // namespace shs_internal

@@ -18,7 +18,7 @@ from ._abi import (FRAME_PREQUANT, FRAME_PRESENT, SHADING_BLINN_PHONG, SHADING_D
                    SHADING_TOON, FrameDesc, LegacyDraw, RasterStats)
 
 __all__ = [
-    "ShsError", "Context", "Frame", "Draw", "RtFrame", "RtDraw", "RtPcss", "RtPbrDraw", "RtPbr", "RtSky", "SHADING_FLAT", "SHADING_GOURAUD", "SHADING_PHONG",
+    "ShsError", "Context", "Frame", "Draw", "RtFrame", "RtDraw", "RtPcss", "RtPbrDraw", "RtPbr", "RtSky", "RtSkyboxIblDraw", "SHADING_FLAT", "SHADING_GOURAUD", "SHADING_PHONG",
     "SHADING_BLINN_PHONG", "SHADING_TOON", "SHADING_GOOCH", "SHADING_OREN_NAYAR", "SHADING_NORMAL_VIS",
     "SHADING_DEPTH_VIS", "SHADING_TEXTURED", "SHADING_NAMES", "FRAME_PREQUANT", "lib",
 ]
@@ -108,6 +108,7 @@ class RtFrame:
     shading: int = 0             # 0: fragment_shader_full, 1: fragment_shader_softshadow (PCSS; Context.rt_set_pcss),
                                  # 2: fragment_shader_pbr (Context.rt_render_pbr only),
                                  # 3: hello_pbr_light_shafts.cpp's fragment_shader_pbr, PBR under PCSS (Context.rt_render_pbr_soft only)
+                                 # 4: hello_ibl_skybox.cpp's sky-lit fragment_shader_full (Context.rt_render_skybox_ibl only)
 
 
 @dataclass
@@ -141,6 +142,15 @@ class RtPbr:
     exposure: float = 1.75
     min_roughness: float = 0.04
     direct_intensity: float = 3.0
+
+
+@dataclass
+class RtSkyboxIblDraw:
+    """hello_ibl_skybox.cpp's per-object knobs beside an RtDraw (shs_rt_skybox_ibl_draw); the defaults are Uniforms'."""
+    ibl_ambient: float = 0.25
+    ibl_refl: float = 0.35
+    ibl_f0: float = 0.04
+    ibl_refl_mix: float = 1.0
 
 
 @dataclass
@@ -799,6 +809,21 @@ class Context:
             for name in ("metallic", "roughness", "ao", "ibl_diffuse_intensity", "ibl_specular_intensity", "ibl_reflection_strength"):
                 setattr(mat[i], name, float(getattr(m, name)))
         self._check(entry(self._h, ctypes.byref(self._rt_frame_c(frame)), arr, mat, len(draws)))
+        self._rt_size = (frame.width, frame.height)
+
+    def rt_render_skybox_ibl(self, frame, draws, ibl_draws):
+        """shs_rt_render_skybox_ibl: PASS1 of hello_ibl_skybox.cpp (frame.shading 4: Blinn-Phong under the shadow lookup,
+        tinted by and reflecting the sky of rt_set_sky; ibl_draws: one RtSkyboxIblDraw per draw, or None to hand the
+        library a null table), asynchronous."""
+        arr = self._rt_draw_array(draws)
+        knobs = None
+        if ibl_draws is not None:
+            if len(ibl_draws) != len(draws):
+                raise ShsError(-1, "rt_render_skybox_ibl: one RtSkyboxIblDraw per draw")
+            knobs = (_abi.RtSkyboxIblDrawC * max(len(draws), 1))()
+            for i, k in enumerate(ibl_draws):
+                knobs[i] = _abi.RtSkyboxIblDrawC(float(k.ibl_ambient), float(k.ibl_refl), float(k.ibl_f0), float(k.ibl_refl_mix))
+        self._check(self._lib.shs_rt_render_skybox_ibl(self._h, ctypes.byref(self._rt_frame_c(frame)), arr, knobs, len(draws)))
         self._rt_size = (frame.width, frame.height)
 
     def rt_set_pbr(self, pbr=None):

@@ -273,6 +273,12 @@ class RtSkyC(ctypes.Structure):
                 ("fov_degrees", ctypes.c_float), ("exposure", ctypes.c_float)]
 
 
+class RtSkyboxIblDrawC(ctypes.Structure):
+    """shs_rt_skybox_ibl_draw: hello_ibl_skybox.cpp's per-object knobs beside shs_rt_draw (shading 4)."""
+    _fields_ = [("ibl_ambient", ctypes.c_float), ("ibl_refl", ctypes.c_float), ("ibl_f0", ctypes.c_float),
+                ("ibl_refl_mix", ctypes.c_float)]
+
+
 class RtStatsC(ctypes.Structure):
     _fields_ = [("input_tris", ctypes.c_int64), ("polys3", ctypes.c_int64), ("polys4", ctypes.c_int64),
                 ("sub_tris", ctypes.c_int64)]
@@ -398,6 +404,8 @@ SIGNATURES = [
     ("shs_rt_render_pbr_soft", ctypes.c_int, [_P, ctypes.POINTER(RtFrameC), ctypes.POINTER(RtDrawC), ctypes.POINTER(RtPbrDrawC),
                                               ctypes.c_int32]),
     ("shs_rt_ibl_samples", ctypes.c_int, [_P, ctypes.c_int32, _P, _P, _P, _P]),
+    ("shs_rt_render_skybox_ibl", ctypes.c_int, [_P, ctypes.POINTER(RtFrameC), ctypes.POINTER(RtDrawC),
+                                                ctypes.POINTER(RtSkyboxIblDrawC), ctypes.c_int32]),
     ("shs_rt_set_sky", ctypes.c_int, [_P, ctypes.POINTER(RtSkyC)]),
     ("shs_rt_sky_samples", ctypes.c_int, [_P, ctypes.c_int32, _P, _P]),
     ("shs_rt_resolve", ctypes.c_int, [_P, _P, _P, _P]),
