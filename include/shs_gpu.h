@@ -903,7 +903,22 @@ int shs_canvas_light_shafts(shs_ctx *ctx, const shs_canvas_light_shafts_desc *de
  *      diffuse terms take the base colour and whose specular term does not, with the ambient term tinted by
  *      sky.sample(N) and a Schlick-weighted sky.sample(reflect(-V, N)) added: u.sky is the sky bound by
  *      shs_rt_set_sky, the one the background pass draws (no sky bound: u.sky == nullptr, tint 1, no reflection).
- *      The velocity plane is written as for shading 0; the prequant plane's fourth float is the shadow factor. */
+ *      The velocity plane is written as for shading 0; the prequant plane's fourth float is the shadow factor.
+ *   5  the two fragment shaders of hello_water.cpp, through shs_rt_render_water only: fragment_shader_full (:938-994, the
+ *      "atmosphere" shader) for the draws whose shs_rt_water_draw::flags is 0 and fragment_shader_water (:1000-1097) for
+ *      those with SHS_RT_WATER_SURFACE.  That demo's PASS0 and PASS1 rasters, its vertex shader, velocity and
+ *      shadow_uvz_from_world are hello_shadow_mapping.cpp's (tile jobs of 80) and its PASS2 is shs_canvas_motion_blur.
+ *      The frame is shadow pass, reflection pass (a camera pass from the camera mirrored at the water plane, every draw
+ *      non-water, SHS_RT_WATER_REFLECTION off), shs_rt_keep_reflection, camera pass, blur.  The atmosphere shader is
+ *      Blinn-Phong with a sky-coloured ambient term (sky_color_simple along the view ray), exponential fog, Reinhard
+ *      and gamma 2.2; the water shader takes its normal and foam from water_flow_normal_and_foam (:862-930, a hash /
+ *      value-noise / fbm chain over world x, z and shs_rt_water::time_sec, bit for bit the reference's), mixes the
+ *      water's base colour with the reflection canvas's texel under reflection_vp (nearest, distorted by the normal;
+ *      the sky where the lookup leaves the canvas or none is held) by Schlick's fresnel, and adds foam, a glossy
+ *      highlight and the same fog.  The shadow lookup (:716-751) differs from shading 0's: a uv outside [0, 1] is lit
+ *      before the PCF taps, and an empty texel is lit whatever z is.  Both shaders round to the byte
+ *      (clampi(lround(c * 255), 0, 255)) where shadings 0 to 4 truncate; the prequant plane holds c * 255 before that
+ *      rounding and the shadow factor.  The velocity plane is written as for shading 0. */
 typedef struct shs_rt_draw {
     int32_t mesh_id;            /* shs_mesh_upload_soup[_uv] soup (without UVs: vec2(0) per corner) */
     int32_t albedo_tex;         /* shs_texture_upload id (use_texture), 0: base_color */
@@ -931,7 +946,9 @@ typedef struct shs_rt_frame {
                                          3: hello_pbr_light_shafts.cpp's fragment_shader_pbr :768-850 over
                                             pcss_shadow_factor :650-762 (shs_rt_render_pbr_soft),
                                          4: hello_ibl_skybox.cpp's fragment_shader_full :446-524
-                                            (shs_rt_render_skybox_ibl) */
+                                            (shs_rt_render_skybox_ibl),
+                                         5: hello_water.cpp's fragment_shader_full :938-994 and
+                                            fragment_shader_water :1000-1097 per draw (shs_rt_render_water) */
 } shs_rt_frame;
 /* The PCSS constants of shading 1 (hello_shadow_mapping_soft.cpp:101-116), kept in the context. */
 typedef struct shs_rt_pcss {
@@ -960,7 +977,7 @@ typedef struct shs_rt_stats {
 int shs_rt_render_shadow(shs_ctx *ctx, int32_t w, int32_t h, int32_t ref_tile_w, int32_t ref_tile_h, const float light_vp[16],
                          const shs_rt_draw *casters, int32_t n_casters);
 /* SHS_ERR_INVALID: an unknown mesh or texture id, a non-positive size, unknown flags, a shading other than
- * 0 or 1 (2 goes through shs_rt_render_pbr, 3 through shs_rt_render_pbr_soft, 4 through shs_rt_render_skybox_ibl), or SHS_RT_USE_SHADOW without a shadow map rendered before. */
+ * 0 or 1 (2 goes through shs_rt_render_pbr, 3 through shs_rt_render_pbr_soft, 4 through shs_rt_render_skybox_ibl, 5 through shs_rt_render_water), or SHS_RT_USE_SHADOW without a shadow map rendered before. */
 int shs_rt_render(shs_ctx *ctx, const shs_rt_frame *frame, const shs_rt_draw *draws, int32_t n_draws);
 /* Host copies of the last camera pass (any pointer may be NULL): color W*H*4 bytes, depth W*H floats,
  * velocity W*H*2 floats.  Synchronous. */
@@ -1020,7 +1037,7 @@ int shs_rt_ibl_samples(shs_ctx *ctx, int32_t n, const float *dirs3, const float 
  * (:552-611) and CubeMapSky with sample_face_bilinear (:432-517).  (These are not the library path's ProceduralSky /
  * CubemapSky of shs_lib_set_sky; the legacy ProceduralSky :520-549 is not built: no render-target demo constructs it.)
  * The reference draws the sky first and the triangles over it.  Here, with a sky bound, every camera pass
- * (shs_rt_render, shs_rt_render_pbr, shs_rt_render_pbr_soft, shs_rt_render_skybox_ibl, whatever the shading) is followed on the context stream by a background pass
+ * (shs_rt_render, shs_rt_render_pbr, shs_rt_render_pbr_soft, shs_rt_render_skybox_ibl, shs_rt_render_water, whatever the shading) is followed on the context stream by a background pass
  * that colours each pixel that shows no fragment (shs_rt_resolve_ids: -1) -- also one whose fragment kept its depth
  * but not its colour -- from the direction through the pixel's centre (:769-780; canvas x, y with y up).  Such a
  * pixel's prequant floats are (r, g, b) * 255 before the truncation and 1; depth and velocity stay as the raster
@@ -1064,6 +1081,38 @@ typedef struct shs_rt_skybox_ibl_draw {
  * n_draws > 0 and for a non-finite knob (nothing is enqueued). */
 int shs_rt_render_skybox_ibl(shs_ctx *ctx, const shs_rt_frame *frame, const shs_rt_draw *draws,
                              const shs_rt_skybox_ibl_draw *ibl_draws, int32_t n_draws);
+/* hello_water.cpp (shading 5): which of that demo's two fragment shaders a draw runs; element i goes with shs_rt_draw[i]. */
+#define SHS_RT_WATER_SURFACE 1u      /* fragment_shader_water (:1000-1097); 0: fragment_shader_full (:938-994) */
+typedef struct shs_rt_water_draw {
+    uint32_t flags;                  /* SHS_RT_WATER_SURFACE or 0 */
+} shs_rt_water_draw;
+/* The frame's part of hello_water.cpp's Uniforms (:653-655), passed per call because it changes every frame. */
+#define SHS_RT_WATER_REFLECTION 1u   /* u.reflection_color is bound: the context's reflection canvas */
+typedef struct shs_rt_water {
+    float reflection_vp[16];         /* u.reflection_vp: the mirrored camera's proj * view, column-major */
+    float time_sec;                  /* u.time_sec */
+    uint32_t flags;                  /* SHS_RT_WATER_REFLECTION or 0 (refl_col = sky, :1020-1021) */
+} shs_rt_water;
+/* PASS1A / PASS1B of hello_water.cpp: the raster of shs_rt_render with that demo's two fragment shaders, chosen per
+ * draw by water_draws[i].flags.  frame->shading must be 5.  The background pass follows as after every camera pass.
+ * SHS_ERR_INVALID as shs_rt_render, for any other shading, for a null water or a null water_draws with n_draws > 0,
+ * for unknown bits in either flags word, for SHS_RT_WATER_REFLECTION with no reflection canvas held and for a
+ * non-finite time_sec (nothing is enqueued). */
+int shs_rt_render_water(shs_ctx *ctx, const shs_rt_frame *frame, const shs_rt_draw *draws, const shs_rt_water_draw *water_draws,
+                        const shs_rt_water *water, int32_t n_draws);
+/* The last camera pass's colour plane, at its own size and after its background pass if a sky is bound, becomes the
+ * context's reflection canvas: one device-to-device copy on the context stream, no host synchronise (but the first
+ * call of a larger size, which allocates).  Valid until replaced, cleared or shs_destroy; later camera passes do not
+ * touch it.  SHS_ERR_INVALID: no camera pass before it. */
+int shs_rt_keep_reflection(shs_ctx *ctx);
+/* The same canvas from a host image, w * h RGBA in canvas rows (y up), for hosts that draw the reflection elsewhere.
+ * The reflection's size is its own, not the frame's (:1029-1038).  rgba NULL: no reflection canvas.  Synchronous.
+ * SHS_ERR_INVALID: a size outside 1 .. 32767 (the context keeps what it had). */
+int shs_rt_set_reflection(shs_ctx *ctx, const uint8_t *rgba, int32_t w, int32_t h);
+/* water_flow_normal_and_foam (:862-930) for n points through the device function the raster calls: world_pos3 and
+ * normal3 3n, foam n.  Synchronous; for tests of the hash chain, which is bit for bit the reference's.
+ * SHS_ERR_INVALID: a non-finite time_sec. */
+int shs_rt_water_samples(shs_ctx *ctx, int32_t n, const float *world_pos3, float time_sec, float *normal3, float *foam);
 /* ortho_lh_zo (hello_shadow_mapping.cpp:128-140): LH, z in [0, 1]. */
 int shs_ortho_lh_zo(float left, float right, float bottom, float top, float znear, float zfar, float out16[16]);
 

@@ -587,6 +587,126 @@ private:
 };
 
 // -----------------------------------------------------------------------------------------------------
+// Seam 1b, water -- hello-render-target/hello_water.cpp.
+//
+// Replaces RendererSystem::process there, five calls on the context stream with no resolve in between:
+//   1. shs_rt_render_shadow with tile jobs of 80: PASS0 is the hard demo's;
+//   2. shs_rt_render_water, shading = 5, from the camera mirrored at y = WATER_Y (compute_reflection_view_lh :1550-1563,
+//      formed here on the host): PASS1A (:1765-1955), the objects alone, every draw non-water, no reflection bound, the
+//      mirrored position as camera_pos (:1804);
+//   3. shs_rt_keep_reflection: that pass's colour plane becomes u.reflection_color (one device-to-device copy);
+//   4. shs_rt_render_water again through the viewer's camera with the floor, the water plane (SHS_RT_WATER_SURFACE) and
+//      the objects, SHS_RT_WATER_REFLECTION and reflection_vp = proj * refl_view: PASS1B (:1957-2211);
+//   5. shs_canvas_motion_blur over shs_rt_device_targets: combined_motion_blur_pass is the hard demo's text.
+// The demo binds no sky: uncovered pixels keep CLEAR_BG (:86).  Uncompiled, like the other seams.
+// -----------------------------------------------------------------------------------------------------
+template <class SceneT>
+class WaterSystemGPU : public shs::AbstractSystem {
+public:
+    struct Object {
+        typename RenderTargetSystemGPU<SceneT>::Object geom;
+        bool water = false;          // the water plane: fragment_shader_water; it is left out of the reflection pass
+    };
+
+    WaterSystemGPU(SceneT *scene, Device *dev, void *blurred_dev, float water_y = -0.20f, int shadow_size = 2048, int tile = 80)
+        : scene_(scene), dev_(dev), blurred_(blurred_dev), water_y_(water_y), sm_(shadow_size), tile_(tile) {}
+
+    std::vector<Object> objects;     // geom.model / prev_model per frame
+
+    void process(float dt) override {
+        time_accum_ += dt;
+        shs::Canvas &canvas = *scene_->canvas;
+        const int W = canvas.get_width(), H = canvas.get_height();
+        const shs::Camera3D &cam = *scene_->viewer->camera;
+        const glm::mat4 view = cam.view_matrix, proj = cam.projection_matrix;
+        // compute_reflection_view_lh :1550-1563
+        glm::vec3 rpos = scene_->viewer->position, rdir = cam.direction_vector, rup = cam.up_vector;
+        rpos.y = 2.0f * water_y_ - rpos.y;
+        rdir.y = -rdir.y;
+        rup.y = -rup.y;
+        const glm::mat4 refl_view = glm::lookAtLH(rpos, rpos + rdir, rup);
+        const glm::mat4 refl_vp = proj * refl_view;
+        std::vector<shs_rt_draw> draws(objects.size()), refl_draws;
+        std::vector<shs_rt_water_draw> flags(objects.size()), refl_flags;
+        for (size_t i = 0; i < objects.size(); ++i) {
+            const auto &o = objects[i].geom;
+            shs_rt_draw &d = draws[i];
+            d.mesh_id = o.mesh_id;
+            d.albedo_tex = o.albedo_tex;
+            const glm::mat4 mvp = proj * view * o.model, prev_mvp = prev_proj_ * prev_view_ * o.prev_model;
+            std::memcpy(d.model, glm::value_ptr(o.model), 64);
+            std::memcpy(d.mvp, glm::value_ptr(mvp), 64);
+            std::memcpy(d.prev_mvp, glm::value_ptr(prev_mvp), 64);
+            d.base_color[0] = o.base_color.r; d.base_color[1] = o.base_color.g; d.base_color[2] = o.base_color.b; d.base_color[3] = 255;
+            flags[i].flags = objects[i].water ? SHS_RT_WATER_SURFACE : 0u;
+            if (!objects[i].water) {
+                shs_rt_draw r = d;
+                const glm::mat4 rmvp = refl_vp * o.model;
+                std::memcpy(r.mvp, glm::value_ptr(rmvp), 64);
+                std::memcpy(r.prev_mvp, glm::value_ptr(rmvp), 64);
+                refl_draws.push_back(r);
+                refl_flags.push_back(shs_rt_water_draw{0u});
+            }
+        }
+        // 1. PASS0
+        ok(shs_rt_render_shadow(dev_->ctx, sm_, sm_, tile_, tile_, glm::value_ptr(light_vp), draws.data(), (int32_t)draws.size()));
+        shs_rt_frame f{};
+        f.width = W; f.height = H; f.ref_tile_w = tile_; f.ref_tile_h = tile_;
+        f.clear_color[0] = 24; f.clear_color[1] = 34; f.clear_color[2] = 58; f.clear_color[3] = 255;   // CLEAR_BG :86
+        std::memcpy(f.light_vp, glm::value_ptr(light_vp), 64);
+        std::memcpy(f.light_dir_world, glm::value_ptr(light_dir_world), 12);
+        f.bias_base = 0.0025f; f.bias_slope = 0.01f; f.max_velocity_px = 22.0f;      // SHADOW_BIAS_*, MB_MAX_PIXELS
+        f.flags = SHS_RT_USE_SHADOW | SHS_RT_PCF;
+        f.shading = 5;
+        shs_rt_water wu{};
+        wu.time_sec = time_accum_;
+        // 2. PASS1A from the mirrored camera, 3. keep its colour
+        shs_rt_frame rf = f;
+        std::memcpy(rf.view, glm::value_ptr(refl_view), 64);
+        std::memcpy(rf.camera_pos, glm::value_ptr(rpos), 12);
+        std::memcpy(wu.reflection_vp, glm::value_ptr(glm::mat4(1.0f)), 64);
+        wu.flags = 0u;
+        ok(shs_rt_render_water(dev_->ctx, &rf, refl_draws.data(), refl_flags.data(), &wu, (int32_t)refl_draws.size()));
+        ok(shs_rt_keep_reflection(dev_->ctx));
+        // 4. PASS1B
+        std::memcpy(f.view, glm::value_ptr(view), 64);
+        std::memcpy(f.camera_pos, glm::value_ptr(scene_->viewer->position), 12);
+        std::memcpy(wu.reflection_vp, glm::value_ptr(refl_vp), 64);
+        wu.flags = SHS_RT_WATER_REFLECTION;
+        ok(shs_rt_render_water(dev_->ctx, &f, draws.data(), flags.data(), &wu, (int32_t)draws.size()));
+        // 5. PASS2 over the planes the camera pass left on the device (MB_*)
+        void *color = nullptr, *depth = nullptr, *velocity = nullptr;
+        ok(shs_rt_device_targets(dev_->ctx, &color, &depth, &velocity));
+        shs_canvas_motion_blur_desc mb{};
+        mb.width = W; mb.height = H;
+        std::memcpy(mb.curr_view, glm::value_ptr(view), 64);
+        std::memcpy(mb.curr_proj, glm::value_ptr(proj), 64);
+        std::memcpy(mb.prev_view, glm::value_ptr(prev_view_), 64);
+        std::memcpy(mb.prev_proj, glm::value_ptr(prev_proj_), 64);
+        mb.samples = 12; mb.strength = 0.85f; mb.w_obj = 1.0f; mb.w_cam = 0.35f; mb.soft_knee = 1; mb.knee_px = 18.0f; mb.max_px = 22.0f;
+        ok(shs_canvas_motion_blur(dev_->ctx, &mb, static_cast<const uint8_t *>(color), static_cast<const float *>(depth),
+                                  static_cast<const float *>(velocity), static_cast<uint8_t *>(blurred_), SHS_CANVAS_DEVICE));
+        prev_view_ = view;
+        prev_proj_ = proj;
+    }
+
+    void ok(int rc) const {
+        if (rc != SHS_OK) throw std::runtime_error(shs_last_error(dev_->ctx));
+    }
+
+    glm::mat4 light_vp{1.0f};
+    glm::vec3 light_dir_world{0.4668f, -0.3487f, 0.8127f};   // (the shaders normalise it)
+
+private:
+    SceneT *scene_;
+    Device *dev_;
+    void *blurred_;                  // W * H Color on the device: the frame the host presents
+    float water_y_, time_accum_ = 0.0f;
+    int sm_, tile_;
+    glm::mat4 prev_view_{1.0f}, prev_proj_{1.0f};
+};
+
+// -----------------------------------------------------------------------------------------------------
 // Seam 1c, light shafts -- hello-render-target/hello_pbr_light_shafts.cpp, PASS1.5.
 //
 // light_shafts_pass (:1525-1707) as RendererSystem::process calls it (:2171-2190), over the planes the camera pass

@@ -15,6 +15,10 @@
 // host does what depends on the sun direction and the camera alone) and shs_rt_sky_samples (sky.sample alone).
 // and of hello_ibl_skybox.cpp ("ibl :line"): shs_rt_render_skybox_ibl (its PASS1, ibl :705-860 with fragment_shader_full
 // :446-524), which hands the sky of shs_rt_set_sky to the raster's shade as well as to the background pass.
+// and of hello_water.cpp ("water :line"): shs_rt_render_water (its PASS1A and PASS1B, water :1765-2211 with fragment_shader_full
+// :938-994 and fragment_shader_water :1000-1097 per draw), shs_rt_keep_reflection / shs_rt_set_reflection (u.reflection_color)
+// and shs_rt_water_samples (water_flow_normal_and_foam :862-930 alone); the host does what depends on the frame's time and
+// the light direction alone (water_model).
 // The host forms the matrix products the shaders form first -- u.view * u.model (vertex_shader_full :616),
 // u.light_vp * u.model (shadow_vertex_shader :764) -- and the normal matrix with the GLM restatement in
 // shs_glm.hpp.  Both passes are enqueued on the context stream; the shadow map, the planes and the records
@@ -179,21 +183,68 @@ bool pcss_ok(const shs_rt_pcss &c) {
            c.pcf_samples >= 0 && c.pcf_samples <= 64;
 }
 
+// What water_flow_normal_and_foam (water :862-930) forms from the time alone, with its own float operations in its order
+// (this file is compiled without contraction): fractf :759, hash22 :779-796, glm::normalize(vec2) = v * (1 / sqrt(dot)).
+float fractf1(float x) { return x - std::floor(x); }
+void water_hash22(float p, float out[2]) {
+    float x = fractf1(p * 0.1031f);
+    float y = fractf1(p * 0.1030f);
+    float z = fractf1(p * 0.0973f);
+    const float d = x * (y + 19.19f) + y * (z + 19.19f) + z * (x + 19.19f);
+    x = fractf1(x + d);
+    y = fractf1(y + d);
+    z = fractf1(z + d);
+    out[0] = fractf1((x + y) * z);
+    out[1] = fractf1((x + z) * y);
+}
+shs_dev::RtWaterModel water_model(float time_sec) {
+    shs_dev::RtWaterModel m{};
+    const float vx = 0.15f, vy = 1.0f;
+    const float inv = 1.0f / std::sqrt(vx * vx + vy * vy);
+    m.fd[0] = vx * inv;
+    m.fd[1] = vy * inv;
+    m.perp[0] = -m.fd[1];
+    m.perp[1] = m.fd[0];
+    const float time = time_sec * 0.18f;
+    const float t0 = fractf1(time);
+    const float t1 = fractf1(time + 0.5f);
+    m.w = std::fabs(t0 - 0.5f) * 2.0f;
+    float h[2];
+    water_hash22(std::floor(time), h);
+    m.j0[0] = h[0] * 2.0f; m.j0[1] = h[1] * 2.0f;
+    water_hash22(std::floor(time + 0.5f), h);
+    m.j1[0] = h[0] * 2.0f; m.j1[1] = h[1] * 2.0f;
+    for (int k = 0; k < 2; ++k) {
+        m.off0[k] = (m.fd[k] * (t0 - 0.5f)) * 6.0f;
+        m.off1[k] = (m.fd[k] * (t1 - 0.5f)) * 6.0f;
+        m.tilt[k] = m.fd[k] * 0.15f;
+    }
+    return m;
+}
+
+// The water pass's own arguments beside the frame (shs_rt_render_water)
+struct WaterCall {
+    const shs_rt_water_draw *draws;
+    const shs_rt_water *water;
+};
+// RtWaterGPU and the flag words behind it, as the device reads them
+using WaterTable = std::vector<uint32_t>;
+
 int upload_and_launch(shs_ctx *ctx, shs_dev::RtParams &p, bool shadow_pass, int shading = 0, int sky_model = 0,
-                      const IblTable *h_ibl = nullptr) {
+                      const IblTable *h_ibl = nullptr, const WaterTable *h_water = nullptr) {
     const size_t nd = ctx->rt_h_draws.size();
     // the PBR pass's material table, or the sky-lit pass's knobs (a pass has one of the two at most), rides behind the
     // draw table (sizeof(RtDrawGPU) is a multiple of 16): one copy
     static_assert(sizeof(shs_dev::RtDrawGPU) % 16 == 0, "the material table behind the draws is read as float4s");
-    const size_t npbr = ctx->rt_h_pbr.size(), nibl = h_ibl ? h_ibl->size() : 0;
-    const size_t tail = npbr * sizeof(shs_dev::RtPbrDrawGPU) + nibl * sizeof(shs_dev::RtIblDrawGPU);
+    const size_t npbr = ctx->rt_h_pbr.size(), nibl = h_ibl ? h_ibl->size() : 0, nwater = h_water ? h_water->size() : 0;
+    const size_t tail = npbr * sizeof(shs_dev::RtPbrDrawGPU) + nibl * sizeof(shs_dev::RtIblDrawGPU) + nwater * sizeof(uint32_t);
     const size_t extra = (tail + sizeof(shs_dev::RtDrawGPU) - 1) / sizeof(shs_dev::RtDrawGPU);
     const size_t nslot = nd + extra;
     if (ensure(ctx, ctx->rt_draws, std::max<size_t>(nslot, 1)) || ensure(ctx, ctx->rt_recs, std::max<size_t>((size_t)p.n_recs, 1)) ||
         ensure(ctx, ctx->rt_stats, 4))
         return SHS_ERR_HIP;
     if (!shadow_pass && ensure(ctx, ctx->rt_vary, std::max<size_t>((size_t)p.n_recs, 1))) return SHS_ERR_HIP;
-    if (nd) {
+    if (nd || nwater) {
         const int k = (int)(ctx->rt_pin_next++ & 1u);
         if (!ctx->rt_pin_ev[k]) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->rt_pin_ev[k], hipEventDisableTiming));
         else HIP_TRY(ctx, hipEventSynchronize(ctx->rt_pin_ev[k]));
@@ -207,6 +258,7 @@ int upload_and_launch(shs_ctx *ctx, shs_dev::RtParams &p, bool shadow_pass, int 
         std::memcpy(ctx->rt_pin[k], ctx->rt_h_draws.data(), nd * sizeof(shs_dev::RtDrawGPU));
         if (npbr) std::memcpy(ctx->rt_pin[k] + nd, ctx->rt_h_pbr.data(), npbr * sizeof(shs_dev::RtPbrDrawGPU));
         else if (nibl) std::memcpy(ctx->rt_pin[k] + nd, h_ibl->data(), nibl * sizeof(shs_dev::RtIblDrawGPU));
+        else if (nwater) std::memcpy(ctx->rt_pin[k] + nd, h_water->data(), nwater * sizeof(uint32_t));
         HIP_TRY(ctx, hipMemcpyAsync(ctx->rt_draws.p, ctx->rt_pin[k], nd * sizeof(shs_dev::RtDrawGPU) + tail, hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(ctx, hipEventRecord(ctx->rt_pin_ev[k], ctx->stream));
     }
@@ -214,6 +266,7 @@ int upload_and_launch(shs_ctx *ctx, shs_dev::RtParams &p, bool shadow_pass, int 
     p.draws = ctx->rt_draws.p;
     p.pbr_draws = npbr ? reinterpret_cast<const shs_dev::RtPbrDrawGPU *>(ctx->rt_draws.p + nd) : nullptr;
     p.ibl_draws = nibl ? reinterpret_cast<const shs_dev::RtIblDrawGPU *>(ctx->rt_draws.p + nd) : nullptr;
+    p.water = nwater ? reinterpret_cast<const shs_dev::RtWaterGPU *>(ctx->rt_draws.p + nd) : nullptr;
     p.recs = ctx->rt_recs.p;
     p.vary = ctx->rt_vary.p;
     p.stats = ctx->rt_stats.p;
@@ -223,9 +276,10 @@ int upload_and_launch(shs_ctx *ctx, shs_dev::RtParams &p, bool shadow_pass, int 
 
 // PASS1 of the five demos: pbr null for shading 0 / 1 (shs_rt_render), the per-draw PBR uniforms for shading 2
 // (shs_rt_render_pbr) and 3 (shs_rt_render_pbr_soft); ibl the per-draw knobs of shading 4 (shs_rt_render_skybox_ibl),
-// null for the others.  Nothing of the context changes before the last rejection.
+// null for the others; wc the flags and the frame's uniforms of shading 5 (shs_rt_render_water), null for the others.
+// Nothing of the context changes before the last rejection.
 int render_camera(shs_ctx *ctx, const shs_rt_frame *f, const shs_rt_draw *draws, const shs_rt_pbr_draw *pbr, int32_t n_draws,
-                  const shs_rt_skybox_ibl_draw *ibl = nullptr) {
+                  const shs_rt_skybox_ibl_draw *ibl = nullptr, const WaterCall *wc = nullptr) {
     if (!size_ok(ctx, f->width, f->height, f->ref_tile_w, f->ref_tile_h)) return SHS_ERR_INVALID;
     if (f->flags & ~(SHS_RT_USE_SHADOW | SHS_RT_PCF | SHS_RT_PREQUANT)) {
         ctx->err = "render-target frame: unknown flags";
@@ -298,7 +352,24 @@ int render_camera(shs_ctx *ctx, const shs_rt_frame *f, const shs_rt_draw *draws,
         sky_model = ctx->rt_sky.model;
         p.sky = ctx->rt_sky_model;
     }
-    int rc = upload_and_launch(ctx, p, false, f->shading, sky_model, &h_ibl);
+    WaterTable h_water;
+    if (f->shading == 5) {
+        shs_dev::RtWaterGPU g{};
+        if (wc->water->flags & SHS_RT_WATER_REFLECTION) {
+            g.refl = ctx->rt_refl.p;
+            g.refl_w = ctx->rt_refl_w;
+            g.refl_h = ctx->rt_refl_h;
+        }
+        std::memcpy(g.refl_vp, wc->water->reflection_vp, sizeof g.refl_vp);
+        // sky_color_simple(.., glm::normalize(-L)) normalises its sun_dir again (water :967, :165)
+        const shs_host::vec3 sun = shs_host::gnormalize(shs_host::gnormalize(shs_host::gneg(L)));
+        g.sun[0] = sun.x; g.sun[1] = sun.y; g.sun[2] = sun.z;
+        g.model = water_model(wc->water->time_sec);
+        h_water.resize(sizeof g / sizeof(uint32_t) + (size_t)n_draws);
+        std::memcpy(h_water.data(), &g, sizeof g);
+        for (int32_t i = 0; i < n_draws; ++i) h_water[sizeof g / sizeof(uint32_t) + i] = wc->draws[i].flags;
+    }
+    int rc = upload_and_launch(ctx, p, false, f->shading, sky_model, &h_ibl, &h_water);
     if (!rc && ctx->rt_sky.model != SHS_RT_SKY_NONE) {
         // skybox_background_pass (pbr :733-799) behind the triangles: the pixels the raster left without a fragment
         shs_dev::RtSkyParams q{};
@@ -406,6 +477,100 @@ int shs_rt_render_skybox_ibl(shs_ctx *ctx, const shs_rt_frame *f, const shs_rt_d
     }
     static const shs_rt_skybox_ibl_draw none{};
     return render_camera(ctx, f, draws, nullptr, n_draws, n_draws > 0 ? ibl_draws : &none);
+}
+
+int shs_rt_render_water(shs_ctx *ctx, const shs_rt_frame *f, const shs_rt_draw *draws, const shs_rt_water_draw *water_draws,
+                        const shs_rt_water *water, int32_t n_draws) {
+    if (!ctx || !f || !water || n_draws < 0 || (n_draws > 0 && (!draws || !water_draws))) return SHS_ERR_INVALID;
+    if (f->shading != 5) {
+        ctx->err = "shs_rt_render_water: shading " + std::to_string(f->shading) + " (5: hello_water.cpp's two fragment shaders)";
+        return SHS_ERR_INVALID;
+    }
+    for (int32_t i = 0; i < n_draws; ++i) {
+        if (water_draws[i].flags & ~SHS_RT_WATER_SURFACE) {
+            ctx->err = "shs_rt_render_water: unknown shs_rt_water_draw flags";
+            return SHS_ERR_INVALID;
+        }
+    }
+    if (water->flags & ~SHS_RT_WATER_REFLECTION) {
+        ctx->err = "shs_rt_render_water: unknown shs_rt_water flags";
+        return SHS_ERR_INVALID;
+    }
+    if ((water->flags & SHS_RT_WATER_REFLECTION) && !ctx->rt_have_refl) {
+        ctx->err = "shs_rt_render_water: SHS_RT_WATER_REFLECTION without a reflection canvas (shs_rt_keep_reflection, shs_rt_set_reflection)";
+        return SHS_ERR_INVALID;
+    }
+    if (!std::isfinite(water->time_sec)) {
+        ctx->err = "shs_rt_render_water: a non-finite time_sec";
+        return SHS_ERR_INVALID;
+    }
+    const WaterCall wc = {water_draws, water};
+    return render_camera(ctx, f, draws, nullptr, n_draws, nullptr, &wc);
+}
+
+int shs_rt_keep_reflection(shs_ctx *ctx) {
+    if (!ctx) return SHS_ERR_INVALID;
+    if (!ctx->rt_have_frame) {
+        ctx->err = "shs_rt_keep_reflection: no camera pass before it";
+        return SHS_ERR_INVALID;
+    }
+    if (set_dev(ctx)) return SHS_ERR_HIP;
+    const size_t npx = (size_t)ctx->rt_w * ctx->rt_h;
+    ctx->rt_have_refl = false;
+    if (ensure(ctx, ctx->rt_refl, npx)) return SHS_ERR_HIP;
+    // in stream order after the camera pass (and its background pass) and before whatever reads the canvas
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->rt_refl.p, ctx->rt_color.p, npx * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
+    ctx->rt_refl_w = ctx->rt_w;
+    ctx->rt_refl_h = ctx->rt_h;
+    ctx->rt_have_refl = true;
+    return SHS_OK;
+}
+
+int shs_rt_set_reflection(shs_ctx *ctx, const uint8_t *rgba, int32_t w, int32_t h) {
+    if (!ctx) return SHS_ERR_INVALID;
+    if (!rgba) {   // u.reflection_color == nullptr; a frame in flight keeps reading the old canvas, which stays allocated
+        ctx->rt_have_refl = false;
+        return SHS_OK;
+    }
+    if (w <= 0 || h <= 0 || w > 32767 || h > 32767) {
+        ctx->err = "shs_rt_set_reflection: 1 .. 32767 per side";
+        return SHS_ERR_INVALID;
+    }
+    if (set_dev(ctx)) return SHS_ERR_HIP;
+    const size_t npx = (size_t)w * h;
+    ctx->rt_have_refl = false;
+    if (ensure(ctx, ctx->rt_refl, npx)) return SHS_ERR_HIP;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->rt_refl.p, rgba, npx * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // (the pageable staging is consumed by now)
+    ctx->rt_refl_w = w;
+    ctx->rt_refl_h = h;
+    ctx->rt_have_refl = true;
+    return SHS_OK;
+}
+
+int shs_rt_water_samples(shs_ctx *ctx, int32_t n, const float *world_pos3, float time_sec, float *normal3, float *foam) {
+    if (!ctx || n < 0 || (n > 0 && (!world_pos3 || !normal3 || !foam))) return SHS_ERR_INVALID;
+    if (!std::isfinite(time_sec)) {
+        ctx->err = "shs_rt_water_samples: a non-finite time_sec";
+        return SHS_ERR_INVALID;
+    }
+    if (n == 0) return SHS_OK;
+    if (set_dev(ctx)) return SHS_ERR_HIP;
+    const size_t ns = (size_t)n;
+    if (ensure(ctx, ctx->rt_water_io, 7 * ns)) return SHS_ERR_HIP;   // the workspace: points (3 n), normals (3 n), foam (n)
+    float *io = ctx->rt_water_io.p;
+    HIP_TRY(ctx, hipMemcpyAsync(io, world_pos3, 3 * ns * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    shs_dev::RtWaterSamples q{};
+    q.n = n;
+    q.world = io;
+    q.normal = io + 3 * ns;
+    q.foam = io + 6 * ns;
+    q.water = water_model(time_sec);
+    HIP_TRY(ctx, shs_internal::launch_water_samples(q, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(normal3, q.normal, 3 * ns * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(foam, q.foam, ns * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // (the pageable staging above is consumed by now)
+    return SHS_OK;
 }
 
 int shs_rt_resolve(shs_ctx *ctx, uint8_t *color, float *depth, float *velocity) {

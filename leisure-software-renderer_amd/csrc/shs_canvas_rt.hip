@@ -25,6 +25,15 @@
 //          Schlick-weighted u.sky->sample(reflect(-V, N)) added; u.sky is the sky of the background pass below.
 //          k_rt_raster<false, 4 + sky model>, launched by shs_rt_render_skybox_ibl, is shade_pixel_ibl<SKY>: three
 //          instantiations (no sky, AnalyticSky, CubeMapSky), of which only the last has gathers.
+// and for hello_water.cpp ("water :line"), whose PASS0 / PASS1 rasters, vertex shader, velocity and shadow_uvz_from_world
+// are the hard demo's text (DESIGN.md section 8 lists the routines compared):
+//   shading 5  two fragment shaders in one camera pass, chosen per draw (shs_rt_water_draw): fragment_shader_full
+//          (water :938-994, the "atmosphere" shader: Blinn-Phong under a sky-coloured ambient term, fog, Reinhard, gamma)
+//          and fragment_shader_water (water :1000-1097: a procedural flow normal and foam from water_flow_normal_and_foam
+//          :862-930 over hash12 / noise2 / fbm2, Schlick's fresnel over a planar reflection read from the context's
+//          reflection canvas, fog).  Both round to the byte where the other shadings truncate.  Their shadow lookup
+//          (water :716-751) is not the hard demo's: shadow_factor_water.  k_rt_raster<false, RT_SHADING_WATER>,
+//          launched by shs_rt_render_water, is shade_pixel_water.
 //   the background  skybox_background_pass (pbr :733-799; the same routine in hello_pbr_light_shafts.cpp and
 //          hello_ibl_skybox.cpp) over the legacy AnalyticSky / CubeMapSky of hello-shs-renderer/shs_renderer.hpp:
 //          k_rt_sky<MODEL, ENCODE>, a pass of its own after k_rt_raster when a sky is bound (shs_rt_set_sky), which
@@ -908,9 +917,292 @@ __device__ void shade_pixel_ibl(const RtParams &p, int32_t id, float u, float v,
     pq = make_float4(pr, pg, pb, shadow);
 }
 
+// ---- hello_water.cpp: the atmosphere shader, the water shader and the planar reflection ("water :line") ----
+
+// fractf :759
+__device__ __forceinline__ float fractf1(float x) { return x - floorf(x); }
+
+// hash12 :771-777: q = fract2(p * vec2(123.34, 456.21)); q += dot(q, q + 34.345); fract(q.x * q.y).  Chaotic: every
+// operation below is the reference's, in its order, and rounds once.
+__device__ __forceinline__ float water_hash12(float px, float py) {
+    float qx = fractf1(px * 123.34f), qy = fractf1(py * 456.21f);
+    const float d = qx * (qx + 34.345f) + qy * (qy + 34.345f);
+    qx = qx + d;
+    qy = qy + d;
+    return fractf1(qx * qy);
+}
+
+// noise2 :798-814 (i + vec2(0, 0) leaves every value hash12 can tell apart as it was)
+__device__ __forceinline__ float water_noise2(float px, float py) {
+    const float ix = floorf(px), iy = floorf(py);
+    const float fx = px - ix, fy = py - iy;
+    const float a = water_hash12(ix, iy);
+    const float b = water_hash12(ix + 1.0f, iy);
+    const float c = water_hash12(ix, iy + 1.0f);
+    const float d = water_hash12(ix + 1.0f, iy + 1.0f);
+    const float ux = (fx * fx) * (3.0f - 2.0f * fx), uy = (fy * fy) * (3.0f - 2.0f * fy);
+    const float x1 = a + (b - a) * ux;
+    const float x2 = c + (d - c) * ux;
+    return x1 + (x2 - x1) * uy;
+}
+
+// fbm2 :816-826
+__device__ __forceinline__ float water_fbm2(float px, float py) {
+    float f = 0.0f, a = 0.5f;
+#pragma unroll 1
+    for (int i = 0; i < 4; ++i) {
+        f += a * water_noise2(px, py);
+        px *= 2.02f;
+        py *= 2.02f;
+        a *= 0.5f;
+    }
+    return f;
+}
+
+// sampleN :902-917.  Its h0 and h1 are dead.  The four fbm2 arguments are (p +- vec2(e, 0)) * 1.2 and (p +- vec2(0, e)) * 1.2:
+// a subtraction is the addition of the negated operand, signed zeros included, so one loop serves the four.
+__device__ __forceinline__ f3 water_sample_n(float px, float py) {
+    const float e = 0.18f;
+    float hx = 0.0f, hz = 0.0f, prev = 0.0f;
+#pragma unroll 1
+    for (int k = 0; k < 4; ++k) {
+        const float ox = (k == 0) ? e : (k == 1) ? -e : (k == 2) ? 0.0f : -0.0f;
+        const float oy = (k == 0) ? 0.0f : (k == 1) ? -0.0f : (k == 2) ? e : -e;
+        const float f = water_fbm2((px + ox) * 1.2f, (py + oy) * 1.2f);
+        if (k == 1) hx = prev - f;
+        if (k == 3) hz = prev - f;
+        prev = f;
+    }
+    return normalize3(f3{-hx * 2.4f, 1.0f, -hz * 2.4f});
+}
+
+// water_flow_normal_and_foam :862-930 after the host's part (RtWaterModel)
+__device__ void water_normal_foam(const RtWaterModel &m, f3 wp, f3 &N, float &foam) {
+    const float uvx = wp.x * m.perp[0] + wp.z * m.perp[1];
+    const float uvy = (wp.x * m.fd[0] + wp.z * m.fd[1]) * 2.8f;
+    const float bx = uvx * 0.055f, by = uvy * 0.055f;
+    const f3 nA = water_sample_n((bx + m.j0[0]) + m.off0[0], (by + m.j0[1]) + m.off0[1]);
+    const f3 nB = water_sample_n((bx + m.j1[0]) + m.off1[0], (by + m.j1[1]) + m.off1[1]);
+    f3 n = normalize3(mix3(nA, nB, m.w));
+    n = normalize3(f3{n.x + m.tilt[0], n.y + 0.0f, n.z + m.tilt[1]});
+    N = n;
+    const float curvature = sqrtf(n.x * n.x + n.z * n.z);
+    foam = saturate((curvature - 0.55f) * 1.6f);
+}
+
+// (int)std::lround(x) for any x that is NaN or whose rounded value fits an int: halves away from zero on both sides
+// of zero (lround_x86 above covers [0, n - 1] only; the reflection lookup reaches -0.75 and n - 0.25)
+__device__ __forceinline__ int lround_away_x86(float x) {
+    if (!(x == x)) return 0;
+    const float t = truncf(x);
+    const float d = x - t;   // exact
+    return (int)t + ((d >= 0.5f) ? 1 : ((d <= -0.5f) ? -1 : 0));
+}
+
+// shadow_uvz_from_world and shadow_factor_pcf_2x2 as hello_water.cpp has them (water :696-751).  Not the hard demo's
+// lookup: a uv outside [0, 1] is lit before the PCF taps (the hard demo clamps the taps to the edge), and an empty
+// texel (FLT_MAX) counts as lit whatever z is (the hard demo compares, which differs for a NaN z).
+__device__ float shadow_factor_water(const RtParams &p, f3 wp, float ndotl) {
+    float cx, cy, cz, cw;
+    m4p(p.light_vp, wp.x, wp.y, wp.z, cx, cy, cz, cw);
+    if (fabsf(cw) < 1e-6f) return 1.0f;
+    const float nx = cx / cw, ny = cy / cw, z = cz / cw;
+    if (z < 0.0f || z > 1.0f) return 1.0f;
+    const float u = nx * 0.5f + 0.5f;
+    const float v = 1.0f - (ny * 0.5f + 0.5f);
+    const float slope = 1.0f - g_clamp01(ndotl);
+    const float bias = p.bias_base + p.bias_slope * slope;
+    if (u < 0.0f || u > 1.0f || v < 0.0f || v > 1.0f) return 1.0f;
+    if (!(p.flags & SHS_RT_PCF)) {
+        const int x = lround_x86(u * (float)(p.sw - 1));
+        const int y = lround_x86(v * (float)(p.sh - 1));
+        const float d = sm_sample(p, x, y);
+        if (d == FLT_MAX) return 1.0f;
+        return (z <= d + bias) ? 1.0f : 0.0f;
+    }
+    const float fx = u * (float)(p.sw - 1);
+    const float fy = v * (float)(p.sh - 1);
+    const int x0 = clampi(int_x86(floorf(fx)), 0, p.sw - 1);
+    const int y0 = clampi(int_x86(floorf(fy)), 0, p.sh - 1);
+    const int x1 = clampi(x0 + 1, 0, p.sw - 1);
+    const int y1 = clampi(y0 + 1, 0, p.sh - 1);
+    const float d00 = sm_sample(p, x0, y0), d10 = sm_sample(p, x1, y0), d01 = sm_sample(p, x0, y1), d11 = sm_sample(p, x1, y1);
+    const float s00 = (d00 == FLT_MAX) ? 1.0f : ((z <= d00 + bias) ? 1.0f : 0.0f);
+    const float s10 = (d10 == FLT_MAX) ? 1.0f : ((z <= d10 + bias) ? 1.0f : 0.0f);
+    const float s01 = (d01 == FLT_MAX) ? 1.0f : ((z <= d01 + bias) ? 1.0f : 0.0f);
+    const float s11 = (d11 == FLT_MAX) ? 1.0f : ((z <= d11 + bias) ? 1.0f : 0.0f);
+    return 0.25f * (((s00 + s10) + s01) + s11);
+}
+
+// pow(x, 5.0f), pow(x, 256.0f), pow(x, 520.0f): products in double rounded once, as pow64
+__device__ __forceinline__ float pow5(float x) {
+    const double d = (double)x, d2 = d * d;
+    return (float)(d2 * d2 * d);
+}
+__device__ __forceinline__ float pow256(float x) {
+    double d = (double)x;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) d = d * d;
+    return (float)d;
+}
+__device__ __forceinline__ float pow520(float x) {   // 512 and 8
+    double d = (double)x;
+    d = d * d; d = d * d; d = d * d;
+    double e = d;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) e = e * e;
+    return (float)(e * d);
+}
+
+// One channel's way to the screen in hello_water.cpp (:984-992, :1088-1095): the exposure, tonemap_reinhard, gamma_2p2
+// (glm::clamp, then pow), the channel * 255.  The byte is a rounding, clampi((int)lround(.), 0, 255), where the other
+// shadings truncate: water_byte.
+__device__ __forceinline__ float water_encode(float x) {
+    x = x / (1.0f + x);
+    x = powf(g_clamp01(x), 1.0f / 2.2f);
+    return x * 255.0f;
+}
+__device__ __forceinline__ uint32_t water_byte(float x) { return (uint32_t)clampi(lround_away_x86(x), 0, 255); }
+
+// The shown fragment of hello_water.cpp's camera pass (water :2060-2211, the hard demo's interpolation and velocity)
+// through the shader its draw names: fragment_shader_full (:938-994, the atmosphere shader) or fragment_shader_water
+// (:1000-1097).  One kernel holds both because one frame mixes them per pixel; the branch is per draw, so a wave
+// diverges only where it straddles the water's silhouette.  What the two share is written once: V, the sky along the
+// ray, the shadow lookup, the half vector, the fog and the way to the byte.
+__device__ void shade_pixel_water(const RtParams &p, int32_t id, float u, float v, float w, uint32_t &rgba, float2 &vel, float4 &pq) {
+    const RtRec &r = p.recs[id];
+    const RtVary &y = p.vary[id];
+    const RtDrawGPU &dr = p.draws[r.draw];
+    const float iw0 = r.iw0, iw1 = r.iw1, iw2 = r.iw2;
+    const float invw_sum = (u * iw0 + v * iw1) + w * iw2;
+    {   // velocity (the hard demo's :1002-1011)
+        float pos[4], prev[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            pos[k] = (u * y.pos[k] + v * y.pos[4 + k]) + w * y.pos[8 + k];
+            prev[k] = (u * y.prev[k] + v * y.prev[4 + k]) + w * y.prev[8 + k];
+        }
+        float csx, csy, psx, psy;
+        to_screen(p, pos[0], pos[1], pos[3], csx, csy);
+        to_screen(p, prev[0], prev[1], prev[3], psx, psy);
+        float vx = csx - psx, vy = -(csy - psy);
+        const float len = sqrtf(vx * vx + vy * vy);
+        if (len > p.max_velocity && len > 1e-6f) {
+            const float s = p.max_velocity / len;
+            vx *= s;
+            vy *= s;
+        }
+        vel = make_float2(vx, vy);
+    }
+    f3 wp;
+    wp.x = ((u * (y.world[0] * iw0) + v * (y.world[3] * iw1)) + w * (y.world[6] * iw2)) / invw_sum;
+    wp.y = ((u * (y.world[1] * iw0) + v * (y.world[4] * iw1)) + w * (y.world[7] * iw2)) / invw_sum;
+    wp.z = ((u * (y.world[2] * iw0) + v * (y.world[5] * iw1)) + w * (y.world[8] * iw2)) / invw_sum;
+    const RtWaterGPU &wf = *p.water;
+    const bool is_water = (reinterpret_cast<const uint32_t *>(p.water + 1)[r.draw] & SHS_RT_WATER_SURFACE) != 0u;
+    const f3 L = {p.L[0], p.L[1], p.L[2]};
+    const f3 toc = sub3(f3{p.cam[0], p.cam[1], p.cam[2]}, wp);
+    const f3 V = normalize3(toc);
+    // sky_color_simple(normalize(RAY), normalize(-L)) :157-170; its own normalize(sun_dir) is the host's (RtParams::sun)
+    f3 sky;
+    {
+        const f3 ray = normalize3(f3{-V.x, -V.y, -V.z});
+        const float t = saturate(ray.y * 0.5f + 0.5f);
+        sky = mix3(f3{0.62f, 0.74f, 0.92f}, f3{0.10f, 0.22f, 0.55f}, t);
+        const float sd = dot3(f3{wf.sun[0], wf.sun[1], wf.sun[2]}, normalize3(ray));
+        const float h = sd * 0.5f + 0.5f;
+        const float sun = pow256((h < 0.0f) ? 0.0f : (h > 1.0f ? 1.0f : h));
+        sky = add3(sky, f3{(1.0f * sun) * 8.0f, (0.88f * sun) * 8.0f, (0.65f * sun) * 8.0f});
+    }
+    f3 N;
+    float foam = 0.0f;
+    if (is_water) {
+        water_normal_foam(wf.model, wp, N, foam);
+    } else {
+        const f3 nsum = {(u * y.nrm[0] + v * y.nrm[3]) + w * y.nrm[6], (u * y.nrm[1] + v * y.nrm[4]) + w * y.nrm[7],
+                         (u * y.nrm[2] + v * y.nrm[5]) + w * y.nrm[8]};
+        N = normalize3(normalize3(nsum));
+    }
+    const float ndotl = dot3(N, L);
+    float shadow = 1.0f;
+    if (p.shadow) shadow = shadow_factor_water(p, wp, ndotl);
+    const f3 H = normalize3(add3(L, V));
+    const float ndoth = g_max(dot3(N, H), 0.0f);
+    f3 hdr;
+    float exposure;
+    if (is_water) {
+        const float NoV = g_clamp01(dot3(N, V));
+        const float NoL = g_clamp01(ndotl);
+        const float fresnel = 0.02f + (1.0f - 0.02f) * pow5(1.0f - NoV);
+        f3 refl_col = sky;
+        if (wf.refl) {   // the planar reflection :1021-1044
+            float cx, cy, cz, cw;
+            m4p(wf.refl_vp, wp.x, wp.y, wp.z, cx, cy, cz, cw);
+            if (fabsf(cw) > 1e-6f) {
+                const float rx_ndc = cx / cw, ry_ndc = cy / cw;
+                if (rx_ndc >= -1.0f && rx_ndc <= 1.0f && ry_ndc >= -1.0f && ry_ndc <= 1.0f) {
+                    float sx = (rx_ndc * 0.5f + 0.5f) * (float)(wf.refl_w - 1);
+                    float sy = (1.0f - (ry_ndc * 0.5f + 0.5f)) * (float)(wf.refl_h - 1);
+                    sx += N.x * 0.75f;
+                    sy += N.z * 0.75f;
+                    // sx lies in [-0.75, w - 0.25] or is NaN (|N.x| <= 1 or NaN): lround's halves away from zero on
+                    // either side; a NaN gives (int)LONG_MIN = 0, so rx = 0 and ry_canvas = h - 1
+                    const int rx = lround_away_x86(sx);
+                    const int ry_screen = lround_away_x86(sy);
+                    const int ry_canvas = (wf.refl_h - 1) - ry_screen;
+                    // sample_canvas_nearest :146-151
+                    const uint32_t rc = wf.refl[(size_t)clampi(ry_canvas, 0, wf.refl_h - 1) * wf.refl_w + clampi(rx, 0, wf.refl_w - 1)];
+                    refl_col = f3{(float)(rc & 0xffu) / 255.0f, (float)((rc >> 8) & 0xffu) / 255.0f, (float)((rc >> 16) & 0xffu) / 255.0f};
+                }
+            }
+        }
+        const float spec = pow520(ndoth);
+        const float spec_kill = 1.0f - foam * 0.90f;
+        const float specular = ((1.0f * spec) * 0.95f) * spec_kill;
+        const float diffuse = (1.0f * NoL) * 0.05f;
+        f3 surface = mix3(f3{0.03f, 0.12f, 0.16f}, refl_col, fresnel);
+        const f3 foam_col = mix3(f3{0.75f, 0.85f, 0.95f}, sky, 0.25f);
+        const float foam_gain = foam * (0.35f + 0.65f * (1.0f - NoV));
+        surface = mix3(surface, foam_col, foam_gain);
+        const float sd = shadow * diffuse, ss = shadow * specular;
+        hdr = f3{surface.x * (sky.x * 0.12f + sd) + ss, surface.y * (sky.y * 0.12f + sd) + ss, surface.z * (sky.z * 0.12f + sd) + ss};
+        exposure = 0.90f;
+    } else {
+        f3 base = {dr.colf[0] / 255.0f, dr.colf[1] / 255.0f, dr.colf[2] / 255.0f};
+        if (dr.texels) {
+            // sample_nearest :121-140
+            const float tu = ((u * (y.uv[0] * iw0) + v * (y.uv[2] * iw1)) + w * (y.uv[4] * iw2)) / invw_sum;
+            const float tv = ((u * (y.uv[1] * iw0) + v * (y.uv[3] * iw1)) + w * (y.uv[5] * iw2)) / invw_sum;
+            const float su = saturate(tu), sv = saturate(tv);
+            const int x = clampi(lround_x86(su * (float)(dr.tw - 1)), 0, dr.tw - 1);
+            const int yy = clampi(lround_x86(sv * (float)(dr.th - 1)), 0, dr.th - 1);
+            const uint32_t tc = dr.texels[(size_t)yy * dr.tw + x];
+            base = f3{(float)(tc & 0xffu) / 255.0f, (float)((tc >> 8) & 0xffu) / 255.0f, (float)((tc >> 16) & 0xffu) / 255.0f};
+        }
+        const float NoL = g_max(ndotl, 0.0f);
+        const float diffuse = (1.0f * NoL) * 0.90f;
+        const float specular = (1.0f * pow64(ndoth)) * 0.35f;
+        const float lit = shadow * (diffuse + specular);
+        hdr = f3{base.x * (sky.x * 0.08f + lit), base.y * (sky.y * 0.08f + lit), base.z * (sky.z * 0.08f + lit)};
+        exposure = 1.00f;
+    }
+    // apply_fog_exp2 :172-176 over clampf(length(camera_pos - world_pos), 0, 250), then the exposure
+    float dist = sqrtf(dot3(toc, toc));
+    dist = (dist < 0.0f) ? 0.0f : (dist > 250.0f ? 250.0f : dist);
+    const float tr = exp2f(-0.0065f * dist);
+    const float fr = 1.0f - tr;
+    const float pr = water_encode((hdr.x * tr + sky.x * fr) * exposure);
+    const float pg = water_encode((hdr.y * tr + sky.y * fr) * exposure);
+    const float pb = water_encode((hdr.z * tr + sky.z * fr) * exposure);
+    rgba = water_byte(pr) | (water_byte(pg) << 8) | (water_byte(pb) << 16) | 0xff000000u;
+    pq = make_float4(pr, pg, pb, shadow);
+}
+
 // SHADING: shs_rt_frame::shading of the camera pass, a compile-time choice (the shadow pass ignores it); shading 4 is
-// three instantiations, RT_SHADING_IBL + the sky model it samples (RT_SKY_*)
+// three instantiations, RT_SHADING_IBL + the sky model it samples (RT_SKY_*), which takes the values 4 to 6: shading 5
+// is RT_SHADING_WATER
 constexpr int RT_SHADING_IBL = 4;
+constexpr int RT_SHADING_WATER = 7;
 template <bool SHADOW, int SHADING = 0>
 __global__ __launch_bounds__(256) void k_rt_raster(const RtParams p) {
     __shared__ float4 s_rec[RT_CHUNK * 6];
@@ -1010,6 +1302,8 @@ __global__ __launch_bounds__(256) void k_rt_raster(const RtParams p) {
         if (sid >= 0) shade_pixel_pbr<false>(p, sid, su, sv, sw, px, py, rgba, vel, pq);
     } else if constexpr (SHADING == 3) {
         if (sid >= 0) shade_pixel_pbr<true>(p, sid, su, sv, sw, px, py, rgba, vel, pq);
+    } else if constexpr (SHADING == RT_SHADING_WATER) {
+        if (sid >= 0) shade_pixel_water(p, sid, su, sv, sw, rgba, vel, pq);
     } else if constexpr (SHADING >= RT_SHADING_IBL) {
         if (sid >= 0) shade_pixel_ibl<SHADING - RT_SHADING_IBL>(p, sid, su, sv, sw, rgba, vel, pq);
     } else {
@@ -1040,6 +1334,17 @@ __global__ __launch_bounds__(256) void k_rt_ibl_samples(const RtIblSamples q) {
     const f3 b = ibl_sample_trilinear(q.ibl, q.ibl_mips, d, q.lod[i]);
     q.irr[3 * i] = a.x; q.irr[3 * i + 1] = a.y; q.irr[3 * i + 2] = a.z;
     q.spec[3 * i] = b.x; q.spec[3 * i + 1] = b.y; q.spec[3 * i + 2] = b.z;
+}
+
+// shs_rt_water_samples: one lane per point through the device function the raster calls
+__global__ __launch_bounds__(256) void k_rt_water_samples(const RtWaterSamples q) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= q.n) return;
+    f3 n;
+    float foam;
+    water_normal_foam(q.water, f3{q.world[3 * (size_t)i], q.world[3 * (size_t)i + 1], q.world[3 * (size_t)i + 2]}, n, foam);
+    q.normal[3 * (size_t)i] = n.x; q.normal[3 * (size_t)i + 1] = n.y; q.normal[3 * (size_t)i + 2] = n.z;
+    q.foam[i] = foam;
 }
 
 // ---- skybox_background_pass (pbr :733-799) over the legacy sky models ("sky :line": hello-shs-renderer/shs_renderer.hpp)
@@ -1195,6 +1500,12 @@ hipError_t launch_ibl_samples(const shs_dev::RtIblSamples &q, hipStream_t s) {
     return hipGetLastError();
 }
 
+hipError_t launch_water_samples(const shs_dev::RtWaterSamples &q, hipStream_t s) {
+    if (q.n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(shs_dev::k_rt_water_samples, dim3((q.n + 255) / 256), dim3(256), 0, s, q);
+    return hipGetLastError();
+}
+
 hipError_t launch_canvas_rt_sky(const shs_dev::RtSkyParams &p, int model, int encode, hipStream_t s) {
     using namespace shs_dev;
     const dim3 grid(((uint32_t)p.W * (uint32_t)p.H + 255u) / 256u), block(256);
@@ -1232,6 +1543,7 @@ hipError_t launch_canvas_rt(const shs_dev::RtParams &p, bool shadow_pass, int sh
     else if (shading == 1) hipLaunchKernelGGL((k_rt_raster<false, 1>), dim3(tiles), dim3(256), 0, s, p);
     else if (shading == 2) hipLaunchKernelGGL((k_rt_raster<false, 2>), dim3(tiles), dim3(256), 0, s, p);
     else if (shading == 3) hipLaunchKernelGGL((k_rt_raster<false, 3>), dim3(tiles), dim3(256), 0, s, p);
+    else if (shading == 5) hipLaunchKernelGGL((k_rt_raster<false, RT_SHADING_WATER>), dim3(tiles), dim3(256), 0, s, p);
     else if (shading == 4 && sky_model == RT_SKY_CUBEMAP)
         hipLaunchKernelGGL((k_rt_raster<false, RT_SHADING_IBL + RT_SKY_CUBEMAP>), dim3(tiles), dim3(256), 0, s, p);
     else if (shading == 4 && sky_model == RT_SKY_ANALYTIC)

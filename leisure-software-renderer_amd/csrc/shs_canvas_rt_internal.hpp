@@ -5,7 +5,9 @@
 // hello_pbr_light_shafts.cpp (that shader under the PCSS factor, shading 3 through shs_rt_render_pbr_soft), and of the
 // background pass behind any of them (skybox_background_pass over the legacy sky models, shs_rt_set_sky), and of
 // hello_ibl_skybox.cpp (the hard demo's passes with the sky-lit fragment shader, shading 4 through
-// shs_rt_render_skybox_ibl, which samples the bound sky per pixel).
+// shs_rt_render_skybox_ibl, which samples the bound sky per pixel), and of hello_water.cpp (the hard demo's passes with
+// two fragment shaders chosen per draw, the atmosphere shader and the water shader over a planar reflection, shading 5
+// through shs_rt_render_water).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -103,6 +105,31 @@ struct RtSkyModel {
     const float *srgb_lut;           // 256 floats: pow(c / 255, 2.2) with the host's libm
 };
 
+// ---- hello_water.cpp ("water :line"): what water_flow_normal_and_foam (:862-930) forms from the frame's time alone ----
+// The host does these once per call with the reference's own float operations (shs_abi_canvas_rt.cpp water_model); the
+// per-pixel ones stay in the shader.
+struct RtWaterModel {
+    float fd[2];                     // flow_dir = normalize(vec2(0.15, 1)) :877
+    float perp[2];                   // flow_perp = (-fd.y, fd.x) :878
+    float j0[2], j1[2];              // hash22(floor(time)) * 2, hash22(floor(time + 0.5)) * 2 :896-897
+    float off0[2], off1[2];          // (flow_dir * (t0 - 0.5)) * 6, (flow_dir * (t1 - 0.5)) * 6 :899-900
+    float w;                         // abs(t0 - 0.5) * 2 :891
+    float tilt[2];                   // (fd.x, fd.y) * 0.15 :924 (the y component of the tilt is 0 * 0.15 = 0)
+};
+
+// The frame's part of hello_water.cpp's Uniforms that the two shaders of shading 5 read, in device memory behind the draw
+// table (it changes every frame, as the table does); the n_draws flag words of shs_rt_water_draw follow it, element i
+// going with draws[i].  Every read of it is wave-uniform.
+struct alignas(16) RtWaterGPU {
+    const uint32_t *refl;            // u.reflection_color: the context's reflection canvas in canvas rows, or null
+    int32_t refl_w, refl_h;          // its own size, not the frame's
+    float refl_vp[16];               // u.reflection_vp
+    float sun[3];                    // normalize(normalize(-L)): sky_color_simple's sun_dir as it uses it (water :165)
+    RtWaterModel model;
+    uint32_t pad[3];
+};
+static_assert(sizeof(RtWaterGPU) % 16 == 0, "RtWaterGPU: the flag words follow it");
+
 constexpr int RT_TW = 32, RT_TH = 8;     // raster tile: one 256-thread workgroup, one pixel per lane
 constexpr int RT_CHUNK = 256;            // records examined (and at most staged in LDS) per round
 
@@ -138,6 +165,8 @@ struct RtParams {
     // shading 4 only (appended likewise)
     RtSkyModel sky;                  // u.sky: the sky of shs_rt_set_sky (read by the analytic / cubemap instantiations)
     const RtIblDrawGPU *ibl_draws;   // element i goes with draws[i]
+    // shading 5 only (appended likewise): one pointer, the rest rides behind the draw table with the per-call upload
+    const RtWaterGPU *water;
 };
 
 // sample_cubemap_linear_vec(env_irradiance, dir) and sample_prefiltered_spec_trilinear(spec, dir, lod) for a list
@@ -182,6 +211,15 @@ struct RtSkySamples {
     RtSkyModel sky;
 };
 
+// water_flow_normal_and_foam for a list of points (shs_rt_water_samples): everything on the device
+struct RtWaterSamples {
+    int32_t n;
+    const float *world;              // 3 n
+    float *normal;                   // 3 n
+    float *foam;                     // n
+    RtWaterModel water;
+};
+
 }  // namespace shs_dev
 
 namespace shs_internal {
@@ -191,8 +229,10 @@ hipError_t launch_sky_samples(const shs_dev::RtSkySamples &q, int model, hipStre
 // setup (one lane per input triangle) then raster (one workgroup per 32x8 tile) of either pass
 // shading: shs_rt_frame::shading of the camera pass (0: fragment_shader_full, 1: fragment_shader_softshadow,
 // 2: fragment_shader_pbr, 3: hello_pbr_light_shafts.cpp's fragment_shader_pbr, 4: hello_ibl_skybox.cpp's
-// fragment_shader_full); sky_model: u.sky of shading 4 (RT_SKY_*), which chooses among its three instantiations
+// fragment_shader_full, 5: hello_water.cpp's fragment_shader_full / fragment_shader_water per draw); sky_model: u.sky of
+// shading 4 (RT_SKY_*), which chooses among its three instantiations
 hipError_t launch_canvas_rt(const shs_dev::RtParams &p, bool shadow_pass, int shading, hipStream_t s, int sky_model = 0);
 hipError_t launch_pcss_samples(const shs_dev::RtPcssSamples &q, hipStream_t s);
 hipError_t launch_ibl_samples(const shs_dev::RtIblSamples &q, hipStream_t s);
+hipError_t launch_water_samples(const shs_dev::RtWaterSamples &q, hipStream_t s);
 }  // namespace shs_internal

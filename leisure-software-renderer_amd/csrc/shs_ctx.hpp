@@ -384,6 +384,12 @@ struct shs_ctx {
     // shs_canvas_light_shafts over host buffers (shs_abi_canvas_post.cpp): the staged shadow map and prequant plane
     DevBuf<float> cp_map;
     DevBuf<float4> cp_pq;
+    // shading 5 (hello_water.cpp): the reflection canvas (u.reflection_color) of shs_rt_keep_reflection /
+    // shs_rt_set_reflection in canvas rows at its own size, and the workspace of shs_rt_water_samples
+    DevBuf<uint32_t> rt_refl;
+    int rt_refl_w = 0, rt_refl_h = 0;
+    bool rt_have_refl = false;
+    DevBuf<float> rt_water_io;
 };
 
 // Re-enqueues the tonemap after lib_finish re-issued the camera pass (shs_abi_post.cpp).

@@ -18,7 +18,7 @@ from ._abi import (FRAME_PREQUANT, FRAME_PRESENT, SHADING_BLINN_PHONG, SHADING_D
                    SHADING_TOON, FrameDesc, LegacyDraw, RasterStats)
 
 __all__ = [
-    "ShsError", "Context", "Frame", "Draw", "RtFrame", "RtDraw", "RtPcss", "RtPbrDraw", "RtPbr", "RtSky", "RtSkyboxIblDraw", "SHADING_FLAT", "SHADING_GOURAUD", "SHADING_PHONG",
+    "ShsError", "Context", "Frame", "Draw", "RtFrame", "RtDraw", "RtPcss", "RtPbrDraw", "RtPbr", "RtSky", "RtSkyboxIblDraw", "RtWaterDraw", "RtWater", "SHADING_FLAT", "SHADING_GOURAUD", "SHADING_PHONG",
     "SHADING_BLINN_PHONG", "SHADING_TOON", "SHADING_GOOCH", "SHADING_OREN_NAYAR", "SHADING_NORMAL_VIS",
     "SHADING_DEPTH_VIS", "SHADING_TEXTURED", "SHADING_NAMES", "FRAME_PREQUANT", "lib",
 ]
@@ -109,6 +109,7 @@ class RtFrame:
                                  # 2: fragment_shader_pbr (Context.rt_render_pbr only),
                                  # 3: hello_pbr_light_shafts.cpp's fragment_shader_pbr, PBR under PCSS (Context.rt_render_pbr_soft only)
                                  # 4: hello_ibl_skybox.cpp's sky-lit fragment_shader_full (Context.rt_render_skybox_ibl only)
+                                 # 5: hello_water.cpp's atmosphere and water shaders, chosen per draw (Context.rt_render_water only)
 
 
 @dataclass
@@ -151,6 +152,23 @@ class RtSkyboxIblDraw:
     ibl_refl: float = 0.35
     ibl_f0: float = 0.04
     ibl_refl_mix: float = 1.0
+
+
+@dataclass
+class RtWaterDraw:
+    """Which of hello_water.cpp's two fragment shaders an RtDraw runs (shs_rt_water_draw): fragment_shader_water for the
+    water surface, the atmosphere fragment_shader_full for everything else."""
+    surface: bool = False
+
+
+@dataclass
+class RtWater:
+    """The frame's part of hello_water.cpp's Uniforms (shs_rt_water).  reflection_vp: float32[16], the mirrored camera's
+    proj * view, column-major (None: identity, the Uniforms default); reflection: read the context's reflection canvas
+    (Context.rt_keep_reflection / rt_set_reflection), else the water reflects the sky colour."""
+    reflection_vp: np.ndarray = None
+    time_sec: float = 0.0
+    reflection: bool = False
 
 
 @dataclass
@@ -825,6 +843,51 @@ class Context:
                 knobs[i] = _abi.RtSkyboxIblDrawC(float(k.ibl_ambient), float(k.ibl_refl), float(k.ibl_f0), float(k.ibl_refl_mix))
         self._check(self._lib.shs_rt_render_skybox_ibl(self._h, ctypes.byref(self._rt_frame_c(frame)), arr, knobs, len(draws)))
         self._rt_size = (frame.width, frame.height)
+
+    def rt_render_water(self, frame, draws, water_draws, water):
+        """shs_rt_render_water: PASS1A / PASS1B of hello_water.cpp (frame.shading 5; water_draws: one RtWaterDraw per draw, or
+        None to hand the library a null table; water: an RtWater), asynchronous."""
+        arr = self._rt_draw_array(draws)
+        flags = None
+        if water_draws is not None:
+            if len(water_draws) != len(draws):
+                raise ShsError(-1, "rt_render_water: one RtWaterDraw per draw")
+            flags = (_abi.RtWaterDrawC * max(len(draws), 1))()
+            for i, k in enumerate(water_draws):
+                flags[i].flags = int(k) if isinstance(k, (int, np.integer)) else (_abi.RT_WATER_SURFACE if k.surface else 0)
+        wc = None
+        if water is not None:
+            wc = _abi.RtWaterC()
+            vp = np.eye(4, dtype=np.float32) if water.reflection_vp is None else np.asarray(water.reflection_vp, np.float32)
+            wc.reflection_vp[:] = [float(v) for v in vp.reshape(16)]
+            wc.time_sec = float(water.time_sec)
+            r = water.reflection
+            wc.flags = int(r) if isinstance(r, (int, np.integer)) and not isinstance(r, bool) else (_abi.RT_WATER_REFLECTION if r else 0)
+            wc = ctypes.byref(wc)
+        self._check(self._lib.shs_rt_render_water(self._h, ctypes.byref(self._rt_frame_c(frame)), arr, flags, wc, len(draws)))
+        self._rt_size = (frame.width, frame.height)
+
+    def rt_keep_reflection(self):
+        """shs_rt_keep_reflection: the last camera pass's colour plane becomes the reflection canvas, asynchronous."""
+        self._check(self._lib.shs_rt_keep_reflection(self._h))
+
+    def rt_set_reflection(self, rgba=None):
+        """shs_rt_set_reflection: the reflection canvas from a host image uint8 [h, w, 4] in canvas rows (None: none)."""
+        if rgba is None:
+            self._check(self._lib.shs_rt_set_reflection(self._h, None, 0, 0))
+            return
+        rgba = np.ascontiguousarray(rgba, np.uint8)
+        if rgba.ndim != 3 or rgba.shape[2] != 4:
+            raise ShsError(-1, f"rt_set_reflection: an image of shape {rgba.shape}")
+        self._check(self._lib.shs_rt_set_reflection(self._h, _ptr(rgba), rgba.shape[1], rgba.shape[0]))
+
+    def rt_water_samples(self, world_pos, time_sec):
+        """shs_rt_water_samples: water_flow_normal_and_foam of n points -> (normal float32 [n, 3], foam float32 [n])."""
+        pos = np.ascontiguousarray(world_pos, np.float32).reshape(-1, 3)
+        n = pos.shape[0]
+        nrm, foam = np.empty((n, 3), np.float32), np.empty(n, np.float32)
+        self._check(self._lib.shs_rt_water_samples(self._h, n, _ptr(pos), float(time_sec), _ptr(nrm), _ptr(foam)))
+        return nrm, foam
 
     def rt_set_pbr(self, pbr=None):
         """shs_rt_set_pbr: the constants of shadings 2 and 3 (an RtPbr; None: the demo's)."""

@@ -279,6 +279,20 @@ class RtSkyboxIblDrawC(ctypes.Structure):
                 ("ibl_refl_mix", ctypes.c_float)]
 
 
+RT_WATER_SURFACE = 1        # SHS_RT_WATER_SURFACE
+RT_WATER_REFLECTION = 1     # SHS_RT_WATER_REFLECTION
+
+
+class RtWaterDrawC(ctypes.Structure):
+    """shs_rt_water_draw: which of hello_water.cpp's two fragment shaders a draw runs (shading 5)."""
+    _fields_ = [("flags", ctypes.c_uint32)]
+
+
+class RtWaterC(ctypes.Structure):
+    """shs_rt_water: the frame's part of hello_water.cpp's Uniforms (:653-655)."""
+    _fields_ = [("reflection_vp", _F16), ("time_sec", ctypes.c_float), ("flags", ctypes.c_uint32)]
+
+
 class RtStatsC(ctypes.Structure):
     _fields_ = [("input_tris", ctypes.c_int64), ("polys3", ctypes.c_int64), ("polys4", ctypes.c_int64),
                 ("sub_tris", ctypes.c_int64)]
@@ -406,6 +420,11 @@ SIGNATURES = [
     ("shs_rt_ibl_samples", ctypes.c_int, [_P, ctypes.c_int32, _P, _P, _P, _P]),
     ("shs_rt_render_skybox_ibl", ctypes.c_int, [_P, ctypes.POINTER(RtFrameC), ctypes.POINTER(RtDrawC),
                                                 ctypes.POINTER(RtSkyboxIblDrawC), ctypes.c_int32]),
+    ("shs_rt_render_water", ctypes.c_int, [_P, ctypes.POINTER(RtFrameC), ctypes.POINTER(RtDrawC), ctypes.POINTER(RtWaterDrawC),
+                                           ctypes.POINTER(RtWaterC), ctypes.c_int32]),
+    ("shs_rt_keep_reflection", ctypes.c_int, [_P]),
+    ("shs_rt_set_reflection", ctypes.c_int, [_P, _P, ctypes.c_int32, ctypes.c_int32]),
+    ("shs_rt_water_samples", ctypes.c_int, [_P, ctypes.c_int32, _P, ctypes.c_float, _P, _P]),
     ("shs_rt_set_sky", ctypes.c_int, [_P, ctypes.POINTER(RtSkyC)]),
     ("shs_rt_sky_samples", ctypes.c_int, [_P, ctypes.c_int32, _P, _P]),
     ("shs_rt_resolve", ctypes.c_int, [_P, _P, _P, _P]),
