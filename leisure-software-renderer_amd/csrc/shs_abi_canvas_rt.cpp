@@ -24,6 +24,7 @@
 // shs_glm.hpp.  Both passes are enqueued on the context stream; the shadow map, the planes and the records
 // live in the context, so a camera pass reads the map of the shadow pass before it in stream order.
 #include <cmath>
+#include <cstddef>
 #include <cstring>
 
 #include "shs_canvas_rt_internal.hpp"
@@ -65,13 +66,27 @@ int ensure_srgb_table(shs_ctx *ctx) {
 float saturate(float v) { return (v < 0.0f) ? 0.0f : (v > 1.0f ? 1.0f : v); }
 float clampf(float v, float lo, float hi) { return (v < lo) ? lo : (v > hi ? hi : v); }
 
-// The draw table of either pass (zm: view for the camera pass, light_vp for the shadow pass).  Returns the
-// triangle count, or -1 with ctx->err set.  pbr: the PBR pass's per-draw uniforms (element i with draws[i]), or
-// null for the other passes; ibl: the sky-lit pass's per-draw knobs likewise, converted into *h_ibl (the caller's: the
-// table is a few draws long and lives for one call, so the context holds no copy).
-using IblTable = std::vector<shs_dev::RtIblDrawGPU>;
-int64_t build_draws(shs_ctx *ctx, const shs_rt_draw *draws, int32_t n, const float *zmat, bool camera,
-                    const shs_rt_pbr_draw *pbr = nullptr, const shs_rt_skybox_ibl_draw *ibl = nullptr, IblTable *h_ibl = nullptr) {
+// What a pass has beside its frame and its draws: one of the three at most (the shadow pass and shadings 0 and 1 have
+// none), element i going with draws[i].  From it the pass builds its tail table, the bytes that ride behind the draw
+// table in the same upload, and names the RtParams pointer that receives their device address.
+struct PassExtras {
+    const shs_rt_pbr_draw *pbr = nullptr;             // shadings 2 and 3: the per-draw uniforms
+    const shs_rt_skybox_ibl_draw *ibl = nullptr;      // shading 4: the per-draw knobs
+    const shs_rt_water_draw *water_draws = nullptr;   // shading 5: the per-draw flags
+    const shs_rt_water *water = nullptr;              //   and the frame's uniforms
+    // the tail table: the context's rt_h_pbr, or `bytes` (a few draws long and alive for one call, so the context holds
+    // no copy): the sky-lit pass's RtIblDrawGPUs, or the water pass's RtWaterGPU and the flag words behind it
+    std::vector<unsigned char> bytes;
+    const void *tail = nullptr;
+    size_t tail_bytes = 0, tail_slot = 0;             // tail_slot: offsetof(RtParams, the pointer to the tail)
+    void set_tail(const void *data, size_t n, size_t slot) { tail = data, tail_bytes = n, tail_slot = slot; }
+    template <class T>
+    void append(const T &v) { bytes.insert(bytes.end(), (const unsigned char *)&v, (const unsigned char *)(&v + 1)); }
+};
+
+// The draw table of either pass (zm: view for the camera pass, light_vp for the shadow pass) and the per-draw tail
+// table of x.pbr or x.ibl.  Returns the triangle count, or -1 with ctx->err set.
+int64_t build_draws(shs_ctx *ctx, const shs_rt_draw *draws, int32_t n, const float *zmat, bool camera, PassExtras &x) {
     ctx->rt_h_draws.clear();
     ctx->rt_h_pbr.clear();
     int64_t total = 0;
@@ -105,10 +120,10 @@ int64_t build_draws(shs_ctx *ctx, const shs_rt_draw *draws, int32_t n, const flo
         shs_host::mul(zmat, in.model, o.zm);
         shs_host::normal_matrix(in.model, o.n3);
         for (int k = 0; k < 3; ++k) o.colf[k] = (float)in.base_color[k];
-        if (pbr) {
+        if (x.pbr) {
             // u.normal_mat is the caller's (pbr :1482, :1557); the per-draw steps of fragment_shader_pbr (pbr :646-652,
             // :697, :706) are done here once
-            const shs_rt_pbr_draw &m = pbr[i];
+            const shs_rt_pbr_draw &m = x.pbr[i];
             std::memcpy(o.n3, m.normal_mat, 9 * sizeof(float));
             shs_dev::RtPbrDrawGPU g{};
             for (int k = 0; k < 3; ++k) g.base[k] = srgb_table()[in.base_color[k]];
@@ -119,10 +134,10 @@ int64_t build_draws(shs_ctx *ctx, const shs_rt_draw *draws, int32_t n, const flo
             g.ibl_specular = saturate(m.ibl_specular_intensity) * saturate(m.ibl_reflection_strength);
             ctx->rt_h_pbr.push_back(g);
         }
-        if (ibl) {
+        if (x.ibl) {
             // the saturates of fragment_shader_full (ibl :502, :509), once per draw; their products stay in the shader
-            const shs_rt_skybox_ibl_draw &k = ibl[i];
-            h_ibl->push_back({saturate(k.ibl_ambient), saturate(k.ibl_refl), k.ibl_f0, saturate(k.ibl_refl_mix)});
+            const shs_rt_skybox_ibl_draw &k = x.ibl[i];
+            x.append(shs_dev::RtIblDrawGPU{saturate(k.ibl_ambient), saturate(k.ibl_refl), k.ibl_f0, saturate(k.ibl_refl_mix)});
         }
         ctx->rt_h_draws.push_back(o);
         total += m.n_tris;
@@ -131,6 +146,8 @@ int64_t build_draws(shs_ctx *ctx, const shs_rt_draw *draws, int32_t n, const flo
             return -1;
         }
     }
+    if (x.pbr) x.set_tail(ctx->rt_h_pbr.data(), ctx->rt_h_pbr.size() * sizeof(shs_dev::RtPbrDrawGPU), offsetof(shs_dev::RtParams, pbr_draws));
+    if (x.ibl) x.set_tail(x.bytes.data(), x.bytes.size(), offsetof(shs_dev::RtParams, ibl_draws));
     return total;
 }
 
@@ -222,29 +239,30 @@ shs_dev::RtWaterModel water_model(float time_sec) {
     return m;
 }
 
-// The water pass's own arguments beside the frame (shs_rt_render_water)
-struct WaterCall {
-    const shs_rt_water_draw *draws;
-    const shs_rt_water *water;
-};
-// RtWaterGPU and the flag words behind it, as the device reads them
-using WaterTable = std::vector<uint32_t>;
+// The seven constants of shs_rt_pcss into the kernel arguments that carry them (RtParams, RtPcssSamples)
+template <class Args>
+void fill_pcss(Args &a, const shs_rt_pcss &c) {
+    a.pcss_light = c.light_uv_radius;
+    a.pcss_search = c.search_radius_texels;
+    a.pcss_min = c.min_filter_texels;
+    a.pcss_max = c.max_filter_texels;
+    a.pcss_eps = c.epsilon;
+    a.pcss_blockers = c.blocker_samples;
+    a.pcss_taps = c.pcf_samples;
+}
 
-int upload_and_launch(shs_ctx *ctx, shs_dev::RtParams &p, bool shadow_pass, int shading = 0, int sky_model = 0,
-                      const IblTable *h_ibl = nullptr, const WaterTable *h_water = nullptr) {
+int upload_and_launch(shs_ctx *ctx, shs_dev::RtParams &p, bool shadow_pass, int shading, int sky_model, const PassExtras &x) {
     const size_t nd = ctx->rt_h_draws.size();
-    // the PBR pass's material table, or the sky-lit pass's knobs (a pass has one of the two at most), rides behind the
-    // draw table (sizeof(RtDrawGPU) is a multiple of 16): one copy
+    // the pass's tail table rides behind the draw table (sizeof(RtDrawGPU) is a multiple of 16): one copy
     static_assert(sizeof(shs_dev::RtDrawGPU) % 16 == 0, "the material table behind the draws is read as float4s");
-    const size_t npbr = ctx->rt_h_pbr.size(), nibl = h_ibl ? h_ibl->size() : 0, nwater = h_water ? h_water->size() : 0;
-    const size_t tail = npbr * sizeof(shs_dev::RtPbrDrawGPU) + nibl * sizeof(shs_dev::RtIblDrawGPU) + nwater * sizeof(uint32_t);
+    const size_t tail = x.tail_bytes;
     const size_t extra = (tail + sizeof(shs_dev::RtDrawGPU) - 1) / sizeof(shs_dev::RtDrawGPU);
     const size_t nslot = nd + extra;
     if (ensure(ctx, ctx->rt_draws, std::max<size_t>(nslot, 1)) || ensure(ctx, ctx->rt_recs, std::max<size_t>((size_t)p.n_recs, 1)) ||
         ensure(ctx, ctx->rt_stats, 4))
         return SHS_ERR_HIP;
     if (!shadow_pass && ensure(ctx, ctx->rt_vary, std::max<size_t>((size_t)p.n_recs, 1))) return SHS_ERR_HIP;
-    if (nd || nwater) {
+    if (nd || tail) {   // (the water pass has a tail without a draw)
         const int k = (int)(ctx->rt_pin_next++ & 1u);
         if (!ctx->rt_pin_ev[k]) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->rt_pin_ev[k], hipEventDisableTiming));
         else HIP_TRY(ctx, hipEventSynchronize(ctx->rt_pin_ev[k]));
@@ -256,17 +274,16 @@ int upload_and_launch(shs_ctx *ctx, shs_dev::RtParams &p, bool shadow_pass, int 
             ctx->rt_pin_cap[k] = nslot;
         }
         std::memcpy(ctx->rt_pin[k], ctx->rt_h_draws.data(), nd * sizeof(shs_dev::RtDrawGPU));
-        if (npbr) std::memcpy(ctx->rt_pin[k] + nd, ctx->rt_h_pbr.data(), npbr * sizeof(shs_dev::RtPbrDrawGPU));
-        else if (nibl) std::memcpy(ctx->rt_pin[k] + nd, h_ibl->data(), nibl * sizeof(shs_dev::RtIblDrawGPU));
-        else if (nwater) std::memcpy(ctx->rt_pin[k] + nd, h_water->data(), nwater * sizeof(uint32_t));
+        if (tail) std::memcpy(ctx->rt_pin[k] + nd, x.tail, tail);
         HIP_TRY(ctx, hipMemcpyAsync(ctx->rt_draws.p, ctx->rt_pin[k], nd * sizeof(shs_dev::RtDrawGPU) + tail, hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(ctx, hipEventRecord(ctx->rt_pin_ev[k], ctx->stream));
     }
     if (!shadow_pass) HIP_TRY(ctx, hipMemsetAsync(ctx->rt_stats.p, 0, 4 * sizeof(unsigned long long), ctx->stream));
     p.draws = ctx->rt_draws.p;
-    p.pbr_draws = npbr ? reinterpret_cast<const shs_dev::RtPbrDrawGPU *>(ctx->rt_draws.p + nd) : nullptr;
-    p.ibl_draws = nibl ? reinterpret_cast<const shs_dev::RtIblDrawGPU *>(ctx->rt_draws.p + nd) : nullptr;
-    p.water = nwater ? reinterpret_cast<const shs_dev::RtWaterGPU *>(ctx->rt_draws.p + nd) : nullptr;
+    if (tail) {   // pbr_draws, ibl_draws or water; the other two stay null
+        const void *dev = ctx->rt_draws.p + nd;
+        std::memcpy(reinterpret_cast<char *>(&p) + x.tail_slot, &dev, sizeof dev);
+    }
     p.recs = ctx->rt_recs.p;
     p.vary = ctx->rt_vary.p;
     p.stats = ctx->rt_stats.p;
@@ -274,12 +291,10 @@ int upload_and_launch(shs_ctx *ctx, shs_dev::RtParams &p, bool shadow_pass, int 
     return SHS_OK;
 }
 
-// PASS1 of the five demos: pbr null for shading 0 / 1 (shs_rt_render), the per-draw PBR uniforms for shading 2
-// (shs_rt_render_pbr) and 3 (shs_rt_render_pbr_soft); ibl the per-draw knobs of shading 4 (shs_rt_render_skybox_ibl),
-// null for the others; wc the flags and the frame's uniforms of shading 5 (shs_rt_render_water), null for the others.
-// Nothing of the context changes before the last rejection.
-int render_camera(shs_ctx *ctx, const shs_rt_frame *f, const shs_rt_draw *draws, const shs_rt_pbr_draw *pbr, int32_t n_draws,
-                  const shs_rt_skybox_ibl_draw *ibl = nullptr, const WaterCall *wc = nullptr) {
+// PASS1 of the six demos: x empty for shading 0 / 1 (shs_rt_render), x.pbr for shading 2 (shs_rt_render_pbr) and 3
+// (shs_rt_render_pbr_soft), x.ibl for shading 4 (shs_rt_render_skybox_ibl), x.water_draws and x.water for shading 5
+// (shs_rt_render_water).  Nothing of the context changes before the last rejection.
+int render_camera(shs_ctx *ctx, const shs_rt_frame *f, const shs_rt_draw *draws, int32_t n_draws, PassExtras x) {
     if (!size_ok(ctx, f->width, f->height, f->ref_tile_w, f->ref_tile_h)) return SHS_ERR_INVALID;
     if (f->flags & ~(SHS_RT_USE_SHADOW | SHS_RT_PCF | SHS_RT_PREQUANT)) {
         ctx->err = "render-target frame: unknown flags";
@@ -290,8 +305,7 @@ int render_camera(shs_ctx *ctx, const shs_rt_frame *f, const shs_rt_draw *draws,
         return SHS_ERR_INVALID;
     }
     if (set_dev(ctx)) return SHS_ERR_HIP;
-    IblTable h_ibl;
-    const int64_t n_tris = build_draws(ctx, draws, n_draws, f->view, true, pbr, ibl, &h_ibl);
+    const int64_t n_tris = build_draws(ctx, draws, n_draws, f->view, true, x);
     if (n_tris < 0) return SHS_ERR_INVALID;
     const size_t npx = (size_t)f->width * f->height;
     const bool pq = (f->flags & SHS_RT_PREQUANT) != 0;
@@ -329,14 +343,7 @@ int render_camera(shs_ctx *ctx, const shs_rt_frame *f, const shs_rt_draw *draws,
         const int rr = ensure_rotations(ctx, f->width, f->height);
         if (rr) return rr;
         p.rot = ctx->rt_rot.p;
-        const shs_rt_pcss &c = ctx->rt_pcss;
-        p.pcss_light = c.light_uv_radius;
-        p.pcss_search = c.search_radius_texels;
-        p.pcss_min = c.min_filter_texels;
-        p.pcss_max = c.max_filter_texels;
-        p.pcss_eps = c.epsilon;
-        p.pcss_blockers = c.blocker_samples;
-        p.pcss_taps = c.pcf_samples;
+        fill_pcss(p, ctx->rt_pcss);
     }
     if (f->shading == 2 || f->shading == 3) {
         if (ensure_srgb_table(ctx)) return SHS_ERR_HIP;
@@ -352,24 +359,23 @@ int render_camera(shs_ctx *ctx, const shs_rt_frame *f, const shs_rt_draw *draws,
         sky_model = ctx->rt_sky.model;
         p.sky = ctx->rt_sky_model;
     }
-    WaterTable h_water;
     if (f->shading == 5) {
         shs_dev::RtWaterGPU g{};
-        if (wc->water->flags & SHS_RT_WATER_REFLECTION) {
+        if (x.water->flags & SHS_RT_WATER_REFLECTION) {
             g.refl = ctx->rt_refl.p;
             g.refl_w = ctx->rt_refl_w;
             g.refl_h = ctx->rt_refl_h;
         }
-        std::memcpy(g.refl_vp, wc->water->reflection_vp, sizeof g.refl_vp);
+        std::memcpy(g.refl_vp, x.water->reflection_vp, sizeof g.refl_vp);
         // sky_color_simple(.., glm::normalize(-L)) normalises its sun_dir again (water :967, :165)
         const shs_host::vec3 sun = shs_host::gnormalize(shs_host::gnormalize(shs_host::gneg(L)));
         g.sun[0] = sun.x; g.sun[1] = sun.y; g.sun[2] = sun.z;
-        g.model = water_model(wc->water->time_sec);
-        h_water.resize(sizeof g / sizeof(uint32_t) + (size_t)n_draws);
-        std::memcpy(h_water.data(), &g, sizeof g);
-        for (int32_t i = 0; i < n_draws; ++i) h_water[sizeof g / sizeof(uint32_t) + i] = wc->draws[i].flags;
+        g.model = water_model(x.water->time_sec);
+        x.append(g);
+        for (int32_t i = 0; i < n_draws; ++i) x.append(x.water_draws[i].flags);
+        x.set_tail(x.bytes.data(), x.bytes.size(), offsetof(shs_dev::RtParams, water));
     }
-    int rc = upload_and_launch(ctx, p, false, f->shading, sky_model, &h_ibl, &h_water);
+    int rc = upload_and_launch(ctx, p, false, f->shading, sky_model, x);
     if (!rc && ctx->rt_sky.model != SHS_RT_SKY_NONE) {
         // skybox_background_pass (pbr :733-799) behind the triangles: the pixels the raster left without a fragment
         shs_dev::RtSkyParams q{};
@@ -402,6 +408,18 @@ int render_camera(shs_ctx *ctx, const shs_rt_frame *f, const shs_rt_draw *draws,
     return SHS_OK;
 }
 
+// shs_rt_render_pbr and shs_rt_render_pbr_soft: the same entry but for the shading it takes and how it names itself
+int render_pbr(shs_ctx *ctx, const shs_rt_frame *f, const shs_rt_draw *draws, const shs_rt_pbr_draw *pbr_draws, int32_t n_draws,
+               int32_t shading, const char *entry, const char *shader) {
+    if (!ctx || !f || n_draws < 0 || (n_draws > 0 && (!draws || !pbr_draws))) return SHS_ERR_INVALID;
+    if (f->shading != shading) {
+        ctx->err = std::string(entry) + ": shading " + std::to_string(f->shading) + " (" + std::to_string(shading) + ": " + shader + ")";
+        return SHS_ERR_INVALID;
+    }
+    static const shs_rt_pbr_draw none{};
+    return render_camera(ctx, f, draws, n_draws, PassExtras{n_draws > 0 ? pbr_draws : &none});
+}
+
 }  // namespace
 
 extern "C" {
@@ -411,7 +429,8 @@ int shs_rt_render_shadow(shs_ctx *ctx, int32_t w, int32_t h, int32_t ref_tile_w,
     if (!ctx || !light_vp || n_casters < 0 || (n_casters > 0 && !casters)) return SHS_ERR_INVALID;
     if (!size_ok(ctx, w, h, ref_tile_w, ref_tile_h)) return SHS_ERR_INVALID;
     if (set_dev(ctx)) return SHS_ERR_HIP;
-    const int64_t n_tris = build_draws(ctx, casters, n_casters, light_vp, false);
+    PassExtras none;
+    const int64_t n_tris = build_draws(ctx, casters, n_casters, light_vp, false, none);
     if (n_tris < 0) return SHS_ERR_INVALID;
     if (ensure(ctx, ctx->rt_shadow, (size_t)w * h)) return SHS_ERR_HIP;
     shs_dev::RtParams p{};
@@ -423,7 +442,7 @@ int shs_rt_render_shadow(shs_ctx *ctx, int32_t w, int32_t h, int32_t ref_tile_w,
     p.n_recs = (int32_t)n_tris;
     p.depth = ctx->rt_shadow.p;
     // the shadow pass shares the stats words with the camera pass: its own count is not reported
-    const int rc = upload_and_launch(ctx, p, true);
+    const int rc = upload_and_launch(ctx, p, true, 0, SHS_RT_SKY_NONE, none);
     if (rc) return rc;
     ctx->rt_sw = w;
     ctx->rt_sh = h;
@@ -438,27 +457,15 @@ int shs_rt_render(shs_ctx *ctx, const shs_rt_frame *f, const shs_rt_draw *draws,
                    " (0: fragment_shader_full, 1: fragment_shader_softshadow; 2, fragment_shader_pbr, goes through shs_rt_render_pbr)";
         return SHS_ERR_INVALID;
     }
-    return render_camera(ctx, f, draws, nullptr, n_draws);
+    return render_camera(ctx, f, draws, n_draws, PassExtras{});
 }
 
 int shs_rt_render_pbr(shs_ctx *ctx, const shs_rt_frame *f, const shs_rt_draw *draws, const shs_rt_pbr_draw *pbr_draws, int32_t n_draws) {
-    if (!ctx || !f || n_draws < 0 || (n_draws > 0 && (!draws || !pbr_draws))) return SHS_ERR_INVALID;
-    if (f->shading != 2) {
-        ctx->err = "shs_rt_render_pbr: shading " + std::to_string(f->shading) + " (2: fragment_shader_pbr)";
-        return SHS_ERR_INVALID;
-    }
-    static const shs_rt_pbr_draw none{};
-    return render_camera(ctx, f, draws, n_draws > 0 ? pbr_draws : &none, n_draws);
+    return render_pbr(ctx, f, draws, pbr_draws, n_draws, 2, "shs_rt_render_pbr", "fragment_shader_pbr");
 }
 
 int shs_rt_render_pbr_soft(shs_ctx *ctx, const shs_rt_frame *f, const shs_rt_draw *draws, const shs_rt_pbr_draw *pbr_draws, int32_t n_draws) {
-    if (!ctx || !f || n_draws < 0 || (n_draws > 0 && (!draws || !pbr_draws))) return SHS_ERR_INVALID;
-    if (f->shading != 3) {
-        ctx->err = "shs_rt_render_pbr_soft: shading " + std::to_string(f->shading) + " (3: fragment_shader_pbr under PCSS)";
-        return SHS_ERR_INVALID;
-    }
-    static const shs_rt_pbr_draw none{};
-    return render_camera(ctx, f, draws, n_draws > 0 ? pbr_draws : &none, n_draws);
+    return render_pbr(ctx, f, draws, pbr_draws, n_draws, 3, "shs_rt_render_pbr_soft", "fragment_shader_pbr under PCSS");
 }
 
 int shs_rt_render_skybox_ibl(shs_ctx *ctx, const shs_rt_frame *f, const shs_rt_draw *draws, const shs_rt_skybox_ibl_draw *ibl_draws,
@@ -476,7 +483,7 @@ int shs_rt_render_skybox_ibl(shs_ctx *ctx, const shs_rt_frame *f, const shs_rt_d
         }
     }
     static const shs_rt_skybox_ibl_draw none{};
-    return render_camera(ctx, f, draws, nullptr, n_draws, n_draws > 0 ? ibl_draws : &none);
+    return render_camera(ctx, f, draws, n_draws, PassExtras{nullptr, n_draws > 0 ? ibl_draws : &none});
 }
 
 int shs_rt_render_water(shs_ctx *ctx, const shs_rt_frame *f, const shs_rt_draw *draws, const shs_rt_water_draw *water_draws,
@@ -504,8 +511,7 @@ int shs_rt_render_water(shs_ctx *ctx, const shs_rt_frame *f, const shs_rt_draw *
         ctx->err = "shs_rt_render_water: a non-finite time_sec";
         return SHS_ERR_INVALID;
     }
-    const WaterCall wc = {water_draws, water};
-    return render_camera(ctx, f, draws, nullptr, n_draws, nullptr, &wc);
+    return render_camera(ctx, f, draws, n_draws, PassExtras{nullptr, nullptr, water_draws, water});
 }
 
 int shs_rt_keep_reflection(shs_ctx *ctx) {
@@ -674,14 +680,7 @@ int shs_rt_pcss_samples(shs_ctx *ctx, const float *map, int32_t w, int32_t h, in
     q.bias = io + 3 * ns;
     q.rot = ctx->rt_ps_rot.p;
     q.out = io + 4 * ns;
-    const shs_rt_pcss &c = ctx->rt_pcss;
-    q.pcss_light = c.light_uv_radius;
-    q.pcss_search = c.search_radius_texels;
-    q.pcss_min = c.min_filter_texels;
-    q.pcss_max = c.max_filter_texels;
-    q.pcss_eps = c.epsilon;
-    q.pcss_blockers = c.blocker_samples;
-    q.pcss_taps = c.pcf_samples;
+    fill_pcss(q, ctx->rt_pcss);
     HIP_TRY(ctx, shs_internal::launch_pcss_samples(q, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(out, q.out, ns * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // (the pageable staging above is consumed by now)
