@@ -851,6 +851,122 @@ typedef struct shs_canvas_light_shafts_desc {
 int shs_canvas_light_shafts(shs_ctx *ctx, const shs_canvas_light_shafts_desc *desc, const uint8_t *src, const float *depth,
                             const float *shadow_map, uint8_t *dst, float *prequant, uint32_t flags);
 
+/* ---- Canvas-API post passes: velocity blur, fog, outline, FXAA, bloom source, additive, lens flare ----
+ * The full-screen passes behind the raster in hello_multi_pass.cpp, hello_camera_and_perobject_motion_blur.cpp
+ * and hello_glowing_star.cpp, one thread per pixel, under the conventions of the block above (buffers, flags,
+ * SHS_CANVAS_DEVICE).  SHS_ERR_INVALID, with nothing enqueued and the context untouched, for: a null buffer, a
+ * non-positive size, an unknown flag, a non-finite parameter, a radius or ghost count outside its range,
+ * fog_end - fog_start zero or non-finite, and -- for the four passes that read neighbours (velocity blur, outline,
+ * FXAA, lens flare) -- a dst whose W*H*4 bytes overlap src.  Depth is finite or FLT_MAX.  Every pass but the fog
+ * and the flare is exact float arithmetic: its bytes are the reference's.  Those two evaluate their one
+ * transcendental (std::pow, std::exp) in double and round once to float, where the reference calls the host's
+ * float libm: prequant (may be NULL; W*H*4 floats) receives the three floats just before the byte conversion
+ * and 1, so that a byte off by one can be explained by its float. */
+#define SHS_CANVAS_MAX_OUTLINE_RADIUS 4
+#define SHS_CANVAS_MAX_FLARE_GHOSTS 8
+typedef struct shs_canvas_velocity_blur_desc {
+    int32_t width, height;
+    int32_t samples;            /* MB_SAMPLES (12; the glowing star's 8) */
+    float strength;             /* MB_STRENGTH (1; the glowing star's 1.5) */
+} shs_canvas_velocity_blur_desc;
+/* motion_blur_pass (hello_multi_pass.cpp:605-683): velocity * strength, `samples` tent-weighted taps along it;
+ * no camera term, no knee, no clamp.  samples <= 1 copies. */
+int shs_canvas_velocity_blur(shs_ctx *ctx, const shs_canvas_velocity_blur_desc *desc, const uint8_t *src,
+                             const float *velocity, uint8_t *dst, uint32_t flags);
+typedef struct shs_canvas_fog_desc {
+    int32_t width, height;
+    uint8_t fog_color[4];       /* FOG_COLOR (28, 30, 38, 255); the alpha is not used */
+    float fog_start, fog_end;   /* FOG_START_Z (20), FOG_END_Z (80); fog_end < fog_start is allowed */
+    float fog_power;            /* FOG_POWER (1.25) */
+} shs_canvas_fog_desc;
+/* fog_pass (hello_multi_pass.cpp:764-819).  dst == src is allowed (a pixel reads only its own).  prequant: the
+ * ia * a + t * b sums and 1; (0, 0, 0, -1) for an empty pixel, which the pass copies. */
+int shs_canvas_fog(shs_ctx *ctx, const shs_canvas_fog_desc *desc, const uint8_t *src, const float *depth, uint8_t *dst,
+                   float *prequant, uint32_t flags);
+typedef struct shs_canvas_outline_desc {
+    int32_t width, height;
+    int32_t radius;             /* EDGE_RADIUS (1): 0 .. SHS_CANVAS_MAX_OUTLINE_RADIUS */
+    float threshold;            /* EDGE_THRESHOLD (0.75) */
+    float strength;             /* EDGE_STRENGTH (0.15) */
+} shs_canvas_outline_desc;
+/* outline_pass (hello_multi_pass.cpp:689-758): an empty centre is copied, empty neighbours are skipped. */
+int shs_canvas_outline(shs_ctx *ctx, const shs_canvas_outline_desc *desc, const uint8_t *src, const float *depth,
+                       uint8_t *dst, uint32_t flags);
+typedef struct shs_canvas_fxaa_desc {
+    int32_t width, height;
+    float reduce_min;           /* FXAA_REDUCE_MIN (1 / 128) */
+    float reduce_mul;           /* FXAA_REDUCE_MUL (1 / 8) */
+    float span_max;             /* FXAA_SPAN_MAX (8) */
+} shs_canvas_fxaa_desc;
+/* fxaa_pass (hello_multi_pass.cpp:1000-1114); the 0.02 contrast gate is the reference's constant. */
+int shs_canvas_fxaa(shs_ctx *ctx, const shs_canvas_fxaa_desc *desc, const uint8_t *src, uint8_t *dst, uint32_t flags);
+typedef struct shs_canvas_spec_bright_desc {
+    int32_t width, height;
+    float threshold;            /* SPEC_GLOW_THRESHOLD (0.139) */
+    float intensity;            /* SPEC_GLOW_INTENSITY (13.25) */
+} shs_canvas_spec_bright_desc;
+/* build_spec_bright_pass (hello_glowing_star.cpp:700-752): spec01 is the W*H float plane rt_scene.spec; the gold
+ * tint is the reference's.  A NaN in the plane gives a black pixel, as std::max(0.0f, NaN) does. */
+int shs_canvas_spec_bright(shs_ctx *ctx, const shs_canvas_spec_bright_desc *desc, const float *spec01, uint8_t *dst,
+                           uint32_t flags);
+/* additive_composite_pass (hello_glowing_star.cpp:754-795): out = base + mul_color(add, strength), clamped.
+ * out may be base or add (a pixel reads only its own). */
+int shs_canvas_additive(shs_ctx *ctx, int32_t width, int32_t height, const uint8_t *base, const uint8_t *add,
+                        float strength, uint8_t *out, uint32_t flags);
+typedef struct shs_canvas_lens_flare_desc {
+    int32_t width, height;
+    float intensity;            /* FLARE_INTENSITY (0.55) */
+    float halo_intensity;       /* FLARE_HALO_INTENS (0.35) */
+    float chroma_shift_px;      /* FLARE_CHROMA_SHIFT (0.8) */
+    int32_t n_ghosts;           /* FLARE_GHOSTS (3): 1 .. SHS_CANVAS_MAX_FLARE_GHOSTS */
+    float ghost_scales[SHS_CANVAS_MAX_FLARE_GHOSTS];   /* the first n_ghosts (0.55, 0.85, 1.25) */
+} shs_canvas_lens_flare_desc;
+/* pseudo_lens_flare_pass (hello_glowing_star.cpp:802-906); the halo scale and the ring's constants are the
+ * reference's.  prequant: rr, gg, bb before color_from_rgbaf's clamp, and 1. */
+int shs_canvas_lens_flare(shs_ctx *ctx, const shs_canvas_lens_flare_desc *desc, const uint8_t *src, uint8_t *dst,
+                          float *prequant, uint32_t flags);
+
+/* A demo's whole post chain in one call, on scratch canvases the context owns (grown on demand, released by
+ * shs_destroy).  The frame's width and height apply to every step: those of the embedded descs are ignored.
+ * color, depth and velocity are what the raster left (shs_rt_device_targets, or host copies); color is only read,
+ * dst (W*H*4 bytes) receives the presented frame and may be color.  Everything is checked before the first step
+ * is enqueued; with SHS_CANVAS_DEVICE the chain never synchronises with the host (the autofocus depth stays on
+ * the device). */
+#define SHS_CANVAS_BLUR_VELOCITY_FIRST 0   /* hello_multi_pass.cpp:1379-1426 */
+#define SHS_CANVAS_BLUR_COMBINED_FIRST 1   /* the same chain with shs_canvas_motion_blur as its first step */
+#define SHS_CANVAS_BLUR_COMBINED_LATE  2   /* hello_camera_and_perobject_motion_blur.cpp:1544-1606: DoF, fog,
+                                            * outline, then shs_canvas_motion_blur, then FXAA */
+typedef struct shs_canvas_multi_pass_frame_desc {
+    int32_t width, height;
+    int32_t blur_mode;          /* SHS_CANVAS_BLUR_* */
+    int32_t enable_dof;         /* ENABLE_DOF (1) */
+    int32_t enable_fxaa;        /* ENABLE_FXAA (1) */
+    shs_canvas_velocity_blur_desc velocity_blur;   /* blur_mode 0 */
+    shs_canvas_motion_blur_desc motion_blur;       /* blur_mode 1, 2 */
+    shs_canvas_dof_desc dof;
+    shs_canvas_fog_desc fog;
+    shs_canvas_outline_desc outline;
+    shs_canvas_fxaa_desc fxaa;
+} shs_canvas_multi_pass_frame_desc;
+/* Blur, the DoF step (shs_canvas_dof), fog, outline, FXAA; a disabled DoF or FXAA passes its input on. */
+int shs_canvas_multi_pass_frame(shs_ctx *ctx, const shs_canvas_multi_pass_frame_desc *desc, const uint8_t *color,
+                                const float *depth, const float *velocity, uint8_t *dst, uint32_t flags);
+typedef struct shs_canvas_glow_frame_desc {
+    int32_t width, height;
+    int32_t enable_dof;         /* ENABLE_DOF (1) */
+    int32_t enable_bloom;       /* ENABLE_BLOOM (1); 0: bloom_out is black, as the reference clears it */
+    int32_t enable_flare;       /* ENABLE_FLARE (1); 0: flare_out is black */
+    int32_t bloom_iterations;   /* BLOOM_BLUR_ITERS (10): horizontal + vertical shs_canvas_gaussian_blur each, >= 0 */
+    shs_canvas_velocity_blur_desc velocity_blur;
+    shs_canvas_dof_desc dof;
+    shs_canvas_spec_bright_desc spec_bright;
+    shs_canvas_lens_flare_desc lens_flare;
+} shs_canvas_glow_frame_desc;
+/* hello_glowing_star.cpp:1233-1310: velocity blur, DoF, bright pass over spec01, the bloom's Gaussian iterations,
+ * flare over the bloom, and the two additive composites (strength 1) onto the DoF's output. */
+int shs_canvas_glow_frame(shs_ctx *ctx, const shs_canvas_glow_frame_desc *desc, const uint8_t *color, const float *depth,
+                          const float *velocity, const float *spec01, uint8_t *dst, uint32_t flags);
+
 /* ---- Canvas render-target raster: shadow pass and shadowed camera pass ------------------------------
  * The raster the hello-render-target/ demos share, for its simplest complete host
  * hello_shadow_mapping.cpp (paths relative to cpp-folders/src/hello-render-target/):

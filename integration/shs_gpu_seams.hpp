@@ -753,6 +753,96 @@ private:
     Device *dev_;
 };
 
+// -----------------------------------------------------------------------------------------------------
+// Seam 1c, post chains -- hello-render-target/hello_multi_pass.cpp (:1379-1426),
+// hello_camera_and_perobject_motion_blur.cpp (:1544-1606) and hello_glowing_star.cpp (:1233-1310).
+//
+// Everything those main loops do between sys->render() and copy_to_SDLSurface, as one call over the planes the
+// raster left on the device (shs_rt_device_targets), or over the demo's own RT_ColorDepthMotion when the raster ran
+// on the host.  The defaults are the demos' file-scope constants; a host with other values sets the desc's members.
+// present(): the frame into the canvas the demo presents (fxaa_out / final_out), the only copy back.  Uncompiled,
+// like the other seams.
+// -----------------------------------------------------------------------------------------------------
+class PostChainGPU {
+public:
+    explicit PostChainGPU(Device *dev) : dev_(dev) {}
+
+    // hello_multi_pass.cpp's constants (:66-100)
+    static shs_canvas_multi_pass_frame_desc multi_pass_defaults(int W, int H) {
+        shs_canvas_multi_pass_frame_desc d{};
+        d.width = W; d.height = H;
+        d.blur_mode = SHS_CANVAS_BLUR_VELOCITY_FIRST;
+        d.enable_dof = 1; d.enable_fxaa = 1;
+        d.velocity_blur.samples = 12; d.velocity_blur.strength = 1.0f;
+        d.dof.blur_iterations = 4; d.dof.autofocus_radius = 6; d.dof.focus_x = W / 2; d.dof.focus_y = H / 2;
+        d.dof.range = 34.0f; d.dof.max_blur = 0.75f;
+        const uint8_t fog[4] = {28, 30, 38, 255};
+        std::memcpy(d.fog.fog_color, fog, 4);
+        d.fog.fog_start = 20.0f; d.fog.fog_end = 80.0f; d.fog.fog_power = 1.25f;
+        d.outline.radius = 1; d.outline.threshold = 0.75f; d.outline.strength = 0.15f;
+        d.fxaa.reduce_min = 1.0f / 128.0f; d.fxaa.reduce_mul = 1.0f / 8.0f; d.fxaa.span_max = 8.0f;
+        return d;
+    }
+
+    // hello_camera_and_perobject_motion_blur.cpp: the same passes in its order, combined_motion_blur_pass after the
+    // outline.  The caller fills the motion blur's constants (MB_*) once; the matrices change every frame.
+    static void use_combined_blur(shs_canvas_multi_pass_frame_desc &d, const glm::mat4 &curr_view, const glm::mat4 &curr_proj,
+                                  const glm::mat4 &prev_view, const glm::mat4 &prev_proj) {
+        d.blur_mode = SHS_CANVAS_BLUR_COMBINED_LATE;
+        std::memcpy(d.motion_blur.curr_view, glm::value_ptr(curr_view), 64);
+        std::memcpy(d.motion_blur.curr_proj, glm::value_ptr(curr_proj), 64);
+        std::memcpy(d.motion_blur.prev_view, glm::value_ptr(prev_view), 64);
+        std::memcpy(d.motion_blur.prev_proj, glm::value_ptr(prev_proj), 64);
+    }
+
+    // hello_glowing_star.cpp's constants (:62-90)
+    static shs_canvas_glow_frame_desc glow_defaults(int W, int H) {
+        shs_canvas_glow_frame_desc d{};
+        d.width = W; d.height = H;
+        d.enable_dof = 1; d.enable_bloom = 1; d.enable_flare = 1; d.bloom_iterations = 10;
+        d.velocity_blur.samples = 8; d.velocity_blur.strength = 1.5f;
+        d.dof.blur_iterations = 3; d.dof.autofocus_radius = 6; d.dof.focus_x = W / 2; d.dof.focus_y = H / 2;
+        d.dof.range = 22.0f; d.dof.max_blur = 0.80f;
+        d.spec_bright.threshold = 0.139f; d.spec_bright.intensity = 13.25f;
+        d.lens_flare.intensity = 0.55f; d.lens_flare.halo_intensity = 0.35f; d.lens_flare.chroma_shift_px = 0.8f;
+        d.lens_flare.n_ghosts = 3;
+        const float scales[3] = {0.55f, 0.85f, 1.25f};
+        std::memcpy(d.lens_flare.ghost_scales, scales, sizeof scales);
+        return d;
+    }
+
+    // over the last shs_rt_render*'s planes; frame: a device buffer of the host's, W*H*4 bytes
+    void multi_pass(const shs_canvas_multi_pass_frame_desc &d, void *frame) {
+        void *color = nullptr, *depth = nullptr, *vel = nullptr;
+        ok(shs_rt_device_targets(dev_->ctx, &color, &depth, &vel));
+        ok(shs_canvas_multi_pass_frame(dev_->ctx, &d, static_cast<const uint8_t *>(color), static_cast<const float *>(depth),
+                                       static_cast<const float *>(vel), static_cast<uint8_t *>(frame), SHS_CANVAS_DEVICE));
+    }
+
+    // the demo's own targets on the host (RT_ColorDepthMotion: color, depth, motion) into the canvas it presents
+    template <class RtT>
+    void multi_pass_host(const shs_canvas_multi_pass_frame_desc &d, RtT &rt, shs::Canvas &fxaa_out) {
+        ok(shs_canvas_multi_pass_frame(dev_->ctx, &d, reinterpret_cast<const uint8_t *>(rt.color.buffer().raw()),
+                                       rt.depth.buffer().raw(), &rt.motion.vel[0].x,   // MotionBuffer::vel (:453-489)
+                                       reinterpret_cast<uint8_t *>(fxaa_out.buffer().raw()), 0));
+    }
+
+    // hello_glowing_star.cpp's RT (color, depth, velocity, spec) into final_out
+    template <class RtT>
+    void glow_host(const shs_canvas_glow_frame_desc &d, RtT &rt, shs::Canvas &final_out) {
+        ok(shs_canvas_glow_frame(dev_->ctx, &d, reinterpret_cast<const uint8_t *>(rt.color.buffer().raw()),
+                                 rt.depth.buffer().raw(), &rt.velocity.raw()[0].x, rt.spec.raw(),
+                                 reinterpret_cast<uint8_t *>(final_out.buffer().raw()), 0));
+    }
+
+    void ok(int rc) const {
+        if (rc != SHS_OK) throw std::runtime_error(shs_last_error(dev_->ctx));
+    }
+
+private:
+    Device *dev_;
+};
+
 // =====================================================================================================
 // Seam 3 -- the library's plugin pipeline (shs-renderer-lib/include/shs/pipeline/).
 // =====================================================================================================

@@ -390,6 +390,10 @@ struct shs_ctx {
     int rt_refl_w = 0, rt_refl_h = 0;
     bool rt_have_refl = false;
     DevBuf<float> rt_water_io;
+    // the frame chains of shs_abi_canvas_fx.cpp: the demos' intermediate canvases (fx_a, fx_b, fx_c) and, for host
+    // buffers, the staged inputs and the frame before it is copied back
+    DevBuf<uint32_t> fx_a, fx_b, fx_c, fx_in, fx_out;
+    DevBuf<float> fx_depth, fx_vel, fx_spec;
 };
 
 // Re-enqueues the tonemap after lib_finish re-issued the camera pass (shs_abi_post.cpp).

@@ -762,6 +762,197 @@ class Context:
                                                       None if pq is None else _ptr(pq), self.CANVAS_DEVICE if dev else 0))
         return (dst, pq) if prequant else dst
 
+    # -- Canvas-API post passes (hello_multi_pass.cpp, hello_glowing_star.cpp) --------------------
+    # The demos' constants (hello_multi_pass.cpp:66-100; hello_glowing_star.cpp:62-90 where it says so); a frame
+    # method's per-pass dicts override them.  dof and motion_blur are canvas_dof's / canvas_motion_blur's arguments.
+    FX_DEFAULTS = {
+        "velocity_blur": dict(samples=12, strength=1.0),
+        "fog": dict(fog_color=(28, 30, 38, 255), fog_start=20.0, fog_end=80.0, fog_power=1.25),
+        "outline": dict(radius=1, threshold=0.75, strength=0.15),
+        "fxaa": dict(reduce_min=1.0 / 128.0, reduce_mul=1.0 / 8.0, span_max=8.0),
+        "spec_bright": dict(threshold=0.139, intensity=13.25),                                       # glowing star
+        "lens_flare": dict(intensity=0.55, halo_intensity=0.35, chroma_shift_px=0.8, ghost_scales=(0.55, 0.85, 1.25)),
+        "dof": dict(iterations=4, radius=6, focus=None, range_=34.0, max_blur=0.75),
+        "motion_blur": dict(curr_view=None, curr_proj=None, prev_view=None, prev_proj=None, samples=12, strength=0.85,
+                            w_obj=1.0, w_cam=0.35, soft_knee=True, knee_px=18.0, max_px=22.0),
+    }
+    _FX_DESCS = {"velocity_blur": _abi.CanvasVelocityBlurDescC, "fog": _abi.CanvasFogDescC, "outline": _abi.CanvasOutlineDescC,
+                 "fxaa": _abi.CanvasFxaaDescC, "spec_bright": _abi.CanvasSpecBrightDescC, "lens_flare": _abi.CanvasLensFlareDescC,
+                 "dof": _abi.CanvasDofDescC, "motion_blur": _abi.CanvasMotionBlurDescC}
+
+    @classmethod
+    def fx_desc(cls, kind, W, H, params=None, into=None):
+        """The C desc of one post pass (kind: a key of FX_DEFAULTS) at W x H from FX_DEFAULTS and params; into: a desc
+        to fill (a frame desc's member)."""
+        vals = dict(cls.FX_DEFAULTS[kind])
+        unknown = set(params or ()) - set(vals)
+        if unknown:
+            raise TypeError(f"{kind}: unknown parameters {sorted(unknown)}")
+        vals.update(params or {})
+        d = cls._FX_DESCS[kind]() if into is None else into
+        d.width, d.height = int(W), int(H)
+        if kind == "dof":
+            d.blur_iterations, d.autofocus_radius = int(vals["iterations"]), int(vals["radius"])
+            d.focus_x, d.focus_y = (W // 2, H // 2) if vals["focus"] is None else vals["focus"]
+            d.range, d.max_blur = float(vals["range_"]), float(vals["max_blur"])
+            return d
+        if kind == "lens_flare":
+            scales = [float(s) for s in vals.pop("ghost_scales")]
+            if len(scales) > _abi.CANVAS_MAX_FLARE_GHOSTS:
+                raise ValueError(f"lens_flare: at most {_abi.CANVAS_MAX_FLARE_GHOSTS} ghosts")
+            d.n_ghosts = len(scales)
+            for k in range(_abi.CANVAS_MAX_FLARE_GHOSTS):
+                d.ghost_scales[k] = scales[k] if k < len(scales) else 0.0
+        for name, v in vals.items():
+            if name in ("curr_view", "curr_proj", "prev_view", "prev_proj"):
+                if v is None:
+                    raise TypeError(f"motion_blur: {name} is required")
+                getattr(d, name)[:] = [float(f) for f in np.asarray(v, np.float32).reshape(16)]
+            elif name == "fog_color":
+                d.fog_color[:] = [int(c) for c in v]
+            elif isinstance(getattr(d, name), int):
+                setattr(d, name, int(v))
+            else:
+                setattr(d, name, float(v))
+        return d
+
+    def _fx_call(self, fn, desc, inputs, like, dst, prequant, H, W):
+        """One post-pass entry: inputs (arrays or tensors, all where `like` lives) -> dst [, prequant]."""
+        dev = _is_device(like)
+        if any(_is_device(a) != dev for a in inputs):
+            raise ValueError("canvas pass: every buffer must live where the first does")
+        if dev:
+            self._on_torch_stream()
+        if dst is None:
+            if dev:
+                import torch
+                dst = torch.empty((H, W, 4), dtype=torch.uint8, device=like.device)
+            else:
+                dst = np.empty((H, W, 4), np.uint8)
+        args = [_ptr(a) for a in inputs] + [_ptr(dst)]
+        pq = None
+        if prequant is not None:
+            if prequant:
+                if dev:
+                    import torch
+                    pq = torch.empty((H, W, 4), dtype=torch.float32, device=like.device)
+                else:
+                    pq = np.empty((H, W, 4), np.float32)
+            args.append(None if pq is None else _ptr(pq))
+        self._check(fn(self._h, ctypes.byref(desc), *args, self.CANVAS_DEVICE if dev else 0))
+        return (dst, pq) if prequant else dst
+
+    def canvas_velocity_blur(self, src, velocity, samples=12, strength=1.0, dst=None):
+        """motion_blur_pass (hello_multi_pass.cpp:605-683): src uint8 [H, W, 4], velocity float32 [H, W, 2] -> dst.
+        Host arrays (synchronous) or torch CUDA tensors (asynchronous on the context stream), as every canvas pass."""
+        H, W = src.shape[:2]
+        d = self.fx_desc("velocity_blur", W, H, dict(samples=samples, strength=strength))
+        return self._fx_call(self._lib.shs_canvas_velocity_blur, d, [_host_c(src, np.uint8), _host_c(velocity, np.float32)],
+                             src, dst, None, H, W)
+
+    def canvas_fog(self, src, depth, fog_color=(28, 30, 38, 255), fog_start=20.0, fog_end=80.0, fog_power=1.25, dst=None,
+                   prequant=False):
+        """fog_pass (hello_multi_pass.cpp:764-819); dst may be src.  prequant: also float32 [H, W, 4], the three sums
+        before the byte conversion and 1 ((0, 0, 0, -1): an empty pixel, copied)."""
+        H, W = src.shape[:2]
+        d = self.fx_desc("fog", W, H, dict(fog_color=fog_color, fog_start=fog_start, fog_end=fog_end, fog_power=fog_power))
+        return self._fx_call(self._lib.shs_canvas_fog, d, [_host_c(src, np.uint8), _host_c(depth, np.float32)], src, dst,
+                             bool(prequant), H, W)
+
+    def canvas_outline(self, src, depth, radius=1, threshold=0.75, strength=0.15, dst=None):
+        """outline_pass (hello_multi_pass.cpp:689-758)."""
+        H, W = src.shape[:2]
+        d = self.fx_desc("outline", W, H, dict(radius=radius, threshold=threshold, strength=strength))
+        return self._fx_call(self._lib.shs_canvas_outline, d, [_host_c(src, np.uint8), _host_c(depth, np.float32)], src, dst,
+                             None, H, W)
+
+    def canvas_fxaa(self, src, reduce_min=1.0 / 128.0, reduce_mul=1.0 / 8.0, span_max=8.0, dst=None):
+        """fxaa_pass (hello_multi_pass.cpp:1000-1114)."""
+        H, W = src.shape[:2]
+        d = self.fx_desc("fxaa", W, H, dict(reduce_min=reduce_min, reduce_mul=reduce_mul, span_max=span_max))
+        return self._fx_call(self._lib.shs_canvas_fxaa, d, [_host_c(src, np.uint8)], src, dst, None, H, W)
+
+    def canvas_spec_bright(self, spec01, threshold=0.139, intensity=13.25, dst=None):
+        """build_spec_bright_pass (hello_glowing_star.cpp:700-752): spec01 float32 [H, W] -> uint8 [H, W, 4]."""
+        H, W = spec01.shape[:2]
+        d = self.fx_desc("spec_bright", W, H, dict(threshold=threshold, intensity=intensity))
+        return self._fx_call(self._lib.shs_canvas_spec_bright, d, [_host_c(spec01, np.float32)], spec01, dst, None, H, W)
+
+    def canvas_additive(self, base, add, strength=1.0, out=None):
+        """additive_composite_pass (hello_glowing_star.cpp:754-795); out may be base."""
+        H, W = base.shape[:2]
+        dev = _is_device(base)
+        if _is_device(add) != dev:
+            raise ValueError("canvas_additive: add must live where base does")
+        if dev:
+            self._on_torch_stream()
+        if out is None:
+            out = _empty_like(base)
+        base, add = _host_c(base, np.uint8), _host_c(add, np.uint8)
+        self._check(self._lib.shs_canvas_additive(self._h, W, H, _ptr(base), _ptr(add), float(strength), _ptr(out),
+                                                  self.CANVAS_DEVICE if dev else 0))
+        return out
+
+    def canvas_lens_flare(self, src, intensity=0.55, halo_intensity=0.35, chroma_shift_px=0.8, ghost_scales=(0.55, 0.85, 1.25),
+                          dst=None, prequant=False):
+        """pseudo_lens_flare_pass (hello_glowing_star.cpp:802-906) over the bloom canvas.  prequant: also float32
+        [H, W, 4], rr / gg / bb before the clamp and 1."""
+        H, W = src.shape[:2]
+        d = self.fx_desc("lens_flare", W, H, dict(intensity=intensity, halo_intensity=halo_intensity,
+                                                  chroma_shift_px=chroma_shift_px, ghost_scales=ghost_scales))
+        return self._fx_call(self._lib.shs_canvas_lens_flare, d, [_host_c(src, np.uint8)], src, dst, bool(prequant), H, W)
+
+    def multi_pass_frame_desc(self, W, H, blur_mode=0, enable_dof=True, enable_fxaa=True, **passes):
+        d = _abi.CanvasMultiPassFrameDescC()
+        d.width, d.height, d.blur_mode = int(W), int(H), int(blur_mode)
+        d.enable_dof, d.enable_fxaa = int(bool(enable_dof)), int(bool(enable_fxaa))
+        unknown = set(passes) - {"velocity_blur", "motion_blur", "dof", "fog", "outline", "fxaa"}
+        if unknown:
+            raise TypeError(f"canvas_multi_pass_frame: unknown passes {sorted(unknown)}")
+        for kind in ("velocity_blur", "dof", "fog", "outline", "fxaa"):
+            self.fx_desc(kind, W, H, passes.get(kind), into=getattr(d, kind))
+        if blur_mode != _abi.CANVAS_BLUR_VELOCITY_FIRST:
+            self.fx_desc("motion_blur", W, H, passes.get("motion_blur"), into=d.motion_blur)
+        return d
+
+    def canvas_multi_pass_frame(self, color, depth, velocity, blur_mode=0, enable_dof=True, enable_fxaa=True, dst=None,
+                                **passes):
+        """A whole post chain in one call (include/shs_gpu.h): blur_mode 0 hello_multi_pass.cpp:1379-1426 (velocity
+        blur, DoF, fog, outline, FXAA), 1 the same with canvas_motion_blur first, 2
+        hello_camera_and_perobject_motion_blur.cpp's order (DoF, fog, outline, canvas_motion_blur, FXAA).  passes:
+        velocity_blur=, motion_blur=, dof=, fog=, outline=, fxaa= dicts over FX_DEFAULTS (motion_blur needs the four
+        matrices).  color is only read; dst may be color."""
+        H, W = color.shape[:2]
+        d = self.multi_pass_frame_desc(W, H, blur_mode, enable_dof, enable_fxaa, **passes)
+        return self._fx_call(self._lib.shs_canvas_multi_pass_frame, d,
+                             [_host_c(color, np.uint8), _host_c(depth, np.float32), _host_c(velocity, np.float32)], color, dst,
+                             None, H, W)
+
+    # hello_glowing_star.cpp:62-73: the star's blur and DoF constants
+    GLOW_DEFAULTS = {"velocity_blur": dict(samples=8, strength=1.5), "dof": dict(iterations=3, range_=22.0, max_blur=0.80)}
+
+    def glow_frame_desc(self, W, H, enable_dof=True, enable_bloom=True, enable_flare=True, bloom_iterations=10, **passes):
+        d = _abi.CanvasGlowFrameDescC()
+        d.width, d.height, d.bloom_iterations = int(W), int(H), int(bloom_iterations)
+        d.enable_dof, d.enable_bloom, d.enable_flare = int(bool(enable_dof)), int(bool(enable_bloom)), int(bool(enable_flare))
+        unknown = set(passes) - {"velocity_blur", "dof", "spec_bright", "lens_flare"}
+        if unknown:
+            raise TypeError(f"canvas_glow_frame: unknown passes {sorted(unknown)}")
+        for kind in ("velocity_blur", "dof", "spec_bright", "lens_flare"):
+            self.fx_desc(kind, W, H, dict(self.GLOW_DEFAULTS.get(kind, {}), **(passes.get(kind) or {})), into=getattr(d, kind))
+        return d
+
+    def canvas_glow_frame(self, color, depth, velocity, spec01, enable_dof=True, enable_bloom=True, enable_flare=True,
+                          bloom_iterations=10, dst=None, **passes):
+        """hello_glowing_star.cpp:1233-1310 in one call: velocity blur, DoF, bright pass over spec01 (float32 [H, W]),
+        bloom_iterations x (horizontal, vertical) Gaussian, flare, two additive composites.  passes: velocity_blur=,
+        dof=, spec_bright=, lens_flare= dicts over GLOW_DEFAULTS and FX_DEFAULTS."""
+        H, W = color.shape[:2]
+        d = self.glow_frame_desc(W, H, enable_dof, enable_bloom, enable_flare, bloom_iterations, **passes)
+        return self._fx_call(self._lib.shs_canvas_glow_frame, d,
+                             [_host_c(color, np.uint8), _host_c(depth, np.float32), _host_c(velocity, np.float32),
+                              _host_c(spec01, np.float32)], color, dst, None, H, W)
+
     # -- Canvas render-target raster (hello_shadow_mapping.cpp PASS0 / PASS1) ---------------------
     def _rt_draw_array(self, draws):
         arr = (_abi.RtDrawC * max(len(draws), 1))()

@@ -225,6 +225,55 @@ class CanvasLightShaftsDescC(ctypes.Structure):
 
 
 CANVAS_LIGHT_SHAFTS_MAX_STEPS = 4096
+CANVAS_MAX_OUTLINE_RADIUS = 4
+CANVAS_MAX_FLARE_GHOSTS = 8
+CANVAS_BLUR_VELOCITY_FIRST, CANVAS_BLUR_COMBINED_FIRST, CANVAS_BLUR_COMBINED_LATE = 0, 1, 2
+
+
+class CanvasVelocityBlurDescC(ctypes.Structure):
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("samples", ctypes.c_int32), ("strength", ctypes.c_float)]
+
+
+class CanvasFogDescC(ctypes.Structure):
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("fog_color", ctypes.c_uint8 * 4),
+                ("fog_start", ctypes.c_float), ("fog_end", ctypes.c_float), ("fog_power", ctypes.c_float)]
+
+
+class CanvasOutlineDescC(ctypes.Structure):
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("radius", ctypes.c_int32),
+                ("threshold", ctypes.c_float), ("strength", ctypes.c_float)]
+
+
+class CanvasFxaaDescC(ctypes.Structure):
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("reduce_min", ctypes.c_float),
+                ("reduce_mul", ctypes.c_float), ("span_max", ctypes.c_float)]
+
+
+class CanvasSpecBrightDescC(ctypes.Structure):
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("threshold", ctypes.c_float),
+                ("intensity", ctypes.c_float)]
+
+
+class CanvasLensFlareDescC(ctypes.Structure):
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("intensity", ctypes.c_float),
+                ("halo_intensity", ctypes.c_float), ("chroma_shift_px", ctypes.c_float), ("n_ghosts", ctypes.c_int32),
+                ("ghost_scales", ctypes.c_float * CANVAS_MAX_FLARE_GHOSTS)]
+
+
+class CanvasMultiPassFrameDescC(ctypes.Structure):
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("blur_mode", ctypes.c_int32),
+                ("enable_dof", ctypes.c_int32), ("enable_fxaa", ctypes.c_int32),
+                ("velocity_blur", CanvasVelocityBlurDescC), ("motion_blur", CanvasMotionBlurDescC), ("dof", CanvasDofDescC),
+                ("fog", CanvasFogDescC), ("outline", CanvasOutlineDescC), ("fxaa", CanvasFxaaDescC)]
+
+
+class CanvasGlowFrameDescC(ctypes.Structure):
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("enable_dof", ctypes.c_int32),
+                ("enable_bloom", ctypes.c_int32), ("enable_flare", ctypes.c_int32), ("bloom_iterations", ctypes.c_int32),
+                ("velocity_blur", CanvasVelocityBlurDescC), ("dof", CanvasDofDescC), ("spec_bright", CanvasSpecBrightDescC),
+                ("lens_flare", CanvasLensFlareDescC)]
+
+
 RT_USE_SHADOW, RT_PCF, RT_PREQUANT = 1, 2, 4
 
 
@@ -404,6 +453,16 @@ SIGNATURES = [
     ("shs_canvas_gaussian_blur", ctypes.c_int, [_P, ctypes.c_int32, ctypes.c_int32, _P, _P, ctypes.c_int32, ctypes.c_uint32]),
     ("shs_canvas_dof", ctypes.c_int, [_P, ctypes.POINTER(CanvasDofDescC), _P, _P, _P, _F, ctypes.c_uint32]),
     ("shs_canvas_light_shafts", ctypes.c_int, [_P, ctypes.POINTER(CanvasLightShaftsDescC), _P, _P, _P, _P, _P, ctypes.c_uint32]),
+    ("shs_canvas_velocity_blur", ctypes.c_int, [_P, ctypes.POINTER(CanvasVelocityBlurDescC), _P, _P, _P, ctypes.c_uint32]),
+    ("shs_canvas_fog", ctypes.c_int, [_P, ctypes.POINTER(CanvasFogDescC), _P, _P, _P, _P, ctypes.c_uint32]),
+    ("shs_canvas_outline", ctypes.c_int, [_P, ctypes.POINTER(CanvasOutlineDescC), _P, _P, _P, ctypes.c_uint32]),
+    ("shs_canvas_fxaa", ctypes.c_int, [_P, ctypes.POINTER(CanvasFxaaDescC), _P, _P, ctypes.c_uint32]),
+    ("shs_canvas_spec_bright", ctypes.c_int, [_P, ctypes.POINTER(CanvasSpecBrightDescC), _P, _P, ctypes.c_uint32]),
+    ("shs_canvas_additive", ctypes.c_int, [_P, ctypes.c_int32, ctypes.c_int32, _P, _P, ctypes.c_float, _P, ctypes.c_uint32]),
+    ("shs_canvas_lens_flare", ctypes.c_int, [_P, ctypes.POINTER(CanvasLensFlareDescC), _P, _P, _P, ctypes.c_uint32]),
+    ("shs_canvas_multi_pass_frame", ctypes.c_int, [_P, ctypes.POINTER(CanvasMultiPassFrameDescC), _P, _P, _P, _P,
+                                                   ctypes.c_uint32]),
+    ("shs_canvas_glow_frame", ctypes.c_int, [_P, ctypes.POINTER(CanvasGlowFrameDescC), _P, _P, _P, _P, _P, ctypes.c_uint32]),
     ("shs_rt_device_shadow_map", ctypes.c_int, [_P, ctypes.POINTER(_P), ctypes.POINTER(ctypes.c_int32),
                                                 ctypes.POINTER(ctypes.c_int32)]),
     ("shs_rt_render_shadow", ctypes.c_int, [_P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _F,
