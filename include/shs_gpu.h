@@ -1064,7 +1064,10 @@ typedef struct shs_rt_frame {
                                          4: hello_ibl_skybox.cpp's fragment_shader_full :446-524
                                             (shs_rt_render_skybox_ibl),
                                          5: hello_water.cpp's fragment_shader_full :938-994 and
-                                            fragment_shader_water :1000-1097 per draw (shs_rt_render_water) */
+                                            fragment_shader_water :1000-1097 per draw (shs_rt_render_water),
+                                         6: hello_multi_pass.cpp's blinn_phong_fragment_shader :207-237,
+                                         7: hello_glowing_star.cpp's star_fragment_shader :269-308
+                                            (both shs_rt_render_motion) */
 } shs_rt_frame;
 /* The PCSS constants of shading 1 (hello_shadow_mapping_soft.cpp:101-116), kept in the context. */
 typedef struct shs_rt_pcss {
@@ -1093,7 +1096,7 @@ typedef struct shs_rt_stats {
 int shs_rt_render_shadow(shs_ctx *ctx, int32_t w, int32_t h, int32_t ref_tile_w, int32_t ref_tile_h, const float light_vp[16],
                          const shs_rt_draw *casters, int32_t n_casters);
 /* SHS_ERR_INVALID: an unknown mesh or texture id, a non-positive size, unknown flags, a shading other than
- * 0 or 1 (2 goes through shs_rt_render_pbr, 3 through shs_rt_render_pbr_soft, 4 through shs_rt_render_skybox_ibl, 5 through shs_rt_render_water), or SHS_RT_USE_SHADOW without a shadow map rendered before. */
+ * 0 or 1 (2 goes through shs_rt_render_pbr, 3 through shs_rt_render_pbr_soft, 4 through shs_rt_render_skybox_ibl, 5 through shs_rt_render_water, 6 and 7 through shs_rt_render_motion), or SHS_RT_USE_SHADOW without a shadow map rendered before. */
 int shs_rt_render(shs_ctx *ctx, const shs_rt_frame *frame, const shs_rt_draw *draws, int32_t n_draws);
 /* Host copies of the last camera pass (any pointer may be NULL): color W*H*4 bytes, depth W*H floats,
  * velocity W*H*2 floats.  Synchronous. */
@@ -1153,7 +1156,7 @@ int shs_rt_ibl_samples(shs_ctx *ctx, int32_t n, const float *dirs3, const float 
  * (:552-611) and CubeMapSky with sample_face_bilinear (:432-517).  (These are not the library path's ProceduralSky /
  * CubemapSky of shs_lib_set_sky; the legacy ProceduralSky :520-549 is not built: no render-target demo constructs it.)
  * The reference draws the sky first and the triangles over it.  Here, with a sky bound, every camera pass
- * (shs_rt_render, shs_rt_render_pbr, shs_rt_render_pbr_soft, shs_rt_render_skybox_ibl, shs_rt_render_water, whatever the shading) is followed on the context stream by a background pass
+ * (shs_rt_render, shs_rt_render_pbr, shs_rt_render_pbr_soft, shs_rt_render_skybox_ibl, shs_rt_render_water, shs_rt_render_motion, whatever the shading) is followed on the context stream by a background pass
  * that colours each pixel that shows no fragment (shs_rt_resolve_ids: -1) -- also one whose fragment kept its depth
  * but not its colour -- from the direction through the pixel's centre (:769-780; canvas x, y with y up).  Such a
  * pixel's prequant floats are (r, g, b) * 255 before the truncation and 1; depth and velocity stay as the raster
@@ -1229,6 +1232,33 @@ int shs_rt_set_reflection(shs_ctx *ctx, const uint8_t *rgba, int32_t w, int32_t 
  * normal3 3n, foam n.  Synchronous; for tests of the hash chain, which is bit for bit the reference's.
  * SHS_ERR_INVALID: a non-finite time_sec. */
 int shs_rt_water_samples(shs_ctx *ctx, int32_t n, const float *world_pos3, float time_sec, float *normal3, float *foam);
+/* The camera pass of hello_multi_pass.cpp, hello_camera_and_perobject_motion_blur.cpp (shading 6) and
+ * hello_glowing_star.cpp (shading 7): draw_triangle_tile_color_depth_motion (hello_multi_pass.cpp:525-599, the same text
+ * at hello_camera_and_perobject_motion_blur.cpp:542-615) and draw_triangle_color_depth_velocity_spec
+ * (hello_glowing_star.cpp:354-435).  It is not the raster of shs_rt_render: there is no near-plane clip and no w test (a
+ * corner behind the camera projects mirrored), back faces are culled (area <= 0), the world position is interpolated
+ * screen-linearly like every other varying, the velocity clamp's second threshold is 0.0001, and a fragment that wins the
+ * strict depth test always writes its colour.  Shading 6 is blinn_phong_fragment_shader (:207-237: ambient 0.35,
+ * specular 0.5 * pow(., 64)); shading 7 is star_fragment_shader (:269-308: ambient 0.20, spec01 = clampf(3.85 *
+ * pow(., 256), 0, 1), (ambient + diffuse) * (colour * 0.85) + spec01 * (1, 0.90, 0.55)), which also fills the spec plane
+ * below.  Read of the frame: width, height, ref_tile_w/h (80 x 80 in the two blur demos; the star's single job is the
+ * whole frame: pass width, height), clear_color, view, light_dir_world, camera_pos, max_velocity_px (40, 22 and 30 in the
+ * three demos), flags, shading; of a draw: mesh_id, model, mvp, prev_mvp, base_color.  light_vp and bias_* are not read.
+ * With SHS_RT_PREQUANT the plane's fourth float is 1 for shading 6 and spec01 for shading 7.  A pixel's id is 2 * triangle
+ * (one record per triangle, fan index 0); shs_rt_stats: polys3 = polys4 = 0, sub_tris counts the triangles for which
+ * area <= 0 is false.  shs_rt_resolve*, shs_rt_device_targets and shs_rt_get_stats serve this pass like any other camera
+ * pass, and with a sky bound the background pass follows it as after every camera pass (the three demos bind none).
+ * SHS_ERR_INVALID, with nothing enqueued: another shading, a non-positive size or tile, unknown flags, SHS_RT_USE_SHADOW
+ * or SHS_RT_PCF (these demos have no shadow map), a non-zero albedo_tex (the shaders read the base colour only), an
+ * unknown mesh id, a non-finite or negative max_velocity_px. */
+int shs_rt_render_motion(shs_ctx *ctx, const shs_rt_frame *frame, const shs_rt_draw *draws, int32_t n_draws);
+/* RT_ColorDepthVelocitySpec::spec (hello_glowing_star.cpp:314-341) of the last camera pass, if it was a shading-7 frame:
+ * W*H floats in canvas rows, spec01 where a fragment is shown and 0 elsewhere.  shs_rt_resolve_spec copies it to the host
+ * (synchronous); shs_rt_device_spec returns the device plane, final in the context stream's order, for
+ * shs_canvas_glow_frame with SHS_CANVAS_DEVICE.  The plane is allocated by the first shading-7 frame of a size.
+ * SHS_ERR_INVALID after any other camera pass. */
+int shs_rt_resolve_spec(shs_ctx *ctx, float *spec);
+int shs_rt_device_spec(shs_ctx *ctx, void **spec_dev);
 /* ortho_lh_zo (hello_shadow_mapping.cpp:128-140): LH, z in [0, 1]. */
 int shs_ortho_lh_zo(float left, float right, float bottom, float top, float znear, float zfar, float out16[16]);
 

@@ -819,6 +819,16 @@ public:
                                        static_cast<const float *>(vel), static_cast<uint8_t *>(frame), SHS_CANVAS_DEVICE));
     }
 
+    // the star's chain over the last shs_rt_render_motion's planes (shading 7: the spec plane comes with them)
+    void glow(const shs_canvas_glow_frame_desc &d, void *frame) {
+        void *color = nullptr, *depth = nullptr, *vel = nullptr, *spec = nullptr;
+        ok(shs_rt_device_targets(dev_->ctx, &color, &depth, &vel));
+        ok(shs_rt_device_spec(dev_->ctx, &spec));
+        ok(shs_canvas_glow_frame(dev_->ctx, &d, static_cast<const uint8_t *>(color), static_cast<const float *>(depth),
+                                 static_cast<const float *>(vel), static_cast<const float *>(spec), static_cast<uint8_t *>(frame),
+                                 SHS_CANVAS_DEVICE));
+    }
+
     // the demo's own targets on the host (RT_ColorDepthMotion: color, depth, motion) into the canvas it presents
     template <class RtT>
     void multi_pass_host(const shs_canvas_multi_pass_frame_desc &d, RtT &rt, shs::Canvas &fxaa_out) {
@@ -841,6 +851,77 @@ public:
 
 private:
     Device *dev_;
+};
+
+// -----------------------------------------------------------------------------------------------------
+// Seam 1c, the raster of those three demos -- RendererSystem::process of hello_multi_pass.cpp,
+// hello_camera_and_perobject_motion_blur.cpp and hello_glowing_star.cpp.
+//
+// Their tile jobs over draw_triangle_tile_color_depth_motion (hello_multi_pass.cpp:525-599) / the star's single call of
+// draw_triangle_color_depth_velocity_spec (hello_glowing_star.cpp:354-435) become one shs_rt_render_motion; the whole
+// frame is then
+//   raster.process(dt);                       // colour, depth, velocity (and spec) stay on the device
+//   chain.multi_pass(desc, frame_dev);        // hello_multi_pass.cpp; with use_combined_blur(desc, ...) the other blur demo
+//   chain.glow(glow_desc, frame_dev);         // hello_glowing_star.cpp
+// and one copy of frame_dev into the canvas the demo presents.  star: shading 7 and a single job covering the frame;
+// otherwise shading 6 and tile jobs of `tile`.  max_velocity_px: MB_MAX_PIXELS, 40 / 22 / 30 in the three demos.
+// Objects are RenderTargetSystemGPU's (mesh_id, model, prev_model, base_color); a texture is rejected.  Uncompiled,
+// like the other seams.
+// -----------------------------------------------------------------------------------------------------
+template <class SceneT>
+class MotionRasterGPU : public shs::AbstractSystem {
+public:
+    MotionRasterGPU(SceneT *scene, Device *dev, bool star, float max_velocity_px, int tile = 80)
+        : scene_(scene), dev_(dev), star_(star), max_px_(max_velocity_px), tile_(tile) {}
+
+    std::vector<typename RenderTargetSystemGPU<SceneT>::Object> objects;     // model / prev_model per frame
+
+    void process(float) override {
+        shs::Canvas &canvas = *scene_->canvas;
+        const int W = canvas.get_width(), H = canvas.get_height();
+        const shs::Camera3D &cam = *scene_->viewer->camera;
+        const glm::mat4 view = cam.view_matrix, proj = cam.projection_matrix;
+        std::vector<shs_rt_draw> draws(objects.size());
+        for (size_t i = 0; i < objects.size(); ++i) {
+            const auto &o = objects[i];
+            shs_rt_draw &d = draws[i];
+            d.mesh_id = o.mesh_id;
+            d.albedo_tex = 0;
+            const glm::mat4 mvp = proj * view * o.model, prev_mvp = prev_proj_ * prev_view_ * o.prev_model;
+            std::memcpy(d.model, glm::value_ptr(o.model), 64);
+            std::memcpy(d.mvp, glm::value_ptr(mvp), 64);
+            std::memcpy(d.prev_mvp, glm::value_ptr(prev_mvp), 64);
+            d.base_color[0] = o.base_color.r; d.base_color[1] = o.base_color.g; d.base_color[2] = o.base_color.b; d.base_color[3] = 255;
+        }
+        shs_rt_frame f{};
+        f.width = W; f.height = H;
+        f.ref_tile_w = star_ ? W : tile_;
+        f.ref_tile_h = star_ ? H : tile_;
+        std::memcpy(f.clear_color, clear_color, 4);
+        std::memcpy(f.view, glm::value_ptr(view), 64);
+        std::memcpy(f.light_dir_world, glm::value_ptr(light_dir_world), 12);
+        std::memcpy(f.camera_pos, glm::value_ptr(scene_->viewer->position), 12);
+        f.max_velocity_px = max_px_;
+        f.shading = star_ ? 7 : 6;
+        ok(shs_rt_render_motion(dev_->ctx, &f, draws.data(), (int32_t)draws.size()));
+        prev_view_ = view;
+        prev_proj_ = proj;
+    }
+
+    void ok(int rc) const {
+        if (rc != SHS_OK) throw std::runtime_error(shs_last_error(dev_->ctx));
+    }
+
+    glm::vec3 light_dir_world{-1.0f, -0.4f, 1.0f};   // (the shaders normalise it)
+    uint8_t clear_color[4] = {20, 20, 25, 255};
+
+private:
+    SceneT *scene_;
+    Device *dev_;
+    bool star_;
+    float max_px_;
+    int tile_;
+    glm::mat4 prev_view_{1.0f}, prev_proj_{1.0f};
 };
 
 // =====================================================================================================

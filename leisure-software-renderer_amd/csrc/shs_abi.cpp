@@ -102,7 +102,7 @@ int shs_destroy(shs_ctx *ctx) {
     release(ctx->rt_depth); release(ctx->rt_vel); release(ctx->rt_shadow); release(ctx->rt_pq); release(ctx->rt_ids);
     release(ctx->rt_rot); release(ctx->rt_ps_rot); release(ctx->rt_ps_map); release(ctx->rt_ps_io);
     release(ctx->rt_ibl); release(ctx->rt_srgb_lut); release(ctx->rt_is_io); release(ctx->rt_sky_io);
-    release(ctx->rt_refl); release(ctx->rt_water_io);
+    release(ctx->rt_refl); release(ctx->rt_water_io); release(ctx->rt_spec);
     for (int k = 0; k < 2; ++k) {
         if (ctx->rt_pin[k]) (void)hipHostFree(ctx->rt_pin[k]);
         if (ctx->rt_pin_ev[k]) (void)hipEventDestroy(ctx->rt_pin_ev[k]);

@@ -19,6 +19,10 @@
 // :938-994 and fragment_shader_water :1000-1097 per draw), shs_rt_keep_reflection / shs_rt_set_reflection (u.reflection_color)
 // and shs_rt_water_samples (water_flow_normal_and_foam :862-930 alone); the host does what depends on the frame's time and
 // the light direction alone (water_model).
+// and of hello_multi_pass.cpp, hello_camera_and_perobject_motion_blur.cpp and hello_glowing_star.cpp: shs_rt_render_motion
+// (their one unclipped raster, multi :525-599 / star :354-435, behind blinn_phong_fragment_shader multi :207-237 or
+// star_fragment_shader star :269-308), shs_rt_resolve_spec / shs_rt_device_spec (RT_ColorDepthVelocitySpec::spec); their
+// vertex shaders (multi :191-205, star :254-267) form the same two products and the same normal matrix.
 // The host forms the matrix products the shaders form first -- u.view * u.model (vertex_shader_full :616),
 // u.light_vp * u.model (shadow_vertex_shader :764) -- and the normal matrix with the GLM restatement in
 // shs_glm.hpp.  Both passes are enqueued on the context stream; the shadow map, the planes and the records
@@ -293,7 +297,8 @@ int upload_and_launch(shs_ctx *ctx, shs_dev::RtParams &p, bool shadow_pass, int 
 
 // PASS1 of the six demos: x empty for shading 0 / 1 (shs_rt_render), x.pbr for shading 2 (shs_rt_render_pbr) and 3
 // (shs_rt_render_pbr_soft), x.ibl for shading 4 (shs_rt_render_skybox_ibl), x.water_draws and x.water for shading 5
-// (shs_rt_render_water).  Nothing of the context changes before the last rejection.
+// (shs_rt_render_water); and the one camera pass of the three unclipped demos, x empty, for shadings 6 and 7
+// (shs_rt_render_motion).  Nothing of the context changes before the last rejection.
 int render_camera(shs_ctx *ctx, const shs_rt_frame *f, const shs_rt_draw *draws, int32_t n_draws, PassExtras x) {
     if (!size_ok(ctx, f->width, f->height, f->ref_tile_w, f->ref_tile_h)) return SHS_ERR_INVALID;
     if (f->flags & ~(SHS_RT_USE_SHADOW | SHS_RT_PCF | SHS_RT_PREQUANT)) {
@@ -310,7 +315,7 @@ int render_camera(shs_ctx *ctx, const shs_rt_frame *f, const shs_rt_draw *draws,
     const size_t npx = (size_t)f->width * f->height;
     const bool pq = (f->flags & SHS_RT_PREQUANT) != 0;
     if (ensure(ctx, ctx->rt_color, npx) || ensure(ctx, ctx->rt_depth, npx) || ensure(ctx, ctx->rt_vel, 2 * npx) ||
-        ensure(ctx, ctx->rt_ids, npx) || (pq && ensure(ctx, ctx->rt_pq, npx)))
+        ensure(ctx, ctx->rt_ids, npx) || (pq && ensure(ctx, ctx->rt_pq, npx)) || (f->shading == 7 && ensure(ctx, ctx->rt_spec, npx)))
         return SHS_ERR_HIP;
     shs_dev::RtParams p{};
     p.W = f->width; p.H = f->height;
@@ -339,6 +344,7 @@ int render_camera(shs_ctx *ctx, const shs_rt_frame *f, const shs_rt_draw *draws,
     p.velocity = reinterpret_cast<float2 *>(ctx->rt_vel.p);
     p.prequant = pq ? ctx->rt_pq.p : nullptr;
     p.ids = ctx->rt_ids.p;
+    p.spec = f->shading == 7 ? ctx->rt_spec.p : nullptr;
     if (f->shading == 1 || f->shading == 3) {
         const int rr = ensure_rotations(ctx, f->width, f->height);
         if (rr) return rr;
@@ -405,6 +411,7 @@ int render_camera(shs_ctx *ctx, const shs_rt_frame *f, const shs_rt_draw *draws,
     ctx->rt_n_tris = n_tris;
     ctx->rt_have_frame = true;
     ctx->rt_have_pq = pq;
+    ctx->rt_have_spec = f->shading == 7;
     return SHS_OK;
 }
 
@@ -512,6 +519,44 @@ int shs_rt_render_water(shs_ctx *ctx, const shs_rt_frame *f, const shs_rt_draw *
         return SHS_ERR_INVALID;
     }
     return render_camera(ctx, f, draws, n_draws, PassExtras{nullptr, nullptr, water_draws, water});
+}
+
+int shs_rt_render_motion(shs_ctx *ctx, const shs_rt_frame *f, const shs_rt_draw *draws, int32_t n_draws) {
+    if (!ctx || !f || n_draws < 0 || (n_draws > 0 && !draws)) return SHS_ERR_INVALID;
+    if (f->shading != 6 && f->shading != 7) {
+        ctx->err = "shs_rt_render_motion: shading " + std::to_string(f->shading) +
+                   " (6: hello_multi_pass.cpp's blinn_phong_fragment_shader, 7: hello_glowing_star.cpp's star_fragment_shader)";
+        return SHS_ERR_INVALID;
+    }
+    if (f->flags & (SHS_RT_USE_SHADOW | SHS_RT_PCF)) {
+        ctx->err = "shs_rt_render_motion: SHS_RT_USE_SHADOW / SHS_RT_PCF (these demos have no shadow map)";
+        return SHS_ERR_INVALID;
+    }
+    if (!(std::isfinite(f->max_velocity_px) && f->max_velocity_px >= 0.0f)) {
+        ctx->err = "shs_rt_render_motion: max_velocity_px is not finite or is negative";
+        return SHS_ERR_INVALID;
+    }
+    for (int32_t i = 0; i < n_draws; ++i) {
+        if (draws[i].albedo_tex != 0) {   // (the shaders read u.color only)
+            ctx->err = "shs_rt_render_motion: a draw with albedo_tex (shadings 6 and 7 have no texture)";
+            return SHS_ERR_INVALID;
+        }
+    }
+    return render_camera(ctx, f, draws, n_draws, PassExtras{});
+}
+
+int shs_rt_resolve_spec(shs_ctx *ctx, float *spec) {
+    if (!ctx || !spec || !ctx->rt_have_frame || !ctx->rt_have_spec) return SHS_ERR_INVALID;
+    if (set_dev(ctx)) return SHS_ERR_HIP;
+    HIP_TRY(ctx, hipMemcpyAsync(spec, ctx->rt_spec.p, (size_t)ctx->rt_w * ctx->rt_h * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return SHS_OK;
+}
+
+int shs_rt_device_spec(shs_ctx *ctx, void **spec_dev) {
+    if (!ctx || !ctx->rt_have_frame || !ctx->rt_have_spec) return SHS_ERR_INVALID;
+    if (spec_dev) *spec_dev = ctx->rt_spec.p;
+    return SHS_OK;
 }
 
 int shs_rt_keep_reflection(shs_ctx *ctx) {

@@ -34,6 +34,17 @@
 //          reflection canvas, fog).  Both round to the byte where the other shadings truncate.  Their shadow lookup
 //          (water :716-751) is not the hard demo's: shadow_factor_water.  k_rt_raster<false, 7> (rt_variant(5, .)),
 //          launched by shs_rt_render_water, is shade_pixel_water.
+// and for hello_multi_pass.cpp ("multi :line"; hello_camera_and_perobject_motion_blur.cpp carries the same text at
+// :542-615 and :224-254) and hello_glowing_star.cpp ("star :line"), whose one raster is not the hard demo's:
+//   draw_triangle_tile_color_depth_motion (multi :525-599) / draw_triangle_color_depth_velocity_spec (star :354-435): no
+//          near-plane clip and no w test, back faces culled (area <= 0), every varying screen-linear, the velocity clamp's
+//          second threshold 0.0001, and a fragment that wins the depth test always writes its colour.
+//          k_rt_setup_motion is the setup without the clip; the raster's candidate walk drops the invw_sum rule.
+//   shading 6  blinn_phong_fragment_shader (multi :207-237): k_rt_raster<false, 8>, shade_pixel_motion<false>.
+//   shading 7  star_fragment_shader (star :269-308), which returns spec01 beside the colour: k_rt_raster<false, 9>,
+//          shade_pixel_motion<true>, the one instantiation that stores a fourth plane (RtParams::spec).  The star's
+//          single job is the whole frame (its host passes ref_tile = the frame's size).
+//          Both launched by shs_rt_render_motion.
 //   the background  skybox_background_pass (pbr :733-799; the same routine in hello_pbr_light_shafts.cpp and
 //          hello_ibl_skybox.cpp) over the legacy AnalyticSky / CubeMapSky of hello-shs-renderer/shs_renderer.hpp:
 //          k_rt_sky<MODEL, ENCODE>, a pass of its own after k_rt_raster when a sky is bound (shs_rt_set_sky), which
@@ -152,7 +163,10 @@ __device__ double2 danger_margin(const RtRec &r) {
 }
 
 // The pixel-independent part of barycentric_coordinate (shs_renderer.hpp:802-815), the area test and the
-// bbox over the corners that are not NaN.  false: the sub-triangle draws nothing.
+// bbox over the corners that are not NaN.  false: the sub-triangle draws nothing.  CULL_BACK: the area rule of the
+// unclipped raster (multi :560, star :392), which draws positive areas only and does not reject a NaN; every
+// barycentric of such a triangle is NaN, its depth is NaN and the pixel loop's depth test fails.
+template <bool CULL_BACK = false>
 __device__ bool rec_geometry(RtRec &r, const float (&sx)[3], const float (&sy)[3], int W, int H) {
     r.ax = sx[0]; r.ay = sy[0];
     r.v0x = sx[1] - sx[0]; r.v0y = sy[1] - sy[0];
@@ -182,7 +196,11 @@ __device__ bool rec_geometry(RtRec &r, const float (&sx)[3], const float (&sy)[3
     const int cy1 = unbounded ? H - 1 : floor_clamped((float)((double)mxy + exy), -1, H - 1);
     r.gbx = pack16(cx0, cx1);
     r.gby = pack16(cy0, cy1);
-    if (fabsf(area) < 1e-8f) return false;
+    if constexpr (CULL_BACK) {
+        if (area <= 0.0f) return false;
+    } else {
+        if (fabsf(area) < 1e-8f) return false;
+    }
     r.flags = RT_VALID | (area < 0.0f ? RT_NEG_AREA : 0u);
     // |denom| < 1e-5 (a double comparison): every barycentric is -1, nothing passes -- not staged
     if ((double)fabsf(r.denom) < 1e-5) r.flags = 0u;
@@ -194,6 +212,19 @@ __device__ __forceinline__ void store_rec(RtRec *dst, const RtRec &r) {
     float4 *d = reinterpret_cast<float4 *>(dst);
 #pragma unroll
     for (int k = 0; k < 6; ++k) d[k] = s[k];
+}
+
+// The corners' varyings of a camera-pass sub-triangle as the shaded pixels read them
+__device__ __forceinline__ void store_vary(RtVary &v, const Vy *const (&tv)[3]) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { v.pos[4 * i + k] = tv[i]->p[k]; v.prev[4 * i + k] = tv[i]->q[k]; }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { v.world[3 * i + k] = tv[i]->wp[k]; v.nrm[3 * i + k] = tv[i]->n[k]; }
+        v.uv[2 * i] = tv[i]->uv[0];
+        v.uv[2 * i + 1] = tv[i]->uv[1];
+    }
 }
 
 // One camera-pass sub-triangle {a, b, c} (:931-959 up to the pixel loops): its record and varyings.  Returns
@@ -221,16 +252,33 @@ __device__ bool emit_camera(const RtParams &p, int32_t id, int32_t draw, const V
         r.iw0 = (fabsf(a.p[3]) < 1e-6f) ? 0.0f : 1.0f / a.p[3];
         r.iw1 = (fabsf(b.p[3]) < 1e-6f) ? 0.0f : 1.0f / b.p[3];
         r.iw2 = (fabsf(c.p[3]) < 1e-6f) ? 0.0f : 1.0f / c.p[3];
-        RtVary &v = p.vary[id];
+        store_vary(p.vary[id], tv);
+    }
+    store_rec(&p.recs[id], r);
+    return ok;
+}
+
+// The unclipped raster's triangle (multi :536-560; star :364-392): the corners in their own order, straight through
+// Canvas::clip_to_screen with no w test (a corner behind the camera projects mirrored; w = 0 gives Inf or NaN screen
+// coordinates, which the bbox fold and the barycentrics take as the reference's do), positive areas only.
+__device__ bool emit_motion(const RtParams &p, int32_t id, int32_t draw, const Vy (&in)[3]) {
+    RtRec r{};
+    r.draw = draw;
+    float sx[3], sy[3];
 #pragma unroll
-        for (int i = 0; i < 3; ++i) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) { v.pos[4 * i + k] = tv[i]->p[k]; v.prev[4 * i + k] = tv[i]->q[k]; }
-#pragma unroll
-            for (int k = 0; k < 3; ++k) { v.world[3 * i + k] = tv[i]->wp[k]; v.nrm[3 * i + k] = tv[i]->n[k]; }
-            v.uv[2 * i] = tv[i]->uv[0];
-            v.uv[2 * i + 1] = tv[i]->uv[1];
-        }
+    for (int i = 0; i < 3; ++i) {
+        const float w = in[i].p[3];
+        const float nx = in[i].p[0] / w, ny = in[i].p[1] / w;
+        sx[i] = (nx + 1.0f) * 0.5f * (float)(p.W - 1);
+        sy[i] = (1.0f - ny) * 0.5f * (float)(p.H - 1);
+    }
+    const bool ok = rec_geometry<true>(r, sx, sy, p.W, p.H);
+    if (!ok) {
+        r.flags = 0u;
+    } else {
+        r.z0 = in[0].vz; r.z1 = in[1].vz; r.z2 = in[2].vz;
+        const Vy *tv[3] = {&in[0], &in[1], &in[2]};
+        store_vary(p.vary[id], tv);
     }
     store_rec(&p.recs[id], r);
     return ok;
@@ -248,6 +296,27 @@ __device__ __forceinline__ int find_draw(const RtParams &p, int t) {
     int d = 0;
     while (d + 1 < p.n_draws && t >= p.draws[d + 1].base) ++d;
     return d;
+}
+
+// vertex_shader_full :602-620 at the three corners of the draw's triangle `local`; blinn_phong_vertex_shader_mb
+// (multi :191-205) and star_vertex_shader (star :254-267) are the same operations with uv = vec2(0)
+__device__ __forceinline__ void vertex_shader_full(const RtDrawGPU &dr, int local, Vy (&in)[3]) {
+    const float *pos = dr.pos + 9 * (size_t)local;
+    const float *nrm = dr.nrm + 9 * (size_t)local;
+    const float *uv = dr.uv ? dr.uv + 6 * (size_t)local : nullptr;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const float x = pos[3 * i], y = pos[3 * i + 1], z = pos[3 * i + 2];
+        m4p(dr.mvp, x, y, z, in[i].p[0], in[i].p[1], in[i].p[2], in[i].p[3]);
+        m4p(dr.prev_mvp, x, y, z, in[i].q[0], in[i].q[1], in[i].q[2], in[i].q[3]);
+        float ww, vx, vy, vw;
+        m4p(dr.model, x, y, z, in[i].wp[0], in[i].wp[1], in[i].wp[2], ww);
+        const f3 n = normalize3(m3v(dr.n3, f3{nrm[3 * i], nrm[3 * i + 1], nrm[3 * i + 2]}));
+        in[i].n[0] = n.x; in[i].n[1] = n.y; in[i].n[2] = n.z;
+        in[i].uv[0] = uv ? uv[2 * i] : 0.0f;
+        in[i].uv[1] = uv ? uv[2 * i + 1] : 0.0f;
+        m4p(dr.zm, x, y, z, vx, vy, in[i].vz, vw);
+    }
 }
 
 template <bool SHADOW>
@@ -280,22 +349,8 @@ __global__ __launch_bounds__(256) void k_rt_setup(const RtParams p) {
         store_rec(&p.recs[t], r);
         return;
     }
-    const float *nrm = dr.nrm + 9 * (size_t)local;
-    const float *uv = dr.uv ? dr.uv + 6 * (size_t)local : nullptr;
     Vy in[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {   // vertex_shader_full :602-620
-        const float x = pos[3 * i], y = pos[3 * i + 1], z = pos[3 * i + 2];
-        m4p(dr.mvp, x, y, z, in[i].p[0], in[i].p[1], in[i].p[2], in[i].p[3]);
-        m4p(dr.prev_mvp, x, y, z, in[i].q[0], in[i].q[1], in[i].q[2], in[i].q[3]);
-        float ww, vx, vy, vw;
-        m4p(dr.model, x, y, z, in[i].wp[0], in[i].wp[1], in[i].wp[2], ww);
-        const f3 n = normalize3(m3v(dr.n3, f3{nrm[3 * i], nrm[3 * i + 1], nrm[3 * i + 2]}));
-        in[i].n[0] = n.x; in[i].n[1] = n.y; in[i].n[2] = n.z;
-        in[i].uv[0] = uv ? uv[2 * i] : 0.0f;
-        in[i].uv[1] = uv ? uv[2 * i + 1] : 0.0f;
-        m4p(dr.zm, x, y, z, vx, vy, in[i].vz, vw);
-    }
+    vertex_shader_full(dr, local, in);
     // clip_poly_near_z :877-913: at most four vertices leave a triangle
     Vy poly[4];
     int n = 0;
@@ -329,6 +384,22 @@ __global__ __launch_bounds__(256) void k_rt_setup(const RtParams p) {
     wave_count(&p.stats[3], r1);
 }
 
+// The setup of shadings 6 and 7: one lane per input triangle, the vertex shader, no clip.  One record per triangle at
+// id 2 t, so that a pixel's id reads as for every other camera pass; slot 2 t + 1 is empty.  Counter 3 is the number of
+// triangles the area rule keeps; there are no clipped polygons to count.
+__global__ __launch_bounds__(256) void k_rt_setup_motion(const RtParams p) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= p.n_tris) return;
+    const int d = find_draw(p, t);
+    const RtDrawGPU &dr = p.draws[d];
+    Vy in[3];
+    vertex_shader_full(dr, t - dr.base, in);
+    const bool ok = emit_motion(p, 2 * t, d, in);
+    RtRec none{};
+    store_rec(&p.recs[2 * t + 1], none);
+    wave_count(&p.stats[3], ok);
+}
+
 // ---- k_rt_raster -----------------------------------------------------------------------------------
 
 // The reference's visited interval of one axis inside the job [tmin, tmax] (:806-815, :822): the float bbox
@@ -355,9 +426,11 @@ __device__ __forceinline__ bool axis_meets(float mn, float mx, int g0, int g1, i
 
 // The camera pass's instantiation k_rt_raster<false, rt_variant(shading, sky model)> of shs_rt_frame::shading: shadings 0
 // to 3 are their own number, shading 4 is three instantiations, one per sky model its shader samples (RT_SKY_*: 4 to 6),
-// and shading 5 follows them.  The kernel's ladder and the launcher both go through this one mapping.
-constexpr int RT_VARIANTS = 8;
-constexpr int rt_variant(int shading, int sky_model) { return shading == 5 ? 7 : shading == 4 ? 4 + sky_model : shading; }
+// and shadings 5 to 7 follow them.  The kernel's ladder and the launcher both go through this one mapping.
+constexpr int RT_VARIANTS = 10;
+constexpr int rt_variant(int shading, int sky_model) { return shading >= 5 ? shading + 2 : shading == 4 ? 4 + sky_model : shading; }
+// Shadings 6 and 7 sit behind the unclipped raster: screen-linear varyings, so no fragment loses its colour to invw_sum
+constexpr bool rt_unclipped(int variant) { return variant >= rt_variant(6, 0); }
 
 // VARIANT: the fragment shader, a compile-time choice (the shadow pass ignores it)
 template <bool SHADOW, int VARIANT = 0>
@@ -435,9 +508,11 @@ __global__ __launch_bounds__(256) void k_rt_raster(const RtParams p) {
                 } else {
                     if (!(z < best)) continue;
                     best = z;
-                    const float4 a5 = s_rec[c * 6 + 5];   // (iw0, iw1, iw2, draw)
-                    const float invw_sum = (u * a5.x + v * a5.y) + w * a5.z;
-                    if (invw_sum <= 1e-8f) continue;
+                    if constexpr (!rt_unclipped(VARIANT)) {
+                        const float4 a5 = s_rec[c * 6 + 5];   // (iw0, iw1, iw2, draw)
+                        const float invw_sum = (u * a5.x + v * a5.y) + w * a5.z;
+                        if (invw_sum <= 1e-8f) continue;
+                    }
                     sid = s_id[c];
                     su = u; sv = v; sw = w;
                 }
@@ -453,7 +528,12 @@ __global__ __launch_bounds__(256) void k_rt_raster(const RtParams p) {
     uint32_t rgba = p.clear_rgba;
     float2 vel = make_float2(0.0f, 0.0f);
     float4 pq = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if constexpr (VARIANT == rt_variant(1, 0)) {
+    float spec01 = 0.0f;   // (shading 7 alone stores it)
+    if constexpr (VARIANT == rt_variant(6, 0)) {
+        if (sid >= 0) shade_pixel_motion<false>(p, sid, su, sv, sw, rgba, vel, pq, spec01);
+    } else if constexpr (VARIANT == rt_variant(7, 0)) {
+        if (sid >= 0) shade_pixel_motion<true>(p, sid, su, sv, sw, rgba, vel, pq, spec01);
+    } else if constexpr (VARIANT == rt_variant(1, 0)) {
         if (sid >= 0) shade_pixel_soft(p, sid, su, sv, sw, px, py, rgba, pq);   // the velocity plane stays zero
     } else if constexpr (VARIANT == rt_variant(2, 0)) {
         if (sid >= 0) shade_pixel_pbr<false>(p, sid, su, sv, sw, px, py, rgba, vel, pq);
@@ -472,6 +552,7 @@ __global__ __launch_bounds__(256) void k_rt_raster(const RtParams p) {
     p.velocity[o] = vel;
     p.ids[o] = sid;
     if (p.prequant) p.prequant[o] = pq;
+    if constexpr (VARIANT == rt_variant(7, 0)) p.spec[o] = spec01;
 }
 
 // shs_rt_pcss_samples: one lane per sample through the device function the raster calls
@@ -608,6 +689,7 @@ hipError_t launch_canvas_rt(const shs_dev::RtParams &p, bool shadow_pass, int sh
     if (p.n_tris > 0) {
         const int grid = (p.n_tris + 255) / 256;
         if (shadow_pass) hipLaunchKernelGGL(k_rt_setup<true>, dim3(grid), dim3(256), 0, s, p);
+        else if (rt_unclipped(rt_variant(shading, sky_model))) hipLaunchKernelGGL(k_rt_setup_motion, dim3(grid), dim3(256), 0, s, p);
         else hipLaunchKernelGGL(k_rt_setup<false>, dim3(grid), dim3(256), 0, s, p);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;

@@ -4,6 +4,8 @@
 // "pbr :line" / "shafts :line" / "ibl :line" / "water :line" citations).
 //   Frag            the shown fragment's record, varyings and draw, and the interpolations of the camera pass
 //                   (:971-1013; soft :961-979; pbr :986-1035; ibl :810-852; water :2060-2211): world(), normal(), uv()
+//   FragLinear      the same for the unclipped raster of hello_multi_pass.cpp ("multi :line"; the same text in
+//                   hello_camera_and_perobject_motion_blur.cpp) and hello_glowing_star.cpp ("star :line"): no 1 / w
 //   frag_velocity   the velocity of the fragment (:1002-1011; pbr :1017-1026; ibl :841-850; the water demo's is the
 //                   hard demo's text)
 //   frag_base01     the base colour in [0, 1]: the draw's, or sample_nearest of its texture
@@ -98,6 +100,28 @@ struct Frag {
     }
 };
 
+// The shown fragment of the unclipped raster (multi :575-581; star :407-413): every varying is interpolated
+// screen-linearly, so the record's 1 / w terms are not read.
+struct FragLinear {
+    const RtVary &y;
+    const RtDrawGPU &dr;
+    float u, v, w;
+
+    __device__ __forceinline__ FragLinear(const RtParams &p, int32_t id, float u_, float v_, float w_)
+        : y(p.vary[id]), dr(p.draws[p.recs[id].draw]), u(u_), v(v_), w(w_) {}
+
+    __device__ __forceinline__ f3 world() const {
+        return {bary3(u, v, w, y.world[0], y.world[3], y.world[6]), bary3(u, v, w, y.world[1], y.world[4], y.world[7]),
+                bary3(u, v, w, y.world[2], y.world[5], y.world[8])};
+    }
+    // normalised by the raster and again by the fragment shader's first line, as Frag::normal
+    __device__ __forceinline__ f3 normal() const {
+        const f3 nsum = {bary3(u, v, w, y.nrm[0], y.nrm[3], y.nrm[6]), bary3(u, v, w, y.nrm[1], y.nrm[4], y.nrm[7]),
+                         bary3(u, v, w, y.nrm[2], y.nrm[5], y.nrm[8])};
+        return normalize3(normalize3(nsum));
+    }
+};
+
 // Canvas::clip_to_screen's x and y of an interpolated clip position
 __device__ __forceinline__ void to_screen(const RtParams &p, float x, float y, float w, float &sx, float &sy) {
     const float nx = x / w, ny = y / w;
@@ -106,8 +130,9 @@ __device__ __forceinline__ void to_screen(const RtParams &p, float x, float y, f
 }
 
 // The velocity of the fragment: position and prev_position interpolated screen-linearly (their z is not read),
-// both to the screen, the difference with y up, clamped to max_velocity in length.
-__device__ __forceinline__ float2 frag_velocity(const RtParams &p, const RtVary &y, float u, float v, float w) {
+// both to the screen, the difference with y up, clamped to max_velocity in length.  min_len: the second threshold of
+// the clamp, 1e-6f in the clipped demos and 0.0001f in the unclipped ones ("multi :589", "star :422").
+__device__ __forceinline__ float2 frag_velocity(const RtParams &p, const RtVary &y, float u, float v, float w, float min_len = 1e-6f) {
     float csx, csy, psx, psy;
     to_screen(p, bary3(u, v, w, y.pos[0], y.pos[4], y.pos[8]), bary3(u, v, w, y.pos[1], y.pos[5], y.pos[9]),
               bary3(u, v, w, y.pos[3], y.pos[7], y.pos[11]), csx, csy);
@@ -115,7 +140,7 @@ __device__ __forceinline__ float2 frag_velocity(const RtParams &p, const RtVary 
               bary3(u, v, w, y.prev[3], y.prev[7], y.prev[11]), psx, psy);
     float vx = csx - psx, vy = -(csy - psy);
     const float len = sqrtf(vx * vx + vy * vy);
-    if (len > p.max_velocity && len > 1e-6f) {
+    if (len > p.max_velocity && len > min_len) {
         const float s = p.max_velocity / len;
         vx *= s;
         vy *= s;

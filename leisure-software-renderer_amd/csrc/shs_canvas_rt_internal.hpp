@@ -7,7 +7,9 @@
 // hello_ibl_skybox.cpp (the hard demo's passes with the sky-lit fragment shader, shading 4 through
 // shs_rt_render_skybox_ibl, which samples the bound sky per pixel), and of hello_water.cpp (the hard demo's passes with
 // two fragment shaders chosen per draw, the atmosphere shader and the water shader over a planar reflection, shading 5
-// through shs_rt_render_water).
+// through shs_rt_render_water), and of hello_multi_pass.cpp, hello_camera_and_perobject_motion_blur.cpp and
+// hello_glowing_star.cpp (one raster without the near-plane clip, screen-linear varyings, back faces culled; shadings 6
+// and 7 through shs_rt_render_motion, the latter with a fourth plane, spec01).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -167,6 +169,8 @@ struct RtParams {
     const RtIblDrawGPU *ibl_draws;   // element i goes with draws[i]
     // shading 5 only (appended likewise): one pointer, the rest rides behind the draw table with the per-call upload
     const RtWaterGPU *water;
+    // shading 7 only (appended likewise): RT_ColorDepthVelocitySpec::spec in canvas rows, 0 where no fragment is shown
+    float *spec;
 };
 
 // sample_cubemap_linear_vec(env_irradiance, dir) and sample_prefiltered_spec_trilinear(spec, dir, lod) for a list
@@ -229,8 +233,10 @@ hipError_t launch_sky_samples(const shs_dev::RtSkySamples &q, int model, hipStre
 // setup (one lane per input triangle) then raster (one workgroup per 32x8 tile) of either pass
 // shading: shs_rt_frame::shading of the camera pass (0: fragment_shader_full, 1: fragment_shader_softshadow,
 // 2: fragment_shader_pbr, 3: hello_pbr_light_shafts.cpp's fragment_shader_pbr, 4: hello_ibl_skybox.cpp's
-// fragment_shader_full, 5: hello_water.cpp's fragment_shader_full / fragment_shader_water per draw); sky_model: u.sky of
-// shading 4 (RT_SKY_*), which chooses among its three instantiations
+// fragment_shader_full, 5: hello_water.cpp's fragment_shader_full / fragment_shader_water per draw, 6: hello_multi_pass.cpp's
+// blinn_phong_fragment_shader, 7: hello_glowing_star.cpp's star_fragment_shader -- 6 and 7 behind the unclipped setup and
+// the screen-linear raster of those demos); sky_model: u.sky of shading 4 (RT_SKY_*), which chooses among its three
+// instantiations
 hipError_t launch_canvas_rt(const shs_dev::RtParams &p, bool shadow_pass, int shading, hipStream_t s, int sky_model = 0);
 hipError_t launch_pcss_samples(const shs_dev::RtPcssSamples &q, hipStream_t s);
 hipError_t launch_ibl_samples(const shs_dev::RtIblSamples &q, hipStream_t s);

@@ -596,5 +596,44 @@ __device__ void shade_pixel_water(const RtParams &p, int32_t id, float u, float 
     pq = make_float4(pr, pg, pb, shadow);
 }
 
+// ---- hello_multi_pass.cpp ("multi :line"; hello_camera_and_perobject_motion_blur.cpp carries the same text) and
+// ---- hello_glowing_star.cpp ("star :line"): the shaders behind the unclipped raster -------------------------------
+
+// The shown fragment of draw_triangle_tile_color_depth_motion (multi :575-595) / draw_triangle_color_depth_velocity_spec
+// (star :407-431): screen-linear varyings, the velocity under the 0.0001 threshold, then blinn_phong_fragment_shader
+// (multi :207-237; STAR false) or star_fragment_shader (star :269-308; STAR true), which also returns spec01.  The
+// demos have no shadow map and no texture.  clampf (star :103-108) passes a NaN on: spec01 and the colour floats are NaN
+// then, and the bytes 0.
+template <bool STAR>
+__device__ void shade_pixel_motion(const RtParams &p, int32_t id, float u, float v, float w, uint32_t &rgba, float2 &vel, float4 &pq,
+                                   float &spec01) {
+    const FragLinear f(p, id, u, v, w);
+    vel = frag_velocity(p, f.y, u, v, w, 0.0001f);
+    const f3 wp = f.world();
+    const f3 N = f.normal();
+    const f3 L = {p.L[0], p.L[1], p.L[2]};
+    const f3 V = normalize3(sub3(f3{p.cam[0], p.cam[1], p.cam[2]}, wp));
+    const float ambient = (STAR ? 0.20f : 0.35f) * 1.0f;
+    const float diffuse = g_max(dot3(N, L), 0.0f) * 1.0f;
+    const f3 H = normalize3(add3(L, V));
+    const float ndoth = g_max(dot3(N, H), 0.0f);
+    const f3 base = {f.dr.colf[0] / 255.0f, f.dr.colf[1] / 255.0f, f.dr.colf[2] / 255.0f};
+    f3 result;
+    if constexpr (STAR) {
+        const float s = 3.85f * pow256(ndoth);
+        spec01 = (s < 0.0f) ? 0.0f : (s > 1.0f ? 1.0f : s);
+        const float lit = ambient + diffuse;
+        // (ambient + diffuse) * (colour * 0.85) + spec01 * (1, 0.90, 0.55)
+        result = {lit * (base.x * 0.85f) + spec01 * 1.0f, lit * (base.y * 0.85f) + spec01 * 0.90f, lit * (base.z * 0.85f) + spec01 * 0.55f};
+    } else {
+        const float specular = (0.5f * pow64(ndoth)) * 1.0f;
+        const float lit = (ambient + diffuse) + specular;
+        result = {lit * base.x, lit * base.y, lit * base.z};
+    }
+    const float pr = g_clamp01(result.x) * 255, pg = g_clamp01(result.y) * 255, pb = g_clamp01(result.z) * 255;
+    rgba = pack_rgba(pr, pg, pb);
+    pq = make_float4(pr, pg, pb, STAR ? spec01 : 1.0f);
+}
+
 }  // namespace
 }  // namespace shs_dev

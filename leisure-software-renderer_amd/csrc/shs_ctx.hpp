@@ -390,6 +390,10 @@ struct shs_ctx {
     int rt_refl_w = 0, rt_refl_h = 0;
     bool rt_have_refl = false;
     DevBuf<float> rt_water_io;
+    // shading 7 (hello_glowing_star.cpp): the spec01 plane in canvas rows, allocated by the first shading-7 frame;
+    // rt_have_spec: the last camera pass wrote it
+    DevBuf<float> rt_spec;
+    bool rt_have_spec = false;
     // the frame chains of shs_abi_canvas_fx.cpp: the demos' intermediate canvases (fx_a, fx_b, fx_c) and, for host
     // buffers, the staged inputs and the frame before it is copied back
     DevBuf<uint32_t> fx_a, fx_b, fx_c, fx_in, fx_out;

@@ -110,6 +110,8 @@ class RtFrame:
                                  # 3: hello_pbr_light_shafts.cpp's fragment_shader_pbr, PBR under PCSS (Context.rt_render_pbr_soft only)
                                  # 4: hello_ibl_skybox.cpp's sky-lit fragment_shader_full (Context.rt_render_skybox_ibl only)
                                  # 5: hello_water.cpp's atmosphere and water shaders, chosen per draw (Context.rt_render_water only)
+                                 # 6: hello_multi_pass.cpp's blinn_phong_fragment_shader, 7: hello_glowing_star.cpp's
+                                 #    star_fragment_shader, both behind the unclipped raster (Context.rt_render_motion only)
 
 
 @dataclass
@@ -1057,6 +1059,26 @@ class Context:
             wc = ctypes.byref(wc)
         self._check(self._lib.shs_rt_render_water(self._h, ctypes.byref(self._rt_frame_c(frame)), arr, flags, wc, len(draws)))
         self._rt_size = (frame.width, frame.height)
+
+    def rt_render_motion(self, frame, draws):
+        """shs_rt_render_motion: the unclipped camera pass of hello_multi_pass.cpp / hello_camera_and_perobject_motion_blur.cpp
+        (frame.shading 6) and hello_glowing_star.cpp (frame.shading 7, which also fills the spec plane), asynchronous."""
+        arr = self._rt_draw_array(draws)
+        self._check(self._lib.shs_rt_render_motion(self._h, ctypes.byref(self._rt_frame_c(frame)), arr, len(draws)))
+        self._rt_size = (frame.width, frame.height)
+
+    def rt_resolve_spec(self):
+        """-> spec01 float32 [H, W] of the last shading-7 frame, canvas rows (0 where no fragment is shown)."""
+        W, H = self._rt_dims()
+        spec = np.empty((H, W), np.float32)
+        self._check(self._lib.shs_rt_resolve_spec(self._h, _ptr(spec)))
+        return spec
+
+    def rt_device_spec(self):
+        """Device pointer of the last shading-7 frame's spec plane (W*H float32)."""
+        a = ctypes.c_void_p()
+        self._check(self._lib.shs_rt_device_spec(self._h, ctypes.byref(a)))
+        return a.value
 
     def rt_keep_reflection(self):
         """shs_rt_keep_reflection: the last camera pass's colour plane becomes the reflection canvas, asynchronous."""

@@ -481,6 +481,9 @@ SIGNATURES = [
                                                 ctypes.POINTER(RtSkyboxIblDrawC), ctypes.c_int32]),
     ("shs_rt_render_water", ctypes.c_int, [_P, ctypes.POINTER(RtFrameC), ctypes.POINTER(RtDrawC), ctypes.POINTER(RtWaterDrawC),
                                            ctypes.POINTER(RtWaterC), ctypes.c_int32]),
+    ("shs_rt_render_motion", ctypes.c_int, [_P, ctypes.POINTER(RtFrameC), ctypes.POINTER(RtDrawC), ctypes.c_int32]),
+    ("shs_rt_resolve_spec", ctypes.c_int, [_P, _P]),
+    ("shs_rt_device_spec", ctypes.c_int, [_P, ctypes.POINTER(_P)]),
     ("shs_rt_keep_reflection", ctypes.c_int, [_P]),
     ("shs_rt_set_reflection", ctypes.c_int, [_P, _P, ctypes.c_int32, ctypes.c_int32]),
     ("shs_rt_water_samples", ctypes.c_int, [_P, ctypes.c_int32, _P, ctypes.c_float, _P, _P]),
