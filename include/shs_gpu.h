@@ -925,6 +925,34 @@ typedef struct shs_canvas_lens_flare_desc {
  * reference's.  prequant: rr, gg, bb before color_from_rgbaf's clamp, and 1. */
 int shs_canvas_lens_flare(shs_ctx *ctx, const shs_canvas_lens_flare_desc *desc, const uint8_t *src, uint8_t *dst,
                           float *prequant, uint32_t flags);
+#define SHS_CANVAS_MAX_OBJECT_BLUR_SAMPLES 64
+typedef struct shs_canvas_object_blur_desc {
+    int32_t width, height;
+    float multiplier;           /* BLUR_MULTIPLIER (1.85) */
+    float velocity_scale;       /* the host's clampf(target_dt / dt, 0.25f, 4.0f) (:782-784; 1 at 60 frames a second);
+                                 * taken as it is, not clamped here */
+    float min_vel2;             /* MIN_VEL2_THRESHOLD (0.25): a scaled velocity whose squared length is below it copies */
+    int32_t max_samples;        /* MAX_BLUR_SAMPLES (20): 2 .. SHS_CANVAS_MAX_OBJECT_BLUR_SAMPLES */
+    float depth_eps;            /* DEPTH_REJECT_EPS (0.15) */
+    int32_t depth_rows;         /* 0: depth is in canvas rows like src, read at y; 1: in screen rows, read at
+                                 * height - 1 - y -- the demo's case (:508-509, :524-525) and what shs_rt_render_plain leaves */
+} shs_canvas_object_blur_desc;
+/* post_process_motion_blur (hello_per_object_motion_blur.cpp:461-552): v = velocity * (multiplier * velocity_scale);
+ * dot(v, v) < min_vel2 copies; otherwise (int)length(v) samples, clamped to 2 .. max_samples, over a kernel centred on the
+ * pixel (offsets -0.5 .. +0.5 of v), each at ((int)(x - v.x * o), (int)(y - v.y * o)); a sample outside the canvas is
+ * skipped, one whose depth differs from the pixel's by more than depth_eps is skipped (an empty depth is FLT_MAX, so an
+ * empty pixel gathers empty samples only); the mean of the rest through color_from_rgbaf, or the source pixel when none is
+ * left.  The (int) conversions are the x86-64 ones: a NaN or Inf velocity gives two samples outside the canvas and the
+ * pixel is copied.  Exact float arithmetic: the bytes are the reference's.  src, velocity (W*H*2 floats, +Y up) and dst in
+ * canvas rows.  SHS_ERR_INVALID, with nothing enqueued: a null buffer, a non-positive size, an unknown flag, a non-finite
+ * parameter, max_samples outside its range, depth_rows other than 0 or 1, a dst whose bytes overlap src. */
+int shs_canvas_object_blur(shs_ctx *ctx, const shs_canvas_object_blur_desc *desc, const uint8_t *src, const float *depth,
+                           const float *velocity, uint8_t *dst, uint32_t flags);
+/* hello_ping_pong.cpp:611-618: `iterations` (BLUR_ITERATIONS, 3) rounds of shs_canvas_gaussian_blur, horizontal from
+ * color into a scratch canvas the context owns, vertical back into color; color (W*H*4 bytes) holds the result.
+ * iterations 0 leaves color as it is.  SHS_ERR_INVALID: a null buffer, a non-positive size, an unknown flag,
+ * iterations < 0. */
+int shs_canvas_ping_pong_blur(shs_ctx *ctx, int32_t width, int32_t height, int32_t iterations, uint8_t *color, uint32_t flags);
 
 /* A demo's whole post chain in one call, on scratch canvases the context owns (grown on demand, released by
  * shs_destroy).  The frame's width and height apply to every step: those of the embedded descs are ignored.
@@ -1067,7 +1095,11 @@ typedef struct shs_rt_frame {
                                             fragment_shader_water :1000-1097 per draw (shs_rt_render_water),
                                          6: hello_multi_pass.cpp's blinn_phong_fragment_shader :207-237,
                                          7: hello_glowing_star.cpp's star_fragment_shader :269-308
-                                            (both shs_rt_render_motion) */
+                                            (both shs_rt_render_motion),
+                                         8: hello_per_object_motion_blur.cpp's velocity_fragment_shader :139-177,
+                                         9: hello_depth_of_field.cpp's and 10: hello_ping_pong.cpp's
+                                            blinn_phong_fragment_shader (all three shs_rt_render_plain, whose depth
+                                            plane is in screen rows) */
 } shs_rt_frame;
 /* The PCSS constants of shading 1 (hello_shadow_mapping_soft.cpp:101-116), kept in the context. */
 typedef struct shs_rt_pcss {
@@ -1096,7 +1128,7 @@ typedef struct shs_rt_stats {
 int shs_rt_render_shadow(shs_ctx *ctx, int32_t w, int32_t h, int32_t ref_tile_w, int32_t ref_tile_h, const float light_vp[16],
                          const shs_rt_draw *casters, int32_t n_casters);
 /* SHS_ERR_INVALID: an unknown mesh or texture id, a non-positive size, unknown flags, a shading other than
- * 0 or 1 (2 goes through shs_rt_render_pbr, 3 through shs_rt_render_pbr_soft, 4 through shs_rt_render_skybox_ibl, 5 through shs_rt_render_water, 6 and 7 through shs_rt_render_motion), or SHS_RT_USE_SHADOW without a shadow map rendered before. */
+ * 0 or 1 (2 goes through shs_rt_render_pbr, 3 through shs_rt_render_pbr_soft, 4 through shs_rt_render_skybox_ibl, 5 through shs_rt_render_water, 6 and 7 through shs_rt_render_motion, 8 to 10 through shs_rt_render_plain), or SHS_RT_USE_SHADOW without a shadow map rendered before. */
 int shs_rt_render(shs_ctx *ctx, const shs_rt_frame *frame, const shs_rt_draw *draws, int32_t n_draws);
 /* Host copies of the last camera pass (any pointer may be NULL): color W*H*4 bytes, depth W*H floats,
  * velocity W*H*2 floats.  Synchronous. */
@@ -1156,7 +1188,7 @@ int shs_rt_ibl_samples(shs_ctx *ctx, int32_t n, const float *dirs3, const float 
  * (:552-611) and CubeMapSky with sample_face_bilinear (:432-517).  (These are not the library path's ProceduralSky /
  * CubemapSky of shs_lib_set_sky; the legacy ProceduralSky :520-549 is not built: no render-target demo constructs it.)
  * The reference draws the sky first and the triangles over it.  Here, with a sky bound, every camera pass
- * (shs_rt_render, shs_rt_render_pbr, shs_rt_render_pbr_soft, shs_rt_render_skybox_ibl, shs_rt_render_water, shs_rt_render_motion, whatever the shading) is followed on the context stream by a background pass
+ * (shs_rt_render, shs_rt_render_pbr, shs_rt_render_pbr_soft, shs_rt_render_skybox_ibl, shs_rt_render_water, shs_rt_render_motion, shs_rt_render_plain, whatever the shading) is followed on the context stream by a background pass
  * that colours each pixel that shows no fragment (shs_rt_resolve_ids: -1) -- also one whose fragment kept its depth
  * but not its colour -- from the direction through the pixel's centre (:769-780; canvas x, y with y up).  Such a
  * pixel's prequant floats are (r, g, b) * 255 before the truncation and 1; depth and velocity stay as the raster
@@ -1259,6 +1291,31 @@ int shs_rt_render_motion(shs_ctx *ctx, const shs_rt_frame *frame, const shs_rt_d
  * SHS_ERR_INVALID after any other camera pass. */
 int shs_rt_resolve_spec(shs_ctx *ctx, float *spec);
 int shs_rt_device_spec(shs_ctx *ctx, void **spec_dev);
+/* The camera pass of the three plain demos, the unclipped raster of shs_rt_render_motion again (no clip, no w test,
+ * area <= 0 culled, every varying screen-linear, strict '<' depth with the first of equal depths winning, a winning
+ * fragment always shows; ids 2 * triangle, polys3 = polys4 = 0, sub_tris the triangles the area rule keeps), for
+ * frame->shading
+ *   8: hello_per_object_motion_blur.cpp's draw_triangle_velocity_tile :391-455 with velocity_fragment_shader :139-177:
+ *      view-z depth; velocity = (vec2(pos) / pos.w - vec2(prev) / prev.w) * 0.5f * vec2(W, H) on the clip positions
+ *      interpolated to the pixel, +Y up, not clamped (max_velocity_px is not read): where an interpolated w is 0 the Inf
+ *      or NaN is stored as it comes;
+ *   9: hello_depth_of_field.cpp's draw_triangle_tile :524-574: view-z depth, the velocity plane all zero;
+ *  10: hello_ping_pong.cpp's draw_triangle_tile :352-400: depth clip.z / clip.w per corner, interpolated
+ *      screen-linearly; the velocity plane all zero; frame->view is not read.
+ * The colour of all three is shading 6's Blinn-Phong with an ambient term of 0.15 (0.35 there).
+ * THE DEPTH PLANE IS IN SCREEN ROWS: after this pass, and after this pass only, the depth of screen pixel (px, py), py
+ * counted from the top, is at py * W + px -- the reference's three demos hand ZBuffer::test_and_set_depth the screen row,
+ * so that is what their ZBuffer holds -- while colour, velocity, ids and prequant are in canvas rows, (H - 1 - py) * W + px,
+ * as after every other camera pass.  hello_per_object_motion_blur.cpp turns the row over when it reads
+ * (shs_canvas_object_blur with depth_rows = 1); hello_depth_of_field.cpp does not, and shs_canvas_dof over this plane as
+ * it is reproduces that demo's frame, its autofocus and composite reading a depth upside down against the colour.
+ * Pixels nothing covers keep FLT_MAX, the clear colour, zero velocity and id -1.  shs_rt_resolve*,
+ * shs_rt_device_targets, shs_rt_get_stats and the sky background pass serve this pass like any other camera pass;
+ * shs_rt_resolve_spec and shs_rt_device_spec answer SHS_ERR_INVALID after it.
+ * SHS_ERR_INVALID, with nothing enqueued: another shading (and shadings 8 to 10 through every other shs_rt_render*
+ * entry), a non-positive size or tile, unknown flags, SHS_RT_USE_SHADOW or SHS_RT_PCF, a non-zero albedo_tex, an unknown
+ * mesh id. */
+int shs_rt_render_plain(shs_ctx *ctx, const shs_rt_frame *frame, const shs_rt_draw *draws, int32_t n_draws);
 /* ortho_lh_zo (hello_shadow_mapping.cpp:128-140): LH, z in [0, 1]. */
 int shs_ortho_lh_zo(float left, float right, float bottom, float top, float znear, float zfar, float out16[16]);
 

@@ -829,6 +829,45 @@ public:
                                  SHS_CANVAS_DEVICE));
     }
 
+    // hello_per_object_motion_blur.cpp:786 over the last shs_rt_render_plain's planes (shading 8).  That pass leaves the
+    // depth plane in SCREEN rows, as the demo's ZBuffer holds it: depth_rows = 1.  velocity_scale: the host's
+    // clampf(target_dt / dt, 0.25f, 4.0f) (:782-784).  frame: a device buffer of the host's, W*H*4 bytes, not the colour plane.
+    static shs_canvas_object_blur_desc object_blur_defaults(int W, int H, float velocity_scale) {
+        shs_canvas_object_blur_desc d{};
+        d.width = W; d.height = H;
+        d.multiplier = 1.85f; d.velocity_scale = velocity_scale; d.min_vel2 = 0.25f; d.max_samples = 20; d.depth_eps = 0.15f;
+        d.depth_rows = 1;
+        return d;
+    }
+    void object_blur(const shs_canvas_object_blur_desc &d, void *frame) {
+        void *color = nullptr, *depth = nullptr, *vel = nullptr;
+        ok(shs_rt_device_targets(dev_->ctx, &color, &depth, &vel));
+        ok(shs_canvas_object_blur(dev_->ctx, &d, static_cast<const uint8_t *>(color), static_cast<const float *>(depth),
+                                  static_cast<const float *>(vel), static_cast<uint8_t *>(frame), SHS_CANVAS_DEVICE));
+    }
+
+    // hello_depth_of_field.cpp:786-812 over the last shs_rt_render_plain's planes (shading 9), in place on the colour plane.
+    // The depth plane goes in as it lies, in screen rows: that demo reads its ZBuffer unflipped (:270, :321).
+    static shs_canvas_dof_desc dof_defaults(int W, int H) {
+        shs_canvas_dof_desc d{};
+        d.width = W; d.height = H;
+        d.blur_iterations = 3; d.autofocus_radius = 6; d.focus_x = W / 2; d.focus_y = H / 2;
+        d.range = 24.0f; d.max_blur = 0.6f;
+        return d;
+    }
+    void dof(const shs_canvas_dof_desc &d) {
+        void *color = nullptr, *depth = nullptr, *vel = nullptr;
+        ok(shs_rt_device_targets(dev_->ctx, &color, &depth, &vel));
+        ok(shs_canvas_dof(dev_->ctx, &d, static_cast<uint8_t *>(color), static_cast<const float *>(depth), nullptr, nullptr, SHS_CANVAS_DEVICE));
+    }
+
+    // hello_ping_pong.cpp:611-618 over the last shs_rt_render_plain's colour plane (shading 10), in place
+    void ping_pong(int W, int H, int iterations = 3) {
+        void *color = nullptr, *depth = nullptr, *vel = nullptr;
+        ok(shs_rt_device_targets(dev_->ctx, &color, &depth, &vel));
+        ok(shs_canvas_ping_pong_blur(dev_->ctx, W, H, iterations, static_cast<uint8_t *>(color), SHS_CANVAS_DEVICE));
+    }
+
     // the demo's own targets on the host (RT_ColorDepthMotion: color, depth, motion) into the canvas it presents
     template <class RtT>
     void multi_pass_host(const shs_canvas_multi_pass_frame_desc &d, RtT &rt, shs::Canvas &fxaa_out) {
@@ -865,8 +904,16 @@ private:
 //   chain.glow(glow_desc, frame_dev);         // hello_glowing_star.cpp
 // and one copy of frame_dev into the canvas the demo presents.  star: shading 7 and a single job covering the frame;
 // otherwise shading 6 and tile jobs of `tile`.  max_velocity_px: MB_MAX_PIXELS, 40 / 22 / 30 in the three demos.
-// Objects are RenderTargetSystemGPU's (mesh_id, model, prev_model, base_color); a texture is rejected.  Uncompiled,
-// like the other seams.
+// Objects are RenderTargetSystemGPU's (mesh_id, model, prev_model, base_color); a texture is rejected.
+//
+// The three plain demos are the same raster through shs_rt_render_plain: set plain_shading to 8
+// (hello_per_object_motion_blur.cpp, draw_triangle_velocity_tile :391-455), 9 (hello_depth_of_field.cpp :524-574) or 10
+// (hello_ping_pong.cpp :352-400), tile jobs of 80.  Their depth plane is then in screen rows.  The whole frame is
+//   raster.process(dt);
+//   chain.object_blur(blur_desc, frame_dev);  // hello_per_object_motion_blur.cpp; the frame is frame_dev
+//   chain.dof(dof_desc);                      // hello_depth_of_field.cpp; the frame is the colour plane
+//   chain.ping_pong(W, H);                    // hello_ping_pong.cpp; the frame is the colour plane
+// Uncompiled, like the other seams.
 // -----------------------------------------------------------------------------------------------------
 template <class SceneT>
 class MotionRasterGPU : public shs::AbstractSystem {
@@ -902,8 +949,9 @@ public:
         std::memcpy(f.light_dir_world, glm::value_ptr(light_dir_world), 12);
         std::memcpy(f.camera_pos, glm::value_ptr(scene_->viewer->position), 12);
         f.max_velocity_px = max_px_;
-        f.shading = star_ ? 7 : 6;
-        ok(shs_rt_render_motion(dev_->ctx, &f, draws.data(), (int32_t)draws.size()));
+        f.shading = plain_shading ? plain_shading : star_ ? 7 : 6;
+        if (plain_shading) ok(shs_rt_render_plain(dev_->ctx, &f, draws.data(), (int32_t)draws.size()));
+        else ok(shs_rt_render_motion(dev_->ctx, &f, draws.data(), (int32_t)draws.size()));
         prev_view_ = view;
         prev_proj_ = proj;
     }
@@ -914,6 +962,7 @@ public:
 
     glm::vec3 light_dir_world{-1.0f, -0.4f, 1.0f};   // (the shaders normalise it)
     uint8_t clear_color[4] = {20, 20, 25, 255};
+    int plain_shading = 0;                           // 8, 9 or 10: one of the three plain demos (shs_rt_render_plain)
 
 private:
     SceneT *scene_;

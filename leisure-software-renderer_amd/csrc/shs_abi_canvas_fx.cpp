@@ -4,7 +4,9 @@
 //   shs_canvas_spec_bright, _additive, _lens_flare           hello_glowing_star.cpp's;
 //   shs_canvas_multi_pass_frame                              hello_multi_pass.cpp:1379-1426 and
 //                                                            hello_camera_and_perobject_motion_blur.cpp:1544-1606;
-//   shs_canvas_glow_frame                                    hello_glowing_star.cpp:1233-1310.
+//   shs_canvas_glow_frame                                    hello_glowing_star.cpp:1233-1310;
+//   shs_canvas_object_blur                                   hello_per_object_motion_blur.cpp's post_process_motion_blur :461-552;
+//   shs_canvas_ping_pong_blur                                hello_ping_pong.cpp:611-618.
 // Every entry checks all of its input first, so a rejected call enqueues nothing.  Host buffers are staged through
 // the context's device buffers and the call is synchronous; device buffers (SHS_CANVAS_DEVICE) are used in place
 // and the call only enqueues.  What does not depend on the pixel is derived here, each a single float operation of
@@ -363,6 +365,61 @@ int shs_canvas_lens_flare(shs_ctx *ctx, const shs_canvas_lens_flare_desc *d, con
     TRY(run_flare(ctx, *d, d->width, d->height, s, o, pq));
     TRY(stage_back(ctx, dev, o, dst, npx));
     TRY(stage_back(ctx, dev, pq, prequant, npx));
+    return finish(ctx, dev);
+}
+
+int shs_canvas_object_blur(shs_ctx *ctx, const shs_canvas_object_blur_desc *d, const uint8_t *src, const float *depth,
+                           const float *velocity, uint8_t *dst, uint32_t flags) {
+    if (!ctx || !d || !src || !depth || !velocity || !dst) return SHS_ERR_INVALID;
+    if (!frame_ok(ctx, d->width, d->height, flags)) return SHS_ERR_INVALID;
+    if (!all_finite({d->multiplier, d->velocity_scale, d->min_vel2, d->depth_eps}))
+        return fail(ctx, "object blur: a non-finite parameter"), SHS_ERR_INVALID;
+    if (!(d->max_samples >= 2 && d->max_samples <= SHS_CANVAS_MAX_OBJECT_BLUR_SAMPLES))
+        return fail(ctx, "object blur: max_samples 2 .. SHS_CANVAS_MAX_OBJECT_BLUR_SAMPLES"), SHS_ERR_INVALID;
+    if (d->depth_rows != 0 && d->depth_rows != 1) return fail(ctx, "object blur: depth_rows is 0 (canvas rows) or 1 (screen rows)"), SHS_ERR_INVALID;
+    const size_t npx = (size_t)d->width * d->height;
+    if (overlap(src, dst, npx)) return fail(ctx, "object blur: dst overlaps src"), SHS_ERR_INVALID;
+    if (set_dev(ctx)) return SHS_ERR_HIP;
+    const bool dev = (flags & SHS_CANVAS_DEVICE) != 0;
+    shs_dev::CanvasObjBlurParams p{};
+    const float *v;
+    TRY(stage_in(ctx, dev, ctx->cp_a, src, npx, p.src));
+    TRY(stage_in(ctx, dev, ctx->cp_depth, depth, npx, p.depth));
+    TRY(stage_in(ctx, dev, ctx->cp_vel, velocity, 2 * npx, v));
+    TRY(stage_out(ctx, dev, ctx->cp_b, dst, npx, p.dst));
+    p.velocity = reinterpret_cast<const float2 *>(v);
+    p.W = d->width;
+    p.H = d->height;
+    p.max_samples = d->max_samples;
+    p.depth_rows = d->depth_rows;
+    p.scale = d->multiplier * d->velocity_scale;   // (BLUR_MULTIPLIER * velocity_scale) :495
+    p.min_vel2 = d->min_vel2;
+    p.depth_eps = d->depth_eps;
+    HIP_TRY(ctx, shs_internal::launch_canvas_object_blur(p, ctx->stream));
+    TRY(stage_back(ctx, dev, p.dst, dst, npx));
+    return finish(ctx, dev);
+}
+
+int shs_canvas_ping_pong_blur(shs_ctx *ctx, int32_t width, int32_t height, int32_t iterations, uint8_t *color, uint32_t flags) {
+    if (!ctx || !color) return SHS_ERR_INVALID;
+    if (!frame_ok(ctx, width, height, flags)) return SHS_ERR_INVALID;
+    if (iterations < 0) return fail(ctx, "ping-pong blur: iterations >= 0"), SHS_ERR_INVALID;
+    if (iterations == 0) return SHS_OK;
+    if (set_dev(ctx)) return SHS_ERR_HIP;
+    const size_t npx = (size_t)width * height;
+    const bool dev = (flags & SHS_CANVAS_DEVICE) != 0;
+    if (ensure(ctx, ctx->fx_pong, npx)) return SHS_ERR_HIP;
+    uint32_t *ping = reinterpret_cast<uint32_t *>(color), *pong = ctx->fx_pong.p;
+    if (!dev) {
+        if (ensure(ctx, ctx->cp_a, npx)) return SHS_ERR_HIP;
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->cp_a.p, color, npx * 4, hipMemcpyHostToDevice, ctx->stream));
+        ping = ctx->cp_a.p;
+    }
+    for (int it = 0; it < iterations; ++it) {   // ping -> pong horizontal, pong -> ping vertical (:615-616)
+        HIP_TRY(ctx, shs_internal::launch_canvas_gaussian(ping, pong, width, height, true, ctx->stream));
+        HIP_TRY(ctx, shs_internal::launch_canvas_gaussian(pong, ping, width, height, false, ctx->stream));
+    }
+    TRY(stage_back(ctx, dev, ping, color, npx));
     return finish(ctx, dev);
 }
 

@@ -23,6 +23,9 @@
 // (their one unclipped raster, multi :525-599 / star :354-435, behind blinn_phong_fragment_shader multi :207-237 or
 // star_fragment_shader star :269-308), shs_rt_resolve_spec / shs_rt_device_spec (RT_ColorDepthVelocitySpec::spec); their
 // vertex shaders (multi :191-205, star :254-267) form the same two products and the same normal matrix.
+// and of hello_per_object_motion_blur.cpp, hello_depth_of_field.cpp and hello_ping_pong.cpp: shs_rt_render_plain (that
+// unclipped raster again, per_object :391-455 / dof :524-574 / ping_pong :352-400, shadings 8 to 10, with the depth plane in
+// screen rows).
 // The host forms the matrix products the shaders form first -- u.view * u.model (vertex_shader_full :616),
 // u.light_vp * u.model (shadow_vertex_shader :764) -- and the normal matrix with the GLM restatement in
 // shs_glm.hpp.  Both passes are enqueued on the context stream; the shadow map, the planes and the records
@@ -298,7 +301,7 @@ int upload_and_launch(shs_ctx *ctx, shs_dev::RtParams &p, bool shadow_pass, int 
 // PASS1 of the six demos: x empty for shading 0 / 1 (shs_rt_render), x.pbr for shading 2 (shs_rt_render_pbr) and 3
 // (shs_rt_render_pbr_soft), x.ibl for shading 4 (shs_rt_render_skybox_ibl), x.water_draws and x.water for shading 5
 // (shs_rt_render_water); and the one camera pass of the three unclipped demos, x empty, for shadings 6 and 7
-// (shs_rt_render_motion).  Nothing of the context changes before the last rejection.
+// (shs_rt_render_motion) and 8 to 10 (shs_rt_render_plain).  Nothing of the context changes before the last rejection.
 int render_camera(shs_ctx *ctx, const shs_rt_frame *f, const shs_rt_draw *draws, int32_t n_draws, PassExtras x) {
     if (!size_ok(ctx, f->width, f->height, f->ref_tile_w, f->ref_tile_h)) return SHS_ERR_INVALID;
     if (f->flags & ~(SHS_RT_USE_SHADOW | SHS_RT_PCF | SHS_RT_PREQUANT)) {
@@ -542,6 +545,28 @@ int shs_rt_render_motion(shs_ctx *ctx, const shs_rt_frame *f, const shs_rt_draw 
             return SHS_ERR_INVALID;
         }
     }
+    return render_camera(ctx, f, draws, n_draws, PassExtras{});
+}
+
+int shs_rt_render_plain(shs_ctx *ctx, const shs_rt_frame *f, const shs_rt_draw *draws, int32_t n_draws) {
+    if (!ctx || !f || n_draws < 0 || (n_draws > 0 && !draws)) return SHS_ERR_INVALID;
+    if (f->shading < 8 || f->shading > 10) {
+        ctx->err = "shs_rt_render_plain: shading " + std::to_string(f->shading) +
+                   " (8: hello_per_object_motion_blur.cpp's velocity_fragment_shader, 9: hello_depth_of_field.cpp's and 10: "
+                   "hello_ping_pong.cpp's blinn_phong_fragment_shader)";
+        return SHS_ERR_INVALID;
+    }
+    if (f->flags & (SHS_RT_USE_SHADOW | SHS_RT_PCF)) {
+        ctx->err = "shs_rt_render_plain: SHS_RT_USE_SHADOW / SHS_RT_PCF (these demos have no shadow map)";
+        return SHS_ERR_INVALID;
+    }
+    for (int32_t i = 0; i < n_draws; ++i) {
+        if (draws[i].albedo_tex != 0) {   // (the shaders read u.color only)
+            ctx->err = "shs_rt_render_plain: a draw with albedo_tex (shadings 8 to 10 have no texture)";
+            return SHS_ERR_INVALID;
+        }
+    }
+    // (shading 10: ping :50-59 forms no view z; the view * model product the draw table carries goes unread on the device)
     return render_camera(ctx, f, draws, n_draws, PassExtras{});
 }
 

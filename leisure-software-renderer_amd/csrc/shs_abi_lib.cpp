@@ -548,7 +548,7 @@ void shs_lib_release(shs_ctx *ctx) {
     release(ctx->dd_objs); release(ctx->dd_tris); release(ctx->dd_depth0); release(ctx->dd_depth); release(ctx->dd_lit_b);
     release(ctx->dd_rgba); release(ctx->dd_keys); release(ctx->dd_big);
     release(ctx->cp_a); release(ctx->cp_b); release(ctx->cp_src); release(ctx->cp_depth); release(ctx->cp_vel); release(ctx->cp_focus); release(ctx->cp_map); release(ctx->cp_pq);
-    release(ctx->fx_a); release(ctx->fx_b); release(ctx->fx_c); release(ctx->fx_in); release(ctx->fx_out); release(ctx->fx_depth); release(ctx->fx_vel); release(ctx->fx_spec);
+    release(ctx->fx_a); release(ctx->fx_b); release(ctx->fx_c); release(ctx->fx_in); release(ctx->fx_out); release(ctx->fx_depth); release(ctx->fx_vel); release(ctx->fx_spec); release(ctx->fx_pong);
     if (ctx->h_lib_counters) (void)hipHostFree(ctx->h_lib_counters);
     ctx->h_lib_counters = nullptr;
 }

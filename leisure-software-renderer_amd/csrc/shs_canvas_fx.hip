@@ -6,7 +6,8 @@
 //   k_canvas_fxaa           fxaa_pass (:1000-1114) over luma_from_color (:159-165) and color_from_rgbaf (:139-146);
 //   k_canvas_spec_bright    build_spec_bright_pass (hello_glowing_star.cpp:700-752);
 //   k_canvas_additive       additive_composite_pass (:754-795) over mul_color / add_color_clamped (:146-164);
-//   k_canvas_lens_flare     pseudo_lens_flare_pass (:802-906).
+//   k_canvas_lens_flare     pseudo_lens_flare_pass (:802-906);
+//   k_canvas_object_blur    post_process_motion_blur (hello_per_object_motion_blur.cpp:461-552).
 // One thread per pixel over 64 x 4 pixel blocks; every float expression keeps the reference's operands and order
 // (-ffp-contract=off, correctly rounded '/' and sqrt), so the output bytes are the reference's.  The two
 // transcendentals -- the fog's std::pow and the flare's std::exp -- are the function in double rounded once to
@@ -232,6 +233,46 @@ __global__ __launch_bounds__(256) void k_canvas_lens_flare(CanvasFlareParams p) 
     if (p.pq) p.pq[i] = make_float4(rr, gg, bb, 1.0f);
 }
 
+// post_process_motion_blur (hello_per_object_motion_blur.cpp:461-552): a kernel centred on the pixel, as many samples as
+// the scaled speed in pixels, each kept where its depth lies within eps of the pixel's; the source pixel where the motion
+// is small or nothing survives.  Every index is checked before it is used: a sample outside the canvas is skipped, a
+// depth outside it is FLT_MAX.
+__global__ __launch_bounds__(256) void k_canvas_object_blur(CanvasObjBlurParams p) {
+    FX_PIXEL(p.W, p.H);
+    const float2 vf = p.velocity[i];
+    const float vx = vf.x * p.scale, vy = vf.y * p.scale;
+    const float vv = vx * vx + vy * vy;
+    if (vv < p.min_vel2) {
+        p.dst[i] = p.src[i];
+        return;
+    }
+    int samples = int_x86(sqrtf(vv));
+    if (samples < 2) samples = 2;
+    if (samples > p.max_samples) samples = p.max_samples;
+    // ZBuffer::get_depth_at at canvas (x, row): the plane's own row is the screen row when depth_rows is set
+    const float z0 = p.depth[(size_t)(p.depth_rows ? p.H - 1 - y : y) * p.W + x];
+    float r = 0.0f, g = 0.0f, b = 0.0f, wsum = 0.0f;
+    for (int k = 0; k < samples; ++k) {
+        const float t = (float)k / (float)(samples - 1);
+        const float o = t - 0.5f;
+        const int sx = int_x86((float)x - vx * o);
+        const int sy = int_x86((float)y - vy * o);
+        if (sx < 0 || sx >= p.W || sy < 0 || sy >= p.H) continue;
+        const float zs = p.depth[(size_t)(p.depth_rows ? p.H - 1 - sy : sy) * p.W + sx];
+        if (fabsf(zs - z0) > p.depth_eps) continue;
+        const uint32_t c = p.src[(size_t)sy * p.W + sx];
+        r += chan(c, 0);
+        g += chan(c, 1);
+        b += chan(c, 2);
+        wsum += 1.0f;
+    }
+    if (wsum <= 0.0f) {
+        p.dst[i] = p.src[i];
+        return;
+    }
+    p.dst[i] = rgbaf(r / wsum, g / wsum, b / wsum);
+}
+
 #undef FX_PIXEL
 
 }  // namespace shs_dev
@@ -274,6 +315,11 @@ hipError_t launch_canvas_additive(const uint32_t *base, const uint32_t *add, uin
 
 hipError_t launch_canvas_lens_flare(const CanvasFlareParams &p, hipStream_t s) {
     hipLaunchKernelGGL(k_canvas_lens_flare, px_grid(p.W, p.H), dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_canvas_object_blur(const CanvasObjBlurParams &p, hipStream_t s) {
+    hipLaunchKernelGGL(k_canvas_object_blur, px_grid(p.W, p.H), dim3(256), 0, s, p);
     return hipGetLastError();
 }
 

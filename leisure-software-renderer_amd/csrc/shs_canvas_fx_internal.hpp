@@ -1,5 +1,5 @@
 // shs_canvas_fx_internal.hpp -- launch interface of shs_canvas_fx.hip: the Canvas-API post passes of
-// hello_multi_pass.cpp and hello_glowing_star.cpp (paths relative to hello-render-target/).  Buffers indexed
+// hello_multi_pass.cpp, hello_glowing_star.cpp and hello_per_object_motion_blur.cpp (paths relative to hello-render-target/).  Buffers indexed
 // y * W + x, as the passes index their canvases.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -72,9 +72,22 @@ struct CanvasFlareParams {
     float weight[FX_MAX_GHOSTS];   // 0.45f + 0.55f * (1.0f - float(i) / float(n_ghosts))
 };
 
+// post_process_motion_blur (hello_per_object_motion_blur.cpp:461-552)
+struct CanvasObjBlurParams {
+    const uint32_t *src;
+    const float *depth;       // the ZBuffer's raw plane (FLT_MAX = empty)
+    const float2 *velocity;   // Buffer<glm::vec2> (canvas px, +Y up)
+    uint32_t *dst;
+    int32_t W, H, max_samples;
+    int32_t depth_rows;       // 0: depth in canvas rows, read at y; 1: in screen rows, read at H - 1 - y (:508, :524)
+    float scale;              // BLUR_MULTIPLIER * velocity_scale
+    float min_vel2, depth_eps;
+};
+
 }  // namespace shs_dev
 
 namespace shs_internal {
+hipError_t launch_canvas_object_blur(const shs_dev::CanvasObjBlurParams &p, hipStream_t s);
 hipError_t launch_canvas_velocity_blur(const shs_dev::CanvasVBlurParams &p, hipStream_t s);
 hipError_t launch_canvas_fog(const shs_dev::CanvasFogParams &p, hipStream_t s);
 hipError_t launch_canvas_outline(const shs_dev::CanvasOutlineParams &p, hipStream_t s);

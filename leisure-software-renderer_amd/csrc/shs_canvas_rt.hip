@@ -45,6 +45,15 @@
 //          shade_pixel_motion<true>, the one instantiation that stores a fourth plane (RtParams::spec).  The star's
 //          single job is the whole frame (its host passes ref_tile = the frame's size).
 //          Both launched by shs_rt_render_motion.
+// and for the three plain demos, whose rasters are that unclipped one again -- hello_per_object_motion_blur.cpp
+// ("per :line") draw_triangle_velocity_tile :391-455, hello_depth_of_field.cpp ("dof :line") draw_triangle_tile :524-574,
+// hello_ping_pong.cpp ("ping :line") draw_triangle_tile :352-400 -- with the Blinn-Phong body of shading 6 under an
+// ambient term of 0.15 and a depth plane in SCREEN rows (all three hand test_and_set_depth the screen py):
+//   shading 8  velocity_fragment_shader (per :139-177): the velocity per pixel from the interpolated clip positions, no
+//          clamp.  k_rt_raster<false, 10>.
+//   shading 9  dof :60-120 and shading 10 ping :65-98: no velocity; k_rt_raster<false, 11> for both.  Shading 10's depth is
+//          clip z / clip w per corner (ping :389): k_rt_setup_motion<true>.
+//          All launched by shs_rt_render_plain.
 //   the background  skybox_background_pass (pbr :733-799; the same routine in hello_pbr_light_shafts.cpp and
 //          hello_ibl_skybox.cpp) over the legacy AnalyticSky / CubeMapSky of hello-shs-renderer/shs_renderer.hpp:
 //          k_rt_sky<MODEL, ENCODE>, a pass of its own after k_rt_raster when a sky is bound (shs_rt_set_sky), which
@@ -261,6 +270,9 @@ __device__ bool emit_camera(const RtParams &p, int32_t id, int32_t draw, const V
 // The unclipped raster's triangle (multi :536-560; star :364-392): the corners in their own order, straight through
 // Canvas::clip_to_screen with no w test (a corner behind the camera projects mirrored; w = 0 gives Inf or NaN screen
 // coordinates, which the bbox fold and the barycentrics take as the reference's do), positive areas only.
+// NDC_Z: the corners' depth is clip_to_screen's third component, clip z / clip w (hello_ping_pong.cpp:389), where the
+// other demos interpolate the vertex shader's view z.
+template <bool NDC_Z>
 __device__ bool emit_motion(const RtParams &p, int32_t id, int32_t draw, const Vy (&in)[3]) {
     RtRec r{};
     r.draw = draw;
@@ -276,7 +288,11 @@ __device__ bool emit_motion(const RtParams &p, int32_t id, int32_t draw, const V
     if (!ok) {
         r.flags = 0u;
     } else {
-        r.z0 = in[0].vz; r.z1 = in[1].vz; r.z2 = in[2].vz;
+        if constexpr (NDC_Z) {
+            r.z0 = in[0].p[2] / in[0].p[3]; r.z1 = in[1].p[2] / in[1].p[3]; r.z2 = in[2].p[2] / in[2].p[3];
+        } else {
+            r.z0 = in[0].vz; r.z1 = in[1].vz; r.z2 = in[2].vz;
+        }
         const Vy *tv[3] = {&in[0], &in[1], &in[2]};
         store_vary(p.vary[id], tv);
     }
@@ -386,7 +402,9 @@ __global__ __launch_bounds__(256) void k_rt_setup(const RtParams p) {
 
 // The setup of shadings 6 and 7: one lane per input triangle, the vertex shader, no clip.  One record per triangle at
 // id 2 t, so that a pixel's id reads as for every other camera pass; slot 2 t + 1 is empty.  Counter 3 is the number of
-// triangles the area rule keeps; there are no clipped polygons to count.
+// triangles the area rule keeps; there are no clipped polygons to count.  It is also the setup of shadings 8 to 10, the
+// same raster; NDC_Z (shading 10): the per-corner depth is clip z / clip w and the view-z product is not read.
+template <bool NDC_Z>
 __global__ __launch_bounds__(256) void k_rt_setup_motion(const RtParams p) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= p.n_tris) return;
@@ -394,7 +412,7 @@ __global__ __launch_bounds__(256) void k_rt_setup_motion(const RtParams p) {
     const RtDrawGPU &dr = p.draws[d];
     Vy in[3];
     vertex_shader_full(dr, t - dr.base, in);
-    const bool ok = emit_motion(p, 2 * t, d, in);
+    const bool ok = emit_motion<NDC_Z>(p, 2 * t, d, in);
     RtRec none{};
     store_rec(&p.recs[2 * t + 1], none);
     wave_count(&p.stats[3], ok);
@@ -426,11 +444,16 @@ __device__ __forceinline__ bool axis_meets(float mn, float mx, int g0, int g1, i
 
 // The camera pass's instantiation k_rt_raster<false, rt_variant(shading, sky model)> of shs_rt_frame::shading: shadings 0
 // to 3 are their own number, shading 4 is three instantiations, one per sky model its shader samples (RT_SKY_*: 4 to 6),
-// and shadings 5 to 7 follow them.  The kernel's ladder and the launcher both go through this one mapping.
-constexpr int RT_VARIANTS = 10;
-constexpr int rt_variant(int shading, int sky_model) { return shading >= 5 ? shading + 2 : shading == 4 ? 4 + sky_model : shading; }
-// Shadings 6 and 7 sit behind the unclipped raster: screen-linear varyings, so no fragment loses its colour to invw_sum
+// and shadings 5 to 8 follow them; shadings 9 and 10 share one instantiation (they differ in the setup's depth alone).
+// The kernel's ladder and the launcher both go through this one mapping.
+constexpr int RT_VARIANTS = 12;
+constexpr int rt_variant(int shading, int sky_model) {
+    return shading >= 9 ? 11 : shading >= 5 ? shading + 2 : shading == 4 ? 4 + sky_model : shading;
+}
+// Shadings 6 to 10 sit behind the unclipped raster: screen-linear varyings, so no fragment loses its colour to invw_sum
 constexpr bool rt_unclipped(int variant) { return variant >= rt_variant(6, 0); }
+// Shadings 8 to 10 (the three plain demos) hand the ZBuffer the screen row: their depth plane is stored at py * W + px
+constexpr bool rt_screen_depth(int variant) { return variant >= rt_variant(8, 0); }
 
 // VARIANT: the fragment shader, a compile-time choice (the shadow pass ignores it)
 template <bool SHADOW, int VARIANT = 0>
@@ -532,7 +555,11 @@ __global__ __launch_bounds__(256) void k_rt_raster(const RtParams p) {
     if constexpr (VARIANT == rt_variant(6, 0)) {
         if (sid >= 0) shade_pixel_motion<false>(p, sid, su, sv, sw, rgba, vel, pq, spec01);
     } else if constexpr (VARIANT == rt_variant(7, 0)) {
-        if (sid >= 0) shade_pixel_motion<true>(p, sid, su, sv, sw, rgba, vel, pq, spec01);
+        if (sid >= 0) shade_pixel_motion<true, RtAmbient20>(p, sid, su, sv, sw, rgba, vel, pq, spec01);
+    } else if constexpr (VARIANT == rt_variant(8, 0)) {
+        if (sid >= 0) shade_pixel_motion<false, RtAmbient15, RT_VEL_PER_PIXEL>(p, sid, su, sv, sw, rgba, vel, pq, spec01);
+    } else if constexpr (VARIANT == rt_variant(9, 0)) {
+        if (sid >= 0) shade_pixel_motion<false, RtAmbient15, RT_VEL_NONE>(p, sid, su, sv, sw, rgba, vel, pq, spec01);
     } else if constexpr (VARIANT == rt_variant(1, 0)) {
         if (sid >= 0) shade_pixel_soft(p, sid, su, sv, sw, px, py, rgba, pq);   // the velocity plane stays zero
     } else if constexpr (VARIANT == rt_variant(2, 0)) {
@@ -548,7 +575,10 @@ __global__ __launch_bounds__(256) void k_rt_raster(const RtParams p) {
     }
     const size_t o = (size_t)(p.H - 1 - py) * p.W + px;   // canvas rows
     p.color[o] = rgba;
-    p.depth[o] = best;
+    // the depth row: the canvas row, or for the three plain demos the screen row their test_and_set_depth(px, py, z) is
+    // given (per :432, dof :563, ping :390)
+    if constexpr (rt_screen_depth(VARIANT)) p.depth[(size_t)py * p.W + px] = best;
+    else p.depth[o] = best;
     p.velocity[o] = vel;
     p.ids[o] = sid;
     if (p.prequant) p.prequant[o] = pq;
@@ -689,7 +719,8 @@ hipError_t launch_canvas_rt(const shs_dev::RtParams &p, bool shadow_pass, int sh
     if (p.n_tris > 0) {
         const int grid = (p.n_tris + 255) / 256;
         if (shadow_pass) hipLaunchKernelGGL(k_rt_setup<true>, dim3(grid), dim3(256), 0, s, p);
-        else if (rt_unclipped(rt_variant(shading, sky_model))) hipLaunchKernelGGL(k_rt_setup_motion, dim3(grid), dim3(256), 0, s, p);
+        else if (shading == 10) hipLaunchKernelGGL(k_rt_setup_motion<true>, dim3(grid), dim3(256), 0, s, p);
+        else if (rt_unclipped(rt_variant(shading, sky_model))) hipLaunchKernelGGL(k_rt_setup_motion<false>, dim3(grid), dim3(256), 0, s, p);
         else hipLaunchKernelGGL(k_rt_setup<false>, dim3(grid), dim3(256), 0, s, p);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;

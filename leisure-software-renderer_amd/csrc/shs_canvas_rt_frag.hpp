@@ -148,6 +148,17 @@ __device__ __forceinline__ float2 frag_velocity(const RtParams &p, const RtVary 
     return make_float2(vx, vy);
 }
 
+// velocity_fragment_shader's velocity (hello_per_object_motion_blur.cpp:170-174), formed per pixel: the interpolated
+// clip position and previous clip position (:436-437), each over its own interpolated w, the difference, * 0.5f, *
+// viewport_size = (W, H).  +Y up as it stands; no clamp and no threshold, so a w of 0 stores the Inf or NaN it gives.
+__device__ __forceinline__ float2 frag_velocity_ndc(const RtParams &p, const RtVary &y, float u, float v, float w) {
+    const float cw = bary3(u, v, w, y.pos[3], y.pos[7], y.pos[11]);
+    const float qw = bary3(u, v, w, y.prev[3], y.prev[7], y.prev[11]);
+    const float cx = bary3(u, v, w, y.pos[0], y.pos[4], y.pos[8]) / cw, cy = bary3(u, v, w, y.pos[1], y.pos[5], y.pos[9]) / cw;
+    const float qx = bary3(u, v, w, y.prev[0], y.prev[4], y.prev[8]) / qw, qy = bary3(u, v, w, y.prev[1], y.prev[5], y.prev[9]) / qw;
+    return make_float2((cx - qx) * 0.5f * (float)p.W, (cy - qy) * 0.5f * (float)p.H);
+}
+
 // sample_nearest (shs_renderer.hpp:367-377; soft :167-186; water :121-140) up to the texel
 __device__ __forceinline__ uint32_t sample_nearest_texel(const RtDrawGPU &dr, float tu, float tv) {
     const float su = saturate(tu), sv = saturate(tv);

@@ -9,7 +9,9 @@
 // two fragment shaders chosen per draw, the atmosphere shader and the water shader over a planar reflection, shading 5
 // through shs_rt_render_water), and of hello_multi_pass.cpp, hello_camera_and_perobject_motion_blur.cpp and
 // hello_glowing_star.cpp (one raster without the near-plane clip, screen-linear varyings, back faces culled; shadings 6
-// and 7 through shs_rt_render_motion, the latter with a fourth plane, spec01).
+// and 7 through shs_rt_render_motion, the latter with a fourth plane, spec01), and of hello_per_object_motion_blur.cpp,
+// hello_depth_of_field.cpp and hello_ping_pong.cpp (that raster again with the depth plane in screen rows; shadings 8 to 10
+// through shs_rt_render_plain).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -235,7 +237,9 @@ hipError_t launch_sky_samples(const shs_dev::RtSkySamples &q, int model, hipStre
 // 2: fragment_shader_pbr, 3: hello_pbr_light_shafts.cpp's fragment_shader_pbr, 4: hello_ibl_skybox.cpp's
 // fragment_shader_full, 5: hello_water.cpp's fragment_shader_full / fragment_shader_water per draw, 6: hello_multi_pass.cpp's
 // blinn_phong_fragment_shader, 7: hello_glowing_star.cpp's star_fragment_shader -- 6 and 7 behind the unclipped setup and
-// the screen-linear raster of those demos); sky_model: u.sky of shading 4 (RT_SKY_*), which chooses among its three
+// the screen-linear raster of those demos, as are 8: hello_per_object_motion_blur.cpp's velocity_fragment_shader, 9:
+// hello_depth_of_field.cpp's and 10: hello_ping_pong.cpp's blinn_phong_fragment_shader, whose depth plane is stored in
+// screen rows); sky_model: u.sky of shading 4 (RT_SKY_*), which chooses among its three
 // instantiations
 hipError_t launch_canvas_rt(const shs_dev::RtParams &p, bool shadow_pass, int shading, hipStream_t s, int sky_model = 0);
 hipError_t launch_pcss_samples(const shs_dev::RtPcssSamples &q, hipStream_t s);

@@ -604,16 +604,27 @@ __device__ void shade_pixel_water(const RtParams &p, int32_t id, float u, float 
 // (multi :207-237; STAR false) or star_fragment_shader (star :269-308; STAR true), which also returns spec01.  The
 // demos have no shadow map and no texture.  clampf (star :103-108) passes a NaN on: spec01 and the colour floats are NaN
 // then, and the bytes 0.
-template <bool STAR>
+// The same body serves the three plain demos (hello_per_object_motion_blur.cpp "per :line", hello_depth_of_field.cpp,
+// hello_ping_pong.cpp), whose Blinn-Phong shader is multi :207-237 with another ambient term (per :145, dof :88,
+// ping :72).  AMBIENT: ambientStrength, a type that carries the constant.  VELOCITY: how the velocity plane is filled,
+// RT_VEL_CLAMPED (multi :583-591), RT_VEL_PER_PIXEL (velocity_fragment_shader, per :170-174) or RT_VEL_NONE (the plane
+// stays zero: those demos have no velocity target).
+struct RtAmbient35 { static constexpr float value = 0.35f; };
+struct RtAmbient20 { static constexpr float value = 0.20f; };
+struct RtAmbient15 { static constexpr float value = 0.15f; };
+enum { RT_VEL_CLAMPED = 0, RT_VEL_PER_PIXEL = 1, RT_VEL_NONE = 2 };
+
+template <bool STAR, class AMBIENT = RtAmbient35, int VELOCITY = RT_VEL_CLAMPED>
 __device__ void shade_pixel_motion(const RtParams &p, int32_t id, float u, float v, float w, uint32_t &rgba, float2 &vel, float4 &pq,
                                    float &spec01) {
     const FragLinear f(p, id, u, v, w);
-    vel = frag_velocity(p, f.y, u, v, w, 0.0001f);
+    if constexpr (VELOCITY == RT_VEL_CLAMPED) vel = frag_velocity(p, f.y, u, v, w, 0.0001f);
+    else if constexpr (VELOCITY == RT_VEL_PER_PIXEL) vel = frag_velocity_ndc(p, f.y, u, v, w);
     const f3 wp = f.world();
     const f3 N = f.normal();
     const f3 L = {p.L[0], p.L[1], p.L[2]};
     const f3 V = normalize3(sub3(f3{p.cam[0], p.cam[1], p.cam[2]}, wp));
-    const float ambient = (STAR ? 0.20f : 0.35f) * 1.0f;
+    const float ambient = AMBIENT::value * 1.0f;
     const float diffuse = g_max(dot3(N, L), 0.0f) * 1.0f;
     const f3 H = normalize3(add3(L, V));
     const float ndoth = g_max(dot3(N, H), 0.0f);

@@ -397,6 +397,8 @@ struct shs_ctx {
     // the frame chains of shs_abi_canvas_fx.cpp: the demos' intermediate canvases (fx_a, fx_b, fx_c) and, for host
     // buffers, the staged inputs and the frame before it is copied back
     DevBuf<uint32_t> fx_a, fx_b, fx_c, fx_in, fx_out;
+    // shs_canvas_ping_pong_blur's scratch canvas (hello_ping_pong.cpp's pong.color)
+    DevBuf<uint32_t> fx_pong;
     DevBuf<float> fx_depth, fx_vel, fx_spec;
 };
 

@@ -112,6 +112,9 @@ class RtFrame:
                                  # 5: hello_water.cpp's atmosphere and water shaders, chosen per draw (Context.rt_render_water only)
                                  # 6: hello_multi_pass.cpp's blinn_phong_fragment_shader, 7: hello_glowing_star.cpp's
                                  #    star_fragment_shader, both behind the unclipped raster (Context.rt_render_motion only)
+                                 # 8: hello_per_object_motion_blur.cpp's velocity_fragment_shader, 9: hello_depth_of_field.cpp's
+                                 #    and 10: hello_ping_pong.cpp's Blinn-Phong shader (Context.rt_render_plain only; the depth
+                                 #    plane is then in screen rows)
 
 
 @dataclass
@@ -777,10 +780,13 @@ class Context:
         "dof": dict(iterations=4, radius=6, focus=None, range_=34.0, max_blur=0.75),
         "motion_blur": dict(curr_view=None, curr_proj=None, prev_view=None, prev_proj=None, samples=12, strength=0.85,
                             w_obj=1.0, w_cam=0.35, soft_knee=True, knee_px=18.0, max_px=22.0),
+        # hello_per_object_motion_blur.cpp:56-62; velocity_scale is the host's clampf(target_dt / dt, 0.25, 4), 1 at 60 Hz;
+        # depth_rows 1: the depth plane is in screen rows, as rt_render_plain leaves it
+        "object_blur": dict(multiplier=1.85, velocity_scale=1.0, min_vel2=0.25, max_samples=20, depth_eps=0.15, depth_rows=1),
     }
     _FX_DESCS = {"velocity_blur": _abi.CanvasVelocityBlurDescC, "fog": _abi.CanvasFogDescC, "outline": _abi.CanvasOutlineDescC,
                  "fxaa": _abi.CanvasFxaaDescC, "spec_bright": _abi.CanvasSpecBrightDescC, "lens_flare": _abi.CanvasLensFlareDescC,
-                 "dof": _abi.CanvasDofDescC, "motion_blur": _abi.CanvasMotionBlurDescC}
+                 "dof": _abi.CanvasDofDescC, "motion_blur": _abi.CanvasMotionBlurDescC, "object_blur": _abi.CanvasObjectBlurDescC}
 
     @classmethod
     def fx_desc(cls, kind, W, H, params=None, into=None):
@@ -903,6 +909,25 @@ class Context:
         d = self.fx_desc("lens_flare", W, H, dict(intensity=intensity, halo_intensity=halo_intensity,
                                                   chroma_shift_px=chroma_shift_px, ghost_scales=ghost_scales))
         return self._fx_call(self._lib.shs_canvas_lens_flare, d, [_host_c(src, np.uint8)], src, dst, bool(prequant), H, W)
+
+    def canvas_object_blur(self, src, depth, velocity, dst=None, **params):
+        """post_process_motion_blur (hello_per_object_motion_blur.cpp:461-552): src uint8 [H, W, 4], depth float32 [H, W]
+        (FLT_MAX = empty), velocity float32 [H, W, 2] (+Y up) -> dst.  params over FX_DEFAULTS["object_blur"]; depth_rows 1
+        (the default): depth is in screen rows, what rt_render_plain leaves; 0: in canvas rows like src."""
+        H, W = src.shape[:2]
+        d = self.fx_desc("object_blur", W, H, params)
+        return self._fx_call(self._lib.shs_canvas_object_blur, d,
+                             [_host_c(src, np.uint8), _host_c(depth, np.float32), _host_c(velocity, np.float32)], src, dst, None, H, W)
+
+    def canvas_ping_pong_blur(self, color, iterations=3):
+        """hello_ping_pong.cpp:611-618: iterations x (horizontal, vertical) canvas_gaussian_blur on color in place, over a
+        scratch canvas the context owns -> color."""
+        H, W = color.shape[:2]
+        dev = _is_device(color)
+        if dev:
+            self._on_torch_stream()
+        self._check(self._lib.shs_canvas_ping_pong_blur(self._h, W, H, int(iterations), _ptr(color), self.CANVAS_DEVICE if dev else 0))
+        return color
 
     def multi_pass_frame_desc(self, W, H, blur_mode=0, enable_dof=True, enable_fxaa=True, **passes):
         d = _abi.CanvasMultiPassFrameDescC()
@@ -1065,6 +1090,14 @@ class Context:
         (frame.shading 6) and hello_glowing_star.cpp (frame.shading 7, which also fills the spec plane), asynchronous."""
         arr = self._rt_draw_array(draws)
         self._check(self._lib.shs_rt_render_motion(self._h, ctypes.byref(self._rt_frame_c(frame)), arr, len(draws)))
+        self._rt_size = (frame.width, frame.height)
+
+    def rt_render_plain(self, frame, draws):
+        """shs_rt_render_plain: the unclipped camera pass of hello_per_object_motion_blur.cpp (frame.shading 8, velocity per
+        pixel), hello_depth_of_field.cpp (9) and hello_ping_pong.cpp (10, NDC-z depth), asynchronous.  The depth plane it
+        leaves is in SCREEN rows (row 0 is the top of the screen); every other plane is in canvas rows."""
+        arr = self._rt_draw_array(draws)
+        self._check(self._lib.shs_rt_render_plain(self._h, ctypes.byref(self._rt_frame_c(frame)), arr, len(draws)))
         self._rt_size = (frame.width, frame.height)
 
     def rt_resolve_spec(self):

@@ -260,6 +260,15 @@ class CanvasLensFlareDescC(ctypes.Structure):
                 ("ghost_scales", ctypes.c_float * CANVAS_MAX_FLARE_GHOSTS)]
 
 
+CANVAS_MAX_OBJECT_BLUR_SAMPLES = 64
+
+
+class CanvasObjectBlurDescC(ctypes.Structure):
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("multiplier", ctypes.c_float),
+                ("velocity_scale", ctypes.c_float), ("min_vel2", ctypes.c_float), ("max_samples", ctypes.c_int32),
+                ("depth_eps", ctypes.c_float), ("depth_rows", ctypes.c_int32)]
+
+
 class CanvasMultiPassFrameDescC(ctypes.Structure):
     _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("blur_mode", ctypes.c_int32),
                 ("enable_dof", ctypes.c_int32), ("enable_fxaa", ctypes.c_int32),
@@ -482,6 +491,9 @@ SIGNATURES = [
     ("shs_rt_render_water", ctypes.c_int, [_P, ctypes.POINTER(RtFrameC), ctypes.POINTER(RtDrawC), ctypes.POINTER(RtWaterDrawC),
                                            ctypes.POINTER(RtWaterC), ctypes.c_int32]),
     ("shs_rt_render_motion", ctypes.c_int, [_P, ctypes.POINTER(RtFrameC), ctypes.POINTER(RtDrawC), ctypes.c_int32]),
+    ("shs_rt_render_plain", ctypes.c_int, [_P, ctypes.POINTER(RtFrameC), ctypes.POINTER(RtDrawC), ctypes.c_int32]),
+    ("shs_canvas_object_blur", ctypes.c_int, [_P, ctypes.POINTER(CanvasObjectBlurDescC), _P, _P, _P, _P, ctypes.c_uint32]),
+    ("shs_canvas_ping_pong_blur", ctypes.c_int, [_P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_uint32]),
     ("shs_rt_resolve_spec", ctypes.c_int, [_P, _P]),
     ("shs_rt_device_spec", ctypes.c_int, [_P, ctypes.POINTER(_P)]),
     ("shs_rt_keep_reflection", ctypes.c_int, [_P]),
