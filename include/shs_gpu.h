@@ -1004,6 +1004,8 @@ int shs_canvas_glow_frame(shs_ctx *ctx, const shs_canvas_glow_frame_desc *desc, 
  *                         vertex_shader_full (:602-620) and fragment_shader_full (:699-750): near-plane
  *                         clipping in clip space, both windings, view-z depth, perspective-correct
  *                         world position and UV, per-pixel velocity, Blinn-Phong with the shadow lookup.
+ *   shs_rt_render_shadow_edge  PASS0 of hello_ibl_skybox_xsimd.cpp instead: another raster rule into the same map
+ *                         (edge functions, back faces dropped, depth bits that depend on the SIMD width), below.
  * The reference clamps a triangle's bbox to the tile job that runs it, so the pixels it visits depend on
  * the job size (ref_tile_w x ref_tile_h; the demo: 80 x 80 for both passes): the same set is visited here.
  * The planes -- colour (Canvas pixels), depth (ZBuffer: view z, FLT_MAX = empty) and velocity
@@ -1062,7 +1064,20 @@ int shs_canvas_glow_frame(shs_ctx *ctx, const shs_canvas_glow_frame_desc *desc, 
  *      highlight and the same fog.  The shadow lookup (:716-751) differs from shading 0's: a uv outside [0, 1] is lit
  *      before the PCF taps, and an empty texel is lit whatever z is.  Both shaders round to the byte
  *      (clampi(lround(c * 255), 0, 255)) where shadings 0 to 4 truncate; the prequant plane holds c * 255 before that
- *      rounding and the shadow factor.  The velocity plane is written as for shading 0. */
+ *      rounding and the shadow factor.  The velocity plane is written as for shading 0.
+ *   (6 to 10: the unclipped demos, further down.)
+ *   11 fragment_shader_full of hello_ibl_skybox_optimized.cpp (:875-958; the same text in hello_ibl_skybox_xsimd.cpp
+ *      :822-911), through shs_rt_render_ibl_phong only (the shader needs the per-draw knobs of shs_rt_ibl_phong_draw).
+ *      Both demos' PASS1 raster (optimized :1125-1291) is hello_shadow_mapping.cpp's with tile jobs of 160; the
+ *      optimized demo's PASS0 is shs_rt_render_shadow, the xsimd demo's is shs_rt_render_shadow_edge; their
+ *      skybox_background_pass is shs_rt_set_sky with SHS_RT_SKY_CUBEMAP and SHS_RT_SKY_ENCODE_CLAMP, and their PASS2 is
+ *      shs_canvas_motion_blur over shs_rt_device_targets.  Blinn-Phong with the draw's shininess under the shadow lookup
+ *      of shading 0, the specular term not taking the base colour, a legacy ambient of 0.18; plus, from the IBL of
+ *      shs_rt_set_ibl, the irradiance along N weighted by kd = 1 - F and the prefiltered specular along reflect(-V, N)
+ *      at lod = sqrt(2 / (shininess + 2)) * (mips - 1) weighted by ks = F (Schlick over ibl_f0); the shadow factor
+ *      multiplies the direct term only.  The IBL precompute of those demos (irradiance and prefiltered mips from the
+ *      skybox) stays with the caller.  pow(., shininess) is one double-precision pow rounded once.  The velocity plane
+ *      is written as for shading 0; the prequant plane's fourth float is the shadow factor. */
 typedef struct shs_rt_draw {
     int32_t mesh_id;            /* shs_mesh_upload_soup[_uv] soup (without UVs: vec2(0) per corner) */
     int32_t albedo_tex;         /* shs_texture_upload id (use_texture), 0: base_color */
@@ -1099,7 +1114,9 @@ typedef struct shs_rt_frame {
                                          8: hello_per_object_motion_blur.cpp's velocity_fragment_shader :139-177,
                                          9: hello_depth_of_field.cpp's and 10: hello_ping_pong.cpp's
                                             blinn_phong_fragment_shader (all three shs_rt_render_plain, whose depth
-                                            plane is in screen rows) */
+                                            plane is in screen rows),
+                                         11: hello_ibl_skybox_optimized.cpp's and hello_ibl_skybox_xsimd.cpp's
+                                            fragment_shader_full, optimized :875-958 (shs_rt_render_ibl_phong) */
 } shs_rt_frame;
 /* The PCSS constants of shading 1 (hello_shadow_mapping_soft.cpp:101-116), kept in the context. */
 typedef struct shs_rt_pcss {
@@ -1128,7 +1145,7 @@ typedef struct shs_rt_stats {
 int shs_rt_render_shadow(shs_ctx *ctx, int32_t w, int32_t h, int32_t ref_tile_w, int32_t ref_tile_h, const float light_vp[16],
                          const shs_rt_draw *casters, int32_t n_casters);
 /* SHS_ERR_INVALID: an unknown mesh or texture id, a non-positive size, unknown flags, a shading other than
- * 0 or 1 (2 goes through shs_rt_render_pbr, 3 through shs_rt_render_pbr_soft, 4 through shs_rt_render_skybox_ibl, 5 through shs_rt_render_water, 6 and 7 through shs_rt_render_motion, 8 to 10 through shs_rt_render_plain), or SHS_RT_USE_SHADOW without a shadow map rendered before. */
+ * 0 or 1 (2 goes through shs_rt_render_pbr, 3 through shs_rt_render_pbr_soft, 4 through shs_rt_render_skybox_ibl, 5 through shs_rt_render_water, 6 and 7 through shs_rt_render_motion, 8 to 10 through shs_rt_render_plain, 11 through shs_rt_render_ibl_phong), or SHS_RT_USE_SHADOW without a shadow map rendered before. */
 int shs_rt_render(shs_ctx *ctx, const shs_rt_frame *frame, const shs_rt_draw *draws, int32_t n_draws);
 /* Host copies of the last camera pass (any pointer may be NULL): color W*H*4 bytes, depth W*H floats,
  * velocity W*H*2 floats.  Synchronous. */
@@ -1232,6 +1249,37 @@ typedef struct shs_rt_skybox_ibl_draw {
  * n_draws > 0 and for a non-finite knob (nothing is enqueued). */
 int shs_rt_render_skybox_ibl(shs_ctx *ctx, const shs_rt_frame *frame, const shs_rt_draw *draws,
                              const shs_rt_skybox_ibl_draw *ibl_draws, int32_t n_draws);
+/* hello_ibl_skybox_optimized.cpp's and hello_ibl_skybox_xsimd.cpp's per-object knobs that their fragment_shader_full reads
+ * beside shs_rt_draw (Uniforms, optimized :757-764; set per object :1737-1741, :1805-1809, :1862-1866): element i goes
+ * with shs_rt_draw[i].  The shader saturates ibl_ambient, ibl_refl and ibl_refl_mix; ibl_f0 is used as given. */
+typedef struct shs_rt_ibl_phong_draw {
+    float ibl_ambient;     /* the weight of the diffuse irradiance term (0.30) */
+    float ibl_refl;        /* the weight of the prefiltered-specular term (0.35) */
+    float ibl_f0;          /* Schlick's reflectivity at normal incidence (0.04) */
+    float ibl_refl_mix;    /* per-object multiplier of the specular term (1) */
+    float shininess;       /* the direct specular exponent and, through sqrt(2 / (shininess + 2)), the IBL lod's roughness
+                              (64); >= 0 */
+} shs_rt_ibl_phong_draw;
+/* PASS1 of hello_ibl_skybox_optimized.cpp and of hello_ibl_skybox_xsimd.cpp (shading 11): the raster of shs_rt_render with
+ * those demos' fragment_shader_full (optimized :875-958), which reads the IBL bound by shs_rt_set_ibl (none bound:
+ * u.ibl == nullptr, both IBL terms 0); the background pass follows as after every camera pass.  frame->shading must be
+ * 11.  SHS_ERR_INVALID as shs_rt_render, for any other shading, for a null ibl_draws with n_draws > 0, for a non-finite
+ * knob and for shininess < 0 (nothing is enqueued).  The reference would take a negative exponent; no demo passes one,
+ * and sqrt(2 / (shininess + 2)) stops being a number at -2. */
+int shs_rt_render_ibl_phong(shs_ctx *ctx, const shs_rt_frame *frame, const shs_rt_draw *draws,
+                            const shs_rt_ibl_phong_draw *ibl_draws, int32_t n_draws);
+/* PASS0 of hello_ibl_skybox_xsimd.cpp (draw_triangle_tile_shadow_xsimd :1016-1191) into the map shs_rt_render_shadow fills:
+ * shs_rt_resolve_shadow, shs_rt_device_shadow_map, SHS_RT_USE_SHADOW and shs_canvas_light_shafts serve it unchanged.  Not
+ * that pass's rule: edge functions with inclusive tests (E >= 0), so back faces (area <= 0) are dropped; a box of
+ * (int)floor / (int)ceil of the corners' extent clamped to the tile job and then to the map; the depth from E / area
+ * weights.  simd_lanes is the reference build's xsimd::batch<float>::size (8 for AVX2, 4 for SSE2 / NEON, 16 for AVX-512):
+ * a row of a job is walked from the box's first column in groups of simd_lanes texels while a whole group fits, which
+ * sum an edge function as A x + (B y + C), and the rest of the row as (A x + B y) + C, so a texel's depth depends on
+ * simd_lanes and on the tile job size.  (int)floor / (int)ceil of a value that is not finite or does not fit an int is
+ * undefined in the reference: a triangle with a screen corner that is not finite or is at least 2^31 in magnitude is
+ * dropped.  SHS_ERR_INVALID: what shs_rt_render_shadow rejects, a simd_lanes other than 1, 2, 4, 8, 16. */
+int shs_rt_render_shadow_edge(shs_ctx *ctx, int32_t w, int32_t h, int32_t ref_tile_w, int32_t ref_tile_h, const float light_vp[16],
+                              const shs_rt_draw *casters, int32_t n_casters, int32_t simd_lanes);
 /* hello_water.cpp (shading 5): which of that demo's two fragment shaders a draw runs; element i goes with shs_rt_draw[i]. */
 #define SHS_RT_WATER_SURFACE 1u      /* fragment_shader_water (:1000-1097); 0: fragment_shader_full (:938-994) */
 typedef struct shs_rt_water_draw {

@@ -587,6 +587,128 @@ private:
 };
 
 // -----------------------------------------------------------------------------------------------------
+// Seam 1b, IBL-lit -- hello-render-target/hello_ibl_skybox_optimized.cpp and hello_ibl_skybox_xsimd.cpp.
+//
+// Replaces RendererSystem::process of either file (optimized :1572-1970), four calls on the context stream with no
+// resolve in between:
+//   1. PASS0 with tile jobs of 160 over the 2048^2 map (TILE_SIZE_X / TILE_SIZE_Y :127-128, SHADOW_MAP_SIZE :133):
+//      shs_rt_render_shadow for the optimized file (its draw_triangle_tile_shadow :1065-1108 is the hard demo's), or
+//      shs_rt_render_shadow_edge for the xsimd file (draw_triangle_tile_shadow_xsimd, xsimd :1016-1191), whose simd_lanes
+//      is xsimd::batch<float>::size of the build being replaced (8 for AVX2, 4 for SSE2 / NEON, 16 for AVX-512);
+//   2. shs_rt_set_sky with SHS_RT_SKY_CUBEMAP, SHS_RT_SKY_ENCODE_CLAMP and the viewer's camera: skybox_background_pass;
+//   3. shs_rt_render_ibl_phong, shading = 11: the hard demo's raster (:1125-1291) with these files' fragment_shader_full
+//      (:875-958) and the per-object knobs (:1737-1741, :1805-1809, :1862-1866), over the IBL bound once by set_ibl()
+//      below -- the host's own precompute (build_irradiance_cubemap, build_prefiltered_spec) through shs_rt_set_ibl;
+//   4. shs_canvas_motion_blur over shs_rt_device_targets into a device buffer of the host's, with MB_* :147-155
+//      (combined_motion_blur_pass of both files is that pass: DESIGN.md section 4).
+// Uncompiled, like the other seams.
+// -----------------------------------------------------------------------------------------------------
+template <class SceneT>
+class IblPhongSystemGPU : public shs::AbstractSystem {
+public:
+    struct Object {
+        typename RenderTargetSystemGPU<SceneT>::Object geom;
+        shs_rt_ibl_phong_draw ibl{0.30f, 0.35f, 0.04f, 1.0f, 64.0f};   // Uniforms :757-764
+    };
+
+    // simd_lanes 0: the optimized file's PASS0; else the xsimd file's, with that batch size
+    IblPhongSystemGPU(SceneT *scene, Device *dev, void *blurred_dev, int simd_lanes = 0, int shadow_size = 2048, int tile = 160)
+        : scene_(scene), dev_(dev), blurred_(blurred_dev), lanes_(simd_lanes), sm_(shadow_size), tile_(tile) {}
+
+    std::vector<Object> objects;     // geom.model / prev_model per frame
+
+    // IBLResources (:520-527) once after the host's precompute: irradiance.face[f] and spec.mip[m].face[f] as rgb floats,
+    // the six faces of a level one after the other, the mips concatenated (mip m of size max(1, base >> m))
+    void set_ibl(int irr_size, const float *irr, int spec_base, int mip_count, const float *spec) {
+        ok(shs_rt_set_ibl(dev_->ctx, irr_size, irr, spec_base, mip_count, spec));
+    }
+    void use_cubemap(const int32_t face_tex[6], float intensity) {
+        sky_ = shs_rt_sky{};
+        sky_.model = SHS_RT_SKY_CUBEMAP;
+        std::memcpy(sky_.face_tex, face_tex, sizeof sky_.face_tex);
+        sky_.intensity = intensity;
+    }
+
+    void process(float) override {
+        shs::Canvas &canvas = *scene_->canvas;
+        const int W = canvas.get_width(), H = canvas.get_height();
+        const shs::Camera3D &cam = *scene_->viewer->camera;
+        const glm::mat4 view = cam.view_matrix, proj = cam.projection_matrix;
+        std::vector<shs_rt_draw> draws(objects.size());
+        std::vector<shs_rt_ibl_phong_draw> knobs(objects.size());
+        for (size_t i = 0; i < objects.size(); ++i) {
+            const auto &o = objects[i].geom;
+            shs_rt_draw &d = draws[i];
+            d.mesh_id = o.mesh_id;
+            d.albedo_tex = o.albedo_tex;
+            const glm::mat4 mvp = proj * view * o.model, prev_mvp = prev_proj_ * prev_view_ * o.prev_model;
+            std::memcpy(d.model, glm::value_ptr(o.model), 64);
+            std::memcpy(d.mvp, glm::value_ptr(mvp), 64);
+            std::memcpy(d.prev_mvp, glm::value_ptr(prev_mvp), 64);
+            d.base_color[0] = o.base_color.r; d.base_color[1] = o.base_color.g; d.base_color[2] = o.base_color.b; d.base_color[3] = 255;
+            knobs[i] = objects[i].ibl;
+        }
+        // 1. PASS0
+        if (lanes_ > 0)
+            ok(shs_rt_render_shadow_edge(dev_->ctx, sm_, sm_, tile_, tile_, glm::value_ptr(light_vp), draws.data(), (int32_t)draws.size(), lanes_));
+        else
+            ok(shs_rt_render_shadow(dev_->ctx, sm_, sm_, tile_, tile_, glm::value_ptr(light_vp), draws.data(), (int32_t)draws.size()));
+        // 2. the sky through this frame's camera, for the background behind the camera pass
+        if (sky_.model != SHS_RT_SKY_NONE) {
+            sky_.encode = SHS_RT_SKY_ENCODE_CLAMP;
+            std::memcpy(sky_.cam_forward, glm::value_ptr(cam.direction_vector), 12);
+            std::memcpy(sky_.cam_right, glm::value_ptr(cam.right_vector), 12);
+            std::memcpy(sky_.cam_up, glm::value_ptr(cam.up_vector), 12);
+            sky_.fov_degrees = cam.field_of_view;
+            ok(shs_rt_set_sky(dev_->ctx, &sky_));
+        } else {
+            ok(shs_rt_set_sky(dev_->ctx, nullptr));
+        }
+        // 3. PASS1
+        shs_rt_frame f{};
+        f.width = W; f.height = H; f.ref_tile_w = tile_; f.ref_tile_h = tile_;
+        f.clear_color[0] = 20; f.clear_color[1] = 20; f.clear_color[2] = 25; f.clear_color[3] = 255;
+        std::memcpy(f.view, glm::value_ptr(view), 64);
+        std::memcpy(f.light_vp, glm::value_ptr(light_vp), 64);
+        std::memcpy(f.light_dir_world, glm::value_ptr(light_dir_world), 12);
+        std::memcpy(f.camera_pos, glm::value_ptr(scene_->viewer->position), 12);
+        f.bias_base = 0.0025f; f.bias_slope = 0.01f; f.max_velocity_px = 22.0f;      // SHADOW_BIAS_* :138-139, MB_MAX_PIXELS :149
+        f.flags = SHS_RT_USE_SHADOW | SHS_RT_PCF;
+        f.shading = 11;
+        ok(shs_rt_render_ibl_phong(dev_->ctx, &f, draws.data(), knobs.data(), (int32_t)draws.size()));
+        // 4. PASS2 over the planes the camera pass left on the device (MB_* :147-155)
+        void *color = nullptr, *depth = nullptr, *velocity = nullptr;
+        ok(shs_rt_device_targets(dev_->ctx, &color, &depth, &velocity));
+        shs_canvas_motion_blur_desc mb{};
+        mb.width = W; mb.height = H;
+        std::memcpy(mb.curr_view, glm::value_ptr(view), 64);
+        std::memcpy(mb.curr_proj, glm::value_ptr(proj), 64);
+        std::memcpy(mb.prev_view, glm::value_ptr(prev_view_), 64);
+        std::memcpy(mb.prev_proj, glm::value_ptr(prev_proj_), 64);
+        mb.samples = 12; mb.strength = 0.85f; mb.w_obj = 1.0f; mb.w_cam = 0.35f; mb.soft_knee = 1; mb.knee_px = 18.0f; mb.max_px = 22.0f;
+        ok(shs_canvas_motion_blur(dev_->ctx, &mb, static_cast<const uint8_t *>(color), static_cast<const float *>(depth),
+                                  static_cast<const float *>(velocity), static_cast<uint8_t *>(blurred_), SHS_CANVAS_DEVICE));
+        prev_view_ = view;
+        prev_proj_ = proj;
+    }
+
+    void ok(int rc) const {
+        if (rc != SHS_OK) throw std::runtime_error(shs_last_error(dev_->ctx));
+    }
+
+    glm::mat4 light_vp{1.0f};
+    glm::vec3 light_dir_world{0.4668f, -0.3487f, 0.8127f};   // (the shader normalises it)
+
+private:
+    SceneT *scene_;
+    Device *dev_;
+    void *blurred_;                  // W * H Color on the device: the frame the host presents
+    int lanes_, sm_, tile_;
+    shs_rt_sky sky_{};
+    glm::mat4 prev_view_{1.0f}, prev_proj_{1.0f};
+};
+
+// -----------------------------------------------------------------------------------------------------
 // Seam 1b, water -- hello-render-target/hello_water.cpp.
 //
 // Replaces RendererSystem::process there, five calls on the context stream with no resolve in between:

@@ -26,6 +26,9 @@
 // and of hello_per_object_motion_blur.cpp, hello_depth_of_field.cpp and hello_ping_pong.cpp: shs_rt_render_plain (that
 // unclipped raster again, per_object :391-455 / dof :524-574 / ping_pong :352-400, shadings 8 to 10, with the depth plane in
 // screen rows).
+// and of hello_ibl_skybox_optimized.cpp ("opt :line") and hello_ibl_skybox_xsimd.cpp ("xsimd :line"): shs_rt_render_ibl_phong
+// (their PASS1, opt :1125-1291 with fragment_shader_full opt :875-958, over the IBL of shs_rt_set_ibl) and
+// shs_rt_render_shadow_edge (the xsimd demo's PASS0, draw_triangle_tile_shadow_xsimd xsimd :1016-1191).
 // The host forms the matrix products the shaders form first -- u.view * u.model (vertex_shader_full :616),
 // u.light_vp * u.model (shadow_vertex_shader :764) -- and the normal matrix with the GLM restatement in
 // shs_glm.hpp.  Both passes are enqueued on the context stream; the shadow map, the planes and the records
@@ -81,6 +84,7 @@ struct PassExtras {
     const shs_rt_skybox_ibl_draw *ibl = nullptr;      // shading 4: the per-draw knobs
     const shs_rt_water_draw *water_draws = nullptr;   // shading 5: the per-draw flags
     const shs_rt_water *water = nullptr;              //   and the frame's uniforms
+    const shs_rt_ibl_phong_draw *ibl_phong = nullptr; // shading 11: the per-draw knobs
     // the tail table: the context's rt_h_pbr, or `bytes` (a few draws long and alive for one call, so the context holds
     // no copy): the sky-lit pass's RtIblDrawGPUs, or the water pass's RtWaterGPU and the flag words behind it
     std::vector<unsigned char> bytes;
@@ -146,6 +150,12 @@ int64_t build_draws(shs_ctx *ctx, const shs_rt_draw *draws, int32_t n, const flo
             const shs_rt_skybox_ibl_draw &k = x.ibl[i];
             x.append(shs_dev::RtIblDrawGPU{saturate(k.ibl_ambient), saturate(k.ibl_refl), k.ibl_f0, saturate(k.ibl_refl_mix)});
         }
+        if (x.ibl_phong) {
+            // the saturates of fragment_shader_full (opt :943-944) and the lod's roughness (opt :929), once per draw
+            const shs_rt_ibl_phong_draw &k = x.ibl_phong[i];
+            x.append(shs_dev::RtIblPhongDrawGPU{saturate(k.ibl_ambient), saturate(k.ibl_refl), k.ibl_f0, saturate(k.ibl_refl_mix), k.shininess,
+                                                std::sqrt(2.0f / (k.shininess + 2.0f)), {0.0f, 0.0f}});
+        }
         ctx->rt_h_draws.push_back(o);
         total += m.n_tris;
         if (total > (1 << 29)) {
@@ -155,6 +165,7 @@ int64_t build_draws(shs_ctx *ctx, const shs_rt_draw *draws, int32_t n, const flo
     }
     if (x.pbr) x.set_tail(ctx->rt_h_pbr.data(), ctx->rt_h_pbr.size() * sizeof(shs_dev::RtPbrDrawGPU), offsetof(shs_dev::RtParams, pbr_draws));
     if (x.ibl) x.set_tail(x.bytes.data(), x.bytes.size(), offsetof(shs_dev::RtParams, ibl_draws));
+    if (x.ibl_phong) x.set_tail(x.bytes.data(), x.bytes.size(), offsetof(shs_dev::RtParams, ibl_phong_draws));
     return total;
 }
 
@@ -258,7 +269,8 @@ void fill_pcss(Args &a, const shs_rt_pcss &c) {
     a.pcss_taps = c.pcf_samples;
 }
 
-int upload_and_launch(shs_ctx *ctx, shs_dev::RtParams &p, bool shadow_pass, int shading, int sky_model, const PassExtras &x) {
+int upload_and_launch(shs_ctx *ctx, shs_dev::RtParams &p, bool shadow_pass, int shading, int sky_model, const PassExtras &x,
+                      bool edge_shadow = false) {
     const size_t nd = ctx->rt_h_draws.size();
     // the pass's tail table rides behind the draw table (sizeof(RtDrawGPU) is a multiple of 16): one copy
     static_assert(sizeof(shs_dev::RtDrawGPU) % 16 == 0, "the material table behind the draws is read as float4s");
@@ -294,14 +306,15 @@ int upload_and_launch(shs_ctx *ctx, shs_dev::RtParams &p, bool shadow_pass, int 
     p.recs = ctx->rt_recs.p;
     p.vary = ctx->rt_vary.p;
     p.stats = ctx->rt_stats.p;
-    HIP_TRY(ctx, shs_internal::launch_canvas_rt(p, shadow_pass, shading, ctx->stream, sky_model));
+    HIP_TRY(ctx, shs_internal::launch_canvas_rt(p, shadow_pass, shading, ctx->stream, sky_model, edge_shadow));
     return SHS_OK;
 }
 
 // PASS1 of the six demos: x empty for shading 0 / 1 (shs_rt_render), x.pbr for shading 2 (shs_rt_render_pbr) and 3
 // (shs_rt_render_pbr_soft), x.ibl for shading 4 (shs_rt_render_skybox_ibl), x.water_draws and x.water for shading 5
 // (shs_rt_render_water); and the one camera pass of the three unclipped demos, x empty, for shadings 6 and 7
-// (shs_rt_render_motion) and 8 to 10 (shs_rt_render_plain).  Nothing of the context changes before the last rejection.
+// (shs_rt_render_motion) and 8 to 10 (shs_rt_render_plain); and PASS1 of the two later IBL demos, x.ibl_phong for shading 11
+// (shs_rt_render_ibl_phong).  Nothing of the context changes before the last rejection.
 int render_camera(shs_ctx *ctx, const shs_rt_frame *f, const shs_rt_draw *draws, int32_t n_draws, PassExtras x) {
     if (!size_ok(ctx, f->width, f->height, f->ref_tile_w, f->ref_tile_h)) return SHS_ERR_INVALID;
     if (f->flags & ~(SHS_RT_USE_SHADOW | SHS_RT_PCF | SHS_RT_PREQUANT)) {
@@ -353,6 +366,10 @@ int render_camera(shs_ctx *ctx, const shs_rt_frame *f, const shs_rt_draw *draws,
         if (rr) return rr;
         p.rot = ctx->rt_rot.p;
         fill_pcss(p, ctx->rt_pcss);
+    }
+    if (f->shading == 11) {   // u.ibl: the levels of shs_rt_set_ibl, as shadings 2 and 3 read them
+        p.ibl = ctx->rt_ibl_mips > 0 ? ctx->rt_ibl.p : nullptr;
+        p.ibl_mips = ctx->rt_ibl_mips;
     }
     if (f->shading == 2 || f->shading == 3) {
         if (ensure_srgb_table(ctx)) return SHS_ERR_HIP;
@@ -434,8 +451,10 @@ int render_pbr(shs_ctx *ctx, const shs_rt_frame *f, const shs_rt_draw *draws, co
 
 extern "C" {
 
-int shs_rt_render_shadow(shs_ctx *ctx, int32_t w, int32_t h, int32_t ref_tile_w, int32_t ref_tile_h, const float light_vp[16],
-                         const shs_rt_draw *casters, int32_t n_casters) {
+// PASS0 into the context's shadow map.  simd_lanes 0: draw_triangle_tile_shadow (shs_rt_render_shadow); else
+// hello_ibl_skybox_xsimd.cpp's draw_triangle_tile_shadow_xsimd with that batch size (shs_rt_render_shadow_edge).
+static int render_shadow(shs_ctx *ctx, int32_t w, int32_t h, int32_t ref_tile_w, int32_t ref_tile_h, const float light_vp[16],
+                         const shs_rt_draw *casters, int32_t n_casters, int32_t simd_lanes) {
     if (!ctx || !light_vp || n_casters < 0 || (n_casters > 0 && !casters)) return SHS_ERR_INVALID;
     if (!size_ok(ctx, w, h, ref_tile_w, ref_tile_h)) return SHS_ERR_INVALID;
     if (set_dev(ctx)) return SHS_ERR_HIP;
@@ -451,8 +470,9 @@ int shs_rt_render_shadow(shs_ctx *ctx, int32_t w, int32_t h, int32_t ref_tile_w,
     p.n_tris = (int32_t)n_tris;
     p.n_recs = (int32_t)n_tris;
     p.depth = ctx->rt_shadow.p;
+    p.simd_lanes = simd_lanes;
     // the shadow pass shares the stats words with the camera pass: its own count is not reported
-    const int rc = upload_and_launch(ctx, p, true, 0, SHS_RT_SKY_NONE, none);
+    const int rc = upload_and_launch(ctx, p, true, 0, SHS_RT_SKY_NONE, none, simd_lanes != 0);
     if (rc) return rc;
     ctx->rt_sw = w;
     ctx->rt_sh = h;
@@ -460,11 +480,52 @@ int shs_rt_render_shadow(shs_ctx *ctx, int32_t w, int32_t h, int32_t ref_tile_w,
     return SHS_OK;
 }
 
+int shs_rt_render_shadow(shs_ctx *ctx, int32_t w, int32_t h, int32_t ref_tile_w, int32_t ref_tile_h, const float light_vp[16],
+                         const shs_rt_draw *casters, int32_t n_casters) {
+    return render_shadow(ctx, w, h, ref_tile_w, ref_tile_h, light_vp, casters, n_casters, 0);
+}
+
+int shs_rt_render_shadow_edge(shs_ctx *ctx, int32_t w, int32_t h, int32_t ref_tile_w, int32_t ref_tile_h, const float light_vp[16],
+                              const shs_rt_draw *casters, int32_t n_casters, int32_t simd_lanes) {
+    if (!ctx) return SHS_ERR_INVALID;
+    if (simd_lanes != 1 && simd_lanes != 2 && simd_lanes != 4 && simd_lanes != 8 && simd_lanes != 16) {
+        ctx->err = "shs_rt_render_shadow_edge: simd_lanes " + std::to_string(simd_lanes) + " (xsimd::batch<float>::size: 1, 2, 4, 8 or 16)";
+        return SHS_ERR_INVALID;
+    }
+    return render_shadow(ctx, w, h, ref_tile_w, ref_tile_h, light_vp, casters, n_casters, simd_lanes);
+}
+
+int shs_rt_render_ibl_phong(shs_ctx *ctx, const shs_rt_frame *f, const shs_rt_draw *draws, const shs_rt_ibl_phong_draw *ibl_draws,
+                            int32_t n_draws) {
+    if (!ctx || !f || n_draws < 0 || (n_draws > 0 && (!draws || !ibl_draws))) return SHS_ERR_INVALID;
+    if (f->shading != 11) {
+        ctx->err = "shs_rt_render_ibl_phong: shading " + std::to_string(f->shading) +
+                   " (11: hello_ibl_skybox_optimized.cpp's and hello_ibl_skybox_xsimd.cpp's fragment_shader_full)";
+        return SHS_ERR_INVALID;
+    }
+    for (int32_t i = 0; i < n_draws; ++i) {
+        const shs_rt_ibl_phong_draw &k = ibl_draws[i];
+        if (!(std::isfinite(k.ibl_ambient) && std::isfinite(k.ibl_refl) && std::isfinite(k.ibl_f0) && std::isfinite(k.ibl_refl_mix) &&
+              std::isfinite(k.shininess))) {
+            ctx->err = "shs_rt_render_ibl_phong: a non-finite knob";
+            return SHS_ERR_INVALID;
+        }
+        if (k.shininess < 0.0f) {
+            ctx->err = "shs_rt_render_ibl_phong: shininess < 0";
+            return SHS_ERR_INVALID;
+        }
+    }
+    static const shs_rt_ibl_phong_draw none{};
+    PassExtras x;
+    x.ibl_phong = n_draws > 0 ? ibl_draws : &none;
+    return render_camera(ctx, f, draws, n_draws, std::move(x));
+}
+
 int shs_rt_render(shs_ctx *ctx, const shs_rt_frame *f, const shs_rt_draw *draws, int32_t n_draws) {
     if (!ctx || !f || n_draws < 0 || (n_draws > 0 && !draws)) return SHS_ERR_INVALID;
     if (f->shading != 0 && f->shading != 1) {
         ctx->err = "render-target frame: shading " + std::to_string(f->shading) +
-                   " (0: fragment_shader_full, 1: fragment_shader_softshadow; 2, fragment_shader_pbr, goes through shs_rt_render_pbr)";
+                   " (0: fragment_shader_full, 1: fragment_shader_softshadow; 2, fragment_shader_pbr, goes through shs_rt_render_pbr; 11, the later IBL demos' fragment_shader_full, through shs_rt_render_ibl_phong)";
         return SHS_ERR_INVALID;
     }
     return render_camera(ctx, f, draws, n_draws, PassExtras{});

@@ -54,6 +54,16 @@
 //   shading 9  dof :60-120 and shading 10 ping :65-98: no velocity; k_rt_raster<false, 11> for both.  Shading 10's depth is
 //          clip z / clip w per corner (ping :389): k_rt_setup_motion<true>.
 //          All launched by shs_rt_render_plain.
+// and for hello_ibl_skybox_optimized.cpp ("opt :line") and hello_ibl_skybox_xsimd.cpp ("xsimd :line"), whose camera raster
+// (opt :1125-1291) is the hard demo's and whose shader is one text in both files:
+//   shading 11 fragment_shader_full (opt :875-958): Blinn-Phong with a per-object exponent under the 2x2 PCF on the direct
+//          term alone, plus the irradiance cubemap along N and the prefiltered-specular mips along reflect(-V, N) at a lod
+//          taken from the exponent (RtParams::ibl, as shading 2).  k_rt_raster<false, 12>, launched by
+//          shs_rt_render_ibl_phong, is shade_pixel_ibl_phong.
+//   the xsimd demo's PASS0  draw_triangle_tile_shadow_xsimd (xsimd :1016-1191): edge functions with inclusive tests, back
+//          faces dropped, a floor / ceil box, and two associations of the edge sum within a row (the SIMD body and the
+//          scalar tail).  k_rt_setup_edge and k_rt_raster<true, RT_SHADOW_EDGE>, launched by shs_rt_render_shadow_edge.
+//          The optimized demo's PASS0 (opt :1065-1108) is the hard demo's.
 //   the background  skybox_background_pass (pbr :733-799; the same routine in hello_pbr_light_shafts.cpp and
 //          hello_ibl_skybox.cpp) over the legacy AnalyticSky / CubeMapSky of hello-shs-renderer/shs_renderer.hpp:
 //          k_rt_sky<MODEL, ENCODE>, a pass of its own after k_rt_raster when a sky is bound (shs_rt_set_sky), which
@@ -418,6 +428,53 @@ __global__ __launch_bounds__(256) void k_rt_setup_motion(const RtParams p) {
     wave_count(&p.stats[3], ok);
 }
 
+// The setup of the edge-function shadow pass: one lane per caster triangle, shadow_vertex_shader (xsimd :995-1000),
+// clip_to_shadow_screen (:1006-1014) and what build_shadow_tri (:1031-1076) forms without the job: the area rule (back
+// faces dropped), 1 / area, the edge functions and (int)floor / (int)ceil of the extent.  Those two conversions are
+// undefined in the reference for a value that is not finite or does not fit an int: a triangle with such a screen
+// corner is dropped here (include/shs_gpu.h says so).
+__global__ __launch_bounds__(256) void k_rt_setup_edge(const RtParams p) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= p.n_tris) return;
+    const int d = find_draw(p, t);
+    const RtDrawGPU &dr = p.draws[d];
+    const float *pos = dr.pos + 9 * (size_t)(t - dr.base);
+    RtEdgeRec r{};
+    r.draw = d;
+    bool ok = true;
+    float sx[3], sy[3], sz[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        float cx, cy, cz, cw;
+        m4p(dr.zm, pos[3 * i], pos[3 * i + 1], pos[3 * i + 2], cx, cy, cz, cw);
+        if (fabsf(cw) < 1e-6f) ok = false;
+        const float nx = cx / cw, ny = cy / cw;
+        sx[i] = (nx * 0.5f + 0.5f) * (float)(p.W - 1);
+        sy[i] = (1.0f - (ny * 0.5f + 0.5f)) * (float)(p.H - 1);
+        sz[i] = cz / cw;
+        if (!(fabsf(sx[i]) < 2147483648.0f) || !(fabsf(sy[i]) < 2147483648.0f)) ok = false;   // (a NaN fails both)
+    }
+    if (ok) {
+        const float area = (sx[1] - sx[0]) * (sy[2] - sy[0]) - (sy[1] - sy[0]) * (sx[2] - sx[0]);
+        if (fabsf(area) < 1e-8f || area <= 0.0f) ok = false;
+        r.inv_area = 1.0f / area;
+    }
+    if (ok) {
+        r.fminx = (int)floorf(fminf(fminf(sx[0], sx[1]), sx[2]));
+        r.cmaxx = (int)ceilf(fmaxf(fmaxf(sx[0], sx[1]), sx[2]));
+        r.fminy = (int)floorf(fminf(fminf(sy[0], sy[1]), sy[2]));
+        r.cmaxy = (int)ceilf(fmaxf(fmaxf(sy[0], sy[1]), sy[2]));
+        r.gbx = pack16(clampi(r.fminx, 0, p.W - 1), clampi(r.cmaxx, 0, p.W - 1));
+        r.gby = pack16(clampi(r.fminy, 0, p.H - 1), clampi(r.cmaxy, 0, p.H - 1));
+        r.A0 = sy[0] - sy[1]; r.B0 = sx[1] - sx[0]; r.C0 = sx[0] * sy[1] - sy[0] * sx[1];
+        r.A1 = sy[1] - sy[2]; r.B1 = sx[2] - sx[1]; r.C1 = sx[1] * sy[2] - sy[1] * sx[2];
+        r.A2 = sy[2] - sy[0]; r.B2 = sx[0] - sx[2]; r.C2 = sx[2] * sy[0] - sy[2] * sx[0];
+        r.z0 = sz[0]; r.z1 = sz[1]; r.z2 = sz[2];
+        r.flags = RT_VALID;
+    }
+    store_rec(&p.recs[t], reinterpret_cast<const RtRec &>(r));
+}
+
 // ---- k_rt_raster -----------------------------------------------------------------------------------
 
 // The reference's visited interval of one axis inside the job [tmin, tmax] (:806-815, :822): the float bbox
@@ -445,19 +502,50 @@ __device__ __forceinline__ bool axis_meets(float mn, float mx, int g0, int g1, i
 // The camera pass's instantiation k_rt_raster<false, rt_variant(shading, sky model)> of shs_rt_frame::shading: shadings 0
 // to 3 are their own number, shading 4 is three instantiations, one per sky model its shader samples (RT_SKY_*: 4 to 6),
 // and shadings 5 to 8 follow them; shadings 9 and 10 share one instantiation (they differ in the setup's depth alone).
+// Shading 11 follows them: it does not read the sky, so it is one instantiation.
 // The kernel's ladder and the launcher both go through this one mapping.
-constexpr int RT_VARIANTS = 12;
+constexpr int RT_VARIANTS = 13;
 constexpr int rt_variant(int shading, int sky_model) {
-    return shading >= 9 ? 11 : shading >= 5 ? shading + 2 : shading == 4 ? 4 + sky_model : shading;
+    return shading == 11 ? 12 : shading >= 9 ? 11 : shading >= 5 ? shading + 2 : shading == 4 ? 4 + sky_model : shading;
 }
 // Shadings 6 to 10 sit behind the unclipped raster: screen-linear varyings, so no fragment loses its colour to invw_sum
-constexpr bool rt_unclipped(int variant) { return variant >= rt_variant(6, 0); }
+constexpr bool rt_unclipped(int variant) { return variant >= rt_variant(6, 0) && variant <= rt_variant(10, 0); }
 // Shadings 8 to 10 (the three plain demos) hand the ZBuffer the screen row: their depth plane is stored at py * W + px
-constexpr bool rt_screen_depth(int variant) { return variant >= rt_variant(8, 0); }
+constexpr bool rt_screen_depth(int variant) { return variant >= rt_variant(8, 0) && variant <= rt_variant(10, 0); }
+// k_rt_raster<true, RT_SHADOW_EDGE>: the edge-function shadow pass (<true, 0> is the barycentric one)
+constexpr int RT_SHADOW_EDGE = 1;
 
-// VARIANT: the fragment shader, a compile-time choice (the shadow pass ignores it)
+// draw_triangle_tile_shadow_xsimd (xsimd :1078-1191) at one texel (x, y) of the job [tminx, tmaxx] x [tminy, tmaxy], over a staged RtEdgeRec:
+// the depth the triangle offers the texel, or FLT_MAX (no write: the map holds at most FLT_MAX) where the job's box, an edge
+// or the z range rejects it.  The box is the extent clamped to the job and then to the map (:1040-1050); inside it a row
+// is walked from the box's min_x in groups of simd_lanes while a whole group fits, whose texels sum an edge function as
+// A fx + (B fy + C) (:1125-1141); the row's remaining texels sum it as (A fx + B fy) + C (:1173-1175).
+__device__ __forceinline__ float edge_texel(const float4 *rec, const RtParams &p, int x, int y, int tminx, int tmaxx, int tminy, int tmaxy) {
+    const float4 a3 = rec[3], a4 = rec[4];   // (z2, flags, fminx, cmaxx) (fminy, cmaxy, gbx, gby)
+    const int min_x = clampi(max(tminx, (int)__float_as_uint(a3.z)), 0, p.W - 1);
+    const int max_x = clampi(min(tmaxx, (int)__float_as_uint(a3.w)), 0, p.W - 1);
+    const int min_y = clampi(max(tminy, (int)__float_as_uint(a4.x)), 0, p.H - 1);
+    const int max_y = clampi(min(tmaxy, (int)__float_as_uint(a4.y)), 0, p.H - 1);
+    if (x < min_x || x > max_x || y < min_y || y > max_y) return FLT_MAX;   // (an empty box holds no texel)
+    const float4 a0 = rec[0], a1 = rec[1], a2 = rec[2];   // (A0 B0 C0 A1) (B1 C1 A2 B2) (C2 inv_area z0 z1)
+    // the texel's lane group starts at xs; simd_lanes is a power of two
+    const int xs = min_x + ((x - min_x) & ~(p.simd_lanes - 1));
+    const bool body = xs + p.simd_lanes - 1 <= max_x;
+    const float fx = (float)x + 0.5f, fy = (float)y + 0.5f;
+    const float e0 = body ? a0.x * fx + (a0.y * fy + a0.z) : (a0.x * fx + a0.y * fy) + a0.z;
+    const float e1 = body ? a0.w * fx + (a1.x * fy + a1.y) : (a0.w * fx + a1.x * fy) + a1.y;
+    const float e2 = body ? a1.z * fx + (a1.w * fy + a2.x) : (a1.z * fx + a1.w * fy) + a2.x;
+    if (!(e0 >= 0.0f && e1 >= 0.0f && e2 >= 0.0f)) return FLT_MAX;
+    const float w0 = e1 * a2.y, w1 = e2 * a2.y, w2 = e0 * a2.y;
+    const float z = (w0 * a2.z + w1 * a2.w) + w2 * a3.x;
+    return (z >= 0.0f && z <= 1.0f) ? z : FLT_MAX;
+}
+
+// VARIANT: the fragment shader, a compile-time choice; of the shadow pass, the raster rule (0: the barycentric one of
+// draw_triangle_tile_shadow, RT_SHADOW_EDGE: the edge functions above)
 template <bool SHADOW, int VARIANT = 0>
 __global__ __launch_bounds__(256) void k_rt_raster(const RtParams p) {
+    constexpr bool EDGE = SHADOW && VARIANT == RT_SHADOW_EDGE;
     __shared__ float4 s_rec[RT_CHUNK * 6];
     __shared__ int32_t s_id[RT_CHUNK];
     __shared__ int s_wave[4];
@@ -488,9 +576,14 @@ __global__ __launch_bounds__(256) void k_rt_raster(const RtParams p) {
             const float4 *g = reinterpret_cast<const float4 *>(&p.recs[ri]);
             const float4 q3 = g[3], q4 = g[4];   // (z2, flags, minx, maxx) (miny, maxy, gbx, gby)
             const uint32_t gbx = __float_as_uint(q4.z), gby = __float_as_uint(q4.w);
-            cand = (__float_as_uint(q3.y) & RT_VALID) && lo16(gbx) <= gx1 && hi16(gbx) >= gx0 && lo16(gby) <= gy1 &&
-                   hi16(gby) >= gy0 && axis_meets(q3.z, q3.w, gx0, gx1, j0x, j1x, p.tile_w, p.W) &&
-                   axis_meets(q4.x, q4.y, gy0, gy1, j0y, j1y, p.tile_h, p.H);
+            if constexpr (EDGE) {
+                // every job's box lies in the extent clamped to the map (RtEdgeRec::gbx, gby): a superset of the visits
+                cand = (__float_as_uint(q3.y) & RT_VALID) && lo16(gbx) <= gx1 && hi16(gbx) >= gx0 && lo16(gby) <= gy1 && hi16(gby) >= gy0;
+            } else {
+                cand = (__float_as_uint(q3.y) & RT_VALID) && lo16(gbx) <= gx1 && hi16(gbx) >= gx0 && lo16(gby) <= gy1 &&
+                       hi16(gby) >= gy0 && axis_meets(q3.z, q3.w, gx0, gx1, j0x, j1x, p.tile_w, p.W) &&
+                       axis_meets(q4.x, q4.y, gy0, gy1, j0y, j1y, p.tile_h, p.H);
+            }
         }
         const unsigned long long m = __ballot(cand);
         if (lane == 0) s_wave[wave] = __popcll(m);
@@ -509,7 +602,17 @@ __global__ __launch_bounds__(256) void k_rt_raster(const RtParams p) {
             s_id[slot] = ri;
         }
         __syncthreads();
-        if (live) {
+        if constexpr (EDGE) {
+            if (live) {
+                // the texel's job, inclusive (xsimd :1726-1728): the same for every record
+                const int jx0 = jx * p.tile_w, jx1 = min((jx + 1) * p.tile_w, p.W) - 1;
+                const int jy0 = jy * p.tile_h, jy1 = min((jy + 1) * p.tile_h, p.H) - 1;
+                for (int c = 0; c < n_c; ++c) {
+                    const float z = edge_texel(&s_rec[c * 6], p, px, py, jx0, jx1, jy0, jy1);
+                    if (z < best) best = z;
+                }
+            }
+        } else if (live) {
             for (int c = 0; c < n_c; ++c) {
                 const float4 a3 = s_rec[c * 6 + 3], a4 = s_rec[c * 6 + 4];
                 int lo, hi;
@@ -566,6 +669,8 @@ __global__ __launch_bounds__(256) void k_rt_raster(const RtParams p) {
         if (sid >= 0) shade_pixel_pbr<false>(p, sid, su, sv, sw, px, py, rgba, vel, pq);
     } else if constexpr (VARIANT == rt_variant(3, 0)) {
         if (sid >= 0) shade_pixel_pbr<true>(p, sid, su, sv, sw, px, py, rgba, vel, pq);
+    } else if constexpr (VARIANT == rt_variant(11, 0)) {
+        if (sid >= 0) shade_pixel_ibl_phong(p, sid, su, sv, sw, rgba, vel, pq);
     } else if constexpr (VARIANT == rt_variant(5, 0)) {
         if (sid >= 0) shade_pixel_water(p, sid, su, sv, sw, rgba, vel, pq);
     } else if constexpr (VARIANT >= rt_variant(4, RT_SKY_NONE)) {
@@ -714,11 +819,12 @@ static bool launch_camera_raster(int variant, std::integer_sequence<int, V...>, 
     return ((variant == V ? (launch_camera_variant<V>(tiles, s, p), true) : false) || ...);
 }
 
-hipError_t launch_canvas_rt(const shs_dev::RtParams &p, bool shadow_pass, int shading, hipStream_t s, int sky_model) {
+hipError_t launch_canvas_rt(const shs_dev::RtParams &p, bool shadow_pass, int shading, hipStream_t s, int sky_model, bool edge_shadow) {
     using namespace shs_dev;
     if (p.n_tris > 0) {
         const int grid = (p.n_tris + 255) / 256;
-        if (shadow_pass) hipLaunchKernelGGL(k_rt_setup<true>, dim3(grid), dim3(256), 0, s, p);
+        if (shadow_pass && edge_shadow) hipLaunchKernelGGL(k_rt_setup_edge, dim3(grid), dim3(256), 0, s, p);
+        else if (shadow_pass) hipLaunchKernelGGL(k_rt_setup<true>, dim3(grid), dim3(256), 0, s, p);
         else if (shading == 10) hipLaunchKernelGGL(k_rt_setup_motion<true>, dim3(grid), dim3(256), 0, s, p);
         else if (rt_unclipped(rt_variant(shading, sky_model))) hipLaunchKernelGGL(k_rt_setup_motion<false>, dim3(grid), dim3(256), 0, s, p);
         else hipLaunchKernelGGL(k_rt_setup<false>, dim3(grid), dim3(256), 0, s, p);
@@ -726,7 +832,8 @@ hipError_t launch_canvas_rt(const shs_dev::RtParams &p, bool shadow_pass, int sh
         if (e != hipSuccess) return e;
     }
     const int tiles = ((p.W + RT_TW - 1) / RT_TW) * ((p.H + RT_TH - 1) / RT_TH);
-    if (shadow_pass) hipLaunchKernelGGL(k_rt_raster<true>, dim3(tiles), dim3(256), 0, s, p);
+    if (shadow_pass && edge_shadow) hipLaunchKernelGGL((k_rt_raster<true, RT_SHADOW_EDGE>), dim3(tiles), dim3(256), 0, s, p);
+    else if (shadow_pass) hipLaunchKernelGGL(k_rt_raster<true>, dim3(tiles), dim3(256), 0, s, p);
     else if (!launch_camera_raster(rt_variant(shading, sky_model), std::make_integer_sequence<int, RT_VARIANTS>{}, tiles, s, p))
         return hipErrorInvalidValue;   // (no such instantiation: the entries of shs_abi_canvas_rt.cpp reject the shading)
     return hipGetLastError();

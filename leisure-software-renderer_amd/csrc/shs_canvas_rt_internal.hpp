@@ -11,7 +11,9 @@
 // hello_glowing_star.cpp (one raster without the near-plane clip, screen-linear varyings, back faces culled; shadings 6
 // and 7 through shs_rt_render_motion, the latter with a fourth plane, spec01), and of hello_per_object_motion_blur.cpp,
 // hello_depth_of_field.cpp and hello_ping_pong.cpp (that raster again with the depth plane in screen rows; shadings 8 to 10
-// through shs_rt_render_plain).
+// through shs_rt_render_plain), and of hello_ibl_skybox_optimized.cpp and hello_ibl_skybox_xsimd.cpp (the hard demo's
+// camera raster with an IBL-lit Blinn-Phong shader of a per-draw exponent, shading 11 through shs_rt_render_ibl_phong, and
+// the latter's edge-function shadow pass, shs_rt_render_shadow_edge).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -37,6 +39,24 @@ struct alignas(16) RtRec {
 };
 static_assert(sizeof(RtRec) == 96, "RtRec is staged as six float4s");
 constexpr uint32_t RT_VALID = 1u, RT_NEG_AREA = 2u;
+
+// The record of the edge-function shadow pass (hello_ibl_skybox_xsimd.cpp's ShadowTriProcessed :1016-1029 before the job's
+// clamp) in an RtRec's slot, the same six float4s with `flags` where RtRec has it: the three edge functions E = A x + B y + C
+// (:1071-1073), 1 / area, the corners' ndc z, (int)floor / (int)ceil of the corners' extent (:1040-1043 before std::max /
+// std::min with the job) and that box clamped to the map, which every job's box lies in.
+struct alignas(16) RtEdgeRec {
+    float A0, B0, C0, A1;
+    float B1, C1, A2, B2;
+    float C2, inv_area, z0, z1;
+    float z2;
+    uint32_t flags;                  // RT_VALID
+    int32_t fminx, cmaxx;            // (int)floor(min x), (int)ceil(max x)
+    int32_t fminy, cmaxy;
+    uint32_t gbx, gby;               // {fminx, cmaxx} / {fminy, cmaxy} clamped to the map, packed int16 (lo | hi << 16)
+    uint32_t pad[3];
+    int32_t draw;
+};
+static_assert(sizeof(RtEdgeRec) == sizeof(RtRec), "RtEdgeRec is staged in RtRec's six float4s");
 
 // The corners' varyings (VaryingsFull) of a camera-pass sub-triangle, read by the pixels it shades.
 struct alignas(16) RtVary {
@@ -82,6 +102,20 @@ struct alignas(16) RtIblDrawGPU {
     float refl_mix;                  // saturate(ibl_refl_mix)
 };
 static_assert(sizeof(RtIblDrawGPU) == 16, "RtIblDrawGPU: one float4");
+
+// The per-draw knobs of hello_ibl_skybox_optimized.cpp's Uniforms (:757-764) after the three saturates of its
+// fragment_shader_full (:943-944) and the lod's roughness (:929), which the host forms with the reference's own float
+// operations; the products stay in the shader.  32 B: two dwordx4 loads of a shaded pixel.
+struct alignas(16) RtIblPhongDrawGPU {
+    float ambient;                   // saturate(ibl_ambient)
+    float refl;                      // saturate(ibl_refl)
+    float f0;                        // ibl_f0
+    float refl_mix;                  // saturate(ibl_refl_mix)
+    float shininess;                 // the exponent of the direct specular term
+    float rough;                     // std::sqrt(2.0f / (shininess + 2.0f))
+    float pad[2];
+};
+static_assert(sizeof(RtIblPhongDrawGPU) == 32, "RtIblPhongDrawGPU: two float4s");
 
 // The EnvIBL levels (shs/resources/ibl.hpp:21-59) in one allocation of float4s: RT_IBL_LEVELS headers, then the
 // texels, rgb padded to 16 B so that a bilinear corner is one dwordx4 load.  Header l holds, as int bits,
@@ -160,6 +194,7 @@ struct RtParams {
     const float4 *rot;               // per screen pixel py * W + px: {cos(ang), sin(ang), cos(ang2), sin(ang2)}
     float pcss_light, pcss_search, pcss_min, pcss_max, pcss_eps;   // shs_rt_pcss
     int32_t pcss_blockers, pcss_taps;
+    int32_t simd_lanes;              // the edge-function shadow pass only: xsimd::batch<float>::size of the reference's build
     // shadings 2 and 3 only (appended likewise)
     const RtPbrDrawGPU *pbr_draws;   // element i goes with draws[i]
     const float *srgb_lut;           // 256 floats: pow(c / 255, 2.2) with the host's libm
@@ -168,12 +203,19 @@ struct RtParams {
     float pbr_exposure, pbr_intensity;   // shs_rt_pbr (min_roughness is folded into RtPbrDrawGPU::roughness)
     // shading 4 only (appended likewise)
     RtSkyModel sky;                  // u.sky: the sky of shs_rt_set_sky (read by the analytic / cubemap instantiations)
-    const RtIblDrawGPU *ibl_draws;   // element i goes with draws[i]
+    // and shading 11, which reads ibl / ibl_mips above as shadings 2 and 3 do: one pointer's slot for the two tables, and
+    // simd_lanes in the padding behind pcss_taps, because the struct's size is part of every kernel that takes it
+    // (k_rt_setup<true> allocates two more registers when it grows)
+    union {
+        const RtIblDrawGPU *ibl_draws;              // shading 4: element i goes with draws[i]
+        const RtIblPhongDrawGPU *ibl_phong_draws;   // shading 11: likewise
+    };
     // shading 5 only (appended likewise): one pointer, the rest rides behind the draw table with the per-call upload
     const RtWaterGPU *water;
     // shading 7 only (appended likewise): RT_ColorDepthVelocitySpec::spec in canvas rows, 0 where no fragment is shown
     float *spec;
 };
+static_assert(sizeof(RtParams) == 512, "RtParams: new members go into its padding or share a slot (see ibl_draws)");
 
 // sample_cubemap_linear_vec(env_irradiance, dir) and sample_prefiltered_spec_trilinear(spec, dir, lod) for a list
 // of directions (shs_rt_ibl_samples): everything on the device
@@ -240,8 +282,10 @@ hipError_t launch_sky_samples(const shs_dev::RtSkySamples &q, int model, hipStre
 // the screen-linear raster of those demos, as are 8: hello_per_object_motion_blur.cpp's velocity_fragment_shader, 9:
 // hello_depth_of_field.cpp's and 10: hello_ping_pong.cpp's blinn_phong_fragment_shader, whose depth plane is stored in
 // screen rows); sky_model: u.sky of shading 4 (RT_SKY_*), which chooses among its three
-// instantiations
-hipError_t launch_canvas_rt(const shs_dev::RtParams &p, bool shadow_pass, int shading, hipStream_t s, int sky_model = 0);
+// instantiations; 11: hello_ibl_skybox_optimized.cpp's / hello_ibl_skybox_xsimd.cpp's fragment_shader_full behind the clipped
+// raster of shading 0.  edge_shadow (with shadow_pass): hello_ibl_skybox_xsimd.cpp's edge-function PASS0 (p.simd_lanes)
+hipError_t launch_canvas_rt(const shs_dev::RtParams &p, bool shadow_pass, int shading, hipStream_t s, int sky_model = 0,
+                            bool edge_shadow = false);
 hipError_t launch_pcss_samples(const shs_dev::RtPcssSamples &q, hipStream_t s);
 hipError_t launch_ibl_samples(const shs_dev::RtIblSamples &q, hipStream_t s);
 hipError_t launch_water_samples(const shs_dev::RtWaterSamples &q, hipStream_t s);

@@ -357,6 +357,64 @@ __device__ void shade_pixel_ibl(const RtParams &p, int32_t id, float u, float v,
     pq = make_float4(pr, pg, pb, shadow);
 }
 
+// ---- hello_ibl_skybox_optimized.cpp ("opt :line"; hello_ibl_skybox_xsimd.cpp carries the same text at :822-911): Blinn-Phong
+// with a per-object exponent, lit by the irradiance cubemap and the prefiltered-specular mip chain -----------------
+
+// glm::pow(x, shininess) with the exponent a per-draw datum: one double pow, rounded to float once.  The double
+// result's error is some 2^-52 of its value, 2^28 times below half a float ulp, so the float is the correctly rounded
+// power but where the exact value lies that close to a rounding boundary; the reference's powf is the host libm's, as
+// close to correct.  pow(x, 0) is 1 for every x, a NaN included, and pow(0, s > 0) is 0, as powf has them.
+__device__ __forceinline__ float pow_var(float x, float e) { return (float)pow((double)x, (double)e); }
+
+// The shown fragment of the demo's camera pass (opt :1125-1291: the hard demo's raster, interpolation and velocity)
+// through fragment_shader_full (opt :875-958): the hard demo's Blinn-Phong with the draw's shininess, the specular term
+// not taking the base colour, under the hard demo's shadow lookup on the direct term alone; then the irradiance along N
+// and the prefiltered specular along reflect(-V, N) at lod = sqrt(2 / (shininess + 2)) * (mips - 1), split by Schlick's F
+// into kd = 1 - F and ks = F.  The file-local CubeMapF samplers (opt :246-330, :504-518) are ibl.hpp:215-286 but for
+// Math::saturate where those have std::clamp, which keep a NaN alike: ibl_sample_cube / ibl_sample_trilinear.  The
+// direct term and the shadow lookup are finished (amb + direct, three floats) before the IBL gathers start.
+__device__ void shade_pixel_ibl_phong(const RtParams &p, int32_t id, float u, float v, float w, uint32_t &rgba, float2 &vel, float4 &pq) {
+    const Frag f(p, id, u, v, w);
+    vel = frag_velocity(p, f.y, u, v, w);
+    const f3 wp = f.world();
+    const f3 N = f.normal();
+    const f3 L = {p.L[0], p.L[1], p.L[2]};
+    const f3 V = normalize3(sub3(f3{p.cam[0], p.cam[1], p.cam[2]}, wp));
+    const float4 kn = reinterpret_cast<const float4 *>(&p.ibl_phong_draws[f.r.draw])[0];   // ambient, refl, f0, refl_mix
+    const float4 ks = reinterpret_cast<const float4 *>(&p.ibl_phong_draws[f.r.draw])[1];   // shininess, rough
+    const float ndotl = dot3(N, L);
+    const float diffuse = g_max(ndotl, 0.0f) * 1.0f;
+    const f3 H = normalize3(add3(L, V));
+    const float spec = pow_var(g_max(dot3(N, H), 0.0f), ks.x);
+    const float specular = (0.45f * spec) * 1.0f;
+    const f3 base = frag_base01(f);
+    float shadow = 1.0f;
+    if (p.shadow) shadow = shadow_factor(p, wp, ndotl);
+    // amb + direct: 0.18 * base + shadow * (diffuse * base + specular)
+    f3 c = {0.18f * base.x + shadow * (diffuse * base.x + specular), 0.18f * base.y + shadow * (diffuse * base.y + specular),
+            0.18f * base.z + shadow * (diffuse * base.z + specular)};
+    f3 ibl_diffuse = {0.0f, 0.0f, 0.0f}, ibl_spec = {0.0f, 0.0f, 0.0f};
+    if (p.ibl) {
+        const f3 irr = ibl_sample_cube(p.ibl, 0, N);
+        const float lod = ks.y * (float)(p.ibl_mips - 1);
+        const f3 pre = ibl_sample_trilinear(p.ibl, p.ibl_mips, reflect3(f3{-V.x, -V.y, -V.z}, N), lod);
+        // Math::schlick_fresnel(u.ibl_f0, max(0, N.V)) (shs_renderer.hpp:164-169)
+        const float fx = 1.0f - saturate(g_max(0.0f, dot3(N, V)));
+        const float fx2 = fx * fx;
+        const float fx5 = fx2 * fx2 * fx;
+        const float F = kn.z + (1.0f - kn.z) * fx5;
+        const float kd = 1.0f - F;
+        ibl_diffuse = {(kd * irr.x) * kn.x, (kd * irr.y) * kn.x, (kd * irr.z) * kn.x};
+        ibl_spec = {((F * pre.x) * kn.y) * kn.w, ((F * pre.y) * kn.y) * kn.w, ((F * pre.z) * kn.y) * kn.w};
+    }
+    // result = ((amb + direct) + ibl_diffuse * baseColor) + ibl_spec
+    const float pr = g_clamp01((c.x + ibl_diffuse.x * base.x) + ibl_spec.x) * 255;
+    const float pg = g_clamp01((c.y + ibl_diffuse.y * base.y) + ibl_spec.y) * 255;
+    const float pb = g_clamp01((c.z + ibl_diffuse.z * base.z) + ibl_spec.z) * 255;
+    rgba = pack_rgba(pr, pg, pb);
+    pq = make_float4(pr, pg, pb, shadow);
+}
+
 // ---- hello_water.cpp: the atmosphere shader, the water shader and the planar reflection ("water :line") ----
 
 // fractf :759

@@ -18,7 +18,7 @@ from ._abi import (FRAME_PREQUANT, FRAME_PRESENT, SHADING_BLINN_PHONG, SHADING_D
                    SHADING_TOON, FrameDesc, LegacyDraw, RasterStats)
 
 __all__ = [
-    "ShsError", "Context", "Frame", "Draw", "RtFrame", "RtDraw", "RtPcss", "RtPbrDraw", "RtPbr", "RtSky", "RtSkyboxIblDraw", "RtWaterDraw", "RtWater", "SHADING_FLAT", "SHADING_GOURAUD", "SHADING_PHONG",
+    "ShsError", "Context", "Frame", "Draw", "RtFrame", "RtDraw", "RtPcss", "RtPbrDraw", "RtPbr", "RtSky", "RtSkyboxIblDraw", "RtIblPhongDraw", "RtWaterDraw", "RtWater", "SHADING_FLAT", "SHADING_GOURAUD", "SHADING_PHONG",
     "SHADING_BLINN_PHONG", "SHADING_TOON", "SHADING_GOOCH", "SHADING_OREN_NAYAR", "SHADING_NORMAL_VIS",
     "SHADING_DEPTH_VIS", "SHADING_TEXTURED", "SHADING_NAMES", "FRAME_PREQUANT", "lib",
 ]
@@ -115,6 +115,8 @@ class RtFrame:
                                  # 8: hello_per_object_motion_blur.cpp's velocity_fragment_shader, 9: hello_depth_of_field.cpp's
                                  #    and 10: hello_ping_pong.cpp's Blinn-Phong shader (Context.rt_render_plain only; the depth
                                  #    plane is then in screen rows)
+                                 # 11: hello_ibl_skybox_optimized.cpp's / hello_ibl_skybox_xsimd.cpp's fragment_shader_full, Blinn-Phong
+                                 #    with a per-draw shininess plus the IBL of rt_set_ibl (Context.rt_render_ibl_phong only)
 
 
 @dataclass
@@ -157,6 +159,17 @@ class RtSkyboxIblDraw:
     ibl_refl: float = 0.35
     ibl_f0: float = 0.04
     ibl_refl_mix: float = 1.0
+
+
+@dataclass
+class RtIblPhongDraw:
+    """hello_ibl_skybox_optimized.cpp's / hello_ibl_skybox_xsimd.cpp's per-object knobs beside an RtDraw
+    (shs_rt_ibl_phong_draw); the defaults are Uniforms'."""
+    ibl_ambient: float = 0.30
+    ibl_refl: float = 0.35
+    ibl_f0: float = 0.04
+    ibl_refl_mix: float = 1.0
+    shininess: float = 64.0
 
 
 @dataclass
@@ -1061,6 +1074,32 @@ class Context:
                 knobs[i] = _abi.RtSkyboxIblDrawC(float(k.ibl_ambient), float(k.ibl_refl), float(k.ibl_f0), float(k.ibl_refl_mix))
         self._check(self._lib.shs_rt_render_skybox_ibl(self._h, ctypes.byref(self._rt_frame_c(frame)), arr, knobs, len(draws)))
         self._rt_size = (frame.width, frame.height)
+
+    def rt_render_ibl_phong(self, frame, draws, ibl_draws):
+        """shs_rt_render_ibl_phong: PASS1 of hello_ibl_skybox_optimized.cpp / hello_ibl_skybox_xsimd.cpp (frame.shading 11:
+        Blinn-Phong with a per-draw shininess under the shadow lookup, plus the irradiance and prefiltered-specular terms
+        of the IBL of rt_set_ibl; ibl_draws: one RtIblPhongDraw per draw, or None to hand the library a null table),
+        asynchronous."""
+        arr = self._rt_draw_array(draws)
+        knobs = None
+        if ibl_draws is not None:
+            if len(ibl_draws) != len(draws):
+                raise ShsError(-1, "rt_render_ibl_phong: one RtIblPhongDraw per draw")
+            knobs = (_abi.RtIblPhongDrawC * max(len(draws), 1))()
+            for i, k in enumerate(ibl_draws):
+                knobs[i] = _abi.RtIblPhongDrawC(float(k.ibl_ambient), float(k.ibl_refl), float(k.ibl_f0), float(k.ibl_refl_mix),
+                                                float(k.shininess))
+        self._check(self._lib.shs_rt_render_ibl_phong(self._h, ctypes.byref(self._rt_frame_c(frame)), arr, knobs, len(draws)))
+        self._rt_size = (frame.width, frame.height)
+
+    def rt_render_shadow_edge(self, size, light_vp, casters, ref_tile=(160, 160), lanes=8):
+        """shs_rt_render_shadow_edge: PASS0 of hello_ibl_skybox_xsimd.cpp (the edge-function raster; lanes: the reference
+        build's xsimd::batch<float>::size) over a size = (w, h) map (an int: square), asynchronous."""
+        w, h = (size, size) if isinstance(size, int) else size
+        lvp = np.ascontiguousarray(light_vp, dtype=np.float32).reshape(16)
+        arr = self._rt_draw_array(casters)
+        self._check(self._lib.shs_rt_render_shadow_edge(self._h, w, h, ref_tile[0], ref_tile[1], _fptr(lvp), arr, len(casters), int(lanes)))
+        self._rt_shadow_size = (w, h)
 
     def rt_render_water(self, frame, draws, water_draws, water):
         """shs_rt_render_water: PASS1A / PASS1B of hello_water.cpp (frame.shading 5; water_draws: one RtWaterDraw per draw, or

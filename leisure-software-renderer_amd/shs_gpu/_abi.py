@@ -337,6 +337,12 @@ class RtSkyboxIblDrawC(ctypes.Structure):
                 ("ibl_refl_mix", ctypes.c_float)]
 
 
+class RtIblPhongDrawC(ctypes.Structure):
+    """shs_rt_ibl_phong_draw: hello_ibl_skybox_optimized.cpp's / hello_ibl_skybox_xsimd.cpp's per-object knobs (shading 11)."""
+    _fields_ = [("ibl_ambient", ctypes.c_float), ("ibl_refl", ctypes.c_float), ("ibl_f0", ctypes.c_float),
+                ("ibl_refl_mix", ctypes.c_float), ("shininess", ctypes.c_float)]
+
+
 RT_WATER_SURFACE = 1        # SHS_RT_WATER_SURFACE
 RT_WATER_REFLECTION = 1     # SHS_RT_WATER_REFLECTION
 
@@ -488,6 +494,10 @@ SIGNATURES = [
     ("shs_rt_ibl_samples", ctypes.c_int, [_P, ctypes.c_int32, _P, _P, _P, _P]),
     ("shs_rt_render_skybox_ibl", ctypes.c_int, [_P, ctypes.POINTER(RtFrameC), ctypes.POINTER(RtDrawC),
                                                 ctypes.POINTER(RtSkyboxIblDrawC), ctypes.c_int32]),
+    ("shs_rt_render_ibl_phong", ctypes.c_int, [_P, ctypes.POINTER(RtFrameC), ctypes.POINTER(RtDrawC),
+                                               ctypes.POINTER(RtIblPhongDrawC), ctypes.c_int32]),
+    ("shs_rt_render_shadow_edge", ctypes.c_int, [_P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _F,
+                                                 ctypes.POINTER(RtDrawC), ctypes.c_int32, ctypes.c_int32]),
     ("shs_rt_render_water", ctypes.c_int, [_P, ctypes.POINTER(RtFrameC), ctypes.POINTER(RtDrawC), ctypes.POINTER(RtWaterDrawC),
                                            ctypes.POINTER(RtWaterC), ctypes.c_int32]),
     ("shs_rt_render_motion", ctypes.c_int, [_P, ctypes.POINTER(RtFrameC), ctypes.POINTER(RtDrawC), ctypes.c_int32]),
